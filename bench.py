@@ -2,6 +2,7 @@
 """bench.py — images/sec of one full DCGAN G+D training step (mnist_dcgan.py:147-175) on MI355X.
 
   python bench.py --gpus 1 --steps 50 --warmup 5
+  python bench.py --gpus 1 --steps 50 --warmup 5 --dump-outputs DIR     (+ the last step's outputs and both nets' state as DIR/*.npy)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W          (one rank per GPU, RCCL; weak scaling: 512 images per GPU)
 
@@ -366,6 +367,30 @@ def params_digest(nets):
     return torch.stack([n.flat_params.view(torch.int32).to(torch.int64).sum() for n in nets])
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, out, nets):
+    """--dump-outputs: what the last timed step handed its caller — train_step's returned tensors (the three losses, D's outputs on
+    the real, detached-fake and fake batches) — and the state it left: every parameter and buffer of both nets' state_dict.
+    Written after the timed region as `path`/<name>.npy (float32; int64 buffers as float64), so two builds can be compared file by
+    file on identical inputs (seeded weights and batches)."""
+    import numpy as np
+    arrays = {k: v for k, v in out.items() if torch.is_tensor(v)}
+    for tag, net in nets.items():
+        arrays.update((f"{tag}.{k}", v) for k, v in net.state_dict().items())
+    host = {}
+    for k, v in arrays.items():
+        v = v.detach()
+        host[k] = v.to(torch.float32 if v.is_floating_point() else torch.float64).cpu().numpy()
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_LIMIT_BYTES:
+        sys.exit(f"bench.py --dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    os.makedirs(path, exist_ok=True)
+    for k, a in host.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -383,9 +408,14 @@ def main():
     ap.add_argument("--no-calib", action="store_true", help="skip the bare-MFMA / HBM-copy calibration around the timed region")
     ap.add_argument("--no-secondary", action="store_true", help="skip the short replays of BASELINE configs 3 / 4 / 5 behind the headline (the `secondary` block)")
     ap.add_argument("--cpu-threads", type=int, default=None, help="threads of the CPU baseline (default: min(16, visible cores))")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (the step's returned tensors, both nets' state_dict) "
+                         "as DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
     if args.gpus < 1:
         sys.exit("bench.py: --gpus must be >= 1")
+    if args.steps < 1:
+        sys.exit("bench.py: --steps must be >= 1")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         launch_ranks(args.gpus, sys.argv[1:])      # does not return
@@ -547,6 +577,9 @@ def main():
         replicas_identical = all(torch.equal(a, allg[0]) for a in allg)
         if not replicas_identical:
             sys.exit(f"rank {rank}: replicas diverged — parameter digests {[a.tolist() for a in allg]}")
+
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, {"G": netG, "D": netD})
 
     losses = {k: float(out[k].item()) for k in ("errD_real", "errD_fake", "errG")}
     if not all(v == v and abs(v) < 1e4 for v in losses.values()):

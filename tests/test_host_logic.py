@@ -120,7 +120,17 @@ def test_conv_launch_planning_at_the_bench_shapes():
     """The launch form each bench-shape convolution takes (csrc/conv_igemm.hip: plan_fwd, fwd_use_t64, plan_sk_shape, plan_skn_shape,
     dgrad_as_gemm, plan_wgrad) through pcg_conv_plan_describe — host logic, no device.  Pins the decisions DESIGN.md 3.1.1 tabulates:
     DCGAN's tile counts stay data-parallel (D4's 256 big tiles become 512 tiles of 64x128), the WGAN-GP layers whose tile counts do
-    not fill the chip's 512 workgroup slots take stream-K when the stream has scratch and the r02 forms when it has none."""
+    not fill the chip's 512 workgroup slots take stream-K when the stream has scratch and the r02 forms when it has none.
+    Checked in a fresh process: with assume_scratch = 0 the planner asks whether a stream of the device already holds stream-K
+    scratch, and that scratch lives as long as the process — GPU tests earlier in the same session leave some behind."""
+    here = os.path.dirname(os.path.abspath(__file__))
+    code = "import sys; sys.path[:0] = [%r, %r]; import test_host_logic as t; t._check_bench_shape_plans()" % (ROOT, here)
+    r = subprocess.run([sys.executable] + (["-s"] if sys.flags.no_user_site else []) + ["-c", code],
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
+
+
+def _check_bench_shape_plans():
     import ctypes
     from pcgan_amd import _lib
     lib = _lib.load()
@@ -160,3 +170,25 @@ def test_conv_launch_planning_at_the_bench_shapes():
     # counteRGAN 3x3 64 -> 64
     assert plan(1024, 64, 64, 28, 3, 1, 1, FWD, 1) == "128x64 tiles: 6272"
     assert plan(1024, 64, 64, 28, 3, 1, 1, WGRAD, 1).startswith("64x192 tiles: 3 x")
+
+
+def test_bench_dump_outputs_writes_every_returned_tensor_and_both_state_dicts(tmp_path):
+    """bench.py --dump-outputs: the step's returned tensors and every state_dict entry of both nets as <name>.npy, floats as
+    float32 and integer buffers as float64, the same values, within the 64 MB limit at the reference widths."""
+    import numpy as np
+    import bench
+    from oracle import dcgan_ref as R
+    netG, netD = R.build(None, seed=1)
+    out = {"errG": torch.tensor(0.75), "out_real": torch.rand(512, dtype=torch.float64), "note": "not a tensor"}
+    bench.dump_outputs(str(tmp_path / "d"), out, {"G": netG, "D": netD})
+    want = {"errG", "out_real"} | {f"G.{k}" for k in netG.state_dict()} | {f"D.{k}" for k in netD.state_dict()}
+    files = {f[:-4] for f in os.listdir(tmp_path / "d")}
+    assert files == want
+    total = 0
+    for name in want:
+        a = np.load(tmp_path / "d" / (name + ".npy"))
+        total += a.nbytes
+        assert a.dtype == (np.float64 if name.endswith("num_batches_tracked") else np.float32), name
+    np.testing.assert_array_equal(np.load(tmp_path / "d" / "out_real.npy"), out["out_real"].float().numpy())
+    np.testing.assert_array_equal(np.load(tmp_path / "d" / "G.main.0.weight.npy"), netG.state_dict()["main.0.weight"].numpy())
+    assert total <= bench.DUMP_LIMIT_BYTES

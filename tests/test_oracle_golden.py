@@ -8,7 +8,15 @@ import torch
 
 from oracle import dcgan_ref as R
 
-torch.set_num_threads(4)
+
+@pytest.fixture(autouse=True)
+def _four_cpu_threads():
+    """Every test here runs on 4 CPU threads, the setting its tolerances were fixed with: set per test, because a call at import
+    takes effect at collection and the GPU tests that run in between set their own thread counts."""
+    prev = torch.get_num_threads()
+    torch.set_num_threads(4)
+    yield
+    torch.set_num_threads(prev)
 
 
 @pytest.fixture(scope="module")

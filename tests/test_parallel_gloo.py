@@ -20,7 +20,15 @@ class _FakeNet:
         return self._bufs
 
 
+def _as_cpu_rank():
+    """The ranks here rehearse the CPU path.  GradSync takes the library's RCCL communicator whenever torch.cuda.is_available(),
+    and on a host with one GPU two ranks would then share that device, which RCCL refuses: a rank here sees no GPU, as on a
+    CPU-only host.  (Each rank is a fresh spawned process: the parent is not affected.)"""
+    torch.cuda.is_available = lambda: False
+
+
 def _worker(rank, world, port, q):
+    _as_cpu_rank()
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
     dist.init_process_group("gloo", rank=rank, world_size=world)
@@ -199,6 +207,7 @@ def _toy_countergan_step(rec, netG, netD, optD, optG, real, noise, dp):
 
 
 def _segment_worker(rank, world, port, q, toy="dcgan"):
+    _as_cpu_rank()
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
     dist.init_process_group("gloo", rank=rank, world_size=world)
@@ -351,6 +360,7 @@ def test_gpu_count_from_kfd_topology(tmp_path, monkeypatch):
 
 
 def _syncbn_worker(rank, world, port, q):
+    _as_cpu_rank()
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
     dist.init_process_group("gloo", rank=rank, world_size=world)
