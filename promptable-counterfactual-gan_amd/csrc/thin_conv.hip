@@ -416,6 +416,31 @@ __global__ void __launch_bounds__(256) thin_wgrad_kernel(ThinP p, float* slab, i
   }
 }
 
+// Weight gradient of the thin geometries the kernels above do not instantiate: a wide channel count that is not 4*2^k <= 1024, a
+// kernel shape other than 4x4 / 3x3 / 1x1 (or 4x4 with 2..3 thin channels), a transposed map with stride > 2 (tap_map_idx knows
+// strides 1 and 2 only).  Runtime tap loop through tap_map, one thread per weight element of the block's slab, the block's pixels
+// added in order; off every model's hot path.
+__global__ void __launch_bounds__(256) thin_wgrad_any_kernel(ThinP p, float* slab, int ppb, int wn) {
+  const int p0 = blockIdx.x * ppb;
+  int p1 = p0 + ppb; if (p1 > p.npix) p1 = p.npix;
+  float* myslab = slab + (size_t)blockIdx.x * wn;
+  const int ntc = p.KH * p.KW * p.Cs;
+  for (int e = threadIdx.x; e < ntc * p.C; e += 256) {     // consecutive threads: consecutive wide channels of one pixel
+    const int t = e / p.C, c = e - t * p.C;
+    const int tap = t / p.Cs, cs = t - tap * p.Cs, kh = tap / p.KW, kw = tap - kh * p.KW;
+    float acc = 0.f;
+    for (int pix = p0; pix < p1; ++pix) {
+      uint32_t r, pw, b, ph;
+      p.dIW.divmod((uint32_t)pix, r, pw);
+      p.dIH.divmod(r, b, ph);
+      int qh, qw;
+      if (!tap_map(p, (int)ph, (int)pw, kh, kw, qh, qw)) continue;
+      acc = fmaf(p.thin[(size_t)(((int)b * p.QH + qh) * p.QW + qw) * p.Cs + cs], p.wide[(size_t)pix * p.C + c], acc);
+    }
+    myslab[(size_t)cs * p.wsS + (size_t)tap * p.wsT + (size_t)c * p.wsC] = acc;
+  }
+}
+
 __global__ void __launch_bounds__(256) slab_reduce4_kernel(const float4* __restrict__ s, float4* __restrict__ o, size_t n4,
                                                            size_t stride4, int nslabs, int accumulate) {
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
@@ -768,6 +793,20 @@ ThinWgradPlan plan_thin_wgrad(int npix, int C) {
   return w;
 }
 
+// does thin_wgrad_kernel (and so possibly the row-block forms) serve this geometry?  Otherwise thin_wgrad_any_kernel does.
+bool thin_wgrad_instantiated(const ThinP& p) {
+  const bool k44 = p.KH == 4 && p.KW == 4, k33 = p.KH == 3 && p.KW == 3, k11 = p.KH == 1 && p.KW == 1;
+  return p.C / 4 <= 256 && is_pow2(p.C / 4) && ((k44 && p.Cs == 1) || k33 || k11) && !(p.transposed && p.stride > 2);
+}
+ThinWgradPlan plan_thin_wgrad_any(int npix) {
+  ThinWgradPlan w;
+  int ppb = (npix + 1023) / 1024;           // at most ~1024 slabs
+  if (ppb < 256) ppb = 256;
+  w.ppb = ppb;
+  w.nblocks = (npix + ppb - 1) / ppb;
+  return w;
+}
+
 }  // namespace
 
 int launch_slab_reduce(const float* slab, float* dw, size_t n, size_t slab_stride, int nslabs, int accumulate, hipStream_t s, bool deferrable) {
@@ -1000,16 +1039,17 @@ size_t thin_conv_dgrad_workspace_bytes(const pcg_conv_geom* g) {
 
 size_t thin_conv_wgrad_workspace_bytes(const pcg_conv_geom* g) {
   const bool cin_thin = thin_is_cin(g);
-  const int C = cin_thin ? g->Cout : g->Cin;
-  if (C % 4 != 0 || C / 4 > 256 || !is_pow2(C / 4)) return 0;
-  const int npix = cin_thin ? g->B * g->OH * g->OW : g->B * g->IH * g->IW;
-  const ThinWgradPlan wp = plan_thin_wgrad(npix, C);
-  size_t blocks = (size_t)wp.nblocks;
   ThinP p{};
-  RowsP rp{};
-  size_t patch_bytes = 0;
-  if (fill_common(p, g, cin_thin, cin_thin) == PCG_OK && rows_wgrad_ok(p, g, rp, &patch_bytes) && (size_t)rows_wgrad_blocks(rp) > blocks)
-    blocks = (size_t)rows_wgrad_blocks(rp);
+  if (fill_common(p, g, cin_thin, cin_thin) != PCG_OK) return 0;
+  size_t blocks;
+  if (thin_wgrad_instantiated(p)) {
+    blocks = (size_t)plan_thin_wgrad(p.npix, p.C).nblocks;
+    RowsP rp{};
+    size_t patch_bytes = 0;
+    if (rows_wgrad_ok(p, g, rp, &patch_bytes) && (size_t)rows_wgrad_blocks(rp) > blocks) blocks = (size_t)rows_wgrad_blocks(rp);
+  } else {
+    blocks = (size_t)plan_thin_wgrad_any(p.npix).nblocks;
+  }
   if (full_window(g) && (size_t)((g->B + FULL_ROWS_DW - 1) / FULL_ROWS_DW) > blocks) blocks = (size_t)((g->B + FULL_ROWS_DW - 1) / FULL_ROWS_DW);
   return blocks * (size_t)g->Cout * g->KH * g->KW * g->Cin * sizeof(float);
 }
@@ -1037,10 +1077,21 @@ int thin_conv_wgrad(const pcg_conv_geom* g, const float* x, const float* dy, flo
   }
   // iterate over the wide tensor's pixels: dy (output grid) when Cin is thin, x (input grid) when Cout is thin
   if (int e = fill_common(p, g, cin_thin, /*iter_on_output=*/cin_thin)) return e;
-  PCG_REQUIRE(p.C / 4 <= 256 && is_pow2(p.C / 4), "thin conv wgrad: wide channel count %d must be 4*2^k <= 1024", p.C);
   if (cin_thin) { p.wide = dy; p.thin = x; } else { p.wide = x; p.thin = dy; }
-  const ThinWgradPlan wp = plan_thin_wgrad(p.npix, p.C);
   const int wn = g->Cout * g->KH * g->KW * g->Cin;
+  if (!thin_wgrad_instantiated(p)) {
+    PCG_REQUIRE(!has_xf, "thin conv weight gradient: an input transform needs the row-block form");
+    const ThinWgradPlan ap = plan_thin_wgrad_any(p.npix);
+    const size_t need = (size_t)ap.nblocks * wn * sizeof(float);
+    if (ws == nullptr || ws_bytes < need) {
+      set_error("thin conv wgrad: workspace %zu B < required %zu B", ws_bytes, need);
+      return PCG_ERR_WORKSPACE;
+    }
+    hipLaunchKernelGGL(thin_wgrad_any_kernel, dim3((unsigned)ap.nblocks), dim3(256), 0, s, p, (float*)ws, ap.ppb, wn);
+    if (int e = launch_status("thin_wgrad_any_kernel")) return e;
+    return launch_slab_reduce((const float*)ws, dw, (size_t)wn, (size_t)wn, ap.nblocks, accumulate, s, true);
+  }
+  const ThinWgradPlan wp = plan_thin_wgrad(p.npix, p.C);
   RowsP rp{};
   size_t patch_bytes = 0;
   const bool rows = rows_wgrad_ok(p, g, rp, &patch_bytes);

@@ -17,7 +17,7 @@ __device__ __forceinline__ float thin_load1(thin_rsrc_t r, uint32_t off) {
   return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(r, off, 0, 0));
 }
 
-// pixel index on the "other" grid for tap (kh,kw) of iteration pixel (ph,pw), or -1
+// pixel index on the "other" grid for tap (kh,kw) of iteration pixel (ph,pw), or -1 (the transposed map: strides 1 and 2 only)
 __device__ __forceinline__ int tap_map_idx(const ThinP& p, int b, int ph, int pw, int kh, int kw) {
   int qh, qw;
   bool ok;
