@@ -74,6 +74,14 @@ const char* pcg_target_arch(void);
  * workspace == NULL is always valid (a slower single-kernel path is used).                                        */
 size_t pcg_conv2d_fwd_workspace_bytes(const pcg_conv_geom* g);
 size_t pcg_conv2d_dgrad_workspace_bytes(const pcg_conv_geom* g);
+/* Operand precision of the matrix-core (implicit-GEMM) convolutions, per calling thread (default PCG_PREC_F32).  PCG_PREC_BF16: the two
+ * GEMM operands are rounded once to bf16 (round-to-nearest-even, after any input transform) and the products summed in fp32 — tensors,
+ * workspaces and epilogues stay fp32, and every geometry the fp32 path accepts runs in bf16.  The thin (Cin or Cout <= 3) layers and all
+ * other kernels ignore it.  Each pcg_conv2d_* call reads the calling thread's setting when it enqueues its launches (a HIP-graph capture
+ * records it).  set: PCG_ERR_INVALID for any other value; get: the calling thread's setting.                                          */
+typedef enum pcg_precision { PCG_PREC_F32 = 0, PCG_PREC_BF16 = 1 } pcg_precision;
+int pcg_conv_precision_set(int32_t precision);
+int32_t pcg_conv_precision_get(void);
 int pcg_conv2d_fwd(const pcg_conv_geom* g, const float* x, const float* w, const float* bias /*nullable*/,
                    float* y, void* workspace /*nullable*/, size_t workspace_bytes, pcg_stream_t stream);
 int pcg_conv2d_dgrad(const pcg_conv_geom* g, const float* dy, const float* w, const float* bias_x /*nullable: added per Cin channel (ConvTranspose2d bias)*/,

@@ -22,7 +22,7 @@ import torch.nn.functional as F
 
 from . import ops
 from ._lib import ACT_LRELU, ACT_NONE, ACT_RELU, PcgError
-from .nn import weighted_sum, FlatModule
+from .nn import weighted_sum, FlatModule, in_conv_precision
 from .optim import Adam
 
 
@@ -218,6 +218,8 @@ class _GFn(torch.autograd.Function):
 class ResidualGenerator(FlatModule):
     """generator.py:25-86 — returns (raw_residual, masked_residual)."""
 
+    honours_conv_precision = True   # conv_precision = "bf16" (DESIGN.md §3.7)
+
     def __init__(self, img_shape=(1, 28, 28), num_classes=10, base_ch=64, n_resblocks=6, residual_scaling=0.1):
         super().__init__()
         C, H, W = img_shape
@@ -272,6 +274,7 @@ class ResidualGenerator(FlatModule):
                              residual=residual, alpha=alpha)
         return g, z, y, None, None
 
+    @in_conv_precision
     def _run_forward(self, x, target, mask, keep=True):
         B = x.shape[0]
         H, W = self._hw
@@ -293,6 +296,7 @@ class ResidualGenerator(FlatModule):
         shp = (B, 1, H, W)
         return raw.view(shp), masked.view(shp), saved
 
+    @in_conv_precision
     def _run_backward(self, saved, d_raw, d_masked, need_p):
         inp, g_in, blocks, h_last, g_mid, hm, g_out, mr, target = saved
         if not need_p:
@@ -418,6 +422,8 @@ class _DFn(torch.autograd.Function):
 class Discriminator(FlatModule):
     """discriminator.py:5-38 — logits [B, 1]."""
 
+    honours_conv_precision = True   # conv_precision = "bf16" (DESIGN.md §3.7)
+
     def __init__(self, img_shape=(1, 28, 28), num_classes=Config.num_classes):
         super().__init__()
         C, H, W = img_shape
@@ -445,6 +451,7 @@ class Discriminator(FlatModule):
             return _DFn.apply(self, x, cond_idx, *self.parameters())
         return self._run_forward(x, cond_idx, keep=False)[0]
 
+    @in_conv_precision
     def _run_forward(self, x, cond_idx, keep=True):
         B = x.shape[0]
         H, W = self._hw
@@ -462,6 +469,7 @@ class Discriminator(FlatModule):
         saved = (layers, pooled, gl, (Hq * Wq, Cq), cond_idx) if keep else None
         return logits, saved
 
+    @in_conv_precision
     def _run_backward(self, saved, dlogits, need_x, need_p):
         layers, pooled, gl, (HWq, Cq), cond_idx = saved
         B = pooled.shape[0]
@@ -541,6 +549,8 @@ class CNNClassifier(FlatModule):
     item 3) it is a regular trainable net: Dropout2d(0.25) / Dropout(0.5) masks come from `self.rng` (a device Philox
     stream) or, for runs that must reproduce given draws, from `self.dropout_masks = [mask2d [B,128], mask [B,256]]`."""
 
+    honours_conv_precision = True   # conv_precision = "bf16" (DESIGN.md §3.7)
+
     def __init__(self, num_classes=10):
         super().__init__()
         self.rng = None
@@ -603,6 +613,7 @@ class CNNClassifier(FlatModule):
         return self._run_forward(x, keep=False)[0]
 
     # -- training mode (trainer.py:15-20) ------------------------------------------------------------------------------------
+    @in_conv_precision
     def _train_forward(self, x, masks):
         from .nn import linear_fwd
         B = x.shape[0]
@@ -623,6 +634,7 @@ class CNNClassifier(FlatModule):
         logits = linear_fwd(fc2, hd)
         return logits, (layers, m2d, m1, flat, h, hd, (HW, C))
 
+    @in_conv_precision
     def _train_backward(self, saved, dlogits):
         from .nn import linear_dgrad, linear_wgrad
         layers, m2d, m1, flat, h, hd, (HW, C) = saved
@@ -642,6 +654,7 @@ class CNNClassifier(FlatModule):
             ops.act_bwd(d, y, ACT_RELU, 0.0, out=d)
             d = _conv_bwd(self, conv, g, a, d, True, i > 0)
 
+    @in_conv_precision
     def _run_forward(self, x, keep=True):
         cw, w1, b1, w2, b2, kp = self._pack()
         B = x.shape[0]
@@ -662,6 +675,7 @@ class CNNClassifier(FlatModule):
         saved = (layers, g1, w1, h, g2, w2, kp) if keep else None
         return logits, saved
 
+    @in_conv_precision
     def _run_backward(self, saved, dlogits):
         layers, g1, w1, h, g2, w2, kp = saved
         B = dlogits.shape[0]

@@ -648,9 +648,10 @@ __global__ void __launch_bounds__(IG_THREADS, Cfg::MINW) conv_dgrad_pkernel(Conv
 
 // 64x192 tile of the weight gradient (Cout <= 64, N = KH*KW*Cin a multiple of 192): the same pipeline with the 192-column B loader
 using Cfg64x192 = TileCfg<64, 192, 2, 2>;
+template <class Cfg>
 __global__ void __launch_bounds__(IG_THREADS, 4) conv_wgrad192_kernel(ConvP p, int ktiles_total, int ktiles_per_split, int tiles,
                                                                       int slice_major) {
-  using Cfg = Cfg64x192;
+  static_assert(Cfg::BM == 64 && Cfg::BN == 192, "the 192-column weight-gradient tile");
   extern __shared__ __attribute__((aligned(16))) float smem[];
   prio_entry(p);
   uint32_t tile, split;
@@ -729,6 +730,12 @@ using Cfg128x64 = TileCfg<128, 64, 2, 2, true, 6, 1>;      // measured r02: 3x3 
 #else                                                      // TFLOP/s; the k4 s2 grad-input (four interleaved phases, K = 512) LOSES
 using Cfg128x64 = Cfg128x64P;                              // 9 % (105.7 -> 96.6) and therefore keeps the padded config
 #endif
+
+// The bf16-operand twin of a tile configuration (pcg_conv_precision_set): same tile, prefetch depth and launch bounds,
+// so the same plans, grids and workspace.  Its LDS images are its own (igemm_core.h), so SWZ does not apply, and it has no LDS-DMA form:
+// the `dma` switch (and the persistent experiment of `make lean`) are fp32-only and ignored in bf16 mode.
+template <class C>
+using Bf16Twin = TileCfg<C::BM, C::BN, C::WAVES_M, C::WAVES_N, false, C::MINW, C::PF, false, true>;
 
 // (r04: 192x64 tiles — four consumer waves of 96x32, two workgroups per CU, 1.5x the MFMAs per workgroup — were built and measured:
 //  bit-identical results, no gain: 3x3 64->64 forward 0.4867 -> 0.4943 ms, its grad-input 0.4969 -> 0.5227, D2's k4 s2 grad-input
@@ -901,6 +908,7 @@ int launch_fwd_x(ConvP p, int splits, hipStream_t s) {
   p.tilesN = ceil_div(p.N, Cfg::BN);
   const int tilesM = ceil_div(p.M, Cfg::BM);
 #ifdef PCG_PERSISTENT_KERNELS
+  if constexpr (!Cfg::BF16) {      // the persistent experiment is fp32-only: a bf16 twin takes the launches below
   if (use_persistent()) {
     constexpr size_t smem = stage_smem_bytes<Cfg, true, true>();
     static int once = set_smem(conv_fwd_pkernel<Cfg, XF>, smem);
@@ -908,6 +916,7 @@ int launch_fwd_x(ConvP p, int splits, hipStream_t s) {
     const uint64_t items = (uint64_t)tilesM * p.tilesN * splits;
     hipLaunchKernelGGL((conv_fwd_pkernel<Cfg, XF>), dim3(persistent_grid<Cfg>(items)), dim3(IG_THREADS), smem, s, p, splits);
     return launch_status("conv_fwd_pkernel");
+  }
   }
 #endif
   constexpr size_t smem = smem_bytes<Cfg, true, true>();
@@ -927,6 +936,7 @@ int launch_fwd_x(ConvP p, int splits, hipStream_t s) {
 }
 template <class Cfg>
 int launch_fwd(const ConvP& p, int splits, hipStream_t s) {
+  if (conv_bf16()) return p.in_sc ? launch_fwd_x<Bf16Twin<Cfg>, true>(p, splits, s) : launch_fwd_x<Bf16Twin<Cfg>, false>(p, splits, s);
   return p.in_sc ? launch_fwd_x<Cfg, true>(p, splits, s) : launch_fwd_x<Cfg, false>(p, splits, s);
 }
 
@@ -998,6 +1008,7 @@ int launch_dgrad_x(ConvP p, const DgradPhases& ph, int nphases, int maxMp, hipSt
   p.tilesN = ceil_div(p.N, Cfg::BN);
   const int tilesM = ceil_div(maxMp, Cfg::BM);
 #ifdef PCG_PERSISTENT_KERNELS
+  if constexpr (!Cfg::BF16) {      // (fp32-only, as in launch_fwd_x)
   bool all_have_taps = true;
   for (int i = 0; i < nphases; ++i) all_have_taps = all_have_taps && ph.p[i].nth > 0;
   if (use_persistent() && all_have_taps) {
@@ -1016,6 +1027,7 @@ int launch_dgrad_x(ConvP p, const DgradPhases& ph, int nphases, int maxMp, hipSt
     it.total = (uint32_t)total;
     hipLaunchKernelGGL((conv_dgrad_pkernel<Cfg, XF>), dim3(persistent_grid<Cfg>(total)), dim3(IG_THREADS), smem, s, p, ph, it);
     return launch_status("conv_dgrad_pkernel");
+  }
   }
 #endif
   constexpr size_t smem = smem_bytes<Cfg, true, false>();
@@ -1067,6 +1079,8 @@ int launch_dgrad_x(ConvP p, const DgradPhases& ph, int nphases, int maxMp, hipSt
 }
 template <class Cfg>
 int launch_dgrad(const ConvP& p, const DgradPhases& ph, int nphases, int maxMp, hipStream_t s) {
+  if (conv_bf16())
+    return p.in_sc ? launch_dgrad_x<Bf16Twin<Cfg>, true>(p, ph, nphases, maxMp, s) : launch_dgrad_x<Bf16Twin<Cfg>, false>(p, ph, nphases, maxMp, s);
   return p.in_sc ? launch_dgrad_x<Cfg, true>(p, ph, nphases, maxMp, s) : launch_dgrad_x<Cfg, false>(p, ph, nphases, maxMp, s);
 }
 
@@ -1768,6 +1782,9 @@ static int launch_wgrad_x(const ConvP& p, const WgradPlan& wp, int slice_major, 
 }
 template <class Cfg, bool XFA, bool XFB>
 static int launch_wgrad_sk_x(const ConvP& p, const SkPlan& sk, hipStream_t s) {
+  if constexpr (!Cfg::BF16) {
+    if (conv_bf16()) return launch_wgrad_sk_x<Bf16Twin<Cfg>, XFA, XFB>(p, sk, s);
+  }
   constexpr size_t smem = smem_bytes<Cfg, false, false>();
   static int once = set_smem(conv_wgrad_sk_kernel<Cfg, XFA, XFB>, smem);
   if (once != PCG_OK) return once;
@@ -1775,7 +1792,19 @@ static int launch_wgrad_sk_x(const ConvP& p, const SkPlan& sk, hipStream_t s) {
   return launch_status("conv_wgrad_sk_kernel");
 }
 template <class Cfg>
+static int launch_wgrad192(const ConvP& p, const WgradPlan& wp, int slice_major, hipStream_t s) {
+  constexpr size_t smem = smem_bytes<Cfg, false, false>();
+  static int once = set_smem(conv_wgrad192_kernel<Cfg>, smem);
+  if (once != PCG_OK) return once;
+  hipLaunchKernelGGL((conv_wgrad192_kernel<Cfg>), slice_major ? dim3((unsigned)wp.tiles * wp.splits) : dim3((unsigned)wp.tiles, wp.splits),
+                     dim3(IG_THREADS), smem, s, p, wp.ktiles_total, wp.ktiles_per_split, wp.tiles, slice_major);
+  return launch_status("conv_wgrad192_kernel");
+}
+template <class Cfg>
 static int launch_wgrad(const ConvP& p, const WgradPlan& wp, int slice_major, int xf_side, hipStream_t s) {
+  if constexpr (!Cfg::BF16) {
+    if (conv_bf16()) return launch_wgrad<Bf16Twin<Cfg>>(p, wp, slice_major, xf_side, s);
+  }
   if (xf_side == 1) return launch_wgrad_x<Cfg, false, true>(p, wp, slice_major, s);    // x is a transformed activation
   if (xf_side == 2) return launch_wgrad_x<Cfg, true, false>(p, wp, slice_major, s);    // dy is
   return launch_wgrad_x<Cfg, false, false>(p, wp, slice_major, s);
@@ -1829,12 +1858,7 @@ extern "C" int pcg_conv2d_wgrad_xf(const pcg_conv_geom* g, const float* x, const
   int rc;
   if (wp.wide192 && side == 0) {
     p.tilesN = p.N / 192;
-    constexpr size_t smem = smem_bytes<Cfg64x192, false, false>();
-    static int once = set_smem(conv_wgrad192_kernel, smem);
-    if (once != PCG_OK) return once;
-    hipLaunchKernelGGL(conv_wgrad192_kernel, slice_major ? dim3((unsigned)wp.tiles * wp.splits) : dim3((unsigned)wp.tiles, wp.splits),
-                       dim3(IG_THREADS), smem, s, p, wp.ktiles_total, wp.ktiles_per_split, wp.tiles, slice_major);
-    rc = launch_status("conv_wgrad192_kernel");
+    rc = conv_bf16() ? launch_wgrad192<Bf16Twin<Cfg64x192>>(p, wp, slice_major, s) : launch_wgrad192<Cfg64x192>(p, wp, slice_major, s);
   } else {
     WgradPlan wq = wp;
     if (wp.wide192) {     // an input transform is pending on an operand: the 128-column tiles carry it (re-plan without the 192 tile)

@@ -81,12 +81,17 @@ constexpr int IG_LDK = IG_BK + 4;          // K-major row stride: 144 B = 9*16 (
 template <int NV>
 __device__ __forceinline__ constexpr int mn_krow(int kr0, int i) { return PCG_MN_CONSEC ? NV * kr0 + i : kr0 + (32 / NV) * i; }
 
-template <int BM_, int BN_, int WAVES_M_, int WAVES_N_, bool SWZ_ = false, int MINW_ = 4, int PF_ = PCG_PREFETCH_DEPTH, bool DMA_ = false>
+// BF16_: the operand-precision twin — both operands rounded to bf16 (RNE) as the producers write LDS, products summed in
+//        fp32 on v_mfma_f32_32x32x16_bf16.  Same tile, prefetch and launch bounds as the fp32 config; SWZ / DMA do not apply (below).
+template <int BM_, int BN_, int WAVES_M_, int WAVES_N_, bool SWZ_ = false, int MINW_ = 4, int PF_ = PCG_PREFETCH_DEPTH, bool DMA_ = false,
+          bool BF16_ = false>
 struct TileCfg {
   static constexpr int BM = BM_, BN = BN_, WAVES_M = WAVES_M_, WAVES_N = WAVES_N_;
   static constexpr bool SWZ = SWZ_;
   static constexpr bool DMA = DMA_;          // operand tiles go global -> LDS directly (buffer_load ... lds), see igemm_produce_dma
+  static constexpr bool BF16 = BF16_;
   static_assert(!DMA_ || SWZ_, "LDS-DMA needs the lane-linear (unpadded, swizzled) K-major images");
+  static_assert(!(DMA_ && BF16_), "LDS-DMA copies fp32 bytes: no rounding on the way, no bf16 twin");
   static constexpr int MINW = MINW_, PF = PF_;
   static constexpr int WTM = BM / WAVES_M, WTN = BN / WAVES_N;
   static constexpr int TM = WTM / 32, TN = WTN / 32;
@@ -94,8 +99,75 @@ struct TileCfg {
   static_assert(WTM % 32 == 0 && WTN % 32 == 0, "wave tile must be a multiple of the 32x32 MFMA tile");
 };
 
-template <int ROWS, bool KMAJOR, bool SWZ = false>
-struct LdsImage {
+// bf16 operand images (Cfg::BF16).  Always K-major, whatever the source layout: [rows][40] bf16 (80-byte rows, 32 k + 8 pad; an odd
+// multiple of 16 bytes, so the sixteen rows of a quarter-wave's ds_read_b128 hit sixteen distinct 4-bank groups).  The fragment of
+// v_mfma_f32_32x32x16_bf16 — lane (i, h) holds A[i][k0 + 8h + j], j = 0..7 (cdna_hip_programming.md §3) — is then ONE ds_read_b128 for
+// either operand, and both operands give register slot j the same k.  The producers round once, round-to-nearest-even (a plain
+// __bf16 cast: v_cvt_pk_bf16_f32, NaN stays NaN), after their input transform has run in fp32:
+//   K-major source  a float4 = 4 consecutive k of one row     -> one ds_write_b64
+//   MN-major source a loader thread holds NV consecutive k-rows (mn_krow, PCG_MN_CONSEC) of 4 consecutive columns: transposed in
+//                   registers, per column NV bf16 = one ds_write_b64 (NV = 4) / ds_write_b32 (NV = 2; the 192-row image likewise)
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+constexpr int IG_LDB = IG_BK + 8;          // bf16 row stride (elements): 80 B
+__device__ __forceinline__ uint32_t pack_bf16x2(float lo, float hi) {
+  const bf16x2 v = {(__bf16)lo, (__bf16)hi};
+  return __builtin_bit_cast(uint32_t, v);
+}
+
+template <int ROWS, bool KMAJOR, bool SWZ = false, bool BF = false>
+struct LdsImage;
+
+template <int ROWS, bool KMAJOR, bool SWZ>
+struct LdsImage<ROWS, KMAJOR, SWZ, true> {
+  static constexpr int FLOATS = ROWS * IG_LDB / 2;   // in floats, like the fp32 images (stage offsets)
+  static constexpr int NV = ROWS / 32;
+  static_assert(KMAJOR || PCG_MN_CONSEC, "bf16 MN-major staging transposes the consecutive k-rows a loader thread holds");
+  __device__ static __forceinline__ void store(float* lds, const float4 (&v)[NV], int tid) {
+    char* base = reinterpret_cast<char*>(lds);
+    if constexpr (KMAJOR) {
+      const int kq = tid & 7, r0 = tid >> 3;
+#pragma unroll
+      for (int p = 0; p < NV; ++p)
+        *reinterpret_cast<uint2*>(base + (r0 + 32 * p) * (2 * IG_LDB) + 8 * kq) = make_uint2(pack_bf16x2(v[p].x, v[p].y), pack_bf16x2(v[p].z, v[p].w));
+    } else if constexpr (IG_LOADERS % (ROWS / 4) == 0) {
+      constexpr int C4 = ROWS / 4;
+      const int c4 = tid % C4, kr0 = tid / C4;
+      static_assert((IG_LOADERS / C4) * NV == IG_BK && (NV == 2 || NV == 4), "bf16 MN-major image: 2 or 4 k-rows per loader thread");
+      char* col = base + 4 * c4 * (2 * IG_LDB) + 2 * NV * kr0;    // row 4*c4, k = NV*kr0 (= mn_krow<NV>(kr0, 0))
+      if constexpr (NV == 4) {
+        *reinterpret_cast<uint2*>(col) = make_uint2(pack_bf16x2(v[0].x, v[1].x), pack_bf16x2(v[2].x, v[3].x));
+        *reinterpret_cast<uint2*>(col + 2 * IG_LDB) = make_uint2(pack_bf16x2(v[0].y, v[1].y), pack_bf16x2(v[2].y, v[3].y));
+        *reinterpret_cast<uint2*>(col + 4 * IG_LDB) = make_uint2(pack_bf16x2(v[0].z, v[1].z), pack_bf16x2(v[2].z, v[3].z));
+        *reinterpret_cast<uint2*>(col + 6 * IG_LDB) = make_uint2(pack_bf16x2(v[0].w, v[1].w), pack_bf16x2(v[2].w, v[3].w));
+      } else {
+        *reinterpret_cast<uint32_t*>(col) = pack_bf16x2(v[0].x, v[1].x);
+        *reinterpret_cast<uint32_t*>(col + 2 * IG_LDB) = pack_bf16x2(v[0].y, v[1].y);
+        *reinterpret_cast<uint32_t*>(col + 4 * IG_LDB) = pack_bf16x2(v[0].z, v[1].z);
+        *reinterpret_cast<uint32_t*>(col + 6 * IG_LDB) = pack_bf16x2(v[0].w, v[1].w);
+      }
+    } else {
+      // ROWS = 192: three 64-column sub-images, v[2*s + h] = sub-image s, k-row mn_krow<2>(kr0, h) = 2*kr0 + h
+      static_assert(ROWS % 64 == 0, "bf16 MN-major image: ROWS must divide the loader threads or be a multiple of 64");
+      const int c4 = tid & 15, kr0 = tid >> 4;
+#pragma unroll
+      for (int s = 0; s < ROWS / 64; ++s) {
+        char* col = base + (64 * s + 4 * c4) * (2 * IG_LDB) + 4 * kr0;
+        *reinterpret_cast<uint32_t*>(col) = pack_bf16x2(v[2 * s].x, v[2 * s + 1].x);
+        *reinterpret_cast<uint32_t*>(col + 2 * IG_LDB) = pack_bf16x2(v[2 * s].y, v[2 * s + 1].y);
+        *reinterpret_cast<uint32_t*>(col + 4 * IG_LDB) = pack_bf16x2(v[2 * s].z, v[2 * s + 1].z);
+        *reinterpret_cast<uint32_t*>(col + 6 * IG_LDB) = pack_bf16x2(v[2 * s].w, v[2 * s + 1].w);
+      }
+    }
+  }
+  // fragment for MFMA tile rows [row0, row0+32), k-group ks (16 k's): f[j] = T[row0+i][16ks+8h+j]
+  __device__ static __forceinline__ void frag(const float* lds, int row0, int ks, int li, int lh, bf16x8& f) {
+    f = *reinterpret_cast<const bf16x8*>(reinterpret_cast<const char*>(lds) + (row0 + li) * (2 * IG_LDB) + 32 * ks + 16 * lh);
+  }
+};
+
+template <int ROWS, bool KMAJOR, bool SWZ>
+struct LdsImage<ROWS, KMAJOR, SWZ, false> {
   static constexpr int LDM = ROWS + 4;
   // K-major row stride: 36 floats (padded, conflict-free as is) or 32 floats with the row's eight 16-byte chunks permuted by
   // chunk ^ ((row >> 1) & 7): sixteen consecutive rows reading the same logical chunk (one quarter-wave of a ds_read_b128) then
@@ -164,7 +236,7 @@ __device__ __forceinline__ void lds_barrier() {
 
 template <class Cfg, bool AK, bool BK_>
 constexpr int igemm_smem_floats() {
-  return 2 * (LdsImage<Cfg::BM, AK, Cfg::SWZ>::FLOATS + LdsImage<Cfg::BN, BK_, Cfg::SWZ>::FLOATS);
+  return 2 * (LdsImage<Cfg::BM, AK, Cfg::SWZ, Cfg::BF16>::FLOATS + LdsImage<Cfg::BN, BK_, Cfg::SWZ, Cfg::BF16>::FLOATS);
 }
 
 // Diagnostic build (-DPCG_CLOCK_STAMP): the clock the chip holds INSIDE the main loop = delta s_memtime / delta s_memrealtime x 100 MHz
@@ -234,8 +306,8 @@ struct ClockStamp {
 //   __device__ void transform(float4 (&v)[ROWS/32]);   // applied to the registers of the last load_next before the ds_write
 template <class Cfg, class LA, class LB>
 __device__ __forceinline__ void igemm_produce(LA& la, LB& lb, int ktiles, float* smem, int tid, ClockStamp cs = ClockStamp{nullptr, 0}) {
-  using IA = LdsImage<Cfg::BM, LA::KMAJOR, Cfg::SWZ>;
-  using IB = LdsImage<Cfg::BN, LB::KMAJOR, Cfg::SWZ>;
+  using IA = LdsImage<Cfg::BM, LA::KMAJOR, Cfg::SWZ, Cfg::BF16>;
+  using IB = LdsImage<Cfg::BN, LB::KMAJOR, Cfg::SWZ, Cfg::BF16>;
   static_assert(LA::ROWS == Cfg::BM && LB::ROWS == Cfg::BN, "loader/tile mismatch");
   float* As = smem;
   float* Bs = smem + 2 * IA::FLOATS;
@@ -371,6 +443,7 @@ template <class Cfg, class LA, class LB>
 __device__ __forceinline__ void igemm_produce_dma(LA& la, LB& lb, int ktiles, float* smem, int tid, ClockStamp cs = ClockStamp{nullptr, 0}) {
   using IA = LdsImage<Cfg::BM, true, true>;
   using IB = LdsImage<Cfg::BN, true, true>;
+  static_assert(!Cfg::BF16, "LDS-DMA staging is fp32 only");
   static_assert(LA::KMAJOR && LB::KMAJOR && !LA::XFORM && !LB::XFORM, "LDS-DMA staging: plain K-major operands");
   typedef __attribute__((address_space(3))) void* lds_ptr_t;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -411,11 +484,16 @@ __device__ __forceinline__ void igemm_produce_dma(LA& la, LB& lb, int ktiles, fl
 // 16 MFMAs of k-group g; the hand-over barrier of the k-tile sits BEFORE its last k-group (whose operands are already
 // in registers), and the first fragments of the next tile are fetched right behind it — no LDS latency is exposed at
 // the tile boundary.  (s_setprio 2 here dates from r01; what matters is that the PRODUCERS rank above it — igemm_produce.)
+// The bf16 twin (Cfg::BF16) runs the same loop over k-groups of 16: one 8-element fragment per operand tile and one
+// v_mfma_f32_32x32x16_bf16 per accumulator and k-group — 2 per k-tile instead of 16 fp32 ones.
+template <bool BF> struct MmaFrag { float v[4]; };
+template <> struct MmaFrag<true> { bf16x8 v; };
+
 template <class Cfg, bool AK, bool BK_>
 __device__ __forceinline__ void igemm_consume(int ktiles, f32x16 (&acc)[Cfg::TM][Cfg::TN], const float* smem, ClockStamp cs = ClockStamp{nullptr, 0}) {
-  using IA = LdsImage<Cfg::BM, AK, Cfg::SWZ>;
-  using IB = LdsImage<Cfg::BN, BK_, Cfg::SWZ>;
-  constexpr int KG = IG_BK / 8;  // k-groups per tile
+  using IA = LdsImage<Cfg::BM, AK, Cfg::SWZ, Cfg::BF16>;
+  using IB = LdsImage<Cfg::BN, BK_, Cfg::SWZ, Cfg::BF16>;
+  constexpr int KG = IG_BK / (Cfg::BF16 ? 16 : 8);  // k-groups per tile
   const float* As = smem;
   const float* Bs = smem + 2 * IA::FLOATS;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -429,21 +507,29 @@ __device__ __forceinline__ void igemm_consume(int ktiles, f32x16 (&acc)[Cfg::TM]
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
-  float a[2][Cfg::TM][4], b[2][Cfg::TN][4];
+  MmaFrag<Cfg::BF16> a[2][Cfg::TM], b[2][Cfg::TN];
   auto fetch = [&](const float* as, const float* bs, int ks, int buf) {
 #pragma unroll
-    for (int i = 0; i < Cfg::TM; ++i) IA::frag(as, arow + 32 * i, ks, li, lh, a[buf][i]);
+    for (int i = 0; i < Cfg::TM; ++i) IA::frag(as, arow + 32 * i, ks, li, lh, a[buf][i].v);
 #pragma unroll
-    for (int j = 0; j < Cfg::TN; ++j) IB::frag(bs, brow + 32 * j, ks, li, lh, b[buf][j]);
+    for (int j = 0; j < Cfg::TN; ++j) IB::frag(bs, brow + 32 * j, ks, li, lh, b[buf][j].v);
   };
   auto mma = [&](int buf) {
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
+    if constexpr (Cfg::BF16) {
 #pragma unroll
       for (int i = 0; i < Cfg::TM; ++i)
 #pragma unroll
         for (int j = 0; j < Cfg::TN; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[buf][i][t], b[buf][j][t], acc[i][j], 0, 0, 0);
+          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[buf][i].v, b[buf][j].v, acc[i][j], 0, 0, 0);
+    } else {
+#pragma unroll
+      for (int t = 0; t < 4; ++t)
+#pragma unroll
+        for (int i = 0; i < Cfg::TM; ++i)
+#pragma unroll
+          for (int j = 0; j < Cfg::TN; ++j)
+            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[buf][i].v[t], b[buf][j].v[t], acc[i][j], 0, 0, 0);
+    }
   };
 
   lds_barrier();  // barrier 0: stage 0 is ready
@@ -725,6 +811,7 @@ __device__ __forceinline__ void igemm_produce_stream(Src& src, int S, float* sme
   using IA = LdsImage<Cfg::BM, LA::KMAJOR, Cfg::SWZ>;
   using IB = LdsImage<Cfg::BN, LB::KMAJOR, Cfg::SWZ>;
   static_assert(LA::ROWS == Cfg::BM && LB::ROWS == Cfg::BN, "loader/tile mismatch");
+  static_assert(!Cfg::BF16, "the persistent experiment is fp32 only");
   float* As = smem;
   float* Bs = smem + 2 * IA::FLOATS;
   int left = src.n;                            // k-tiles of the current tile not yet gathered
@@ -786,6 +873,7 @@ template <class Cfg, bool AK, bool BK_, class KtOf, class Epi>
 __device__ __forceinline__ void igemm_consume_stream(int ntiles, KtOf ktiles_of, Epi epilogue, const float* smem, ClockStamp cs = ClockStamp{nullptr, 0}) {
   using IA = LdsImage<Cfg::BM, AK, Cfg::SWZ>;
   using IB = LdsImage<Cfg::BN, BK_, Cfg::SWZ>;
+  static_assert(!Cfg::BF16, "the persistent experiment is fp32 only");
   constexpr int KG = IG_BK / 8;
   const float* As = smem;
   const float* Bs = smem + 2 * IA::FLOATS;
@@ -794,21 +882,29 @@ __device__ __forceinline__ void igemm_consume_stream(int ntiles, KtOf ktiles_of,
   const int li = lane & 31, lh = lane >> 5;
   const int arow = wm * Cfg::WTM, brow = wn * Cfg::WTN;
   f32x16 acc[Cfg::TM][Cfg::TN];
-  float a[2][Cfg::TM][4], b[2][Cfg::TN][4];
+  MmaFrag<Cfg::BF16> a[2][Cfg::TM], b[2][Cfg::TN];
   auto fetch = [&](const float* as, const float* bs, int ks, int buf) {
 #pragma unroll
-    for (int i = 0; i < Cfg::TM; ++i) IA::frag(as, arow + 32 * i, ks, li, lh, a[buf][i]);
+    for (int i = 0; i < Cfg::TM; ++i) IA::frag(as, arow + 32 * i, ks, li, lh, a[buf][i].v);
 #pragma unroll
-    for (int j = 0; j < Cfg::TN; ++j) IB::frag(bs, brow + 32 * j, ks, li, lh, b[buf][j]);
+    for (int j = 0; j < Cfg::TN; ++j) IB::frag(bs, brow + 32 * j, ks, li, lh, b[buf][j].v);
   };
   auto mma = [&](int buf) {
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
+    if constexpr (Cfg::BF16) {
 #pragma unroll
       for (int i = 0; i < Cfg::TM; ++i)
 #pragma unroll
         for (int j = 0; j < Cfg::TN; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[buf][i][t], b[buf][j][t], acc[i][j], 0, 0, 0);
+          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[buf][i].v, b[buf][j].v, acc[i][j], 0, 0, 0);
+    } else {
+#pragma unroll
+      for (int t = 0; t < 4; ++t)
+#pragma unroll
+        for (int i = 0; i < Cfg::TM; ++i)
+#pragma unroll
+          for (int j = 0; j < Cfg::TN; ++j)
+            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[buf][i].v[t], b[buf][j].v[t], acc[i][j], 0, 0, 0);
+    }
   };
   lds_barrier();                                 // barrier 0: the stream's first k-tile is staged
   if (ntiles <= 0) return;

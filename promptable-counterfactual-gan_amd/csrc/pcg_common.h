@@ -19,6 +19,7 @@ namespace pcg {
 // ---- error reporting (thread-local text behind pcg_last_error()) -------------------------------
 void set_error(const char* fmt, ...);
 int launch_status(const char* what);  // PCG_OK or PCG_ERR_LAUNCH after a kernel launch
+bool conv_bf16();                      // the calling thread's pcg_conv_precision_set is PCG_PREC_BF16
 
 #define PCG_REQUIRE(cond, ...)                 \
   do {                                         \

@@ -6,7 +6,10 @@
 namespace pcg {
 namespace {
 thread_local char g_err[512] = "";
+thread_local int32_t g_conv_prec = PCG_PREC_F32;
 }
+
+bool conv_bf16() { return g_conv_prec == PCG_PREC_BF16; }
 
 void set_error(const char* fmt, ...) {
   va_list ap;
@@ -23,7 +26,8 @@ int launch_status(const char* what) {
 }
 }  // namespace pcg
 
-// ABI history.  v5 (r04): + grouped batches (pcg_conv2d_fwd_bn_g, pcg_bn_apply_act_g, pcg_conv2d_dgrad_bn_phases, pcg_conv2d_dgrad_bnbwd_g,
+// ABI history.  v5, additive: + pcg_conv_precision_set / _get (thread-local bf16-operand mode of the implicit-GEMM convolutions).
+// v5 (r04): + grouped batches (pcg_conv2d_fwd_bn_g, pcg_bn_apply_act_g, pcg_conv2d_dgrad_bn_phases, pcg_conv2d_dgrad_bnbwd_g,
 //   pcg_bn_bwd_partial_g(+_workspace_bytes), pcg_bn_act_bwd_premask_g(+pcg_bn_act_bwd_g_workspace_bytes), pcg_bce_pair),
 //   pcg_conv2d_fwd_bnbwd_thin(+_ok, +_workspace_bytes), pcg_conv_weight_adjoint_many, pcg_conv_reset_scratch, pcg_dp_barrier,
 //   pcg_dp_rccl_version; the stream-K scratch registry is keyed by (device, stream).
@@ -35,3 +39,9 @@ int launch_status(const char* what) {
 extern "C" int pcg_abi_version(void) { return 5; }
 extern "C" const char* pcg_last_error(void) { return pcg::g_err; }
 extern "C" const char* pcg_target_arch(void) { return "gfx950"; }
+extern "C" int pcg_conv_precision_set(int32_t precision) {
+  PCG_REQUIRE(precision == PCG_PREC_F32 || precision == PCG_PREC_BF16, "pcg_conv_precision_set: unknown precision %d (0 fp32, 1 bf16)", precision);
+  pcg::g_conv_prec = precision;
+  return PCG_OK;
+}
+extern "C" int32_t pcg_conv_precision_get(void) { return pcg::g_conv_prec; }

@@ -53,6 +53,8 @@ def weights_init(m):
 class Generator(SequentialConvNet):
     """mnist_dcgan.py:72-93."""
 
+    honours_conv_precision = True   # conv_precision = "bf16" (DESIGN.md §3.7)
+
     def __init__(self, cfg=None):
         c = _cfg(cfg)
         g, z, ch = c["g_hidden"], c["z_dim"], c["image_channel"]
@@ -67,6 +69,8 @@ class Generator(SequentialConvNet):
 
 class Discriminator(SequentialConvNet):
     """mnist_dcgan.py:96-116."""
+
+    honours_conv_precision = True   # conv_precision = "bf16" (DESIGN.md §3.7)
 
     def __init__(self, cfg=None):
         c = _cfg(cfg)

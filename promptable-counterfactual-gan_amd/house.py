@@ -24,7 +24,7 @@ from torch.nn.utils import spectral_norm
 from . import ops
 from ._lib import ACT_LRELU, ACT_NONE, ACT_RELU, PcgError, load as _lib_load
 from .countergan import CrossEntropyLoss, abs_mean, grad_norm  # noqa: F401  (same loss kernels)
-from .nn import FlatModule, affine_fwd, linear_dgrad as _lin_dgrad, linear_fwd as _lin_fwd, linear_wgrad as _lin_wgrad, mean, weighted_sum  # noqa: F401
+from .nn import FlatModule, affine_fwd, in_conv_precision, linear_dgrad as _lin_dgrad, linear_fwd as _lin_fwd, linear_wgrad as _lin_wgrad, mean, weighted_sum  # noqa: F401
 from .optim import Adam
 
 FEATURES = ["bedrooms", "bathrooms", "sqft_living", "sqft_lot", "floors", "waterfront", "view", "condition", "grade",
@@ -146,6 +146,7 @@ class ResidualGenerator(FlatModule):
         self._fdesc = (key, d)
         return d
 
+    @in_conv_precision
     def _fused_forward(self, x, target_onehot, mask, noise, tau, hard):
         import ctypes
         from ._lib import HouseGFwdArgs, load
@@ -175,6 +176,7 @@ class ResidualGenerator(FlatModule):
         saved = ("fused", buf, target_onehot, mask, tau, nb)
         return buf["cont"], buf["logits"], (buf["hard"] if hard else buf["soft"]), saved
 
+    @in_conv_precision
     def _fused_backward(self, saved, d_cont, d_logits, d_samples):
         import ctypes
         from ._lib import HouseGBwdArgs, load
@@ -283,6 +285,7 @@ class ResidualGenerator(FlatModule):
             return ops.bn_apply_act(z, C, mean, invstd, bn.weight.data, bn.bias.data, ACT_NONE), mean, invstd
         return ops.bn_apply_act(z, C, bn.running_mean, bn.running_var, bn.weight.data, bn.bias.data, ACT_NONE, var_eps=bn.eps), None, None
 
+    @in_conv_precision
     def _run_forward(self, x, target_onehot, mask, noise, tau, hard, keep=True):
         if keep and self._fused_ok():
             return self._fused_forward(x, target_onehot, mask, noise, tau, hard)
@@ -317,6 +320,7 @@ class ResidualGenerator(FlatModule):
         saved = (cond, inp, blocks, h, soft, seg, tau) if keep else None
         return cont, logits, (hard_y if hard else soft), saved
 
+    @in_conv_precision
     def _run_backward(self, saved, d_cont, d_logits, d_samples):
         if saved[0] == "fused":
             return self._fused_backward(saved, d_cont, d_logits, d_samples)
@@ -490,6 +494,7 @@ class Discriminator(FlatModule):
         return ops.spectral_norm_fwd_batched([l.weight_orig.data for l in lins], [l.weight_u for l in lins], [l.weight_v for l in lins],
                                              1e-12, self.training)
 
+    @in_conv_precision
     def _run_forward(self, x, target_onehot, keep=True, sn=None):
         lins = self._linears()
         if sn is None:
@@ -523,6 +528,7 @@ class Discriminator(FlatModule):
         lins = self._linears()
         return [l.weight_orig.data for l in lins], [l.weight_u for l in lins], [l.weight_v for l in lins], 1e-12
 
+    @in_conv_precision
     def _run_pair(self, x_a, onehot_a, cot_a, x_b, onehot_b, cot_b, sn=None, defer_sn_bwd=False):
         """The critic step's two passes as one: D(a) then D(b) — two successive power iterations, as two forward calls make them —
         and the backward of cot_b . D(b) followed by that of cot_a . D(a) into the gradient buffer (the order the chained calls
@@ -572,6 +578,7 @@ class Discriminator(FlatModule):
         ops.spectral_norm_bwd_batched_seq([seq_b, seq_a], dws, accs, bias_adds)
         return outs[0], outs[1]
 
+    @in_conv_precision
     def _fused_backward(self, saved, dout, need_x, need_p, gtarget=None):
         """gtarget: a flat buffer with the layout of flat_grads that receives this pass's parameter gradients (written, not
         accumulated) instead of the module's gradient buffer — see FlatModule.grad_view_in."""
@@ -602,6 +609,7 @@ class Discriminator(FlatModule):
             ops.spectral_norm_bwd_batched(sn_items)                                          # through W / sigma: one launch
         return dx
 
+    @in_conv_precision
     def _run_backward(self, layers, dout, need_x, need_p, gtarget=None):
         if layers[0] == "fused":
             return self._fused_backward(layers, dout, need_x, need_p, gtarget)
@@ -752,6 +760,7 @@ class NNClassifier(FlatModule):
     def _dropout_sites(self):
         return [(lin, p) for lin, _, p in self._stages()[0] if p is not None]
 
+    @in_conv_precision
     def _train_forward(self, x, masks):
         stages, last = self._stages()
         a = x.contiguous()
@@ -771,6 +780,7 @@ class NNClassifier(FlatModule):
         logits = _lin_fwd(last, a)
         return logits, (saved, last, a)
 
+    @in_conv_precision
     def _train_backward(self, saved_all, dlogits):
         saved, last, a_last = saved_all
         B = a_last.shape[0]
@@ -789,6 +799,7 @@ class NNClassifier(FlatModule):
             if idx > 0:
                 d = _lin_dgrad(lin.weight.data, d, B)
 
+    @in_conv_precision
     def _run_forward(self, x, keep=True, sn_bwd_rider=None, ce=None):
         """sn_bwd_rider: the argument list of a spectral-norm backward (ops.sn_bwd_seq_args) that rides in the fused forward launch
         (the scheduled tabular step: the critic's spectral-norm backward is independent of this classifier).  ce = (target, grad_scale)
@@ -826,6 +837,7 @@ class NNClassifier(FlatModule):
             a = z
         return a, (acts if keep else None)
 
+    @in_conv_precision
     def _run_backward(self, acts, dlogits, sn_fwd_rider=None):
         """sn_fwd_rider = (w_origs, us, vs, eps, reps): that training-mode spectral normalisation rides in the fused backward launch;
         the return value is then (dx, its outputs)."""

@@ -12,6 +12,7 @@ single RCCL call on the flat gradient bucket.  Backward accumulates straight int
 (`p.grad` are views of it), which is autograd's `.grad` accumulation contract without extra add kernels.
 """
 import contextlib
+import functools
 import os
 
 import torch
@@ -25,6 +26,18 @@ def _pad4(n):
     return (n + 3) // 4 * 4
 
 
+def in_conv_precision(fn):
+    """Method decorator: the net's forward / backward sweep runs inside its OWN `conv_precision` (ops.conv_precision).  The library's
+    setting is per thread and autograd runs a backward on a thread of its own, so every entry point of a sweep enters it — the
+    autograd Functions' forward and backward, eval paths, grouped passes, and the deferred weight gradients queued inside the sweep.
+    Nets that do not honour "bf16" (WGAN-GP, house, moons) decorate their sweeps too: they pin fp32 whatever the calling thread set."""
+    @functools.wraps(fn)
+    def run(self, *args, **kwargs):
+        with ops.conv_precision(self.conv_precision):
+            return fn(self, *args, **kwargs)
+    return run
+
+
 class FlatModule(nn.Module):
     """Keeps every parameter of the module tree as a view of one flat buffer (and .grad as views of another)."""
 
@@ -33,6 +46,23 @@ class FlatModule(nn.Module):
         self._flat = None
         self._gflat = None
         self._seg = None  # list of (param, offset, numel)
+
+    # -- operand precision of the matrix-core convolutions ----------------------------------------------------
+    honours_conv_precision = False   # nets with a bf16 mode set this; on any other net "bf16" is refused (and its sweeps pin fp32)
+
+    @property
+    def conv_precision(self):
+        """"fp32" (default) or "bf16": operand precision of this net's implicit-GEMM convolutions, forward and backward
+        (`netG.conv_precision = netD.conv_precision = "bf16"` before training).  Storage, epilogues, thin layers stay fp32."""
+        return self.__dict__.get("_conv_precision", "fp32")
+
+    @conv_precision.setter
+    def conv_precision(self, value):
+        if value not in ops.CONV_PRECISIONS:
+            raise ValueError(f"conv_precision: {value!r} is not one of {sorted(ops.CONV_PRECISIONS)}")
+        if value != "fp32" and not self.honours_conv_precision:
+            raise NotImplementedError(f"{type(self).__name__} has no {value} convolution mode (DESIGN.md §3.7: DCGAN and CounteRGAN nets only)")
+        self.__dict__["_conv_precision"] = value
 
     # -- layout ------------------------------------------------------------------------------------
     def _flatten(self, device=None):
@@ -378,6 +408,7 @@ class SequentialConvNet(FlatModule):
             return False
         return ops.bnin_full_ok(ops.conv_geom(B, H, W, nxt.conv.in_channels, 1, nxt.kh, nxt.kw, nxt.stride, nxt.pad), groups)
 
+    @in_conv_precision
     def _run_forward(self, x, keep=True):
         B, H, W, C = x.shape
         saved = []
@@ -506,6 +537,7 @@ class SequentialConvNet(FlatModule):
             y, _ = self._run_forward_groups(xs, keep=False)
         return y.permute(0, 3, 1, 2)
 
+    @in_conv_precision
     def _run_forward_groups(self, xs, keep=True):
         G = len(xs)
         B, H, W, C = xs[0].shape
@@ -551,6 +583,7 @@ class SequentialConvNet(FlatModule):
             a, H, W = (y if xf is None else z), g.OH, g.OW
         return a, (saved, G, B)
 
+    @in_conv_precision
     def _run_backward_groups(self, saved_all, dy):
         saved, G, B = saved_all
         if not dy.is_contiguous():
@@ -661,6 +694,7 @@ class SequentialConvNet(FlatModule):
             side = self.__dict__["_overlap_stream"] = torch.cuda.Stream()
         return _WgradDefer(side, torch.cuda.current_stream())
 
+    @in_conv_precision
     def _run_backward(self, saved, dy, need_x, need_p):
         if not dy.is_contiguous():
             dy = dy.contiguous()

@@ -467,6 +467,38 @@ def bn_bwd_partial(dm, x, C, mean, invstd, gamma, partial, nparts, dgamma, dbeta
     return dx
 
 
+# ---- operand precision of the matrix-core convolutions (pcg_conv_precision_*) -----------------------------------
+CONV_PRECISIONS = {"fp32": 0, "bf16": 1}
+
+
+class conv_precision:
+    """with ops.conv_precision("bf16"): ... — the implicit-GEMM convolutions launched by THIS thread inside the block round their two
+    GEMM operands to bf16 (RNE) and sum the products in fp32; tensors, workspaces and epilogues stay fp32, the thin edge layers and
+    every other kernel are unaffected.  The library's setting is thread-local (autograd runs a backward on its own thread: a net
+    enters its own precision there too, nn.FlatModule.conv_precision).  The exit restores the previous setting, also on an exception."""
+
+    def __init__(self, precision):
+        if precision not in CONV_PRECISIONS:
+            raise ValueError(f"conv_precision: {precision!r} is not one of {sorted(CONV_PRECISIONS)}")
+        self.value = CONV_PRECISIONS[precision]
+        self._prev = []               # a stack: the same object may be entered again while it is active (nested / recursive use)
+
+    def __enter__(self):
+        lib = _lib.load()
+        self._prev.append(lib.pcg_conv_precision_get())
+        check(lib.pcg_conv_precision_set(self.value), "pcg_conv_precision_set")
+        return self
+
+    def __exit__(self, et, ev, tb):
+        check(_lib.load().pcg_conv_precision_set(self._prev.pop()), "pcg_conv_precision_set")
+        return False
+
+
+def current_conv_precision():
+    """The calling thread's setting: "fp32" or "bf16"."""
+    return "bf16" if _lib.load().pcg_conv_precision_get() == 1 else "fp32"
+
+
 # ---- deferred slab reductions (pcg_slab_defer_*): one reduction launch per backward sweep instead of one per weight gradient -------
 _slab_defer = threading.local()      # per thread, like the library's record (autograd runs a net's backward on its own thread)
 _SLAB_SLOT0 = 16                      # scratch kinds 16, 17, ...: one slab buffer per deferred weight gradient of the sweep

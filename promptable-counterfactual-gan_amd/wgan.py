@@ -26,7 +26,7 @@ import torch.nn as nn
 
 from . import ops
 from ._lib import ACT_LRELU, PcgError
-from .nn import FlatModule, GraphedStep, SequentialConvNet, _compile, linear_dgrad, linear_fwd, linear_wgrad, mean, weighted_sum
+from .nn import FlatModule, GraphedStep, SequentialConvNet, _compile, in_conv_precision, linear_dgrad, linear_fwd, linear_wgrad, mean, weighted_sum
 from .optim import AdamW
 
 
@@ -89,6 +89,7 @@ class Generator(SequentialConvNet):
             return _GFn.apply(self, latent, condition, *self.parameters())
         return self._gen_forward(latent, condition, keep=False)[0]
 
+    @in_conv_precision
     def _gen_forward(self, latent, condition, keep):
         latent, condition = latent.contiguous(), condition.contiguous()
         B = latent.shape[0]
@@ -98,6 +99,7 @@ class Generator(SequentialConvNet):
         y, saved = SequentialConvNet._run_forward(self, seed, keep=keep)                # :77
         return y.permute(0, 3, 1, 2), ((latent, condition, saved) if keep else None)    # one channel: NHWC memory == NCHW memory
 
+    @in_conv_precision
     def _gen_backward(self, saved, dy, need_p):
         if not need_p:
             return
@@ -182,6 +184,7 @@ class Critic(FlatModule):
         return self._run_forward(image, condition, keep=False)[0]
 
     # -- forward ---------------------------------------------------------------------------------------------------------------
+    @in_conv_precision
     def _run_forward(self, image, condition, keep=True):
         B, _, H, W = image.shape
         a = image.contiguous().view(B, H, W, 1)                                          # one channel: NCHW memory == NHWC memory
@@ -205,6 +208,7 @@ class Critic(FlatModule):
         return out, saved
 
     # -- first-order backward (also the forward of _CriticGradFn when keep=True) ------------------------------------------------------
+    @in_conv_precision
     def _run_backward(self, saved, dout, need_x, need_p, keep=False):
         stages, condition, u, h, (HW, C) = saved
         B = u.shape[0]
@@ -260,6 +264,7 @@ class Critic(FlatModule):
             ops.colsum(dz.numel() // g.Cout, g.Cout, dz, gb, accb)
 
     # -- backward of the backward ---------------------------------------------------------------------------------------------------
+    @in_conv_precision
     def _run_double_backward(self, saved, first, r):
         """r: cotangent on dx = d(out)/d(image).  Accumulates d<r, dx>/d(parameters) into the flat gradient buffer."""
         stages, condition, u, h, (HW, C) = saved

@@ -3,6 +3,8 @@
 
   python scripts/conv_microbench.py [--batch 512] [--iters 20] [--only fwd,dgrad,wgrad] [--layers D2,D3,...]
 Prints one line per (layer, op): average ms over `iters` launches (HIP events on the launch stream) and TFLOP/s.
+  --precision bf16                the bf16-operand mode instead of fp32
+  --ab precision=fp32,bf16        both modes in this process, interleaved rounds (random operands: the bf16 MFMA clock depends on the data)
 """
 import argparse
 import os
@@ -42,12 +44,14 @@ def main():
     ap.add_argument("--ab", default=None, help="A/B a tuning switch in THIS process, interleaved rounds: e.g. korder=0,1 or wgrad_order=0,1 "
                                                "(ops.tune / pcg_tune_set); prints the median and min ms per variant")
     ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--precision", default="fp32", choices=sorted(ops.CONV_PRECISIONS), help="operand precision of the MFMA convolutions")
     ap.add_argument("--timeline", type=int, default=0, help="with --clock: print the per-tile timeline (loop end / epilogue end, us since the "
                                                             "stream began) of this many workgroups of the persistent kernels")
     ap.add_argument("--clock", action="store_true", help="report the in-kernel clock (needs the stamp build: make -C csrc stamp; "
                                                          "PCG_LIB=.../csrc/build_stamp/libpcgan_hip.so)")
     args = ap.parse_args()
     lib = pcgan_amd.load()
+    lib.pcg_conv_precision_set(ops.CONV_PRECISIONS[args.precision])      # this thread's launches below
     dev = torch.device("cuda:0")
     stamps = None
     if args.clock:
@@ -126,16 +130,22 @@ def main():
             fn = fns[op]
             if args.ab:
                 key, vals = args.ab.split("=")
-                vals = [int(v) for v in vals.split(",")]
+                vals = [v if key == "precision" else int(v) for v in vals.split(",")]
+
+                def tune(key, v):        # precision: the calling thread's mode (pcg_conv_precision_set); else a pcg_tune_set switch
+                    if key == "precision":
+                        lib.pcg_conv_precision_set(ops.CONV_PRECISIONS[args.precision if v == -1 else v])
+                    else:
+                        ops.tune(key, v)
                 res = {v: [] for v in vals}
                 clk = {}
                 for v in vals:
-                    ops.tune(key, v)
+                    tune(key, v)
                     for _ in range(2):
                         fn()
                 for _ in range(args.rounds):
                     for v in vals:
-                        ops.tune(key, v)
+                        tune(key, v)
                         fn()
                         torch.cuda.synchronize()
                         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -147,7 +157,7 @@ def main():
                         res[v].append(e0.elapsed_time(e1) / args.iters)
                         if stamps is not None:
                             clk.setdefault(v, []).append(clock_mhz())
-                ops.tune(key, -1)
+                tune(key, -1)
                 line = f"{name:4s} {op:6s} B={B} {Cin:4d}->{Cout:4d} {H:3d}x{H:<3d} k{k}s{s}p{p} "
                 for v in vals:
                     r = sorted(res[v])

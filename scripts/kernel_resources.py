@@ -2,7 +2,8 @@
 """Register / scratch / LDS use of every kernel of a .hip source, from the code object metadata hipcc emits for gfx950 (no GPU
 needed):  python scripts/kernel_resources.py promptable-counterfactual-gan_amd/csrc/conv_igemm.hip [more.hip ...]
 Prints vgpr / agpr / sgpr counts, spilled VGPRs, scratch bytes (private_segment_fixed_size) and static LDS per kernel — the
-numbers VERDICT r02 asked to be zero for the conv_* kernels (spills)."""
+numbers VERDICT r02 asked to be zero for the conv_* kernels (spills).  The bf16-operand twins print as ",bf16" beside
+their fp32 configurations."""
 import os
 import re
 import subprocess
@@ -37,7 +38,8 @@ def main():
         print(f"# {src}")
         for nm, r in zip(names, rows):
             nm = re.sub(r"pcg::\(anonymous namespace\)::", "", nm)
-            nm = re.sub(r"pcg::TileCfg<(\d+), (\d+), \d+, \d+, (\w+), (\d+), (\d+)>", r"T<\1x\2,swz=\3,w\4,pf\5>", nm)
+            nm = re.sub(r"pcg::TileCfg<(\d+), (\d+), \d+, \d+, (\w+), (\d+), (\d+), (\w+), true>", r"T<\1x\2,swz=\3,w\4,pf\5,bf16>", nm)   # bf16 twins
+            nm = re.sub(r"pcg::TileCfg<(\d+), (\d+), \d+, \d+, (\w+), (\d+), (\d+)(?:, (\w+), false)?>", r"T<\1x\2,swz=\3,w\4,pf\5>", nm)
             print(f"{nm[:120]:120s} vgpr {r[1]:3d} agpr {r[2]:3d} sgpr {r[3]:3d} spill {r[4]:3d} scratch {r[5]:4d} lds {r[6]}")
 
 

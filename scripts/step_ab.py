@@ -7,6 +7,7 @@
   python scripts/step_ab.py --model dcgan --ab fullbn=0,1        (SequentialConvNet.fuse_full_window_bn)
   python scripts/step_ab.py --model dcgan --ab slabdefer=0,1     (SequentialConvNet.defer_slab_reductions)
   python scripts/step_ab.py --model dcgan --ab foldthin=0,1      (SequentialConvNet.fold_bn_apply_thin)
+  python scripts/step_ab.py --model dcgan --ab precision=fp32,bf16   (FlatModule.conv_precision of the trained nets)
 
 Per variant the step is captured as its own HIP graph (kernel arguments, tuning included, are baked in at capture), then the graphs
 are replayed in alternating rounds; prints min / median ms per step of every variant.  Boxes differ by up to 20 % and drift within a
@@ -28,6 +29,7 @@ def build_dcgan(dev, batch, variant):
     torch.manual_seed(1)
     netG, netD = D.build(None, device="cpu")
     netG.to(dev); netD.to(dev)
+    netG.conv_precision = netD.conv_precision = variant.get("precision", "fp32")
     crit, optD, optG = D.make_optimizers(netG, netD)
     g = torch.Generator().manual_seed(1234)
     real = (torch.rand(batch, 1, 64, 64, generator=g) * 2 - 1).to(dev)
@@ -43,6 +45,7 @@ def build_countergan(dev, batch, variant):
     C.eval()
     for p in C.parameters():
         p.requires_grad = False
+    G.conv_precision = Dn.conv_precision = variant.get("precision", "fp32")
     opt_g, opt_d, bce, ce = K.make_optimizers(G, Dn)
     rng = ops.DeviceRNG(seed=1234)
     cfg = K.Config
@@ -63,13 +66,15 @@ def main():
     pcgan_amd.load()
     dev = torch.device("cuda:0")
     key, vals = a.ab.split("=")
-    vals = [int(v) for v in vals.split(",")]
+    vals = [v if key == "precision" else int(v) for v in vals.split(",")]
     batch = a.batch or (512 if a.model == "dcgan" else 1024)
     graphs = {}
     for v in vals:
         variant = {}
         if key == "pair":
             variant["kwargs"] = {"pair": bool(v)}
+        elif key == "precision":         # the nets' conv_precision (random data: the bf16 MFMA clock depends on it)
+            variant["precision"] = v
         elif key == "overlap":           # nn.SequentialConvNet.wgrad_overlap (class switch: baked into the graph at capture)
             from pcgan_amd.nn import SequentialConvNet
             SequentialConvNet.wgrad_overlap = "bn" if v else None
@@ -97,7 +102,7 @@ def main():
         elif key == "foldthin":
             from pcgan_amd.nn import SequentialConvNet
             SequentialConvNet.fold_bn_apply_thin = True
-        elif key != "pair":
+        elif key not in ("pair", "precision"):
             ops.tune(key, -1)
     res = {v: [] for v in vals}
     for v in vals:
