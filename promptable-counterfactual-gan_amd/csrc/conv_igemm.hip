@@ -53,12 +53,10 @@ __global__ void __launch_bounds__(IG_THREADS, Cfg::MINW) conv_fwd_kernel(ConvP p
 
   if (wave_id() >= 4) {  // producers
     const int tid = threadIdx.x - IG_LOADERS;
-    constexpr bool DMA = Cfg::DMA && !XF;
-    FwdALoader<Cfg::BM, XF> la(p, m_block, tid, DMA);
-    FwdBLoader<Cfg::BN> lb(p, n_block, tid, DMA);
+    FwdALoader<Cfg::BM, XF> la(p, m_block, tid);
+    FwdBLoader<Cfg::BN> lb(p, n_block, tid);
     if (kt_begin) { la.seek(kt_begin); lb.seek(kt_begin); }
-    if constexpr (DMA) igemm_produce_dma<Cfg>(la, lb, ktiles, smem, tid, ClockStamp{p.stamps, p.stamp_slots});
-    else igemm_produce<Cfg>(la, lb, ktiles, smem, tid, ClockStamp{p.stamps, p.stamp_slots});
+    igemm_produce<Cfg>(la, lb, ktiles, smem, tid, ClockStamp{p.stamps, p.stamp_slots});
     return;
   }
   f32x16 acc[Cfg::TM][Cfg::TN];
@@ -494,158 +492,6 @@ __global__ void __launch_bounds__(IG_THREADS, 4) conv_wgrad_sk_kernel(ConvP p, S
   wgrad_sk_segment<Cfg, XFA, XFB>(p, sk, s1, smem);
 }
 
-
-#ifdef PCG_PERSISTENT_KERNELS   // experiment kept out of the shipped library (measured slower: igemm_core.h); `make lean`
-// ---- persistent, tile-pipelined forms (igemm_core.h: igemm_produce_stream / igemm_consume_stream / igemm_store_regs) -------------
-// Work item of the forward launch: (output tile, K-slice); item = slice * tiles + tile.
-template <class Cfg, bool XF>
-struct FwdSrc {
-  using LA = FwdALoader<Cfg::BM, XF>;
-  using LB = FwdBLoader<Cfg::BN>;
-  const ConvP& p; TileWalk walk; uint32_t i, tiles; int tid;
-  LA la; LB lb; int n;
-  __device__ __forceinline__ void decode(uint32_t item, int& m_block, int& n_block, int& kt_begin, int& kt) const {
-    const uint32_t split = item / tiles, tile = item - split * tiles;
-    m_block = (int)(tile / (uint32_t)p.tilesN) * Cfg::BM; n_block = (int)(tile % (uint32_t)p.tilesN) * Cfg::BN;
-    kt_begin = (int)split * p.ktiles_per_split;
-    kt = p.ktiles - kt_begin;
-    if (kt > p.ktiles_per_split) kt = p.ktiles_per_split;
-  }
-  __device__ __forceinline__ FwdSrc(const ConvP& p_, const TileWalk& w, uint32_t tiles_, int tid_, int m0, int n0, int kb0, int kt0)
-      : p(p_), walk(w), i(0), tiles(tiles_), tid(tid_), la(p_, m0, tid_), lb(p_, n0, tid_), n(kt0) {
-    if (kb0) { la.seek(kb0); lb.seek(kb0); }
-  }
-  __device__ __forceinline__ void next_tile() {
-    int m_block, n_block, kb;
-    decode(walk.item(++i), m_block, n_block, kb, n);
-    la = LA(p, m_block, tid); lb = LB(p, n_block, tid);
-    if (kb) { la.seek(kb); lb.seek(kb); }
-  }
-};
-
-template <class Cfg, bool XF>
-__global__ void __launch_bounds__(IG_THREADS, Cfg::MINW) conv_fwd_pkernel(ConvP p, int splits) {
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  const uint32_t tiles = (uint32_t)((p.M + Cfg::BM - 1) / Cfg::BM) * (uint32_t)p.tilesN;
-  const TileWalk walk(tiles * (uint32_t)splits);
-  const int nt = (int)walk.ntiles();
-  if (nt == 0) return;                           // workgroup-uniform
-  auto item_ktiles = [&](uint32_t item) {
-    const int kb = (int)(item / tiles) * p.ktiles_per_split;
-    const int kt = p.ktiles - kb;
-    return kt > p.ktiles_per_split ? p.ktiles_per_split : kt;
-  };
-  int S = 0;
-  for (int t = 0; t < nt; ++t) S += item_ktiles(walk.item(t));
-  if (wave_id() >= 4) {
-    const int tid = threadIdx.x - IG_LOADERS;
-    const uint32_t it0 = walk.item(0), sp0 = it0 / tiles, tl0 = it0 - sp0 * tiles;
-    FwdSrc<Cfg, XF> src(p, walk, tiles, tid, (int)(tl0 / (uint32_t)p.tilesN) * Cfg::BM, (int)(tl0 % (uint32_t)p.tilesN) * Cfg::BN,
-                        (int)sp0 * p.ktiles_per_split, item_ktiles(it0));
-    igemm_produce_stream<Cfg>(src, S, smem, tid);
-    return;
-  }
-  const uint32_t slab_bytes = (uint32_t)((size_t)p.M * p.N * 4);
-  igemm_consume_stream<Cfg, true, true>(nt, [&](int t) { return item_ktiles(walk.item(t)); },
-    [&](int t, f32x16 (&acc)[Cfg::TM][Cfg::TN]) {
-      const uint32_t item = walk.item(t), split = item / tiles, tile = item - split * tiles;
-      const int mt = (int)(tile / (uint32_t)p.tilesN), m_block = mt * Cfg::BM, n_block = (int)(tile % (uint32_t)p.tilesN) * Cfg::BN;
-      float* out = p.out + (size_t)split * (size_t)p.M * (size_t)p.N;
-      const EpiBufs eb = make_epi_bufs(out, slab_bytes, p.epi);
-      RowsAffine rows{p.M, m_block, (uint32_t)p.N * 4u, (uint32_t)n_block * 4u, 0u, 0};
-      igemm_store_regs<Cfg>(acc, n_block, p.N, split == 0 ? p.bias : nullptr, rows, eb,
-                            p.stat_partial ? p.stat_partial + (size_t)mt * Cfg::WAVES_M * 2 * p.N : nullptr, p.act, p.slope, &p.epi);
-    }, smem, ClockStamp{p.stamps, p.stamp_slots});
-}
-
-// Work item of the grad-input launch: (sub-pixel phase, tile of the phase's pixel grid).  Phases of equal size are interleaved (the
-// phases of one pixel tile are neighbours: they gather the same dy rows); otherwise the phases' tile ranges follow each other.
-struct DgradItems {
-  int nph, interleave, cnt[4];       // cnt[p] = tiles of phase p (tilesM_p * tilesN)
-  uint32_t total;
-  __device__ __forceinline__ void decode(uint32_t item, int& py, uint32_t& tile) const {
-    if (interleave) { py = (int)(item % (uint32_t)nph); tile = item / (uint32_t)nph; return; }
-    py = 0;
-    while (py + 1 < nph && item >= (uint32_t)cnt[py]) { item -= (uint32_t)cnt[py]; ++py; }
-    tile = item;
-  }
-};
-
-template <class Cfg, bool XF>
-struct DgradSrc {
-  using LA = DgradALoader<Cfg::BM, XF>;
-  using LB = DgradBLoader<Cfg::BN>;
-  const ConvP& p; const DgradPhases& ph; const DgradItems& items; TileWalk walk; uint32_t i; int tid; uint32_t (*rowpix)[Cfg::BM];
-  LA la; LB lb; int n;
-  __device__ __forceinline__ static int ktiles_of(const ConvP& p, const PhaseInfo& f) { return f.nth * f.ntw * ((p.Cout + IG_BK - 1) / IG_BK); }
-  __device__ __forceinline__ void publish_rows(const PhaseInfo& f, int m_block, uint32_t seq) {   // byte offset of every tile row's output pixel
-    for (int r = tid; r < Cfg::BM; r += IG_LOADERS) {
-      const int m = m_block + r;
-      uint32_t off = OOB_OFF;
-      if (m < f.Mp) {
-        uint32_t t, cc, b, aa;
-        f.dPHw.divmod((uint32_t)m, t, cc);
-        f.dPHh.divmod(t, b, aa);
-        const int pix = ((int)b * p.IH + (int)aa * p.stride + f.ph) * p.IW + (int)cc * p.stride + f.pw;
-        off = (uint32_t)pix * (uint32_t)p.Cin * 4u;
-      }
-      rowpix[seq & 3u][r] = off;
-    }
-  }
-  __device__ __forceinline__ DgradSrc(const ConvP& p_, const DgradPhases& ph_, const DgradItems& it_, const TileWalk& w, int tid_,
-                                      uint32_t (*rowpix_)[Cfg::BM], const PhaseInfo& f0, int m0, int n0)
-      : p(p_), ph(ph_), items(it_), walk(w), i(0), tid(tid_), rowpix(rowpix_), la(p_, f0, m0, tid_), lb(p_, f0, n0, tid_), n(ktiles_of(p_, f0)) {
-    publish_rows(f0, m0, 0);
-  }
-  __device__ __forceinline__ void next_tile() {
-    int py; uint32_t tile;
-    items.decode(walk.item(++i), py, tile);
-    const PhaseInfo& f = ph.p[py];
-    const int m_block = (int)(tile / (uint32_t)p.tilesN) * Cfg::BM, n_block = (int)(tile % (uint32_t)p.tilesN) * Cfg::BN;
-    la = LA(p, f, m_block, tid); lb = LB(p, f, n_block, tid);
-    n = ktiles_of(p, f);
-    publish_rows(f, m_block, i);     // slot i & 3: the consumers are at most three tiles behind (the producers lead by <= 3 k-tiles)
-  }
-};
-
-template <class Cfg, bool XF>
-__global__ void __launch_bounds__(IG_THREADS, Cfg::MINW) conv_dgrad_pkernel(ConvP p, DgradPhases phases, DgradItems items) {
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  __shared__ uint32_t rowpix[4][Cfg::BM];
-  const TileWalk walk(items.total);
-  const int nt = (int)walk.ntiles();
-  if (nt == 0) return;
-  auto item_ktiles = [&](uint32_t item) {
-    int py; uint32_t tile;
-    items.decode(item, py, tile);
-    return DgradSrc<Cfg, XF>::ktiles_of(p, phases.p[py]);
-  };
-  int S = 0;
-  for (int t = 0; t < nt; ++t) S += item_ktiles(walk.item(t));
-  if (wave_id() >= 4) {
-    const int tid = threadIdx.x - IG_LOADERS;
-    int py; uint32_t tile;
-    items.decode(walk.item(0), py, tile);
-    DgradSrc<Cfg, XF> src(p, phases, items, walk, tid, rowpix, phases.p[py], (int)(tile / (uint32_t)p.tilesN) * Cfg::BM,
-                          (int)(tile % (uint32_t)p.tilesN) * Cfg::BN);
-    igemm_produce_stream<Cfg>(src, S, smem, tid);
-    return;
-  }
-  const EpiBufs eb = make_epi_bufs(p.out, p.x_bytes, p.epi);
-  igemm_consume_stream<Cfg, true, false>(nt, [&](int t) { return item_ktiles(walk.item(t)); },
-    [&](int t, f32x16 (&acc)[Cfg::TM][Cfg::TN]) {
-      int py; uint32_t tile;
-      items.decode(walk.item(t), py, tile);
-      const PhaseInfo& f = phases.p[py];
-      const int mt = (int)(tile / (uint32_t)p.tilesN), n_block = (int)(tile % (uint32_t)p.tilesN) * Cfg::BN;
-      RowsTable rows{rowpix[(uint32_t)t & 3u], (uint32_t)n_block * 4u, nullptr, 0u};
-      igemm_store_regs<Cfg>(acc, n_block, p.N, p.bias, rows, eb,
-                            p.stat_partial ? p.stat_partial + (size_t)(f.prow0 + mt * Cfg::WAVES_M) * 2 * p.N : nullptr, p.act, p.slope, &p.epi);
-    }, smem, ClockStamp{p.stamps, p.stamp_slots});
-}
-
-#endif  // PCG_PERSISTENT_KERNELS
-
 // 64x192 tile of the weight gradient (Cout <= 64, N = KH*KW*Cin a multiple of 192): the same pipeline with the 192-column B loader
 using Cfg64x192 = TileCfg<64, 192, 2, 2>;
 template <class Cfg>
@@ -720,7 +566,6 @@ __global__ void __launch_bounds__(256) col2im_kernel(const float4* __restrict__ 
 // host side
 // ------------------------------------------------------------------------------------------------
 using Cfg128x128 = TileCfg<128, 128, 2, 2>;
-using Cfg128x128D = TileCfg<128, 128, 2, 2, true, 4, PCG_PREFETCH_DEPTH, true>;   // operands by LDS-DMA into unpadded swizzled images
 #ifndef PCG_TILE64_SWZ
 #define PCG_TILE64_SWZ 1     // 128x64 tiles: swizzled unpadded LDS images, three workgroups per CU (0: the r01 layout, two per CU)
 #endif
@@ -732,10 +577,9 @@ using Cfg128x64 = Cfg128x64P;                              // 9 % (105.7 -> 96.6
 #endif
 
 // The bf16-operand twin of a tile configuration (pcg_conv_precision_set): same tile, prefetch depth and launch bounds,
-// so the same plans, grids and workspace.  Its LDS images are its own (igemm_core.h), so SWZ does not apply, and it has no LDS-DMA form:
-// the `dma` switch (and the persistent experiment of `make lean`) are fp32-only and ignored in bf16 mode.
+// so the same plans, grids and workspace.  Its LDS images are its own (igemm_core.h), so SWZ does not apply.
 template <class C>
-using Bf16Twin = TileCfg<C::BM, C::BN, C::WAVES_M, C::WAVES_N, false, C::MINW, C::PF, false, true>;
+using Bf16Twin = TileCfg<C::BM, C::BN, C::WAVES_M, C::WAVES_N, false, C::MINW, C::PF, true>;
 
 // (r04: 192x64 tiles — four consumer waves of 96x32, two workgroups per CU, 1.5x the MFMAs per workgroup — were built and measured:
 //  bit-identical results, no gain: 3x3 64->64 forward 0.4867 -> 0.4943 ms, its grad-input 0.4969 -> 0.5227, D2's k4 s2 grad-input
@@ -756,7 +600,7 @@ int check_geom(const pcg_conv_geom* g) {
 }
 
 // Tuning switches for A/B measurements in ONE process (pcg_tune_set; scripts/conv_microbench.py --ab): -1 = the built-in choice.
-struct Tune { int edge_prio = -1, dgrad_swz3 = -1, wgrad_rounds = -1, korder = -1, wgrad_order = -1, dgrad_interleave = -1, persistent = -1, persist_tiles = -1, fwd_splits = -1, dma = -1, stream_k = -1, sk_blocks = -1, dgrad_gemm = -1, t64 = -1; unsigned long long* stamps = nullptr; int stamp_slots = 0; };
+struct Tune { int edge_prio = -1, dgrad_swz3 = -1, wgrad_rounds = -1, korder = -1, wgrad_order = -1, dgrad_interleave = -1, fwd_splits = -1, stream_k = -1, sk_blocks = -1, dgrad_gemm = -1, t64 = -1; unsigned long long* stamps = nullptr; int stamp_slots = 0; };
 Tune g_tune;
 
 ConvP make_params(const pcg_conv_geom* g) {
@@ -803,37 +647,6 @@ int set_smem(K kernel, size_t bytes) {
   if (e != hipSuccess) { set_error("hipFuncSetAttribute(max dynamic LDS=%zu): %s", bytes, hipGetErrorString(e)); return PCG_ERR_LAUNCH; }
   return PCG_OK;
 }
-
-// persistent launches: workgroups resident per CU (what the LDS and register budgets of the tile configuration admit) x CUs
-int cu_count() {
-  static const int cus = [] {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return 256;
-    return prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-  }();
-  return cus;
-}
-template <class Cfg>
-unsigned persistent_grid(uint64_t items) {
-  const unsigned slots = (unsigned)cu_count() * (Cfg::MINW >= 6 ? 3u : 2u);
-  unsigned g = items < slots ? (unsigned)items : slots;
-  // persist_tiles = T > 0: T tiles per workgroup instead of all-resident workgroups — more workgroups than slots, dispatched in
-  // rounds, so they desynchronise like the one-tile kernels while a workgroup's second .. T-th prologue is pipelined away
-  if (g_tune.persist_tiles > 0) g = (unsigned)((items + g_tune.persist_tiles - 1) / g_tune.persist_tiles);
-  if (g >= 8) g &= ~7u;                          // TileWalk: a multiple of 8 keeps the per-XCD runs
-  return g ? g : 1u;
-}
-bool use_persistent() {
-#ifdef PCG_PERSISTENT_KERNELS
-  static const int env = getenv("PCG_PERSISTENT") ? atoi(getenv("PCG_PERSISTENT")) : 0;
-  return (g_tune.persistent >= 0 ? g_tune.persistent : env) != 0;
-#else
-  return false;
-#endif
-}
-template <class Cfg, bool AK, bool BK_>
-constexpr size_t stage_smem_bytes() { return sizeof(float) * (size_t)igemm_smem_floats<Cfg, AK, BK_>(); }
 
 // ---- stream-K scratch: caller-owned, registered per stream (pcg_conv_set_scratch) --------------------------------------
 constexpr int SK_MAX_BLOCKS = 512, SK_MAX_TILES = 4096;
@@ -907,20 +720,8 @@ template <class Cfg, bool XF>
 int launch_fwd_x(ConvP p, int splits, hipStream_t s) {
   p.tilesN = ceil_div(p.N, Cfg::BN);
   const int tilesM = ceil_div(p.M, Cfg::BM);
-#ifdef PCG_PERSISTENT_KERNELS
-  if constexpr (!Cfg::BF16) {      // the persistent experiment is fp32-only: a bf16 twin takes the launches below
-  if (use_persistent()) {
-    constexpr size_t smem = stage_smem_bytes<Cfg, true, true>();
-    static int once = set_smem(conv_fwd_pkernel<Cfg, XF>, smem);
-    if (once != PCG_OK) return once;
-    const uint64_t items = (uint64_t)tilesM * p.tilesN * splits;
-    hipLaunchKernelGGL((conv_fwd_pkernel<Cfg, XF>), dim3(persistent_grid<Cfg>(items)), dim3(IG_THREADS), smem, s, p, splits);
-    return launch_status("conv_fwd_pkernel");
-  }
-  }
-#endif
   constexpr size_t smem = smem_bytes<Cfg, true, true>();
-  if constexpr (Cfg::BM == 128 && Cfg::BN == 128 && !Cfg::DMA) {
+  if constexpr (Cfg::BM == 128 && Cfg::BN == 128) {
     SkPlan sk{};
     if (splits == 1 && plan_sk(tilesM * p.tilesN, p.ktiles, s, &sk)) {
       static int once_sk = set_smem(conv_fwd_sk_kernel<Cfg, XF>, smem);
@@ -1007,29 +808,6 @@ template <class Cfg, bool XF>
 int launch_dgrad_x(ConvP p, const DgradPhases& ph, int nphases, int maxMp, hipStream_t s) {
   p.tilesN = ceil_div(p.N, Cfg::BN);
   const int tilesM = ceil_div(maxMp, Cfg::BM);
-#ifdef PCG_PERSISTENT_KERNELS
-  if constexpr (!Cfg::BF16) {      // (fp32-only, as in launch_fwd_x)
-  bool all_have_taps = true;
-  for (int i = 0; i < nphases; ++i) all_have_taps = all_have_taps && ph.p[i].nth > 0;
-  if (use_persistent() && all_have_taps) {
-    constexpr size_t smem = stage_smem_bytes<Cfg, true, false>();
-    static int once = set_smem(conv_dgrad_pkernel<Cfg, XF>, smem);
-    if (once != PCG_OK) return once;
-    static const int il_env0 = getenv("PCG_DGRAD_INTERLEAVE") ? atoi(getenv("PCG_DGRAD_INTERLEAVE")) : 1;
-    const int il_env = g_tune.dgrad_interleave >= 0 ? g_tune.dgrad_interleave : il_env0;
-    DgradItems it{};
-    it.nph = nphases;
-    bool same = nphases > 1 && il_env && p.w_bytes <= (1u << 20);
-    for (int i = 1; i < nphases; ++i) same = same && ph.p[i].Mp == ph.p[0].Mp;
-    it.interleave = same ? 1 : 0;
-    uint64_t total = 0;
-    for (int i = 0; i < nphases; ++i) { it.cnt[i] = ceil_div(ph.p[i].Mp, Cfg::BM) * p.tilesN; total += (uint64_t)it.cnt[i]; }
-    it.total = (uint32_t)total;
-    hipLaunchKernelGGL((conv_dgrad_pkernel<Cfg, XF>), dim3(persistent_grid<Cfg>(total)), dim3(IG_THREADS), smem, s, p, ph, it);
-    return launch_status("conv_dgrad_pkernel");
-  }
-  }
-#endif
   constexpr size_t smem = smem_bytes<Cfg, true, false>();
   if constexpr (Cfg::BM == 128 && Cfg::BN == 128) {
     bool uniform = true;
@@ -1269,8 +1047,6 @@ static int conv2d_fwd_impl(const pcg_conv_geom* g, const float* x, const float* 
   const bool fuse = act_is_cheap(act) && f.splits == 1;   // the epilogue fuses ReLU / LeakyReLU; tanh / sigmoid run as a second pass
   p.act = fuse ? act : PCG_ACT_NONE; p.slope = act_neg_of(p.act, slope);
   if (f.splits > 1) { p.out = (float*)workspace; p.ktiles_per_split = f.ktiles_per_split; }
-  static const int dma_env = getenv("PCG_DMA") ? atoi(getenv("PCG_DMA")) : 0;
-  const bool dma = (g_tune.dma >= 0 ? g_tune.dma : dma_env) != 0 && !p.in_sc;
   // At most one 128x128 tile per CU (DCGAN D4: 8192 x 512 = 256 tiles): a workgroup alone on a CU runs at ~80 % of the matrix rate
   // (one consumer wave per SIMD exposes its own latencies).  64x128 tiles double the workgroups — two per CU again — at the price
   // of 64x32 wave tiles: measured r03, D4 forward 262 -> 249 us (131 -> 138 TFLOP/s), G2's 260 -> 249; stream-K on the 256 big
@@ -1278,7 +1054,7 @@ static int conv2d_fwd_impl(const pcg_conv_geom* g, const float* x, const float* 
   // Only where the doubled count fills the 512 slots (225..256 big tiles); fewer tiles take stream-K / K-slices as before.
   const bool t64 = fwd_use_t64(p.M, p.N, f.splits);
   if (int e = t64 ? launch_fwd<TileCfg<64, 128, 1, 4>>(p, f.splits, s)
-                  : p.N > 64 ? (dma ? launch_fwd<Cfg128x128D>(p, f.splits, s) : launch_fwd<Cfg128x128>(p, f.splits, s))
+                  : p.N > 64 ? launch_fwd<Cfg128x128>(p, f.splits, s)
                        : launch_fwd<Cfg128x64>(p, f.splits, s)) return e;
   if (f.splits > 1) {
     const size_t n = (size_t)p.M * p.N;
@@ -1944,17 +1720,14 @@ extern "C" int pcg_tune_set(const char* name, int32_t value) {
   else if (!strcmp(name, "wgrad_rounds")) g_tune.wgrad_rounds = value;  // A/B: K-slices of the weight gradient sized for this many rounds of 512 workgroups      // A/B: multi-phase N <= 64 grad-inputs on the three-per-CU tile configuration
   else if (!strcmp(name, "wgrad_order")) g_tune.wgrad_order = value;
   else if (!strcmp(name, "dgrad_interleave")) g_tune.dgrad_interleave = value;
-  else if (!strcmp(name, "persistent")) g_tune.persistent = value;
-  else if (!strcmp(name, "persist_tiles")) g_tune.persist_tiles = value;
   else if (!strcmp(name, "fwd_splits")) g_tune.fwd_splits = value;
   else if (!strcmp(name, "stream_k")) g_tune.stream_k = value;
   else if (!strcmp(name, "sk_blocks")) g_tune.sk_blocks = value;
   else if (!strcmp(name, "dgrad_gemm")) g_tune.dgrad_gemm = value;
   else if (!strcmp(name, "t64")) g_tune.t64 = value;
-  else if (!strcmp(name, "dma")) g_tune.dma = value;
   else {
-    set_error("pcg_tune_set: unknown switch '%s' (korder, edge_prio, dgrad_swz3, wgrad_rounds, wgrad_order, dgrad_interleave, persistent, persist_tiles, fwd_splits, "
-              "stream_k, sk_blocks, dgrad_gemm, t64, dma)", name);
+    set_error("pcg_tune_set: unknown switch '%s' (korder, edge_prio, dgrad_swz3, wgrad_rounds, wgrad_order, dgrad_interleave, fwd_splits, "
+              "stream_k, sk_blocks, dgrad_gemm, t64)", name);
     return PCG_ERR_INVALID;
   }
   return PCG_OK;

@@ -164,15 +164,12 @@ struct FwdALoader {
   FwdKIter it;
   XfK xf;
 
-  // src_swz: LDS-DMA staging (igemm_produce_dma) — the destination of a lane is fixed (base + lane * 16), so the XOR swizzle of the
-  // unpadded K-major image is applied on the SOURCE side: the lane at chunk position tid & 7 of row r fetches the logical chunk
-  // (tid & 7) ^ ((r >> 1) & 7), the same involution LdsImage<.., SWZ>::frag applies on the read side
-  __device__ __forceinline__ FwdALoader(const ConvP& p, int m_block, int tid, bool src_swz = false) {
+  __device__ __forceinline__ FwdALoader(const ConvP& p, int m_block, int tid) {
     if constexpr (XF) xf.init(p);
     rs = make_rsrc(p.x, p.x_bytes);
     IW = p.IW; Cin = p.Cin; KW = p.KW;
     it.init(p);
-    kq4 = (src_swz ? ((tid & 7) ^ ((tid >> 4) & 7)) : (tid & 7)) * 4;
+    kq4 = (tid & 7) * 4;
     const int r0 = tid >> 3;
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
@@ -191,16 +188,6 @@ struct FwdALoader {
   }
   // start at k-tile kt (split-K)
   __device__ __forceinline__ void seek(int kt) { it.seek(kt); }
-  // byte offsets of the next k-tile's NV gathers (OOB_OFF where the hardware is to deliver zeros); advances to the following k-tile
-  __device__ __forceinline__ void next_offsets(uint32_t (&off)[NV]) {
-    const int kh = it.kh(), kw = it.kw(), ci0 = it.ci0;
-    const int tap = kh * KW + kw;
-    const uint32_t delta = (uint32_t)(((kh * IW + kw) * Cin + ci0) * 4);
-    const bool kok = kq4 < Cin - ci0;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) off[i] = (kok && ((mask[i] >> tap) & 1u)) ? base[i] + delta : OOB_OFF;
-    it.advance();
-  }
   __device__ __forceinline__ void load_next(float4 (&v)[NV]) {
     const int kh = it.kh(), kw = it.kw(), ci0 = it.ci0;
     const int tap = kh * KW + kw;
@@ -234,9 +221,9 @@ struct FwdBLoader {
   int Cin, KW, kq4;
   FwdKIter it;
 
-  __device__ __forceinline__ FwdBLoader(const ConvP& p, int n_block, int tid, bool src_swz = false) {
+  __device__ __forceinline__ FwdBLoader(const ConvP& p, int n_block, int tid) {
     rs = make_rsrc(p.w, p.w_bytes);
-    Cin = p.Cin; KW = p.KW; kq4 = (src_swz ? ((tid & 7) ^ ((tid >> 4) & 7)) : (tid & 7)) * 4;
+    Cin = p.Cin; KW = p.KW; kq4 = (tid & 7) * 4;
     it.init(p);
     const int r0 = tid >> 3;
     const int Ktot = p.KH * p.KW * p.Cin;
@@ -247,14 +234,6 @@ struct FwdBLoader {
     }
   }
   __device__ __forceinline__ void seek(int kt) { it.seek(kt); }
-  __device__ __forceinline__ void next_offsets(uint32_t (&off)[NV]) {
-    const int ci0 = it.ci0;
-    const uint32_t delta = (uint32_t)(((it.kh() * KW + it.kw()) * Cin + ci0) * 4);
-    const bool kok = kq4 < Cin - ci0;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) off[i] = kok ? base[i] + delta : OOB_OFF;
-    it.advance();
-  }
   __device__ __forceinline__ void load_next(float4 (&v)[NV]) {
     const int ci0 = it.ci0;
     const uint32_t delta = (uint32_t)(((it.kh() * KW + it.kw()) * Cin + ci0) * 4);
@@ -451,7 +430,7 @@ struct WgradBLoader {
   // pixels per load instruction.  Their (image, oh, ow) decomposition and base offset are computed ONCE per wave on the scalar unit
   // and selected per half; a lane adds its own (tap, channel) part.  r03 stamps of the weight gradient: its producers spent 75 % of
   // the loop issuing gathers (address arithmetic) and the consumers waited 18 % of theirs at the barrier.
-  static constexpr bool SCALAR_PIX = PCG_MN_CONSEC && C4 == 32;
+  static constexpr bool SCALAR_PIX = C4 == 32;
   rsrc_t rs;
   int IH, IW, Cin, stride, K, q0, kr0, OH, OW, dh, dw, ci;  // dh = kh - pad
   int lane_off;      // SCALAR_PIX: ((dh * IW + dw) * Cin + ci) * 4, this lane's part of every offset
@@ -509,22 +488,15 @@ struct WgradBLoader {
         if constexpr (XF) okbits |= (ok ? 1u : 0u) << i;
       }
     } else {
-      uint32_t t, ow, b, oh;
-      if constexpr (PCG_MN_CONSEC) {           // this thread's NV pixels are consecutive: decompose the first, carry for the others
-        dOW.divmod((uint32_t)(q0 + mn_krow<NV>(kr0, 0)), t, ow);
-        dOH.divmod(t, b, oh);
-      }
+      uint32_t t, ow, b, oh;                   // this thread's NV pixels are consecutive: decompose the first, carry for the others
+      dOW.divmod((uint32_t)(q0 + mn_krow<NV>(kr0, 0)), t, ow);
+      dOH.divmod(t, b, oh);
 #pragma unroll
       for (int i = 0; i < NV; ++i) {
         const int q = q0 + mn_krow<NV>(kr0, i);
-        if constexpr (PCG_MN_CONSEC) {
-          if (i > 0) {
-            ++ow;
-            if (ow == (uint32_t)OW) { ow = 0; ++oh; if (oh == (uint32_t)OH) { oh = 0; ++b; } }
-          }
-        } else {
-          dOW.divmod((uint32_t)q, t, ow);
-          dOH.divmod(t, b, oh);
+        if (i > 0) {
+          ++ow;
+          if (ow == (uint32_t)OW) { ow = 0; ++oh; if (oh == (uint32_t)OH) { oh = 0; ++b; } }
         }
         const int ih = (int)oh * stride + dh, iw = (int)ow * stride + dw;
         const bool ok = nok && q < K && (unsigned)ih < (unsigned)IH && (unsigned)iw < (unsigned)IW;
@@ -573,21 +545,14 @@ struct WgradBLoader192 {
   }
   __device__ __forceinline__ void load_next(float4 (&v)[NV]) {
     uint32_t t, ow, b, oh;
-    if constexpr (PCG_MN_CONSEC) {
-      dOW.divmod((uint32_t)(q0 + mn_krow<2>(kr0, 0)), t, ow);
-      dOH.divmod(t, b, oh);
-    }
+    dOW.divmod((uint32_t)(q0 + mn_krow<2>(kr0, 0)), t, ow);
+    dOH.divmod(t, b, oh);
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       const int q = q0 + mn_krow<2>(kr0, h);
-      if constexpr (PCG_MN_CONSEC) {
-        if (h > 0) {
-          ++ow;
-          if (ow == (uint32_t)OW) { ow = 0; ++oh; if (oh == (uint32_t)OH) { oh = 0; ++b; } }
-        }
-      } else {
-        dOW.divmod((uint32_t)q, t, ow);
-        dOH.divmod(t, b, oh);
+      if (h > 0) {
+        ++ow;
+        if (ow == (uint32_t)OW) { ow = 0; ++oh; if (oh == (uint32_t)OH) { oh = 0; ++b; } }
       }
 #pragma unroll
       for (int s = 0; s < 3; ++s) {

@@ -35,7 +35,7 @@ namespace pcg {
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 // Raw buffer resources: num_records = the tensor's size in bytes, so an out-of-range byte offset reads as zeros and a store to it
-// is dropped — padding, ragged edges and K tails without branches (conv_loaders.h), and the register epilogue's edge handling.
+// is dropped — padding, ragged edges and K tails without branches (conv_loaders.h).
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 using rsrc_t = __amdgpu_buffer_rsrc_t;
 constexpr uint32_t OOB_OFF = 0x80000000u;  // >= num_records of any accepted tensor
@@ -47,8 +47,6 @@ __device__ __forceinline__ float4 buf_load4(rsrc_t r, uint32_t off) {
   const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0);
   return make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
 }
-__device__ __forceinline__ float buf_load1(rsrc_t r, uint32_t off) { return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(r, off, 0, 0)); }
-__device__ __forceinline__ void buf_store1(rsrc_t r, uint32_t off, float v) { __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), r, off, 0, 0); }
 
 constexpr int IG_LOADERS = 256;            // threads that gather one k-tile (4 waves)
 constexpr int IG_THREADS = 512;            // 4 consumer + 4 producer waves
@@ -74,24 +72,17 @@ constexpr int IG_LDK = IG_BK + 4;          // K-major row stride: 144 B = 9*16 (
 // MN-major operands (both operands of the weight gradient, the weight operand of the grad-input): k-row (0..31) of a k-tile that a
 // loader thread of row group kr0 fetches as its i-th of NV loads.  Consecutive rows (r03; r01/r02: kr0 + (32 / NV) * i): the weight
 // gradient's x operand is gathered per output PIXEL = k-row, and consecutive pixels share their (image, row) decomposition up to
-// a carry — one FastDiv pair per k-tile and thread instead of NV (WgradBLoader).  PCG_MN_CONSEC=0 builds the strided mapping.
-#ifndef PCG_MN_CONSEC
-#define PCG_MN_CONSEC 1
-#endif
+// a carry — one FastDiv pair per k-tile and thread instead of NV (WgradBLoader).
 template <int NV>
-__device__ __forceinline__ constexpr int mn_krow(int kr0, int i) { return PCG_MN_CONSEC ? NV * kr0 + i : kr0 + (32 / NV) * i; }
+__device__ __forceinline__ constexpr int mn_krow(int kr0, int i) { return NV * kr0 + i; }
 
 // BF16_: the operand-precision twin — both operands rounded to bf16 (RNE) as the producers write LDS, products summed in
-//        fp32 on v_mfma_f32_32x32x16_bf16.  Same tile, prefetch and launch bounds as the fp32 config; SWZ / DMA do not apply (below).
-template <int BM_, int BN_, int WAVES_M_, int WAVES_N_, bool SWZ_ = false, int MINW_ = 4, int PF_ = PCG_PREFETCH_DEPTH, bool DMA_ = false,
-          bool BF16_ = false>
+//        fp32 on v_mfma_f32_32x32x16_bf16.  Same tile, prefetch and launch bounds as the fp32 config; SWZ does not apply (below).
+template <int BM_, int BN_, int WAVES_M_, int WAVES_N_, bool SWZ_ = false, int MINW_ = 4, int PF_ = PCG_PREFETCH_DEPTH, bool BF16_ = false>
 struct TileCfg {
   static constexpr int BM = BM_, BN = BN_, WAVES_M = WAVES_M_, WAVES_N = WAVES_N_;
   static constexpr bool SWZ = SWZ_;
-  static constexpr bool DMA = DMA_;          // operand tiles go global -> LDS directly (buffer_load ... lds), see igemm_produce_dma
   static constexpr bool BF16 = BF16_;
-  static_assert(!DMA_ || SWZ_, "LDS-DMA needs the lane-linear (unpadded, swizzled) K-major images");
-  static_assert(!(DMA_ && BF16_), "LDS-DMA copies fp32 bytes: no rounding on the way, no bf16 twin");
   static constexpr int MINW = MINW_, PF = PF_;
   static constexpr int WTM = BM / WAVES_M, WTN = BN / WAVES_N;
   static constexpr int TM = WTM / 32, TN = WTN / 32;
@@ -105,7 +96,7 @@ struct TileCfg {
 // either operand, and both operands give register slot j the same k.  The producers round once, round-to-nearest-even (a plain
 // __bf16 cast: v_cvt_pk_bf16_f32, NaN stays NaN), after their input transform has run in fp32:
 //   K-major source  a float4 = 4 consecutive k of one row     -> one ds_write_b64
-//   MN-major source a loader thread holds NV consecutive k-rows (mn_krow, PCG_MN_CONSEC) of 4 consecutive columns: transposed in
+//   MN-major source a loader thread holds NV consecutive k-rows (mn_krow) of 4 consecutive columns: transposed in
 //                   registers, per column NV bf16 = one ds_write_b64 (NV = 4) / ds_write_b32 (NV = 2; the 192-row image likewise)
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
@@ -122,7 +113,6 @@ template <int ROWS, bool KMAJOR, bool SWZ>
 struct LdsImage<ROWS, KMAJOR, SWZ, true> {
   static constexpr int FLOATS = ROWS * IG_LDB / 2;   // in floats, like the fp32 images (stage offsets)
   static constexpr int NV = ROWS / 32;
-  static_assert(KMAJOR || PCG_MN_CONSEC, "bf16 MN-major staging transposes the consecutive k-rows a loader thread holds");
   __device__ static __forceinline__ void store(float* lds, const float4 (&v)[NV], int tid) {
     char* base = reinterpret_cast<char*>(lds);
     if constexpr (KMAJOR) {
@@ -276,20 +266,9 @@ struct ClockStamp {
       }
     }
   }
-  // per-tile timeline of the persistent kernels (second half of the buffer: 2 + 32 words per block): mark(k) = 100 MHz ticks since begin();
-  // word 0 = begin() on the chip-wide 100 MHz clock (start skew between blocks), word 1 = hardware id
-  __device__ __forceinline__ void mark(int k) {
-    const int b = blockIdx.x;
-    if (out && threadIdx.x == 0 && b < slots / 36 && k < 32) {
-      unsigned long long* tl = out + 2 * (size_t)slots / 2 + (size_t)b * 34;     // second half of the buffer
-      tl[2 + k] = __builtin_amdgcn_s_memrealtime() - r0;
-      if (k == 0) { tl[0] = r0; tl[1] = (unsigned long long)__builtin_amdgcn_s_getreg(4 | (0 << 6) | (31 << 11)); }   // HW_REG_HW_ID, 32 bits
-    }
-  }
 #else
   __device__ __forceinline__ void begin() {}
   __device__ __forceinline__ void end() {}
-  __device__ __forceinline__ void mark(int) {}
   __device__ __forceinline__ void phase(int) {}
   __device__ __forceinline__ void bar_begin() {}
   __device__ __forceinline__ void bar_end() {}
@@ -347,7 +326,6 @@ __device__ __forceinline__ void igemm_produce(LA& la, LB& lb, int ktiles, float*
   // of a tile: the write of tile t+1 then waited for the gathers of tile t+2 as well — one k-tile of prefetch distance, not
   // two, and in-kernel stamps showed the consumers 26-28 % of their loop in the hand-over barrier while the producers waited
   // there 3-9 %.  Straight-line code gives the pass exact counts: vmcnt(8+..) leaves the younger tile's eight gathers in flight.
-#ifndef PCG_OLD_PRODUCER_LOOP   // (A/B builds)
   for (; kt + 4 < ktiles; kt += 2) {
     cs.sec_begin();
 #ifdef PCG_CLOCK_STAMP
@@ -372,7 +350,6 @@ __device__ __forceinline__ void igemm_produce(LA& la, LB& lb, int ktiles, float*
     cs.sec_end(1);
     cs.bar_begin(); lds_barrier(); cs.bar_end();
   }
-#endif
   for (; kt + 1 < ktiles; kt += 2) {          // the last (up to four) k-tiles: the same steps, each behind its bound
     // kt even: tile kt+1 is in set 1 -> stage 1; refill set 1 with tile kt+3
     la.transform(ra[1]); lb.transform(rb[1]);
@@ -424,60 +401,6 @@ __device__ __forceinline__ void igemm_produce(LA& la, LB& lb, int ktiles, float*
     nxt ^= 1;
   }
   }
-}
-
-// Producer by LDS-DMA (r03).  In-kernel stamps of the register-staged producers (scripts/conv_microbench.py --clock) showed what they
-// spend their k-tile on: 0.1 % waiting for their gathers, 11-14 % issuing the next ones — and 72-81 % inside their eight
-// ds_write_b128, behind consumers whose fp32 MFMAs own the register file's read ports almost every cycle; the consumers in turn
-// sat 16-30 % of their loop in the hand-over barrier waiting for those writes.  `buffer_load_dwordx4 ... lds` moves a gathered
-// 16-byte chunk from memory straight into LDS (lane l of the wave lands at M0 + 16*l; a lane whose offset is out of range lands
-// as zeros — scripts/probes/ldsdma_probe.hip): no VGPR staging, no ds_write, no producer-side register traffic at all.
-//   * the image must be lane-linear: the unpadded K-major image (32 floats per row); one wave-instruction fills eight rows.  Its
-//     XOR swizzle (conflict-free ds_read_b128 fragments) moves to the SOURCE side: the loaders are built with src_swz, the lane at
-//     chunk position c of row r fetches logical chunk c ^ ((r >> 1) & 7) — the involution LdsImage::frag applies when reading.
-//   * two stages; tile t+1 is issued into stage (t+1)&1 right after barrier t (its last readers retired their ds_reads before
-//     that barrier) and must have landed — the issuing wave's vmcnt(0) — before barrier t+1, after which the consumers read it.
-//     One k-tile (1.7-3.5 us of MFMAs) is several loaded L2 round trips.
-// Loaders need next_offsets() (conv_loaders.h); K-major operands only (forward: both; grad-input: the dy operand).
-template <class Cfg, class LA, class LB>
-__device__ __forceinline__ void igemm_produce_dma(LA& la, LB& lb, int ktiles, float* smem, int tid, ClockStamp cs = ClockStamp{nullptr, 0}) {
-  using IA = LdsImage<Cfg::BM, true, true>;
-  using IB = LdsImage<Cfg::BN, true, true>;
-  static_assert(!Cfg::BF16, "LDS-DMA staging is fp32 only");
-  static_assert(LA::KMAJOR && LB::KMAJOR && !LA::XFORM && !LB::XFORM, "LDS-DMA staging: plain K-major operands");
-  typedef __attribute__((address_space(3))) void* lds_ptr_t;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  float* As = smem;
-  float* Bs = smem + 2 * IA::FLOATS;
-  if (PCG_PRODUCER_PRIO) __builtin_amdgcn_s_setprio(PCG_PRODUCER_PRIO);
-  auto issue = [&](int stage) {          // rows 8*wave + 32*p .. +7 of each image: one 1 KB wave-instruction per p
-    uint32_t oa[IA::NV], ob[IB::NV];
-    la.next_offsets(oa); lb.next_offsets(ob);
-#pragma unroll
-    for (int p = 0; p < IA::NV; ++p)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(la.rs, (lds_ptr_t)(As + stage * IA::FLOATS + (8 * wave + 32 * p) * IG_BK), 16, oa[p], 0, 0, 0);
-#pragma unroll
-    for (int p = 0; p < IB::NV; ++p)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(lb.rs, (lds_ptr_t)(Bs + stage * IB::FLOATS + (8 * wave + 32 * p) * IG_BK), 16, ob[p], 0, 0, 0);
-  };
-  if (ktiles > 0) issue(0);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  lds_barrier();                           // barrier 0: stage 0 is ready
-  cs.bar_init();
-#ifdef PCG_CLOCK_STAMP
-  const unsigned long long loop_t0 = __builtin_amdgcn_s_memtime();
-#endif
-  for (int kt = 0; kt < ktiles; ++kt) {
-    cs.sec_begin();
-    if (kt + 1 < ktiles) issue((kt + 1) & 1);
-    cs.sec_end(1);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // tile kt+1 has landed in LDS
-    cs.sec_end(2);
-    cs.bar_begin(); lds_barrier(); cs.bar_end();          // barrier kt+1: stage (kt+1)&1 handed to the consumers, stage kt&1 handed back
-  }
-#ifdef PCG_CLOCK_STAMP
-  cs.bar_flush(1, __builtin_amdgcn_s_memtime() - loop_t0);
-#endif
 }
 
 // Consumer: fragments are double-buffered in registers so that the LDS read of k-group g+1 is in flight under the
@@ -757,386 +680,6 @@ __device__ __forceinline__ void igemm_store_tile(f32x16 (&acc)[Cfg::TM][Cfg::TN]
     }
   }
 }
-
-// ======================================================================================================================
-// Persistent, tile-pipelined form (r03).  In-kernel stamps (scripts/conv_microbench.py --clock) showed where the time of the
-// one-tile-per-workgroup kernels goes: the chip holds 2.37-2.40 GHz inside them and the main loops run at 93-96 % of the MFMA rate,
-// but every tile pays 16-19 us OUTSIDE its main loop — workgroup dispatch, loader set-up, the first gathers' round trip, the LDS-
-// staged epilogue, the final write burst — which is 7 % of a 128x128 tile with K = 2048 and as long as the main loop itself for a
-// 128x64 tile with K = 512.  Here a workgroup is resident for the whole launch and walks a strided list of tiles; the k-tiles of
-// all its tiles form ONE stream through the same two LDS stages and the same barrier protocol:
-//   producers  run ahead across tile boundaries (the next tile's first k-tiles are gathered and staged while the consumers finish
-//              the current one), re-creating their loader state when the stream crosses into the next tile;
-//   consumers  store a finished tile STRAIGHT from the accumulator registers (column on the lane, rows in the registers: one
-//              128-byte row segment per half-wave per store) — no LDS staging, so the stages stay with the producers — zero the
-//              accumulators and continue with the fragments that are already waiting.
-// MEASURED (MI355X, scripts/conv_microbench.py --ab persistent=0,1 and --clock --timeline): NOT faster.  With the
-// plain epilogue it ties the one-tile-per-workgroup kernels on the forward shapes (D2 260.6 vs 261.1 us, D4 +4.6 %) and loses 3-8 %
-// on the grad-input shapes; with the full epilogue compiled in, the whole DCGAN step is 11.20 vs 10.96 ms.  Why: resident
-// workgroups that all walk equal tiles stay in LOCKSTEP — every tile boundary is chip-wide, all consumers leave the matrix pipe
-// together and all write their tiles together (a 32 MB burst: 8-9 us per 128x128 tile boundary), whereas the dispatcher's own
-// round-robin of short-lived workgroups desynchronises after the first round and hides one workgroup's prologue / epilogue
-// behind its CU neighbour's main loop; and a static tile walk ends with its slowest workgroup (main-loop spread 200-252 us).
-// Kept as an opt-in experiment (-DPCG_PERSISTENT_KERNELS: `make -C csrc lean`, pcg_tune_set("persistent", 1)); the shipped
-// library does not compile it.
-// ======================================================================================================================
-#ifdef PCG_PERSISTENT_KERNELS
-
-// Walk of one workgroup over the launch's work items (tiles, or (tile, K-slice) pairs): the `total` items are cut into 8 contiguous
-// runs, one per XCD (blocks b and b + 8 share an XCD and its L2), and the G/8 workgroups of an XCD take the items of their run
-// round-robin — at any time the workgroups of one XCD work on neighbouring tiles (shared halo rows / weight panels in that L2).
-struct TileWalk {
-  uint32_t base, count, q, step;   // this workgroup visits base + q, base + q + step, ... < base + count
-  __device__ __forceinline__ TileWalk(uint32_t total) {
-    const uint32_t w = blockIdx.x, G = gridDim.x;
-    if (G & 7u) {                              // not a multiple of 8 (tiny launches): plain striding
-      base = 0; count = total; q = w; step = G;
-    } else {
-      const uint32_t x = w & 7u, qq = total >> 3, r = total & 7u;
-      base = x < r ? x * (qq + 1) : r * (qq + 1) + (x - r) * qq;
-      count = qq + (x < r ? 1u : 0u);
-      q = w >> 3; step = G >> 3;
-    }
-  }
-  __device__ __forceinline__ uint32_t ntiles() const { return q < count ? (count - q + step - 1) / step : 0u; }
-  __device__ __forceinline__ uint32_t item(uint32_t i) const { return base + q + i * step; }
-};
-
-// Producer side.  Src concept: `la`, `lb` (loaders of the CURRENT tile), `int n` (its k-tiles, >= 1), `bool next_tile()` (advance to
-// this workgroup's next tile and rebuild la / lb / n; false when there is none).  S = k-tiles of the whole stream.
-template <class Cfg, class Src>
-__device__ __forceinline__ void igemm_produce_stream(Src& src, int S, float* smem, int tid) {
-  using LA = decltype(src.la);
-  using LB = decltype(src.lb);
-  using IA = LdsImage<Cfg::BM, LA::KMAJOR, Cfg::SWZ>;
-  using IB = LdsImage<Cfg::BN, LB::KMAJOR, Cfg::SWZ>;
-  static_assert(LA::ROWS == Cfg::BM && LB::ROWS == Cfg::BN, "loader/tile mismatch");
-  static_assert(!Cfg::BF16, "the persistent experiment is fp32 only");
-  float* As = smem;
-  float* Bs = smem + 2 * IA::FLOATS;
-  int left = src.n;                            // k-tiles of the current tile not yet gathered
-  auto issue = [&](float4 (&ra)[IA::NV], float4 (&rb)[IB::NV]) {
-    if (left == 0) { src.next_tile(); left = src.n; }        // only called while the stream has elements left
-    src.la.load_next(ra); src.lb.load_next(rb);
-    --left;
-  };
-  if constexpr (Cfg::PF == 2 && !LA::XFORM && !LB::XFORM) {
-    float4 ra[2][IA::NV], rb[2][IB::NV];
-    if (S > 0) {
-      issue(ra[0], rb[0]);
-      if (S > 1) issue(ra[1], rb[1]);
-      IA::store(As, ra[0], tid);
-      IB::store(Bs, rb[0], tid);
-      if (S > 2) issue(ra[0], rb[0]);
-    }
-    lds_barrier();
-    int g = 0;
-    for (; g + 1 < S; g += 2) {
-      IA::store(As + IA::FLOATS, ra[1], tid);
-      IB::store(Bs + IB::FLOATS, rb[1], tid);
-      if (g + 3 < S) issue(ra[1], rb[1]);
-      lds_barrier();
-      if (g + 2 < S) {
-        IA::store(As, ra[0], tid);
-        IB::store(Bs, rb[0], tid);
-      }
-      if (g + 4 < S) issue(ra[0], rb[0]);
-      lds_barrier();
-    }
-    if (g < S) lds_barrier();
-  } else {
-    float4 ra[IA::NV], rb[IB::NV];
-    if (S > 0) {
-      issue(ra, rb);
-      src.la.transform(ra); src.lb.transform(rb);
-      IA::store(As, ra, tid);
-      IB::store(Bs, rb, tid);
-      if (S > 1) issue(ra, rb);
-    }
-    lds_barrier();
-    int nxt = 1;
-    for (int g = 0; g < S; ++g) {
-      if (g + 1 < S) {
-        src.la.transform(ra); src.lb.transform(rb);      // the state of the loader that issued this k-tile: transform precedes the next issue
-        IA::store(As + nxt * IA::FLOATS, ra, tid);
-        IB::store(Bs + nxt * IB::FLOATS, rb, tid);
-      }
-      if (g + 2 < S) issue(ra, rb);
-      lds_barrier();
-      nxt ^= 1;
-    }
-  }
-}
-
-// Consumer side.  ktiles_of(i) = k-tiles of this workgroup's i-th tile (>= 1); epilogue(i, acc) stores it (registers -> global).
-template <class Cfg, bool AK, bool BK_, class KtOf, class Epi>
-__device__ __forceinline__ void igemm_consume_stream(int ntiles, KtOf ktiles_of, Epi epilogue, const float* smem, ClockStamp cs = ClockStamp{nullptr, 0}) {
-  using IA = LdsImage<Cfg::BM, AK, Cfg::SWZ>;
-  using IB = LdsImage<Cfg::BN, BK_, Cfg::SWZ>;
-  static_assert(!Cfg::BF16, "the persistent experiment is fp32 only");
-  constexpr int KG = IG_BK / 8;
-  const float* As = smem;
-  const float* Bs = smem + 2 * IA::FLOATS;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int wm = wave / Cfg::WAVES_N, wn = wave % Cfg::WAVES_N;
-  const int li = lane & 31, lh = lane >> 5;
-  const int arow = wm * Cfg::WTM, brow = wn * Cfg::WTN;
-  f32x16 acc[Cfg::TM][Cfg::TN];
-  MmaFrag<Cfg::BF16> a[2][Cfg::TM], b[2][Cfg::TN];
-  auto fetch = [&](const float* as, const float* bs, int ks, int buf) {
-#pragma unroll
-    for (int i = 0; i < Cfg::TM; ++i) IA::frag(as, arow + 32 * i, ks, li, lh, a[buf][i].v);
-#pragma unroll
-    for (int j = 0; j < Cfg::TN; ++j) IB::frag(bs, brow + 32 * j, ks, li, lh, b[buf][j].v);
-  };
-  auto mma = [&](int buf) {
-    if constexpr (Cfg::BF16) {
-#pragma unroll
-      for (int i = 0; i < Cfg::TM; ++i)
-#pragma unroll
-        for (int j = 0; j < Cfg::TN; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[buf][i].v, b[buf][j].v, acc[i][j], 0, 0, 0);
-    } else {
-#pragma unroll
-      for (int t = 0; t < 4; ++t)
-#pragma unroll
-        for (int i = 0; i < Cfg::TM; ++i)
-#pragma unroll
-          for (int j = 0; j < Cfg::TN; ++j)
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[buf][i].v[t], b[buf][j].v[t], acc[i][j], 0, 0, 0);
-    }
-  };
-  lds_barrier();                                 // barrier 0: the stream's first k-tile is staged
-  if (ntiles <= 0) return;
-  __builtin_amdgcn_s_setprio(2);
-  cs.begin();
-  fetch(As, Bs, 0, 0);
-  int cur = 0;
-  for (int t = 0; t < ntiles; ++t) {
-    const int n = ktiles_of(t);
-#pragma unroll
-    for (int i = 0; i < Cfg::TM; ++i)
-#pragma unroll
-      for (int j = 0; j < Cfg::TN; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-    for (int kt = 0; kt < n; ++kt) {
-      const float* as = As + cur * IA::FLOATS;
-      const float* bs = Bs + cur * IB::FLOATS;
-#pragma unroll
-      for (int ks = 0; ks < KG - 1; ++ks) {
-        fetch(as, bs, ks + 1, (ks + 1) & 1);
-        mma(ks & 1);
-      }
-      lds_barrier();                             // all reads of stage cur retired; stage cur^1 (the stream's next k-tile) is ready
-      cur ^= 1;
-      if (kt + 1 < n) fetch(As + cur * IA::FLOATS, Bs + cur * IB::FLOATS, 0, KG & 1);
-      mma((KG - 1) & 1);
-    }
-    __builtin_amdgcn_s_setprio(0);
-    cs.mark(2 * t);
-    epilogue(t, acc);                            // registers -> global; the LDS stages stay with the producers
-    cs.mark(2 * t + 1);
-    __builtin_amdgcn_s_setprio(2);
-    // the next tile's first fragments only now: they would be 16 more live registers across the epilogue (one exposed LDS read per tile)
-    if (t + 1 < ntiles) fetch(As + cur * IA::FLOATS, Bs + cur * IB::FLOATS, 0, KG & 1);
-  }
-  cs.end();
-  __builtin_amdgcn_s_setprio(0);
-}
-
-// Epilogue straight from the accumulator registers: element (i, j, r) of lane (li, lh) is row 32i + acc_row(r, lh), column 32j + li
-// of the wave tile, so a store instruction writes two 128-byte row segments (one per half-wave) and every per-column constant
-// (bias, BatchNorm mean / invstd / scale / shift) is ONE value per lane and j.  Same arithmetic per element as igemm_store_tile;
-// the column sums (fused statistics / BatchNorm-backward sums) are taken per lane over its rows in fp64 and the two half-waves
-// added by one shuffle.  Addressing is by 32-bit byte offsets into raw buffer resources of the output (and of the aux tensors of
-// the backward epilogues, which have the output's shape): row_off(row) = offset of the tile row's column n_block, or OOB_OFF for a
-// row outside the problem — such stores are dropped and such loads return zero, no branches.
-struct EpiBufs { rsrc_t out, aux, aux2; };
-__device__ __forceinline__ EpiBufs make_epi_bufs(float* out, uint32_t out_bytes, const EpiAux& e) {
-  EpiBufs b;
-  b.out = make_rsrc(out, out_bytes);
-  b.aux = make_rsrc(reinterpret_cast<const char*>(out) + e.delta_bytes, (e.mode != EPI_NONE && !e.no_addend) ? out_bytes : 0u);
-  b.aux2 = make_rsrc(reinterpret_cast<const char*>(out) + e.delta2_bytes, e.mode == EPI_ADDSUM ? out_bytes : 0u);
-  return b;
-}
-
-// Row addressing policies of the register epilogue.  An element's address is (per-lane VGPR offset) + (wave-uniform SGPR offset):
-// gfx950 range-checks their SUM against num_records (scripts/probes/soffset_probe.hip), so for a row-major [M][N] output the rows
-// beyond M fall out of range by themselves and the sixteen row steps of an accumulator are sixteen SGPR constants — one VGPR of
-// addressing per accumulator instead of sixteen.  begin(lane_row, colb) is called once per accumulator with this lane's first row
-// (wm*WTM + 32*i + 4*lh) and column byte offset inside the tile row; c = (r & 3) + 8 * (r >> 2) is a compile-time constant.
-struct RowsAffine {            // consecutive rows of a row-major [M][N] matrix (forward, split-K slabs)
-  int M, m_block; uint32_t n4, nb4;      // n4 = 4*N, nb4 = 4*n_block
-  uint32_t vbase; int left;
-  __device__ __forceinline__ void begin(int lane_row, uint32_t colb) {
-    const int m = m_block + lane_row;
-    vbase = (uint32_t)m * n4 + nb4 + colb;
-    left = M - m;
-  }
-  __device__ __forceinline__ uint32_t voff(int) const { return vbase; }
-  __device__ __forceinline__ uint32_t soff(int c) const { return (uint32_t)c * n4; }
-  __device__ __forceinline__ bool valid(int c) const { return c < left; }
-};
-struct RowsTable {             // rows map to arbitrary pixels: a table in LDS of byte offsets (or OOB_OFF), one per tile row (grad-input)
-  const uint32_t* table; uint32_t nb4;
-  const uint32_t* p; uint32_t colb;
-  __device__ __forceinline__ void begin(int lane_row, uint32_t colb_) { p = table + lane_row; colb = nb4 + colb_; }
-  __device__ __forceinline__ uint32_t voff(int c) const { return p[c] + colb; }      // OOB_OFF + (< 2^31) stays out of range
-  __device__ __forceinline__ uint32_t soff(int) const { return 0u; }
-  __device__ __forceinline__ bool valid(int c) const { return p[c] < OOB_OFF; }
-};
-__device__ __forceinline__ float buf_load1s(rsrc_t r, uint32_t voff, uint32_t soff) { return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, 0)); }
-__device__ __forceinline__ void buf_store1s(rsrc_t r, uint32_t voff, uint32_t soff, float v) { __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), r, voff, soff, 0); }
-// fence between the accumulators of the epilogue: nothing is scheduled or kept alive across it (the compiler otherwise hoists the
-// address arithmetic and the aux reads of all accumulators to the front — seen: 250+ spilled VGPRs)
-__device__ __forceinline__ void epi_fence() { __builtin_amdgcn_sched_barrier(0); asm volatile("" ::: "memory"); __builtin_amdgcn_sched_barrier(0); }
-
-// What makes this epilogue fast or slow is the in-order vmcnt: waiting for ANY load means waiting for every store issued before
-// it, and a tile's stores complete only after a trip through a memory system that every workgroup is writing into.  So: all
-// per-column constants are loaded before the first store, and the aux reads of accumulator k+1 are issued BEFORE the stores of
-// accumulator k (the counted wait then leaves exactly those stores in flight).  The fp64 column sums sit behind a wave-uniform
-// branch; a lane whose column lies outside N is masked off for the whole accumulator.
-template <class Cfg, class Rows>
-__device__ __forceinline__ void igemm_store_regs(f32x16 (&acc)[Cfg::TM][Cfg::TN], int n_block, int N, const float* bias, Rows rows,
-                                                 const EpiBufs& eb, double* stat_row, int act, float slope, const EpiAux* epi) {
-  // Opaque copy of the thread index: everything below that depends only on it is loop-invariant over the workgroup's tiles, and the
-  // compiler would hoist it out of the tile loop and keep it alive — i.e. spill it — across the main loop.
-  int tix = threadIdx.x;
-  asm volatile("" : "+v"(tix));
-  const int lane = tix & 63, wave = tix >> 6;
-  const int wm = wave / Cfg::WAVES_N, wn = wave % Cfg::WAVES_N, li = lane & 31, lh = lane >> 5;
-  const int emode = epi ? epi->mode : EPI_NONE;       // wave-uniform
-  const bool want_sums = stat_row != nullptr;         // wave-uniform
-  const float neg = epi ? epi->neg : 1.f;
-  constexpr int NA = Cfg::TM * Cfg::TN;               // accumulators of the wave tile, visited j-major: k = j * TM + i
-  int ncol[Cfg::TN];
-  float bv[Cfg::TN], mu[Cfg::TN], is[Cfg::TN], sc[Cfg::TN], sh[Cfg::TN];
-#pragma unroll
-  for (int j = 0; j < Cfg::TN; ++j) {                 // every per-column load before the first store
-    const int n = n_block + wn * Cfg::WTN + 32 * j + li;
-    const bool ok = n < N;
-    ncol[j] = ok ? n : -1;
-    bv[j] = (bias && ok) ? bias[n] : 0.f;
-    mu[j] = 0.f; is[j] = 1.f; sc[j] = 1.f; sh[j] = 0.f;
-    if ((emode == EPI_BNBWD || emode == EPI_ADDSUM) && ok) { mu[j] = epi->mean[n]; is[j] = epi->invstd[n]; }
-    if (emode == EPI_BNBWD && ok) bn_fold(epi->gamma[n], epi->beta[n], mu[j], is[j], sc[j], sh[j]);
-  }
-  auto rows_of = [&](int k) {
-    Rows rw = rows;
-    rw.begin(wm * Cfg::WTM + 32 * (k % Cfg::TM) + 4 * lh, (uint32_t)(4 * (wn * Cfg::WTN + 32 * (k / Cfg::TM) + li)));
-    return rw;
-  };
-#ifdef PCG_EPI_LEAN   // measurement-only build: the plain epilogue without statistics, nothing else compiled in
-  {
-#pragma unroll
-    for (int k = 0; k < NA; ++k) {
-      const int j = k / Cfg::TM, i = k % Cfg::TM;
-      if (ncol[j] >= 0) {
-        const Rows rw = rows_of(k);
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int c = (r & 3) + 8 * (r >> 2);
-          float v = acc[i][j][r] + bv[j];
-          if (act != PCG_ACT_NONE) v = act_neg_scale(v, slope);
-          buf_store1s(eb.out, rw.voff(c), rw.soff(c), v);
-        }
-      }
-      epi_fence();
-    }
-    return;
-  }
-#endif
-  double s1 = 0.0, s2 = 0.0;
-  auto flush_sums = [&](int j) {
-    double* pr = stat_row + (size_t)wm * 2 * N;       // [wm][2][N] inside this tile row's slot
-    s1 += __shfl_xor(s1, 32); s2 += __shfl_xor(s2, 32);
-    if (lh == 0 && ncol[j] >= 0) { pr[ncol[j]] = s1; pr[N + ncol[j]] = s2; }
-    s1 = 0.0; s2 = 0.0;
-  };
-  if (emode == EPI_NONE) {
-#pragma unroll
-    for (int k = 0; k < NA; ++k) {
-      const int j = k / Cfg::TM, i = k % Cfg::TM;
-      if (ncol[j] >= 0) {
-        const Rows rw = rows_of(k);
-        float v[16];
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int c = (r & 3) + 8 * (r >> 2);
-          v[r] = acc[i][j][r] + bv[j];
-          if (act != PCG_ACT_NONE) v[r] = act_neg_scale(v[r], slope);
-          buf_store1s(eb.out, rw.voff(c), rw.soff(c), v[r]);
-        }
-        if (want_sums) {
-#pragma unroll
-          for (int r = 0; r < 16; ++r) { const double d = rw.valid((r & 3) + 8 * (r >> 2)) ? (double)v[r] : 0.0; s1 += d; s2 = fma(d, d, s2); }
-        }
-      }
-      if (want_sums && i == Cfg::TM - 1) flush_sums(j);
-      epi_fence();
-    }
-    return;
-  }
-  // backward-pass epilogues: aux reads software-pipelined one accumulator ahead of the stores
-  float u[2][16];
-  auto load_aux = [&](int k, float (&dst)[16], rsrc_t rs) {
-    if (ncol[k / Cfg::TM] >= 0) {
-      const Rows rw = rows_of(k);
-#pragma unroll
-      for (int r = 0; r < 16; ++r) { const int c = (r & 3) + 8 * (r >> 2); dst[r] = buf_load1s(rs, rw.voff(c), rw.soff(c)); }
-    }
-  };
-  load_aux(0, u[0], eb.aux);
-#pragma unroll
-  for (int k = 0; k < NA; ++k) {
-    const int j = k / Cfg::TM, i = k % Cfg::TM;
-    if (k + 1 < NA) load_aux(k + 1, u[(k + 1) & 1], eb.aux);
-    float (&uu)[16] = u[k & 1];
-    if (ncol[j] >= 0) {
-      const Rows rw = rows_of(k);
-      if (emode == EPI_ADD || emode == EPI_ADDSUM) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int c = (r & 3) + 8 * (r >> 2);
-          const float v = acc[i][j][r] + uu[r];
-          buf_store1s(eb.out, rw.voff(c), rw.soff(c), v);
-          acc[i][j][r] = v;                          // EPI_ADDSUM needs the sum once more
-        }
-        if (emode == EPI_ADDSUM && want_sums) {       // the second aux tensor (the next BatchNorm's pre-normalisation output)
-          float z[16];
-#pragma unroll
-          for (int r = 0; r < 16; ++r) { const int c = (r & 3) + 8 * (r >> 2); z[r] = buf_load1s(eb.aux2, rw.voff(c), rw.soff(c)); }
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const double d = rw.valid((r & 3) + 8 * (r >> 2)) ? (double)neg * (double)acc[i][j][r] : 0.0;
-            s1 += d; s2 = fma(d, (double)((z[r] - mu[j]) * is[j]), s2);
-          }
-        }
-      } else {                                        // EPI_MASK (sc = 1, sh = 0) / EPI_BNBWD: the forward's own expression for the sign
-        float v[16];
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int c = (r & 3) + 8 * (r >> 2);
-          const float pre = fmaf(uu[r], sc[j], sh[j]);
-          v[r] = acc[i][j][r] * (pre > 0.f ? 1.f : neg);
-          buf_store1s(eb.out, rw.voff(c), rw.soff(c), v[r]);
-        }
-        if (want_sums) {
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const double d = rw.valid((r & 3) + 8 * (r >> 2)) ? (double)v[r] : 0.0;
-            s1 += d; s2 = fma(d, (double)((uu[r] - mu[j]) * is[j]), s2);
-          }
-        }
-      }
-    }
-    if (want_sums && i == Cfg::TM - 1) flush_sums(j);
-    epi_fence();
-  }
-}
-
-#endif  // PCG_PERSISTENT_KERNELS
 
 // Accumulator element (tile i,j ; register r) of lane (li,lh) sits at
 //   row = 32*i + (r&3) + 8*(r>>2) + 4*lh   col = 32*j + li      (within the wave tile)

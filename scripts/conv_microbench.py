@@ -45,8 +45,6 @@ def main():
                                                "(ops.tune / pcg_tune_set); prints the median and min ms per variant")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--precision", default="fp32", choices=sorted(ops.CONV_PRECISIONS), help="operand precision of the MFMA convolutions")
-    ap.add_argument("--timeline", type=int, default=0, help="with --clock: print the per-tile timeline (loop end / epilogue end, us since the "
-                                                            "stream began) of this many workgroups of the persistent kernels")
     ap.add_argument("--clock", action="store_true", help="report the in-kernel clock (needs the stamp build: make -C csrc stamp; "
                                                          "PCG_LIB=.../csrc/build_stamp/libpcgan_hip.so)")
     args = ap.parse_args()
@@ -61,22 +59,6 @@ def main():
 
     def clock_mhz():
         half = stamps.numel() // 2
-        if args.timeline:
-            tl = stamps[half:].cpu().view(-1)
-            nb = 0
-            t00 = None
-            rows = []
-            for b in range(min(1024, (half // 2) // 36 if False else 1024)):
-                rec = tl[b * 34:(b + 1) * 34]
-                if int(rec[0]) == 0:
-                    continue
-                rows.append((b, int(rec[0]), int(rec[1]), [int(v) / 100.0 for v in rec[2:] if int(v) > 0]))
-            if rows:
-                t00 = min(r[1] for r in rows)
-                for b, r0, hw, ev in rows[:args.timeline]:
-                    cu = (hw >> 8) & 15; se = (hw >> 13) & 7; tg = (hw >> 16) & 15; simd = (hw >> 4) & 3
-                    print(f"    wg {b:4d} start +{(r0 - t00) / 100.0:6.1f} us hw_id 0x{hw:08x} (se {se} cu {cu} tg {tg}) | " +
-                          " ".join(f"{v:.1f}" for v in ev))
         ph = stamps[half:half + half // 2].cpu().view(-1, 4).double()
         ph = ph[(ph[:, 0] > 0) & (ph[:, 3] > 0)]
         clock_mhz.phases = None

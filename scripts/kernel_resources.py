@@ -10,6 +10,8 @@ import subprocess
 import sys
 import tempfile
 
+from kernel_names import short_kernel_name
+
 
 def demangle(names):
     try:
@@ -37,9 +39,7 @@ def main():
         names = demangle([r[0] for r in rows])
         print(f"# {src}")
         for nm, r in zip(names, rows):
-            nm = re.sub(r"pcg::\(anonymous namespace\)::", "", nm)
-            nm = re.sub(r"pcg::TileCfg<(\d+), (\d+), \d+, \d+, (\w+), (\d+), (\d+), (\w+), true>", r"T<\1x\2,swz=\3,w\4,pf\5,bf16>", nm)   # bf16 twins
-            nm = re.sub(r"pcg::TileCfg<(\d+), (\d+), \d+, \d+, (\w+), (\d+), (\d+)(?:, (\w+), false)?>", r"T<\1x\2,swz=\3,w\4,pf\5>", nm)
+            nm = short_kernel_name(nm)
             print(f"{nm[:120]:120s} vgpr {r[1]:3d} agpr {r[2]:3d} sgpr {r[3]:3d} spill {r[4]:3d} scratch {r[5]:4d} lds {r[6]}")
 
 

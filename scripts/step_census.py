@@ -11,15 +11,9 @@ import argparse
 import collections
 import csv
 import json
-import re
 import sys
 
-
-def short(name):
-    name = name.replace("pcg::(anonymous namespace)::", "").replace("void ", "")
-    name = re.sub(r"pcg::TileCfg<(\d+), (\d+), \d+, \d+(?:, (true|false), \d+, \d+(?:, (?:true|false))?)?>",
-                  lambda m: f"{m.group(1)}x{m.group(2)}" + ("/swz3" if m.group(3) == "true" else ""), name)
-    return name.split("(")[0]
+from kernel_names import short_kernel_name
 
 
 def census(path, marker="adam_kernel", per_step=2, steps=1):
@@ -30,7 +24,7 @@ def census(path, marker="adam_kernel", per_step=2, steps=1):
         raise SystemExit(f"trace has {len(ends)} steps; need {steps + 1}")
     a, b = ends[-steps - 1] + 1, ends[-1] + 1
     seg = rows[a:b]
-    names = [short(r["Kernel_Name"]) for r in seg]
+    names = [short_kernel_name(r["Kernel_Name"]) for r in seg]
     dur = [(int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3 for r in seg]
     per = collections.OrderedDict()
     for n, d in zip(names, dur):

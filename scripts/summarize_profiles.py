@@ -11,17 +11,12 @@ import json
 import os
 import sys
 
+from kernel_names import short_kernel_name
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 tag, stats, steps = sys.argv[1], sys.argv[2], int(sys.argv[3])
 out_dir = os.path.join(ROOT, "profiles")
 os.makedirs(out_dir, exist_ok=True)
-
-
-def short(name):
-    name = name.replace("pcg::(anonymous namespace)::", "").replace("void ", "")
-    name = name.replace("pcg::TileCfg<128, 128, 2, 2>", "128x128").replace("pcg::TileCfg<128, 64, 2, 2>", "128x64")
-    name = name.replace("pcg::TileCfg<64, 128, 1, 4>", "64x128")
-    return name.split("(")[0]
 
 
 rows = list(csv.DictReader(open(stats)))
@@ -33,7 +28,7 @@ with open(os.path.join(out_dir, f"{tag}_kernel_stats.md"), "w") as f:
         t = float(r["TotalDurationNs"])
         if t / tot < 0.0005:
             continue
-        f.write(f"| `{short(r['Name'])}` | {int(r['Calls']) / steps:.1f} | {float(r['AverageNs']) / 1e3:.1f} | "
+        f.write(f"| `{short_kernel_name(r['Name'])}` | {int(r['Calls']) / steps:.1f} | {float(r['AverageNs']) / 1e3:.1f} | "
                 f"{t / 1e6 / steps:.3f} | {100 * t / tot:.1f} |\n")
     f.write(f"\nGPU busy time: {tot / 1e6 / steps:.3f} ms/step\n")
 
@@ -42,7 +37,7 @@ if len(sys.argv) > 5:
         d = collections.defaultdict(lambda: [0, 0.0])
         for r in csv.DictReader(open(path)):
             if r["Counter_Name"] == counter:
-                k = short(r["Kernel_Name"])
+                k = short_kernel_name(r["Kernel_Name"])
                 d[k][0] += 1
                 d[k][1] += float(r["Counter_Value"])
         return d

@@ -14,20 +14,13 @@ import os
 import shutil
 import sys
 
+from kernel_names import short_kernel_name
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 tag = sys.argv[1] if len(sys.argv) > 1 else "r04"
 src = os.path.join(ROOT, "gpurun_out", f"prof_{tag}")
 out = os.path.join(ROOT, "profiles")
 os.makedirs(out, exist_ok=True)
-
-
-def short(name):
-    import re
-    name = name.replace("pcg::(anonymous namespace)::", "").replace("void ", "")
-    # TileCfg<BM, BN, WM, WN[, swizzled, min waves/SIMD, prefetch depth]> -> BMxBN (+ "/swz3" for the unpadded three-per-CU config)
-    name = re.sub(r"pcg::TileCfg<(\d+), (\d+), \d+, \d+(?:, (true|false), \d+, \d+(?:, (?:true|false))?)?>",
-                  lambda m: f"{m.group(1)}x{m.group(2)}" + ("/swz3" if m.group(3) == "true" else ""), name)
-    return name.split("(")[0]
 
 
 def find(sub, pattern):
@@ -51,7 +44,7 @@ def stats_md(sub, dest, title, steps):
             t = float(r["TotalDurationNs"])
             if t / tot < 0.0005:
                 continue
-            f.write(f"| `{short(r['Name'])}` | {int(r['Calls']) / steps:.1f} | {float(r['AverageNs']) / 1e3:.1f} | {t / 1e6 / steps:.3f} | {100 * t / tot:.1f} |\n")
+            f.write(f"| `{short_kernel_name(r['Name'])}` | {int(r['Calls']) / steps:.1f} | {float(r['AverageNs']) / 1e3:.1f} | {t / 1e6 / steps:.3f} | {100 * t / tot:.1f} |\n")
         f.write(f"\nGPU busy time: {tot / 1e6 / steps:.3f} ms/step, {calls / steps:.1f} launches/step\n")
     return path, tot, calls
 
@@ -89,7 +82,7 @@ if trace:
         busy = sum(int(r_["End_Timestamp"]) - int(r_["Start_Timestamp"]) for r_ in rows[a:b]) / 10.0 / 1e3
         nat = sum(1 for r_ in rows[a:b] if "at::native" in r_["Kernel_Name"]) / 10.0
         queues = sorted({r_["Queue_Id"] for r_ in rows[a:b]})
-        per_name = collections.Counter(short(r_["Kernel_Name"]) for r_ in rows[a:b])
+        per_name = collections.Counter(short_kernel_name(r_["Kernel_Name"]) for r_ in rows[a:b])
         json.dump({"launches_per_step": lps, "step_period_us_under_profiler": period, "sum_of_kernel_durations_us": busy,
                    "aten_kernels_per_step": nat, "hw_queues_used": len(queues),
                    "copy_kernels_per_step": sum(v for k, v in per_name.items() if "copyBuffer" in k or "fillBuffer" in k) / 10.0,
@@ -109,7 +102,7 @@ def pmc_summary(fetch_sub, write_sub, dest, cmd):
         d = collections.defaultdict(lambda: [0, 0.0])
         for r_ in csv.DictReader(open(path)):
             if r_["Counter_Name"] == counter:
-                k = short(r_["Kernel_Name"])
+                k = short_kernel_name(r_["Kernel_Name"])
                 d[k][0] += 1
                 d[k][1] += float(r_["Counter_Value"])
         return d

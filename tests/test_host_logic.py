@@ -172,6 +172,27 @@ def _check_bench_shape_plans():
     assert plan(1024, 64, 64, 28, 3, 1, 1, WGRAD, 1).startswith("64x192 tiles: 3 x")
 
 
+def test_tune_switches():
+    """pcg_tune_set accepts exactly the launch-planning switches, and its error message lists them; the names of the removed
+    persistent and LDS-DMA experiments are refused like any unknown name."""
+    from pcgan_amd import _lib
+    lib = _lib.load()
+    switches = ["korder", "edge_prio", "dgrad_swz3", "wgrad_rounds", "wgrad_order", "dgrad_interleave", "fwd_splits", "stream_k",
+                "sk_blocks", "dgrad_gemm", "t64"]
+    try:
+        for name in switches:
+            assert lib.pcg_tune_set(name.encode(), 0) == _lib.PCG_OK, name
+            assert lib.pcg_tune_set(name.encode(), -1) == _lib.PCG_OK, name
+    finally:
+        for name in switches:
+            lib.pcg_tune_set(name.encode(), -1)
+    for name in ("persistent", "persist_tiles", "dma", "no_such_switch"):
+        assert lib.pcg_tune_set(name.encode(), 1) == -1, name          # PCG_ERR_INVALID
+        msg = lib.pcg_last_error().decode()
+        assert f"unknown switch '{name}'" in msg
+        assert msg[msg.index("(") + 1:msg.rindex(")")].split(", ") == switches
+
+
 def test_bench_dump_outputs_writes_every_returned_tensor_and_both_state_dicts(tmp_path):
     """bench.py --dump-outputs: the step's returned tensors and every state_dict entry of both nets as <name>.npy, floats as
     float32 and integer buffers as float64, the same values, within the 64 MB limit at the reference widths."""
