@@ -172,6 +172,18 @@ def _check_bench_shape_plans():
     assert plan(1024, 64, 64, 28, 3, 1, 1, WGRAD, 1).startswith("64x192 tiles: 3 x")
 
 
+def test_igemm_branch_cases_reach_their_forms():
+    """Every case of tests/test_hip_igemm_branches.py (the implicit-GEMM form table and the epilogue forms) reaches the launch form its
+    id names, through pcg_conv_plan_describe(assume_scratch = 1) under its tune switches — host logic, no device, in a fresh process
+    (see test_conv_launch_planning_at_the_bench_shapes)."""
+    here = os.path.dirname(os.path.abspath(__file__))
+    code = "import sys; sys.path[:0] = [%r, %r]; import test_hip_igemm_branches as t; t._check_plans()" % (ROOT, here)
+    env = {k: v for k, v in os.environ.items() if k not in ("PCG_WGRAD_192", "PCG_STREAM_K", "PCG_KORDER", "PCG_DGRAD_INTERLEAVE")}
+    r = subprocess.run([sys.executable] + (["-s"] if sys.flags.no_user_site else []) + ["-c", code],
+                       capture_output=True, text=True, timeout=300, env=env)
+    assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
+
+
 def test_tune_switches():
     """pcg_tune_set accepts exactly the launch-planning switches, and its error message lists them; the names of the removed
     persistent and LDS-DMA experiments are refused like any unknown name."""
