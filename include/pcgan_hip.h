@@ -910,6 +910,65 @@ int pcg_conv_reset_scratch(pcg_stream_t stream);
  * this build stamps, 0 for the shipped library (which compiles no stamp code).  buf = NULL turns it off.                        */
 int pcg_debug_stamp_buffer(void* buf, int64_t bytes);
 
+/* ---- moons CounteRGAN (conditional_counteRGAN/moons): whole training iterations in one launch, one workgroup ------------------
+ * The three nets — ResidualGenerator (models/generator.py:4-24: Linear-BN1d-ReLU x3, Linear), the spectral-norm Discriminator
+ * (models/discriminator.py:6-22: four SN Linears, LeakyReLU 0.2) and the frozen NNClassifier (models/nn_classifier.py:3-15) — at
+ * input_dim 2, 3 classes, hidden 32 or 64 (classifier hidden 32), batch 2..512.  Parameters live in the modules' flat buffers; the
+ * offsets (floats) of every tensor inside them are in the descriptor:
+ *   g_off: net.0.weight/bias, net.1.weight/bias, net.3.*, net.4.*, net.6.*, net.7.*, net.9.weight/bias      (14)
+ *   d_off: net.{0,2,4,6}.weight_orig, then net.{0,2,4,6}.bias                                             (8)
+ *   c_off: net.{0,2,4}.weight/bias                                                                       (6)
+ * Adam runs over the first nG_adam / nD_adam floats of the flat buffers (the optimizer's one segment), with the arithmetic of
+ * pcg_adam_step_capturable (betas, eps, lr; weight decay 0) and its device step counter, advanced by one per iteration.   */
+typedef struct pcg_moons_cf_desc {
+  int32_t hidden, clf_hidden, B, N;        /* hidden 32 | 64, clf_hidden 32, batch 2..512, training rows            */
+  int32_t nG, nD, nC, nG_adam, nD_adam;    /* flat lengths (floats) and the Adam spans                             */
+  int32_t g_off[14], d_off[8], c_off[6];
+  double lr_G, lr_D, beta1, beta2, adam_eps;
+  float bn_eps, bn_momentum, sn_eps, slope;
+  float lambda_cls, lambda_l1, lambda_l2, lambda_mask;
+} pcg_moons_cf_desc;
+
+/* State of one model (every pointer per model, so that several models can later be strided one per workgroup). */
+typedef struct pcg_moons_cf_train_args {
+  const float* X; const int64_t* Y;        /* the training set in HBM: [N][2], [N]                                 */
+  const int64_t* rows;                     /* [n_steps][B] row indices into X / Y (the DataLoader's order)          */
+  const int64_t* target_y;                 /* [n_steps][B] trainer.py:64-65                                         */
+  const float* mask;                       /* [n_steps][B][2] trainer.py:69                                         */
+  float* g_flat; float* d_flat; const float* c_flat;
+  float* g_exp_avg; float* g_exp_avg_sq; int64_t* g_step;
+  float* d_exp_avg; float* d_exp_avg_sq; int64_t* d_step;
+  float* bn_mean[3]; float* bn_var[3]; int64_t* bn_nbt[3];
+  float* sn_u[4]; float* sn_v[4];
+  float* logs;                             /* [n_steps][9]: D_loss, G_loss, mean sigmoid(D_real), mean sigmoid(D_fake),
+                                              g_adv, g_cls, reg_l1, reg_l2, mask_pen (trainer.py:101-113)               */
+  float* scratch; size_t scratch_bytes;    /* activations that do not fit in LDS (pcg_moons_cf_scratch_bytes)       */
+} pcg_moons_cf_train_args;
+
+/* Bytes of global activation scratch a train / forward launch with this descriptor needs (0: the train step keeps them in LDS). */
+size_t pcg_moons_cf_scratch_bytes(const pcg_moons_cf_desc* desc, int32_t forward);
+/* n_steps consecutive iterations of train_countergan's batch loop (trainer.py:58-113) in ONE launch of one workgroup: batch gather,
+ * G forward in training mode (BatchNorm batch statistics, running statistics updated, momentum, unbiased variance, +1 batch),
+ * critic step (D(real), D(fake) with one power iteration each, D_loss = -mean D_real + mean D_fake, backward through both passes and
+ * through sigma, Adam D), generator step (a third power iteration, frozen classifier, G_loss with the four regularisers, backward
+ * to G, Adam G), the nine logged scalars.  Weights, moments and buffers are read once and written once per launch.          */
+int pcg_moons_cf_train_steps(const pcg_moons_cf_desc* desc, const pcg_moons_cf_train_args* args, int32_t n_steps, pcg_stream_t stream);
+
+/* Forward of one net, one workgroup: which = 0 generator (models/generator.py:20-24; out0 = raw_residual, out1 = masked_residual;
+ * train: batch statistics and running-statistics update, else running statistics), 1 critic (discriminator.py:20-22; train: one
+ * power iteration that updates u / v, else sigma from the stored u / v; out0 [B][1]), 2 classifier (nn_classifier.py:14-15;
+ * out0 = logits [B][3]).  onehot [B][3] for 0 and 1, mask [B][2] for 0.  params = the net's flat buffer.                  */
+typedef struct pcg_moons_cf_fwd_args {
+  int32_t which, train, B;
+  const float* x; const float* onehot; const float* mask;
+  float* params;
+  float* bn_mean[3]; float* bn_var[3]; int64_t* bn_nbt[3];
+  float* sn_u[4]; float* sn_v[4];
+  float* out0; float* out1;
+  float* scratch; size_t scratch_bytes;
+} pcg_moons_cf_fwd_args;
+int pcg_moons_cf_forward(const pcg_moons_cf_desc* desc, const pcg_moons_cf_fwd_args* args, pcg_stream_t stream);
+
 /* ---- calibration (diagnostics; not on the step's path) -----------------------------------------------------------------------
  * What THIS box's fp32 matrix pipe and HBM sustain right now — bench.py prints it next to the step (`calib`) so that a run on a
  * slower-clocked box can be told from a slower kernel (the reference has nothing comparable: it publishes no performance numbers,

@@ -68,6 +68,30 @@ class InXform(ctypes.Structure):
     _fields_ = [("scale", _P), ("shift", _P), ("act", _I), ("slope", ctypes.c_float)]
 
 
+class MoonsCfDesc(ctypes.Structure):
+    """pcg_moons_cf_desc (include/pcgan_hip.h)."""
+    _fields_ = ([(n, _I) for n in ("hidden", "clf_hidden", "B", "N", "nG", "nD", "nC", "nG_adam", "nD_adam")] +
+                [("g_off", _I * 14), ("d_off", _I * 8), ("c_off", _I * 6)] +
+                [(n, ctypes.c_double) for n in ("lr_G", "lr_D", "beta1", "beta2", "adam_eps")] +
+                [(n, ctypes.c_float) for n in ("bn_eps", "bn_momentum", "sn_eps", "slope", "lambda_cls", "lambda_l1", "lambda_l2",
+                                               "lambda_mask")])
+
+
+class MoonsCfTrainArgs(ctypes.Structure):
+    """pcg_moons_cf_train_args."""
+    _fields_ = ([(n, _P) for n in ("X", "Y", "rows", "target_y", "mask", "g_flat", "d_flat", "c_flat", "g_exp_avg", "g_exp_avg_sq", "g_step",
+                                   "d_exp_avg", "d_exp_avg_sq", "d_step")] +
+                [("bn_mean", _P * 3), ("bn_var", _P * 3), ("bn_nbt", _P * 3), ("sn_u", _P * 4), ("sn_v", _P * 4)] +
+                [("logs", _P), ("scratch", _P), ("scratch_bytes", ctypes.c_size_t)])
+
+
+class MoonsCfFwdArgs(ctypes.Structure):
+    """pcg_moons_cf_fwd_args."""
+    _fields_ = ([(n, _I) for n in ("which", "train", "B")] + [(n, _P) for n in ("x", "onehot", "mask", "params")] +
+                [("bn_mean", _P * 3), ("bn_var", _P * 3), ("bn_nbt", _P * 3), ("sn_u", _P * 4), ("sn_v", _P * 4)] +
+                [("out0", _P), ("out1", _P), ("scratch", _P), ("scratch_bytes", ctypes.c_size_t)])
+
+
 _c = ctypes
 _vp, _f, _i, _i64, _sz = _c.c_void_p, _c.c_float, _c.c_int, _c.c_int64, _c.c_size_t
 _d = _c.c_double
@@ -276,6 +300,9 @@ PROTOTYPES = {
     "pcg_mean_workspace_bytes": (_sz, []),
     "pcg_mean_fwd": (_i, [_vp, _i64, _vp, _vp, _sz, _vp]),
     "pcg_mean_bwd": (_i, [_vp, _f, _i64, _vp, _vp]),
+    "pcg_moons_cf_scratch_bytes": (_sz, [_c.POINTER(MoonsCfDesc), _i32]),
+    "pcg_moons_cf_train_steps": (_i, [_c.POINTER(MoonsCfDesc), _c.POINTER(MoonsCfTrainArgs), _i32, _vp]),
+    "pcg_moons_cf_forward": (_i, [_c.POINTER(MoonsCfDesc), _c.POINTER(MoonsCfFwdArgs), _vp]),
     "pcg_spectral_norm_fwd": (_i, [_vp, _i32, _i32, _vp, _vp, _f, _i, _vp, _vp, _vp, _vp, _vp]),
     "pcg_spectral_norm_bwd": (_i, [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _i, _vp]),
 }
