@@ -969,6 +969,54 @@ typedef struct pcg_moons_cf_fwd_args {
 } pcg_moons_cf_fwd_args;
 int pcg_moons_cf_forward(const pcg_moons_cf_desc* desc, const pcg_moons_cf_fwd_args* args, pcg_stream_t stream);
 
+/* ---- whole-batch dense layers: nn.Linear (+ nn.BatchNorm1d) (+ activation) for at most 128 rows (csrc/dense_rows.hip) ----------
+ * The MLP GAN of simple_gan/mnist/mnist_gan.py (Generator :44-59, Discriminator :70-77) at batch 64: every operand is dense row-major
+ * fp32, activations [R][features], weights [out][in] as nn.Linear stores them, 1 <= R <= 128.  One workgroup owns ALL rows of 16
+ * output columns, so BatchNorm1d's batch statistics are complete inside it: no partials, no finalize launch, no second pass.
+ * fp32 on v_mfma_f32_16x16x4_f32, fixed summation order (bitwise repeatable).  No workspace.  Refused with PCG_ERR_INVALID and a
+ * pcg_last_error text: R outside 1..128, R < 2 with training-mode BatchNorm (forward or backward), in_features % 4 != 0 in the
+ * forward, x / W not 16-byte aligned in the forward, an unknown activation.
+ *
+ *   pcg_dense_rows_fwd    y[R][O] = act(BN(x[R][I] W^T + bias))            replaces nn.Linear + nn.BatchNorm1d(O, 0.8) + nn.LeakyReLU /
+ *                         nn.Tanh / nn.Sigmoid (mnist_gan.py:46-58,71-76).  bn NULL: no BatchNorm.  bn->training: normalise with the batch
+ *                         mean and biased variance, write save_mean / save_invstd [O] and (nullable) xhat [R][O] for the backward, update
+ *                         running_mean / running_var (momentum, unbiased variance; nullable) and num_batches_tracked (int64, nullable) in
+ *                         the same launch.  Evaluation mode normalises with the running statistics.  bias nullable.
+ *   pcg_dense_rows_dgrad  g = (dz[R][O] W) * act'(y_below), then, with bn, the BatchNorm backward of the layer below:
+ *                         dbeta (+)= sum_r g, dgamma (+)= sum_r g xhat, dx = gamma invstd (g - mean_r g - xhat mean_r(g xhat)); without
+ *                         bn dx = g; below_act PCG_ACT_NONE and bn NULL: plain dx = dz W (the image gradient, mnist_gan.py:126 through D).
+ *                         act' is taken from the layer's OUTPUT y_below[R][I] (LeakyReLU: its sign).
+ *   pcg_dense_rows_wgrad  dW[O][I] (+)= dz^T x, db[O] (+)= column sums of dz (db nullable); one workgroup per 64x64 tile of dW reduces
+ *                         over all rows: no slab split, no tickets.  Writes straight into the flat gradient buffer (mnist_gan.py:126,133). */
+typedef struct {
+  const float* gamma;            /* [O] */
+  const float* beta;             /* [O] */
+  float* running_mean;           /* [O]; training: nullable */
+  float* running_var;            /* [O]; training: nullable */
+  int64_t* num_batches_tracked;  /* one element; nullable */
+  float* save_mean;              /* [O], written in training mode */
+  float* save_invstd;            /* [O], written in training mode */
+  float* xhat;                   /* [R][O] normalised pre-activation, nullable */
+  float eps;                     /* the reference passes 0.8 (mnist_gan.py:48 puts it in the eps slot) */
+  float momentum;
+  int32_t training;
+} pcg_dense_bn;
+typedef struct {
+  const float* xhat;    /* [R][I] as the forward saved it */
+  const float* gamma;   /* [I] */
+  const float* invstd;  /* [I] */
+  float* dgamma;        /* [I] */
+  float* dbeta;         /* [I] */
+  int32_t accumulate;   /* add to dgamma / dbeta instead of overwriting */
+} pcg_dense_bn_bwd;
+int pcg_dense_rows_fwd(const float* x, const float* W, const float* bias /*nullable*/, int32_t R, int32_t I, int32_t O,
+                       const pcg_dense_bn* bn /*nullable*/, int act, float slope, float* y, pcg_stream_t stream);
+int pcg_dense_rows_dgrad(const float* dz, const float* W, int32_t R, int32_t O, int32_t I, int below_act, float below_slope,
+                         const float* y_below /*nullable with PCG_ACT_NONE*/, const pcg_dense_bn_bwd* bn /*nullable*/, float* dx,
+                         pcg_stream_t stream);
+int pcg_dense_rows_wgrad(const float* dz, const float* x, int32_t R, int32_t O, int32_t I, float* dW, float* db /*nullable*/,
+                         int accumulate, pcg_stream_t stream);
+
 /* ---- calibration (diagnostics; not on the step's path) -----------------------------------------------------------------------
  * What THIS box's fp32 matrix pipe and HBM sustain right now — bench.py prints it next to the step (`calib`) so that a run on a
  * slower-clocked box can be told from a slower kernel (the reference has nothing comparable: it publishes no performance numbers,

@@ -92,6 +92,17 @@ class MoonsCfFwdArgs(ctypes.Structure):
                 [("out0", _P), ("out1", _P), ("scratch", _P), ("scratch_bytes", ctypes.c_size_t)])
 
 
+class DenseBn(ctypes.Structure):
+    """pcg_dense_bn."""
+    _fields_ = ([(n, _P) for n in ("gamma", "beta", "running_mean", "running_var", "num_batches_tracked", "save_mean", "save_invstd", "xhat")] +
+                [("eps", ctypes.c_float), ("momentum", ctypes.c_float), ("training", _I)])
+
+
+class DenseBnBwd(ctypes.Structure):
+    """pcg_dense_bn_bwd."""
+    _fields_ = [(n, _P) for n in ("xhat", "gamma", "invstd", "dgamma", "dbeta")] + [("accumulate", _I)]
+
+
 _c = ctypes
 _vp, _f, _i, _i64, _sz = _c.c_void_p, _c.c_float, _c.c_int, _c.c_int64, _c.c_size_t
 _d = _c.c_double
@@ -303,6 +314,9 @@ PROTOTYPES = {
     "pcg_moons_cf_scratch_bytes": (_sz, [_c.POINTER(MoonsCfDesc), _i32]),
     "pcg_moons_cf_train_steps": (_i, [_c.POINTER(MoonsCfDesc), _c.POINTER(MoonsCfTrainArgs), _i32, _vp]),
     "pcg_moons_cf_forward": (_i, [_c.POINTER(MoonsCfDesc), _c.POINTER(MoonsCfFwdArgs), _vp]),
+    "pcg_dense_rows_fwd": (_i, [_vp, _vp, _vp, _i32, _i32, _i32, _c.POINTER(DenseBn), _i, _f, _vp, _vp]),
+    "pcg_dense_rows_dgrad": (_i, [_vp, _vp, _i32, _i32, _i32, _i, _f, _vp, _c.POINTER(DenseBnBwd), _vp, _vp]),
+    "pcg_dense_rows_wgrad": (_i, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _i, _vp]),
     "pcg_spectral_norm_fwd": (_i, [_vp, _i32, _i32, _vp, _vp, _f, _i, _vp, _vp, _vp, _vp, _vp]),
     "pcg_spectral_norm_bwd": (_i, [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _i, _vp]),
 }

@@ -984,6 +984,78 @@ def linear_wgrad(dy, x, B, O, I, dW, db=None, ldy=None, ldx=None, accumulate_w=F
                                int(bool(accumulate_w)), int(bool(accumulate_b)), _p(ws), nbytes, _p(tk), _stream()), "pcg_linear_wgrad")
 
 
+# ---- whole-batch dense layers, at most 128 rows (csrc/dense_rows.hip) ----------------------------------------------
+class DenseBN:
+    """The BatchNorm1d operands of dense_rows_fwd: parameters, buffers, and the tensors the launch leaves for the backward."""
+
+    def __init__(self, gamma, beta, running_mean, running_var, num_batches_tracked, eps, momentum=0.1, training=True, save_mean=None,
+                 save_invstd=None, xhat=None):
+        self.gamma, self.beta, self.running_mean, self.running_var, self.num_batches_tracked = gamma, beta, running_mean, running_var, num_batches_tracked
+        self.eps, self.momentum, self.training = float(eps), float(momentum), bool(training)
+        self.save_mean, self.save_invstd, self.xhat = save_mean, save_invstd, xhat
+
+
+def dense_rows_fwd(x, w, bias=None, act=_lib.ACT_NONE, slope=0.0, bn=None, out=None):
+    """y[R][O] = act(BN(x[R][I] w^T + bias)) in one launch, R <= 128 (pcg_dense_rows_fwd).  bn: a DenseBN; in training mode its
+    save_mean / save_invstd / xhat are allocated here when absent and filled by the launch."""
+    _chk(x, "x"); _chk(w, "w")
+    R, I = x.shape
+    O = w.shape[0]
+    if w.shape[1] != I:
+        raise _lib.PcgError(f"dense_rows_fwd: x has {I} features, the weight takes {w.shape[1]}")
+    y = out if out is not None else torch.empty((R, O), dtype=torch.float32, device=x.device)
+    _chk(y, "out")
+    ref = None
+    if bn is not None:
+        if bn.training:
+            if bn.save_mean is None:
+                bn.save_mean = torch.empty(O, dtype=torch.float32, device=x.device)
+            if bn.save_invstd is None:
+                bn.save_invstd = torch.empty(O, dtype=torch.float32, device=x.device)
+            if bn.xhat is None:
+                bn.xhat = torch.empty((R, O), dtype=torch.float32, device=x.device)
+        nbt = bn.num_batches_tracked if bn.training else None
+        if nbt is not None and nbt.dtype != torch.int64:
+            raise _lib.PcgError(f"dense_rows_fwd: num_batches_tracked must be int64, got {nbt.dtype}")
+        tr = bn.training
+        ref = ctypes.byref(_lib.DenseBn(_p(bn.gamma), _p(bn.beta), _p(bn.running_mean), _p(bn.running_var), _p(nbt), _p(bn.save_mean if tr else None),
+                                        _p(bn.save_invstd if tr else None), _p(bn.xhat if tr else None), bn.eps, bn.momentum, int(tr)))
+    check(_lib.load().pcg_dense_rows_fwd(_p(x), _p(w), _p(bias), R, I, O, ref, int(act), float(slope), _p(y), _stream()), "pcg_dense_rows_fwd")
+    return y
+
+
+def dense_rows_dgrad(dz, w, below_act=_lib.ACT_NONE, below_slope=0.0, y_below=None, bn=None, out=None):
+    """dx = (dz[R][O] w[O][I]) * act'(y_below), then the BatchNorm1d backward of the layer below when bn = (xhat, gamma, invstd,
+    dgamma, dbeta, accumulate) is given, in one launch (pcg_dense_rows_dgrad).  No activation and no bn: plain dx = dz w."""
+    _chk(dz, "dz"); _chk(w, "w")
+    R, O = dz.shape
+    I = w.shape[1]
+    if w.shape[0] != O:
+        raise _lib.PcgError(f"dense_rows_dgrad: dz has {O} features, the weight has {w.shape[0]} rows")
+    dx = out if out is not None else torch.empty((R, I), dtype=torch.float32, device=dz.device)
+    _chk(dx, "out")
+    if y_below is not None:
+        _chk(y_below, "y_below")
+    ref = None
+    if bn is not None:
+        xhat, gamma, invstd, dgamma, dbeta, acc = bn
+        ref = ctypes.byref(_lib.DenseBnBwd(_p(_chk(xhat, "xhat")), _p(gamma), _p(invstd), _p(dgamma), _p(dbeta), int(bool(acc))))
+    check(_lib.load().pcg_dense_rows_dgrad(_p(dz), _p(w), R, O, I, int(below_act), float(below_slope), _p(y_below), ref, _p(dx), _stream()),
+          "pcg_dense_rows_dgrad")
+    return dx
+
+
+def dense_rows_wgrad(dz, x, dW, db=None, accumulate=False):
+    """dW[O][I] (+)= dz^T x, db[O] (+)= column sums of dz over all R <= 128 rows in one launch (pcg_dense_rows_wgrad)."""
+    _chk(dz, "dz"); _chk(x, "x"); _chk(dW, "dW")
+    R, O = dz.shape
+    I = x.shape[1]
+    if x.shape[0] != R or tuple(dW.shape) != (O, I):
+        raise _lib.PcgError(f"dense_rows_wgrad: dz {tuple(dz.shape)}, x {tuple(x.shape)}, dW {tuple(dW.shape)} do not agree")
+    check(_lib.load().pcg_dense_rows_wgrad(_p(dz), _p(x), R, O, I, _p(dW), _p(db), int(bool(accumulate)), _stream()), "pcg_dense_rows_wgrad")
+    return dW
+
+
 def linear_wgrad_grouped(items, B, device):
     """items: list of (dy, x, O, I, dW, db or None, ldy, ldx, accumulate_w, accumulate_b) — layers that reduce over the same B rows,
     all in one launch (the library tiles them for the matrix cores)."""
