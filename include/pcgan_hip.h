@@ -1017,6 +1017,58 @@ int pcg_dense_rows_dgrad(const float* dz, const float* W, int32_t R, int32_t O, 
 int pcg_dense_rows_wgrad(const float* dz, const float* x, int32_t R, int32_t O, int32_t I, float* dW, float* db /*nullable*/,
                          int accumulate, pcg_stream_t stream);
 
+/* ---- moons GAN and conditional GAN: whole training iterations in one launch, one workgroup (csrc/moons_gan.hip) ----------------
+ * simple_gan/moons/make_moons_gan.py (build_generator :33-38, build_discriminator :40-46, the batch loop :61-88) and
+ * conditional_gan/moons/make_moons_cgan.py (Generator :35-46, Discriminator :48-60, the batch loop :90-129) are one family:
+ *   G: Linear(z_dim + label_dim -> hidden), ReLU, Linear(hidden -> 2)           on cat[z, onehot]
+ *   D: Linear(2 + label_dim -> hidden), ReLU, Linear(hidden -> 1), Sigmoid      on cat[x, onehot]
+ * with label_dim 0 for the simple GAN.  hidden 32 | 64 | 128, z_dim a multiple of 4 in [4, 64], label_dim 0 | 2, batch 1..256;
+ * anything else is refused with PCG_ERR_INVALID.  Parameters live in the modules' flat buffers:
+ *   g_off: first Linear weight [hidden][z_dim + label_dim], bias, second Linear weight [2][hidden], bias          (floats, in this order)
+ *   d_off: first Linear weight [hidden][2 + label_dim], bias, second Linear weight [1][hidden], bias
+ * Adam as in pcg_moons_cf_desc: pcg_adam_step_capturable's arithmetic over the first n*_adam floats, weight decay 0, the device step
+ * counters advanced by one per iteration.                                                                                       */
+typedef struct pcg_moons_gan_desc {
+  int32_t hidden, z_dim, label_dim, B, N;  /* B, N: batch and training rows (train only)                           */
+  int32_t nG, nD, nG_adam, nD_adam;        /* flat lengths (floats) and the Adam spans                             */
+  int32_t g_off[4], d_off[4];
+  double lr_G, lr_D, beta1, beta2, adam_eps;
+} pcg_moons_gan_desc;
+
+typedef struct pcg_moons_gan_train_args {
+  const float* X; const int64_t* Y;        /* the training set in HBM: [N][2], [N] (Y: label_dim > 0 only)          */
+  const int64_t* rows;                     /* [n_steps][B] rows of X / Y: the real batch of every iteration.  The caller checks the
+                                              range; the kernel clamps an index into [0, N) rather than read outside X.          */
+  const float* z;                          /* [n_steps][2][B][z_dim]: the D step's draw (:63 / :97), then the G step's (:78 / :116) */
+  const int64_t* labels;                   /* [n_steps][2][B] fake labels (cgan :98, :117); label_dim > 0 only       */
+  float* g_flat; float* d_flat;
+  float* g_exp_avg; float* g_exp_avg_sq; int64_t* g_step;
+  float* d_exp_avg; float* d_exp_avg_sq; int64_t* d_step;
+  float* logs;                             /* [n_steps][2]: loss_D, loss_G                                          */
+  float* scratch; size_t scratch_bytes;    /* activations that do not fit in LDS (pcg_moons_gan_scratch_bytes), 16-byte aligned */
+} pcg_moons_gan_train_args;
+
+/* Bytes of global activation scratch a train launch with this descriptor needs (0: everything stays in LDS, as at 50 x 128). */
+size_t pcg_moons_gan_scratch_bytes(const pcg_moons_gan_desc* desc);
+/* n_steps consecutive iterations of the batch loop (make_moons_gan.py:62-87, make_moons_cgan.py:91-129) in ONE launch of one
+ * workgroup.  D step: fake = G(z_d), loss_D = -mean(log D(real) + log(1 - D(fake))), D's gradients only (what flows into G there is
+ * discarded by the reference: zero_grad :85 / detach :105), Adam D.  G step: fake = G(z_g), loss_G = -mean(log D(fake)) with the
+ * updated D, backward through D into G, Adam G.  Both losses and their gradients are formed from D's logit a (-log D =
+ * softplus(-a), -log(1 - D) = softplus(a)): equal to the reference's expression in exact arithmetic and finite where its bare log
+ * of a saturated sigmoid is inf.  fp32, fixed summation order: n steps in one launch are bit-identical to n launches of one.
+ * Weights and moments are read once and written once per launch.                                                                */
+int pcg_moons_gan_train_steps(const pcg_moons_gan_desc* desc, const pcg_moons_gan_train_args* args, int32_t n_steps, pcg_stream_t stream);
+
+/* Forward of one net over R rows, a grid over blocks of 64 rows: which = 0 generator (make_moons_gan.py:112, make_moons_cgan.py:44-46,
+ * :155; x = z [R][z_dim], 16-byte aligned, out [R][2]), 1 discriminator (:66-68 / :58-60; x [R][2], out [R][1], probabilities).
+ * onehot [R][label_dim] floats (label_dim > 0 only).  params: the net's flat buffer.                                             */
+typedef struct pcg_moons_gan_fwd_args {
+  int32_t which; int64_t R;
+  const float* x; const float* onehot; const float* params;
+  float* out;
+} pcg_moons_gan_fwd_args;
+int pcg_moons_gan_forward(const pcg_moons_gan_desc* desc, const pcg_moons_gan_fwd_args* args, pcg_stream_t stream);
+
 /* ---- calibration (diagnostics; not on the step's path) -----------------------------------------------------------------------
  * What THIS box's fp32 matrix pipe and HBM sustain right now — bench.py prints it next to the step (`calib`) so that a run on a
  * slower-clocked box can be told from a slower kernel (the reference has nothing comparable: it publishes no performance numbers,

@@ -92,6 +92,23 @@ class MoonsCfFwdArgs(ctypes.Structure):
                 [("out0", _P), ("out1", _P), ("scratch", _P), ("scratch_bytes", ctypes.c_size_t)])
 
 
+class MoonsGanDesc(ctypes.Structure):
+    """pcg_moons_gan_desc."""
+    _fields_ = ([(n, _I) for n in ("hidden", "z_dim", "label_dim", "B", "N", "nG", "nD", "nG_adam", "nD_adam")] +
+                [("g_off", _I * 4), ("d_off", _I * 4)] + [(n, ctypes.c_double) for n in ("lr_G", "lr_D", "beta1", "beta2", "adam_eps")])
+
+
+class MoonsGanTrainArgs(ctypes.Structure):
+    """pcg_moons_gan_train_args."""
+    _fields_ = ([(n, _P) for n in ("X", "Y", "rows", "z", "labels", "g_flat", "d_flat", "g_exp_avg", "g_exp_avg_sq", "g_step",
+                                   "d_exp_avg", "d_exp_avg_sq", "d_step", "logs", "scratch")] + [("scratch_bytes", ctypes.c_size_t)])
+
+
+class MoonsGanFwdArgs(ctypes.Structure):
+    """pcg_moons_gan_fwd_args."""
+    _fields_ = [("which", _I), ("R", ctypes.c_int64)] + [(n, _P) for n in ("x", "onehot", "params", "out")]
+
+
 class DenseBn(ctypes.Structure):
     """pcg_dense_bn."""
     _fields_ = ([(n, _P) for n in ("gamma", "beta", "running_mean", "running_var", "num_batches_tracked", "save_mean", "save_invstd", "xhat")] +
@@ -314,6 +331,9 @@ PROTOTYPES = {
     "pcg_moons_cf_scratch_bytes": (_sz, [_c.POINTER(MoonsCfDesc), _i32]),
     "pcg_moons_cf_train_steps": (_i, [_c.POINTER(MoonsCfDesc), _c.POINTER(MoonsCfTrainArgs), _i32, _vp]),
     "pcg_moons_cf_forward": (_i, [_c.POINTER(MoonsCfDesc), _c.POINTER(MoonsCfFwdArgs), _vp]),
+    "pcg_moons_gan_scratch_bytes": (_sz, [_c.POINTER(MoonsGanDesc)]),
+    "pcg_moons_gan_train_steps": (_i, [_c.POINTER(MoonsGanDesc), _c.POINTER(MoonsGanTrainArgs), _i32, _vp]),
+    "pcg_moons_gan_forward": (_i, [_c.POINTER(MoonsGanDesc), _c.POINTER(MoonsGanFwdArgs), _vp]),
     "pcg_dense_rows_fwd": (_i, [_vp, _vp, _vp, _i32, _i32, _i32, _c.POINTER(DenseBn), _i, _f, _vp, _vp]),
     "pcg_dense_rows_dgrad": (_i, [_vp, _vp, _i32, _i32, _i32, _i, _f, _vp, _c.POINTER(DenseBnBwd), _vp, _vp]),
     "pcg_dense_rows_wgrad": (_i, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _i, _vp]),
