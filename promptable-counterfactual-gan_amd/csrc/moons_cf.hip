@@ -10,9 +10,7 @@
 //   global     the training set, the per-step rows / targets / masks, the frozen classifier's parameters (read through L2)
 // Every reduction has a fixed order (wave butterflies, then waves in order; column sums in fixed row partitions): a launch of
 // n steps is bit-identical to n launches of one.
-#include "pcg_common.h"
-
-#include <math.h>
+#include "epoch_wg.h"
 
 namespace pcg {
 namespace {
@@ -20,12 +18,6 @@ namespace {
 constexpr int NT = 256;                                  // four waves; wave l runs layer l's power iteration
 constexpr int F = 2, NC = 3, GIN = 2 * F + NC, DIN = F + NC, CH = 32;
 constexpr int NLOG = 9;
-constexpr size_t LDS_CAP = 160 * 1024;
-
-__device__ __forceinline__ float wave_sum(float v) {
-  for (int s = 32; s > 0; s >>= 1) v += __shfl_xor(v, s, 64);
-  return v;
-}
 
 // K block-wide sums in one pair of barriers; every thread receives all K.  red: 4*K floats.
 template <int K>
@@ -129,8 +121,6 @@ struct Dims {
   static constexpr int dmax() { return DIN * H + H + H * (H / 2) + H / 2 + (H / 2) * (H / 2) + H / 2 + H / 2 + 1 + 4 * 8; }
   static constexpr int SG = (gmax() + NT - 1) / NT, SD = (dmax() + NT - 1) / NT;
 };
-
-__host__ __device__ inline int r4(int n) { return (n + 3) & ~3; }
 
 // Activation layout, floats, every matrix row-major [B][width].  The classifier's three matrices of the generator step overlay
 // the real pass's critic activations, dead by then.
@@ -348,25 +338,8 @@ __device__ void c_forward(const float* x, int ldx, const float* P, const int* co
   __syncthreads();
 }
 
-struct AdamK { float w1, one_minus_w1, beta2, one_minus_beta2, eps; };
-
-// pointwise.hip adam_one (torch's lerp / addcmul / bias-corrected step), weight decay 0
-__device__ __forceinline__ void adam_upd(float& p, float g, float& m, float& v, const AdamK& k, float step_size, float bc2_sqrt) {
-  m = (k.w1 < 0.5f) ? fmaf(k.w1, g - m, m) : g - (g - m) * k.one_minus_w1;
-  v = fmaf(v, k.beta2, k.one_minus_beta2 * g * g);
-  const float denom = sqrtf(v) / bc2_sqrt + k.eps;
-  p = p - step_size * (m / denom);
-}
-
-__device__ __forceinline__ AdamK adam_k(const pcg_moons_cf_desc& d) {
-  return AdamK{(float)(1.0 - d.beta1), (float)(1.0 - (1.0 - d.beta1)), (float)d.beta2, (float)(1.0 - d.beta2), (float)d.adam_eps};
-}
-
-__device__ __forceinline__ void adam_corr(double lr, double beta1, double beta2, int64_t t, float& step_size, float& bc2_sqrt) {
-  const double bc1 = 1.0 - pow(beta1, (double)t);
-  bc2_sqrt = (float)sqrt(1.0 - pow(beta2, (double)t));
-  step_size = (float)(lr / bc1);
-}
+// beta^t for adam_corr: pow() on every thread (moons_gan.hip has binary exponentiation on one thread; each kernel keeps its own)
+__device__ __forceinline__ double pow_t(double beta, int64_t t) { return pow(beta, (double)t); }
 
 template <int H>
 __global__ void __launch_bounds__(NT) moons_cf_train_kernel(const pcg_moons_cf_desc d, const pcg_moons_cf_train_args a, int n_steps,
@@ -491,7 +464,7 @@ __global__ void __launch_bounds__(NT) moons_cf_train_kernel(const pcg_moons_cf_d
     sn_backward<H>(tmp, dP, woff, su[0], sv[0], sig, dG, true, red);
     {
       float ss, bc2;
-      adam_corr(d.lr_D, d.beta1, d.beta2, d_step0 + it + 1, ss, bc2);
+      adam_corr(d.lr_D, d.beta1, d.beta2, d_step0 + it + 1, pow_t, ss, bc2);
 #pragma unroll
       for (int s = 0; s < Dm::SD; ++s) {
         const int i = tid + s * NT;
@@ -596,7 +569,7 @@ __global__ void __launch_bounds__(NT) moons_cf_train_kernel(const pcg_moons_cf_d
     }
     {
       float ss, bc2;
-      adam_corr(d.lr_G, d.beta1, d.beta2, g_step0 + it + 1, ss, bc2);
+      adam_corr(d.lr_G, d.beta1, d.beta2, g_step0 + it + 1, pow_t, ss, bc2);
 #pragma unroll
       for (int s = 0; s < Dm::SG; ++s) {
         const int i = tid + s * NT;
@@ -721,15 +694,9 @@ __global__ void __launch_bounds__(NT) moons_cf_forward_kernel(const pcg_moons_cf
   }
 }
 
-template <int H>
-size_t train_lds_fixed(const pcg_moons_cf_desc& d) { return sizeof(float) * (size_t)smem_layout(H, d.nG, d.nD).total; }
+size_t fixed_bytes(const pcg_moons_cf_desc& d) { return sizeof(float) * (size_t)smem_layout(d.hidden, d.nG, d.nD).total; }
 
 size_t act_bytes(const pcg_moons_cf_desc& d) { return sizeof(float) * (size_t)act_layout(d.hidden, d.B).total; }
-
-bool acts_in_lds(const pcg_moons_cf_desc& d) {
-  const size_t fixed = d.hidden == 32 ? train_lds_fixed<32>(d) : train_lds_fixed<64>(d);
-  return fixed + act_bytes(d) <= LDS_CAP;
-}
 
 size_t fwd_bytes(const pcg_moons_cf_desc& d, int B) {
   const int H = d.hidden;
@@ -761,7 +728,7 @@ using namespace pcg;
 extern "C" size_t pcg_moons_cf_scratch_bytes(const pcg_moons_cf_desc* desc, int32_t forward) {
   if (check_desc(desc) != PCG_OK) return 0;
   if (forward) return fwd_bytes(*desc, desc->B);
-  return acts_in_lds(*desc) ? 0 : act_bytes(*desc);
+  return acts_fit_lds(fixed_bytes(*desc), act_bytes(*desc)) ? 0 : act_bytes(*desc);
 }
 
 extern "C" int pcg_moons_cf_train_steps(const pcg_moons_cf_desc* desc, const pcg_moons_cf_train_args* args, int32_t n_steps,
@@ -774,22 +741,12 @@ extern "C" int pcg_moons_cf_train_steps(const pcg_moons_cf_desc* desc, const pcg
               "pcg_moons_cf_train_steps: null pointer");
   for (int l = 0; l < 3; ++l) PCG_REQUIRE(a.bn_mean[l] && a.bn_var[l] && a.bn_nbt[l], "pcg_moons_cf_train_steps: null BatchNorm buffer");
   for (int l = 0; l < 4; ++l) PCG_REQUIRE(a.sn_u[l] && a.sn_v[l], "pcg_moons_cf_train_steps: null spectral-norm vector");
-  const bool in_lds = acts_in_lds(*desc);
-  const size_t fixed = desc->hidden == 32 ? train_lds_fixed<32>(*desc) : train_lds_fixed<64>(*desc);
-  PCG_REQUIRE(fixed <= LDS_CAP, "pcg_moons_cf_train_steps: %zu bytes of LDS state exceed the CU's", fixed);
-  if (!in_lds) PCG_REQUIRE(a.scratch && a.scratch_bytes >= act_bytes(*desc), "pcg_moons_cf_train_steps: scratch %zu bytes < %zu needed",
-                           a.scratch_bytes, act_bytes(*desc));
-  const size_t lds = fixed + (in_lds ? act_bytes(*desc) : 0);
-  const void* fn = desc->hidden == 32 ? reinterpret_cast<const void*>(&moons_cf_train_kernel<32>)
-                                      : reinterpret_cast<const void*>(&moons_cf_train_kernel<64>);
-  hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) { set_error("hipFuncSetAttribute(max dynamic LDS=%zu): %s", lds, hipGetErrorString(e)); return PCG_ERR_LAUNCH; }
-  hipStream_t s = (hipStream_t)stream;
-  if (desc->hidden == 32)
-    hipLaunchKernelGGL(moons_cf_train_kernel<32>, dim3(1), dim3(NT), lds, s, *desc, a, (int)n_steps, (int)in_lds);
-  else
-    hipLaunchKernelGGL(moons_cf_train_kernel<64>, dim3(1), dim3(NT), lds, s, *desc, a, (int)n_steps, (int)in_lds);
-  return launch_status("moons_cf_train_kernel");
+  bool in_lds;
+  size_t lds;
+  if (int rc = place_acts("pcg_moons_cf_train_steps", fixed_bytes(*desc), act_bytes(*desc), a.scratch, a.scratch_bytes, sizeof(float), in_lds, lds))
+    return rc;
+  return launch_one_wg(desc->hidden == 32 ? moons_cf_train_kernel<32> : moons_cf_train_kernel<64>, "moons_cf_train_kernel", NT, lds,
+                       (hipStream_t)stream, *desc, a, (int)n_steps, (int)in_lds);
 }
 
 extern "C" int pcg_moons_cf_forward(const pcg_moons_cf_desc* desc, const pcg_moons_cf_fwd_args* args, pcg_stream_t stream) {

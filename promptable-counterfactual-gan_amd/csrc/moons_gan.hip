@@ -18,9 +18,7 @@
 // (lane butterflies, rows in order, partitions in order): n steps in one launch are bit-identical to n launches of one step.
 // The losses are taken from the logit a of D: -log D = softplus(-a), -log(1 - D) = softplus(a), finite where the reference's
 // log(sigmoid(a)) gives inf.
-#include "pcg_common.h"
-
-#include <math.h>
+#include "epoch_wg.h"
 
 namespace pcg {
 namespace {
@@ -29,9 +27,6 @@ constexpr int NT = 512, LPR = 16, GROUPS = NT / LPR;      // 8 waves (256 regist
 constexpr int RT = 2;                                      // batch rows per lane group in the G passes: one weight read, two rows
 constexpr int MAXB = 256, MAXZ = 64, MAXL = 2, NQ = 6;    // NQ: per-j partial sums of phase 2 (dV1[j][0..3], dc1[j], dV2[j])
 constexpr int FWD_NT = 256, FWD_ROWS = 64;                // forward: 16 lane groups, four passes per block
-constexpr size_t LDS_CAP = 160 * 1024;
-
-__host__ __device__ constexpr int r4(int n) { return (n + 3) & ~3; }
 
 template <int H>
 struct Dims {
@@ -78,22 +73,7 @@ __device__ __forceinline__ void load_units(const float* v, int l, float (&w)[Dim
   }
 }
 
-__device__ __forceinline__ float wave_sum(float v) {
-  for (int s = 32; s > 0; s >>= 1) v += __shfl_xor(v, s, 64);
-  return v;
-}
-
 __device__ __forceinline__ float softplus(float x) { return fmaxf(x, 0.f) + log1pf(expf(-fabsf(x))); }
-
-struct AdamK { float w1, one_minus_w1, beta2, one_minus_beta2, eps; };
-
-// pointwise.hip adam_one (torch's lerp / addcmul / bias-corrected step), weight decay 0
-__device__ __forceinline__ void adam_upd(float& p, float g, float& m, float& v, const AdamK& k, float step_size, float bc2_sqrt) {
-  m = (k.w1 < 0.5f) ? fmaf(k.w1, g - m, m) : g - (g - m) * k.one_minus_w1;
-  v = fmaf(v, k.beta2, k.one_minus_beta2 * g * g);
-  const float denom = sqrtf(v) / bc2_sqrt + k.eps;
-  p = p - step_size * (m / denom);
-}
 
 // beta^t by binary exponentiation in double: a function of t alone, so a launch of n steps and n launches of one step form the
 // same corrections bit for bit, at a few dozen multiplications where pow() costs hundreds of fp64 instructions per call.  Within
@@ -105,13 +85,6 @@ __device__ __forceinline__ double ipow(double b, int64_t t) {
     b *= b;
   }
   return r;
-}
-
-// pcg_adam_step_capturable's bias corrections for step t: step_size = lr / (1 - beta1^t), bc2_sqrt = sqrt(1 - beta2^t)
-__device__ __forceinline__ void adam_corr(double lr, double beta1, double beta2, int64_t t, float& step_size, float& bc2_sqrt) {
-  const double bc1 = 1.0 - ipow(beta1, t);
-  bc2_sqrt = (float)sqrt(1.0 - ipow(beta2, t));
-  step_size = (float)(lr / bc1);
 }
 
 // Where flat element idx of G lives in LDS: W1 [H][GI] is kept transposed, [GI][H]; everything else at its flat offset.
@@ -265,6 +238,8 @@ __global__ void __launch_bounds__(NT) moons_gan_train_kernel(const pcg_moons_gan
     if (i == oc2) qD[s] = NQ;
   }
   const int64_t g_step0 = a.g_step[0], d_step0 = a.d_step[0];
+  // adam_k(d), spelled out as it was: through the function the compiler reuses 1 - beta1 for 1 - (1 - beta1) (the same value, one
+  // fp64 add fewer), which moves the code of the six train kernels and their time with it (measured: -1.4 %); not in a refactor
   const AdamK ak{(float)(1.0 - d.beta1), (float)(1.0 - (1.0 - d.beta1)), (float)d.beta2, (float)(1.0 - d.beta2), (float)d.adam_eps};
 
   // inputs of iteration `it`: both noise draws with their one-hot labels ([B][GIS], zero padded), the real rows with theirs
@@ -361,8 +336,8 @@ __global__ void __launch_bounds__(NT) moons_gan_train_kernel(const pcg_moons_gan
       q[0] = w0 * v2; q[H] = w1 * v2; q[2 * H] = w2 * v2; q[3 * H] = w3 * v2; q[4 * H] = sc1 * v2; q[5 * H] = sv2;
       if (j == 0) pc2[p] = sc2;
       if (tid == NT - 1) {                 // this iteration's Adam bias corrections, once (fp64), for phases 3 and 6
-        adam_corr(d.lr_D, d.beta1, d.beta2, d_step0 + it + 1, corr[0], corr[1]);
-        adam_corr(d.lr_G, d.beta1, d.beta2, g_step0 + it + 1, corr[2], corr[3]);
+        adam_corr(d.lr_D, d.beta1, d.beta2, d_step0 + it + 1, ipow, corr[0], corr[1]);
+        adam_corr(d.lr_G, d.beta1, d.beta2, g_step0 + it + 1, ipow, corr[2], corr[3]);
       }
     }
     __syncthreads();
@@ -566,7 +541,6 @@ size_t fixed_bytes(const pcg_moons_gan_desc& d) { return sizeof(float) * (size_t
 size_t act_bytes(const pcg_moons_gan_desc& d) {
   return sizeof(float) * (size_t)act_layout(d.hidden, d.B, d.z_dim + (d.label_dim ? 4 : 0)).total;
 }
-bool acts_in_lds(const pcg_moons_gan_desc& d) { return fixed_bytes(d) + act_bytes(d) <= LDS_CAP; }
 
 }  // namespace
 }  // namespace pcg
@@ -575,7 +549,7 @@ using namespace pcg;
 
 extern "C" size_t pcg_moons_gan_scratch_bytes(const pcg_moons_gan_desc* desc) {
   if (check_desc(desc, true) != PCG_OK) return 0;
-  return acts_in_lds(*desc) ? 0 : act_bytes(*desc);
+  return acts_fit_lds(fixed_bytes(*desc), act_bytes(*desc)) ? 0 : act_bytes(*desc);
 }
 
 extern "C" int pcg_moons_gan_train_steps(const pcg_moons_gan_desc* desc, const pcg_moons_gan_train_args* args, int32_t n_steps,
@@ -586,25 +560,16 @@ extern "C" int pcg_moons_gan_train_steps(const pcg_moons_gan_desc* desc, const p
   PCG_REQUIRE(a.X && a.rows && a.z && a.g_flat && a.d_flat && a.g_exp_avg && a.g_exp_avg_sq && a.g_step && a.d_exp_avg && a.d_exp_avg_sq &&
                   a.d_step && a.logs, "pcg_moons_gan_train_steps: null pointer");
   PCG_REQUIRE(desc->label_dim == 0 || (a.Y && a.labels), "pcg_moons_gan_train_steps: label_dim %d needs Y and labels", desc->label_dim);
-  const bool in_lds = acts_in_lds(*desc);
-  const size_t fixed = fixed_bytes(*desc);
-  PCG_REQUIRE(fixed <= LDS_CAP, "pcg_moons_gan_train_steps: %zu bytes of LDS state exceed the CU's", fixed);
-  if (!in_lds) PCG_REQUIRE(a.scratch && a.scratch_bytes >= act_bytes(*desc) && ((uintptr_t)a.scratch & 15) == 0,
-                           "pcg_moons_gan_train_steps: scratch %zu bytes < %zu needed (16-byte aligned)", a.scratch_bytes, act_bytes(*desc));
-  const size_t lds = fixed + (in_lds ? act_bytes(*desc) : 0);
+  bool in_lds;
+  size_t lds;
+  if (int rc = place_acts("pcg_moons_gan_train_steps", fixed_bytes(*desc), act_bytes(*desc), a.scratch, a.scratch_bytes, 16, in_lds, lds))
+    return rc;
   const int H = desc->hidden;
-  hipStream_t s = (hipStream_t)stream;
-  auto launch = [&](auto kernel) -> int {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) { set_error("hipFuncSetAttribute(max dynamic LDS=%zu): %s", lds, hipGetErrorString(e)); return PCG_ERR_LAUNCH; }
-    hipLaunchKernelGGL(kernel, dim3(1), dim3(NT), lds, s, *desc, a, (int)n_steps);
-    return PCG_OK;
+  auto launch = [&](auto kernel) {
+    return launch_one_wg(kernel, "moons_gan_train_kernel", NT, lds, (hipStream_t)stream, *desc, a, (int)n_steps);
   };
-  int rc;
-  if (in_lds) rc = H == 32 ? launch(moons_gan_train_kernel<32, true>) : H == 64 ? launch(moons_gan_train_kernel<64, true>) : launch(moons_gan_train_kernel<128, true>);
-  else rc = H == 32 ? launch(moons_gan_train_kernel<32, false>) : H == 64 ? launch(moons_gan_train_kernel<64, false>) : launch(moons_gan_train_kernel<128, false>);
-  if (rc != PCG_OK) return rc;
-  return launch_status("moons_gan_train_kernel");
+  if (in_lds) return H == 32 ? launch(moons_gan_train_kernel<32, true>) : H == 64 ? launch(moons_gan_train_kernel<64, true>) : launch(moons_gan_train_kernel<128, true>);
+  return H == 32 ? launch(moons_gan_train_kernel<32, false>) : H == 64 ? launch(moons_gan_train_kernel<64, false>) : launch(moons_gan_train_kernel<128, false>);
 }
 
 extern "C" int pcg_moons_gan_forward(const pcg_moons_gan_desc* desc, const pcg_moons_gan_fwd_args* args, pcg_stream_t stream) {

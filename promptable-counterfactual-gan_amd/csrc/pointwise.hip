@@ -2,7 +2,7 @@
 // All HBM-bound streaming kernels (float4 lane accesses, grid-stride).  Reference call sites are listed
 // next to each prototype in include/pcgan_hip.h.
 #include <cstdlib>
-#include "pcg_common.h"
+#include "epoch_wg.h"
 
 namespace pcg {
 namespace {
@@ -127,7 +127,7 @@ __global__ void __launch_bounds__(256) bce_logits_kernel(const float* __restrict
 // hyper[0] = lr / (1 - beta1^step) ; hyper[1] = sqrt(1 - beta2^step)
 struct AdamHyper { float step_size, bc2_sqrt; };
 
-struct AdamConst { float lr, w1, one_minus_w1, beta2, one_minus_beta2, eps, wd; int decoupled; };
+struct AdamConst { float lr; AdamK k; float wd; int decoupled; };
 
 __device__ __forceinline__ void adam_one(float& p, float g, float& m, float& v, const AdamConst& k, float step_size,
                                          float bc2_sqrt) {
@@ -135,13 +135,7 @@ __device__ __forceinline__ void adam_one(float& p, float g, float& m, float& v, 
     if (k.decoupled) p *= (1.f - k.lr * k.wd);   // AdamW
     else g = fmaf(k.wd, p, g);                   // Adam L2
   }
-  // [torch] exp_avg.lerp_(grad, 1-beta1): weight < 0.5 ? a + w(b-a) : b - (b-a)(1-w); the weights are formed in
-  // double on the host (as Python does) and rounded to fp32 once
-  m = (k.w1 < 0.5f) ? fmaf(k.w1, g - m, m) : g - (g - m) * k.one_minus_w1;
-  v = fmaf(v, k.beta2, k.one_minus_beta2 * g * g);
-  const float eps = k.eps;
-  const float denom = sqrtf(v) / bc2_sqrt + eps;
-  p = p - step_size * (m / denom);
+  adam_upd(p, g, m, v, k.k, step_size, bc2_sqrt);
 }
 
 // Capturable stepping without a separate "tick" launch: the step counter lives on the device; every thread reads it at entry and
@@ -256,8 +250,7 @@ __global__ void __launch_bounds__(1024) norm_sum_kernel(const float* __restrict_
 int adam_launch(float* param, const float* grad, float* m, float* v, int64_t n, double lr, double beta1, double beta2, double eps,
                 double wd, int decoupled, AdamHyper hy, int64_t* step_dev, AdamCache* cache_dev, hipStream_t s) {
   const bool al = al16(param) && al16(grad) && al16(m) && al16(v);
-  const AdamConst k{(float)lr, (float)(1.0 - beta1), (float)(1.0 - (1.0 - beta1)), (float)beta2, (float)(1.0 - beta2), (float)eps,
-                    (float)wd, decoupled};
+  const AdamConst k{(float)lr, adam_k(beta1, beta2, eps), (float)wd, decoupled};
   // 16-byte lanes over the bulk, the 1..3 trailing elements on three threads of block 0 (a flat buffer that ends in a bias of one
   // element — the WGAN-GP critic's Linear(1024, 1) — used to send all 25 M parameters down the scalar kernel)
   const int64_t bulk = al ? (n & ~(int64_t)3) : 0;

@@ -16,10 +16,11 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import ops
+from . import _epoch, ops
+from ._epoch import no_autograd, on_gpu      # (no_autograd: re-exported, moons.no_autograd)
 from ._lib import MoonsGanDesc, MoonsGanFwdArgs, MoonsGanTrainArgs, PcgError, load as _lib_load
 from .dcgan import _labels
-from .nn import BCELoss, HipSequential
+from .nn import BCELoss, HipSequential, _pad4
 from .optim import Adam
 
 config = {"n_samples": 2000, "z_dim": 32, "hidden_dim": 128, "batch_size": 50, "lr": 1e-3, "epochs": 500}   # :9-17
@@ -67,10 +68,6 @@ def train_step(generator, discriminator, optimizer_G, optimizer_D, real_batch, z
 HIDDEN_DIMS = (32, 64, 128)     # the kernel's instantiations
 MAX_Z, MAX_BATCH = 64, 256
 LABEL_DIMS = (0, 2)
-
-
-def _pad4(n):
-    return (n + 3) // 4 * 4
 
 
 def check_dims(z_dim, hidden_dim, label_dim=0, batch=None):
@@ -147,19 +144,11 @@ def _gan_desc(z_dim, hidden, label_dim, G=None, D=None, B=1, N=1):
     return d
 
 
-def no_autograd(net, *xs):
-    if torch.is_grad_enabled() and (any(p.requires_grad for p in net.parameters()) or any(x is not None and x.requires_grad for x in xs)):
-        raise PcgError(f"{type(net).__name__}: the fused forward has no autograd backward: call it under torch.no_grad(); train "
-                       "through train_gan / moons_cgan.train / TrainSteps")
-
-
 def gan_forward(net, which, x, onehot=None, label_dim=0):
     """One pcg_moons_gan_forward launch over all rows of x: which = 0 generator (x = z [R][z_dim] -> [R][2]), 1 discriminator
     (x [R][2] -> probabilities [R][1]).  onehot [R][label_dim] when label_dim > 0.  No autograd."""
-    net._ensure_flat()
+    on_gpu(net, x)
     dev = net.flat_params.device
-    if not x.is_cuda:
-        raise PcgError(f"{type(net).__name__}: input is on {x.device}; libpcgan_hip has no CPU path")
     z_dim, hidden, label_dim = net_dims(G=net, label_dim=label_dim) if which == 0 else net_dims(D=net, label_dim=label_dim)
     z_dim = 4 if z_dim is None else z_dim
     check_dims(z_dim, hidden, label_dim)
@@ -193,27 +182,15 @@ class TrainSteps:
     The contents of the parameters' .grad are NOT specified after a run (the kernel keeps gradients in LDS)."""
 
     def __init__(self, G, D, opt_G, opt_D, X, y=None, batch_size=50):
-        from .moons_countergan import _adam_segment
         z_dim, hidden, label_dim = net_dims(G, D)
         B = int(batch_size)
         check_dims(z_dim, hidden, label_dim, batch=B)
-        for opt, what in ((opt_G, "opt_G"), (opt_D, "opt_D")):     # (what needs no device is refused before the device is touched)
-            if type(opt) is not Adam:
-                raise PcgError(f"{what}: the fused step implements pcgan_amd.optim.Adam only")
-            if any(g["weight_decay"] != 0.0 for g in opt.param_groups):
-                raise PcgError(f"{what}: weight decay is not implemented in the fused step (the reference uses none)")
-        for net in (G, D):
-            net._ensure_flat()
-        dev = G.flat_params.device
-        if dev.type != "cuda" or D.flat_params.device != dev:
-            raise PcgError("TrainSteps: both nets must be on one GPU")
-        self.sg, gg = _adam_segment(opt_G, G, "opt_G")
-        self.sd, gd = _adam_segment(opt_D, D, "opt_D")
-        if tuple(gg["betas"]) != tuple(gd["betas"]) or gg["eps"] != gd["eps"]:
-            raise PcgError("TrainSteps: opt_G and opt_D must share betas and eps")
+        _epoch.check_adam_pair(opt_G, opt_D)                       # (what needs no device is refused before the device is touched)
+        dev = _epoch.one_gpu(G, D)
+        self.sg, self.sd = opt_G.flat_segment(G, "opt_G"), opt_D.flat_segment(D, "opt_D")
         self.G, self.D, self.opt_G, self.opt_D, self.B, self.device = G, D, opt_G, opt_D, B, dev
         self.z_dim, self.hidden, self.label_dim = z_dim, hidden, label_dim
-        self.X = torch.as_tensor(np.asarray(X), dtype=torch.float32).contiguous().to(dev)
+        self.X = _epoch.resident(X, torch.float32, dev)
         if self.X.dim() != 2 or self.X.shape[1] != 2 or self.X.shape[0] < 1:
             raise PcgError("TrainSteps: X must be [N][2]")
         self.N = self.X.shape[0]
@@ -226,17 +203,11 @@ class TrainSteps:
                 raise PcgError(f"TrainSteps: y must be [N] with values in [0, {label_dim})")
             self.Y = y.to(dev)
         self.launches = 0
-        d = self._make_desc()
-        nbytes = _lib_load().pcg_moons_gan_scratch_bytes(ctypes.byref(d))
-        self.scratch = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
-        self.scratch_bytes = nbytes
+        self.scratch, self.scratch_bytes = _epoch.alloc_scratch(_lib_load().pcg_moons_gan_scratch_bytes(ctypes.byref(self._make_desc())), dev)
 
     def _make_desc(self):
         d = _gan_desc(self.z_dim, self.hidden, self.label_dim, G=self.G, D=self.D, B=self.B, N=self.N)
-        d.nG_adam, d.nD_adam = self.sg["n"], self.sd["n"]
-        gg, gd = self.opt_G.param_groups[0], self.opt_D.param_groups[0]
-        d.lr_G, d.lr_D = float(gg["lr"]), float(gd["lr"])
-        d.beta1, d.beta2, d.adam_eps = float(gg["betas"][0]), float(gg["betas"][1]), float(gg["eps"])
+        _epoch.fill_adam_desc(d, self.opt_G, self.opt_D, self.sg, self.sd)
         return d
 
     def run(self, rows, z, labels=None, check=True):
@@ -263,11 +234,8 @@ class TrainSteps:
         if L:
             labels = torch.as_tensor(labels).to(dev, torch.int64).contiguous()
             a.Y, a.labels = self.Y.data_ptr(), labels.data_ptr()
-        a.g_flat, a.d_flat = self.G.flat_params.data_ptr(), self.D.flat_params.data_ptr()
-        a.g_exp_avg, a.g_exp_avg_sq, a.g_step = self.sg["exp_avg"].data_ptr(), self.sg["exp_avg_sq"].data_ptr(), self.sg["step"].data_ptr()
-        a.d_exp_avg, a.d_exp_avg_sq, a.d_step = self.sd["exp_avg"].data_ptr(), self.sd["exp_avg_sq"].data_ptr(), self.sd["step"].data_ptr()
+        _epoch.fill_state_args(a, self.G, self.D, self.sg, self.sd, self.scratch, self.scratch_bytes)
         a.logs = logs.data_ptr()
-        a.scratch, a.scratch_bytes = (self.scratch.data_ptr() if self.scratch_bytes else None), self.scratch_bytes
         ops.check(_lib_load().pcg_moons_gan_train_steps(ctypes.byref(d), ctypes.byref(a), n, ops._stream()), "pcg_moons_gan_train_steps")
         self.launches += 1
         return logs

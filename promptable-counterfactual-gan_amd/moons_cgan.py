@@ -16,7 +16,8 @@ import torch.nn as nn
 
 from . import ops
 from ._lib import PcgError
-from .moons import TrainSteps, check_dims, check_epoch, gan_forward, no_autograd, run_epochs
+from ._epoch import no_autograd, on_gpu
+from .moons import TrainSteps, check_dims, check_epoch, gan_forward, run_epochs
 from .nn import FlatModule
 from .optim import Adam
 
@@ -42,8 +43,7 @@ class Generator(FlatModule):
 
     def forward(self, z, label_onehot):
         check_dims(self.z_dim, self.hidden_dim, self.label_dim)
-        if not z.is_cuda:
-            raise PcgError(f"Generator: input is on {z.device}; libpcgan_hip has no CPU path")
+        on_gpu(self, z)
         no_autograd(self, z, label_onehot)
         return gan_forward(self, 0, z, label_onehot, label_dim=self.label_dim)
 
@@ -58,8 +58,7 @@ class Discriminator(FlatModule):
 
     def forward(self, x, label_onehot):
         check_dims(4, self.hidden_dim, self.label_dim)
-        if not x.is_cuda:
-            raise PcgError(f"Discriminator: input is on {x.device}; libpcgan_hip has no CPU path")
+        on_gpu(self, x)
         no_autograd(self, x, label_onehot)
         return gan_forward(self, 1, x, label_onehot, label_dim=self.label_dim)
 

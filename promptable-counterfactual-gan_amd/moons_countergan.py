@@ -20,7 +20,8 @@ import torch
 import torch.nn as nn
 from torch.nn.utils import spectral_norm
 
-from . import ops
+from . import _epoch, ops
+from ._epoch import no_autograd, on_gpu
 from ._lib import MoonsCfDesc, MoonsCfFwdArgs, MoonsCfTrainArgs, PcgError, load as _lib_load
 from .countergan import CrossEntropyLoss
 from .data import MinMax, _split_indices
@@ -97,12 +98,6 @@ def _check_dims(input_dim, hidden_dim, num_classes, clf_hidden=CLF_HIDDEN, batch
         raise PcgError(f"moons CounteRGAN kernels are built for a classifier of hidden width {CLF_HIDDEN}, got {clf_hidden}")
     if batch is not None and not 2 <= batch <= MAX_BATCH:
         raise PcgError(f"moons CounteRGAN kernels take a batch of 2..{MAX_BATCH} rows, got {batch}")
-
-
-def _no_autograd(net, *xs):
-    if torch.is_grad_enabled() and (any(p.requires_grad for p in net.parameters()) or any(x is not None and x.requires_grad for x in xs)):
-        raise PcgError(f"{type(net).__name__}.forward has no autograd backward: call it under torch.no_grad() (or with requires_grad "
-                       "off); train through moons_countergan.train_countergan / TrainSteps")
 
 
 def _offsets(net, names):
@@ -189,12 +184,6 @@ def _chunks(B, can_split):
     return [(i, min(i + MAX_BATCH, B)) for i in range(0, B, MAX_BATCH)]
 
 
-def _on_gpu(net, x):
-    net._ensure_flat()
-    if not x.is_cuda:
-        raise PcgError(f"{type(net).__name__}: input is on {x.device}; libpcgan_hip has no CPU path")
-
-
 class ResidualGenerator(FlatModule):
     """models/generator.py:4-24.  forward(x, target_onehot, mask) -> (raw_residual, masked_residual); training mode uses the batch
     statistics and updates the running ones (momentum 0.1, unbiased variance, num_batches_tracked + 1), eval mode the running ones."""
@@ -212,8 +201,8 @@ class ResidualGenerator(FlatModule):
         _check_dims(self.input_dim, self.hidden_dim, self.num_classes, batch=x.shape[0] if self.training else None)
         if mask is None:
             raise PcgError("ResidualGenerator.forward: mask is required (generator.py:21 concatenates it)")
-        _on_gpu(self, x)
-        _no_autograd(self, x, target_onehot, mask)
+        on_gpu(self, x)
+        no_autograd(self, x, target_onehot, mask)
         outs = [_forward(0, self, self.hidden_dim, self.training, x[i:j], target_onehot[i:j], mask[i:j], G=self)
                 for i, j in _chunks(x.shape[0], not self.training)]
         return torch.cat([o[0] for o in outs]) if len(outs) > 1 else outs[0][0], torch.cat([o[1] for o in outs]) if len(outs) > 1 else outs[0][1]
@@ -234,8 +223,8 @@ class Discriminator(FlatModule):
 
     def forward(self, x, target_onehot):
         _check_dims(self.input_dim, self.hidden_dim, self.num_classes, batch=x.shape[0] if self.training else None)
-        _on_gpu(self, x)
-        _no_autograd(self, x, target_onehot)
+        on_gpu(self, x)
+        no_autograd(self, x, target_onehot)
         outs = [_forward(1, self, self.hidden_dim, self.training, x[i:j], target_onehot[i:j], D=self)[0]
                 for i, j in _chunks(x.shape[0], not self.training)]
         return torch.cat(outs) if len(outs) > 1 else outs[0]
@@ -252,8 +241,8 @@ class NNClassifier(FlatModule):
 
     def forward(self, x):
         _check_dims(self.input_dim, HIDDEN_DIMS[0], self.num_classes, clf_hidden=self.hidden_dim)
-        _on_gpu(self, x)
-        _no_autograd(self, x)
+        on_gpu(self, x)
+        no_autograd(self, x)
         outs = [_forward(2, self, HIDDEN_DIMS[0], False, x[i:j], C=self)[0] for i, j in _chunks(x.shape[0], True)]
         return torch.cat(outs) if len(outs) > 1 else outs[0]
 
@@ -307,24 +296,6 @@ def get_classifier(X_train, y_train, config):
 
 
 # ---- the fused training iterations -------------------------------------------------------------------------------------------
-def _adam_segment(opt, net, what):
-    """The optimizer's one state segment over `net`'s flat buffer (built now if it was not yet): what the kernel updates."""
-    net._ensure_flat()
-    if not isinstance(opt, Adam) or type(opt) is not Adam:
-        raise PcgError(f"{what}: the fused step implements pcgan_amd.optim.Adam only")
-    if opt._stale():
-        if opt._segments is not None and any(int(st["step"].item()) for b in opt._segments for st in b):
-            raise PcgError(f"{what}: parameter storage changed after optimisation started (module moved or re-flattened)")
-        opt._build()
-    segs = [st for b in opt._segments for st in b]
-    if len(segs) != 1 or segs[0]["param"].data_ptr() != net.flat_params.data_ptr():
-        raise PcgError(f"{what}: the optimizer must hold exactly the module's parameters (one flat segment)")
-    g = opt.param_groups[0]
-    if g["weight_decay"] != 0.0:
-        raise PcgError(f"{what}: weight decay is not implemented in the fused step (the reference uses none)")
-    return segs[0], g
-
-
 class TrainSteps:
     """Runs iterations of trainer.py:58-113 on the GPU, n per launch (pcg_moons_cf_train_steps).  Holds the training set in HBM and the
     activation scratch.  run(rows [n][B] int64, target_y [n][B] int64, mask [n][B][2] float32) -> logs [n][9] (LOG_FIELDS).
@@ -340,37 +311,22 @@ class TrainSteps:
         _check_dims(D.input_dim, D.hidden_dim, D.num_classes, clf_hidden=C.hidden_dim)
         if D.hidden_dim != G.hidden_dim:
             raise PcgError(f"TrainSteps: generator hidden {G.hidden_dim} and critic hidden {D.hidden_dim} differ (the kernel takes one)")
-        for net in (G, D, C):
-            net._ensure_flat()
-        dev = G.flat_params.device
-        if dev.type != "cuda" or D.flat_params.device != dev or C.flat_params.device != dev:
-            raise PcgError("TrainSteps: the three nets must be on one GPU")
+        dev = _epoch.one_gpu(G, D, C)
         self.G, self.D, self.C, self.B, self.device = G, D, C, B, dev
-        self.X = torch.as_tensor(np.asarray(X_train), dtype=torch.float32).contiguous().to(dev)
-        self.Y = torch.as_tensor(np.asarray(y_train), dtype=torch.int64).contiguous().to(dev)
+        self.X, self.Y = _epoch.resident(X_train, torch.float32, dev), _epoch.resident(y_train, torch.int64, dev)
         if self.X.dim() != 2 or self.X.shape[1] != INPUT_DIM or self.Y.shape != (self.X.shape[0],):
             raise PcgError(f"TrainSteps: X_train must be [N][{INPUT_DIM}] and y_train [N]")
         self.N = self.X.shape[0]
-        self.sg, gg = _adam_segment(opt_G, G, "opt_G")
-        self.sd, gd = _adam_segment(opt_D, D, "opt_D")
-        if tuple(gg["betas"]) != tuple(gd["betas"]) or gg["eps"] != gd["eps"]:
-            raise PcgError("TrainSteps: opt_G and opt_D must share betas and eps")
+        _epoch.check_adam_pair(opt_G, opt_D)
+        self.sg, self.sd = opt_G.flat_segment(G, "opt_G"), opt_D.flat_segment(D, "opt_D")
         self.opt_G, self.opt_D = opt_G, opt_D
         self.config = config
-        lib = _lib_load()
-        d = self._make_desc()
-        nbytes = lib.pcg_moons_cf_scratch_bytes(ctypes.byref(d), 0)
-        self.scratch = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
-        self.scratch_bytes = nbytes
+        self.scratch, self.scratch_bytes = _epoch.alloc_scratch(_lib_load().pcg_moons_cf_scratch_bytes(ctypes.byref(self._make_desc()), 0), dev)
 
     def _make_desc(self):
         G, D, C, cfg = self.G, self.D, self.C, self.config
         d = _desc(G.hidden_dim, self.B, G=G, D=D, C=C, N=self.N)
-        d.nG_adam, d.nD_adam = self.sg["n"], self.sd["n"]
-        gg, gd = self.opt_G.param_groups[0], self.opt_D.param_groups[0]
-        d.lr_G, d.lr_D = float(gg["lr"]), float(gd["lr"])
-        d.beta1, d.beta2 = float(gg["betas"][0]), float(gg["betas"][1])
-        d.adam_eps = float(gg["eps"])
+        _epoch.fill_adam_desc(d, self.opt_G, self.opt_D, self.sg, self.sd)
         d.lambda_cls, d.lambda_l1 = float(cfg["lambda_cls"]), float(cfg["lambda_reg_l1"])
         d.lambda_l2, d.lambda_mask = float(cfg["lambda_reg_l2"]), float(cfg["lambda_mask"])
         return d
@@ -395,12 +351,10 @@ class TrainSteps:
         a = MoonsCfTrainArgs()
         a.X, a.Y, a.rows, a.target_y, a.mask = (self.X.data_ptr(), self.Y.data_ptr(), rows.data_ptr(), target_y.data_ptr(),
                                                 mask.data_ptr())
-        a.g_flat, a.d_flat, a.c_flat = self.G.flat_params.data_ptr(), self.D.flat_params.data_ptr(), self.C.flat_params.data_ptr()
-        a.g_exp_avg, a.g_exp_avg_sq, a.g_step = self.sg["exp_avg"].data_ptr(), self.sg["exp_avg_sq"].data_ptr(), self.sg["step"].data_ptr()
-        a.d_exp_avg, a.d_exp_avg_sq, a.d_step = self.sd["exp_avg"].data_ptr(), self.sd["exp_avg_sq"].data_ptr(), self.sd["step"].data_ptr()
+        _epoch.fill_state_args(a, self.G, self.D, self.sg, self.sd, self.scratch, self.scratch_bytes)
+        a.c_flat = self.C.flat_params.data_ptr()
         _fill_state(a, G=self.G, D=self.D)
         a.logs = logs.data_ptr()
-        a.scratch, a.scratch_bytes = (self.scratch.data_ptr() if self.scratch_bytes else None), self.scratch_bytes
         ops.check(_lib_load().pcg_moons_cf_train_steps(ctypes.byref(d), ctypes.byref(a), n, ops._stream()), "pcg_moons_cf_train_steps")
         return logs
 

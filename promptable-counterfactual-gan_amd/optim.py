@@ -92,16 +92,31 @@ class Adam(torch.optim.Optimizer):
                     return True
         return False
 
+    def _ensure_built(self, what="Adam"):
+        """The segments exist and lie over the parameters' current storage (built now if they were not yet); moments that have
+        been stepped cannot follow a storage that moved."""
+        if self._stale():
+            if self._segments is not None and any(int(st["step"].item()) for b in self._segments for st in b):
+                raise PcgError(f"{what}: parameter storage changed after optimisation started (module moved or re-flattened)")
+            self._build()
+
+    def flat_segment(self, net, what="Adam"):
+        """The one state segment (param, grad, exp_avg, exp_avg_sq, step, n) over FlatModule `net`'s flat buffer: what a fused
+        trainer hands to its kernel.  Refused unless this optimizer holds exactly the module's parameters."""
+        net._ensure_flat()
+        self._ensure_built(what)
+        segs = [st for b in self._segments for st in b]
+        if len(segs) != 1 or segs[0]["param"].data_ptr() != net.flat_params.data_ptr():
+            raise PcgError(f"{what}: the optimizer must hold exactly the module's parameters (one flat segment)")
+        return segs[0]
+
     @torch.no_grad()
     def step(self, closure=None):
         loss = None
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
-        if self._stale():
-            if self._segments is not None and any(int(st["step"].item()) for b in self._segments for st in b):
-                raise PcgError("Adam: parameter storage changed after optimisation started (module moved or re-flattened)")
-            self._build()
+        self._ensure_built()
         for group, built in zip(self.param_groups, self._segments):
             b1, b2 = group["betas"]
             for st in built:
