@@ -969,6 +969,35 @@ typedef struct pcg_moons_cf_fwd_args {
 } pcg_moons_cf_fwd_args;
 int pcg_moons_cf_forward(const pcg_moons_cf_desc* desc, const pcg_moons_cf_fwd_args* args, pcg_stream_t stream);
 
+/* Counterfactual queries and evaluation of the trained moons CounteRGAN in ONE launch over many workgroups (csrc/moons_cf_eval.hip):
+ * eval_utils.py:29-106 (compute_metrics_per_target: every mask, every target class, every loader batch), :114-124 / :196-206 (the
+ * decision grid) and gradio_app.py:79-95 (one point, one target, one mask).  Both nets in eval mode (BatchNorm: the running
+ * statistics), so rows are independent; nothing of the nets is written.  Of the descriptor hidden, clf_hidden, nG, nC, g_off, c_off
+ * and bn_eps are read (B is not).  One work item is (mask slot m, target slot t, row i):
+ *   h = [x_i, onehot(t), mask]; raw = G(h); masked = raw * mask; x_cf = x_i + masked (no clamp, eval_utils.py:79);
+ *   logits_cf = C(x_cf), logits_x = C(x_i); gain = softmax(logits_cf)[t] - softmax(logits_x)[t]; pred = argmax (first maximum).
+ * Forms:  sweep    masks [M][2], targets 0..T-1 (T <= 3), every row: grid = ceil(N / group) x T x M workgroups
+ *         per row  target [N] (int64, values in [0, 3)) and row_mask [N][2]; masks NULL, M = T = 1
+ *         classifier only  g_flat NULL: logits_x / pred_x of N rows (M = T = 1, every other output NULL)
+ * `group` is the loader's batch_size (eval_utils.py:40), 1 <= group <= 2^24: one workgroup owns the rows [g group, (g+1) group).
+ * Every per-row output is optional (NULL: not written).  sums [M][T][n_groups][4], n_groups = ceil(N / group), optional: over the
+ * group's included rows — y NULL or y[i] != t (eval_utils.py:57) — their count, the count with pred_cf == t, the sum of gain and
+ * the sum of |masked| over both features; fixed summation order, no atomics: bitwise repeatable.                              */
+typedef struct pcg_moons_cf_eval_args {
+  int64_t N; int32_t M, T, group;
+  const float* x; const int64_t* y;        /* [N][2]; [N] or NULL                                                    */
+  const float* masks;                      /* sweep: [M][2]                                                          */
+  const int64_t* target; const float* row_mask;   /* per row: [N], [N][2]                                             */
+  const float* g_flat; const float* c_flat;
+  const float* bn_mean[3]; const float* bn_var[3];
+  float* raw; float* masked; float* x_cf;  /* [M][T][N][2]                                                           */
+  float* logits_cf; float* logits_x;       /* [M][T][N][3]; [N][3]                                                   */
+  int64_t* pred_cf; int64_t* pred_x;       /* [M][T][N]; [N]                                                         */
+  float* gain;                             /* [M][T][N]                                                              */
+  float* sums;                             /* [M][T][n_groups][4]                                                    */
+} pcg_moons_cf_eval_args;
+int pcg_moons_cf_eval(const pcg_moons_cf_desc* desc, const pcg_moons_cf_eval_args* args, pcg_stream_t stream);
+
 /* ---- whole-batch dense layers: nn.Linear (+ nn.BatchNorm1d) (+ activation) for at most 128 rows (csrc/dense_rows.hip) ----------
  * The MLP GAN of simple_gan/mnist/mnist_gan.py (Generator :44-59, Discriminator :70-77) at batch 64: every operand is dense row-major
  * fp32, activations [R][features], weights [out][in] as nn.Linear stores them, 1 <= R <= 128.  One workgroup owns ALL rows of 16

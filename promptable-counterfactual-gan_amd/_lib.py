@@ -92,6 +92,13 @@ class MoonsCfFwdArgs(ctypes.Structure):
                 [("out0", _P), ("out1", _P), ("scratch", _P), ("scratch_bytes", ctypes.c_size_t)])
 
 
+class MoonsCfEvalArgs(ctypes.Structure):
+    """pcg_moons_cf_eval_args."""
+    _fields_ = ([("N", ctypes.c_int64), ("M", _I), ("T", _I), ("group", _I)] +
+                [(n, _P) for n in ("x", "y", "masks", "target", "row_mask", "g_flat", "c_flat")] + [("bn_mean", _P * 3), ("bn_var", _P * 3)] +
+                [(n, _P) for n in ("raw", "masked", "x_cf", "logits_cf", "logits_x", "pred_cf", "pred_x", "gain", "sums")])
+
+
 class MoonsGanDesc(ctypes.Structure):
     """pcg_moons_gan_desc."""
     _fields_ = ([(n, _I) for n in ("hidden", "z_dim", "label_dim", "B", "N", "nG", "nD", "nG_adam", "nD_adam")] +
@@ -331,6 +338,7 @@ PROTOTYPES = {
     "pcg_moons_cf_scratch_bytes": (_sz, [_c.POINTER(MoonsCfDesc), _i32]),
     "pcg_moons_cf_train_steps": (_i, [_c.POINTER(MoonsCfDesc), _c.POINTER(MoonsCfTrainArgs), _i32, _vp]),
     "pcg_moons_cf_forward": (_i, [_c.POINTER(MoonsCfDesc), _c.POINTER(MoonsCfFwdArgs), _vp]),
+    "pcg_moons_cf_eval": (_i, [_c.POINTER(MoonsCfDesc), _c.POINTER(MoonsCfEvalArgs), _vp]),
     "pcg_moons_gan_scratch_bytes": (_sz, [_c.POINTER(MoonsGanDesc)]),
     "pcg_moons_gan_train_steps": (_i, [_c.POINTER(MoonsGanDesc), _c.POINTER(MoonsGanTrainArgs), _i32, _vp]),
     "pcg_moons_gan_forward": (_i, [_c.POINTER(MoonsGanDesc), _c.POINTER(MoonsGanFwdArgs), _vp]),

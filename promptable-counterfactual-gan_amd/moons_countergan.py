@@ -9,10 +9,19 @@
     trainer.py:31-128           -> train_countergan: one epoch = ONE launch of pcg_moons_cf_train_steps (csrc/moons_cf.hip), which
                                    runs every iteration of the batch loop (:58-113) inside one workgroup
 
+    gradio_app.py:79-95         -> counterfactuals: this point, that target class, these features allowed to move (MASKS)
+    eval_utils.py:10-26         -> evaluate_classifier (accuracy, confusion matrix, classifier_confusion.csv)
+    eval_utils.py:29-106        -> compute_metrics_per_target: every mask, target class and loader batch in ONE launch of
+                                   pcg_moons_cf_eval (csrc/moons_cf_eval.hip), one read of the group sums
+    eval_utils.py:196-206       -> decision_regions: the 200 x 200 grid in one launch
+    eval_utils.py:227-268, main.py:42-60 -> evaluate_pipeline, main
+
 The modules' `forward` runs the HIP forward kernel (pcg_moons_cf_forward) without autograd: backward through the single modules is
-not provided — training goes through train_countergan / TrainSteps.  evaluate_pipeline (pandas / matplotlib reporting) is not ported.
+not provided — training goes through train_countergan / TrainSteps.  The evaluation returns lists of dicts and numpy arrays and writes
+its CSV files with plain Python (no pandas / scikit-learn on the product path); the plots are left out.
 """
 import ctypes
+import math
 import os
 
 import numpy as np
@@ -22,7 +31,7 @@ from torch.nn.utils import spectral_norm
 
 from . import _epoch, ops
 from ._epoch import no_autograd, on_gpu
-from ._lib import MoonsCfDesc, MoonsCfFwdArgs, MoonsCfTrainArgs, PcgError, load as _lib_load
+from ._lib import MoonsCfDesc, MoonsCfEvalArgs, MoonsCfFwdArgs, MoonsCfTrainArgs, PcgError, load as _lib_load
 from .countergan import CrossEntropyLoss
 from .data import MinMax, _split_indices
 from .house import epoch_permutation
@@ -441,3 +450,310 @@ def train_countergan(generator, config, X_train, y_train, clf_model, *, draws=No
         if verbose:
             print(f"Generator saved to {config['generator_path']}")
     return {"d_losses": d_losses, "g_losses": g_losses, "logs": logs, "discriminator": D}
+
+
+# ---- counterfactual queries and evaluation (eval_utils.py, gradio_app.py:79-95): one launch of pcg_moons_cf_eval ---------------
+MASKS = {                                                                     # eval_utils.py:231-236, gradio_app.py:85-90
+    "both": np.array([1, 1], dtype=np.float32),
+    "none": np.array([0, 0], dtype=np.float32),
+    "x_only": np.array([1, 0], dtype=np.float32),
+    "y_only": np.array([0, 1], dtype=np.float32),
+}
+METRIC_FIELDS = ("class_flip", "prediction_gain", "avg_actionability")
+ROW_OUTPUTS = ("raw_residual", "masked_residual", "x_cf", "logits_cf", "logits_x", "pred_cf", "pred_x", "gain")
+EVAL_GROUP = 256        # rows per workgroup where the caller names no batch size (queries, the classifier alone)
+_OUT_FIELD = {"raw_residual": "raw", "masked_residual": "masked"}             # the argument struct's names where they differ
+_OUT_SHAPE = {"raw_residual": (INPUT_DIM,), "masked_residual": (INPUT_DIM,), "x_cf": (INPUT_DIM,), "logits_cf": (NUM_CLASSES,),
+              "logits_x": (NUM_CLASSES,), "pred_cf": (), "pred_x": (), "gain": ()}
+
+
+def _mask_vector(mask, what="mask"):
+    """A name from MASKS or a (2,) vector -> float32 ndarray (2,)."""
+    if mask is None:
+        raise PcgError(f"{what} is required (generator.py:21 concatenates it): a name from MASKS or a ({INPUT_DIM},) vector")
+    if isinstance(mask, str):
+        if mask not in MASKS:
+            raise PcgError(f"{what} {mask!r} is not one of {sorted(MASKS)}")
+        return MASKS[mask]
+    m = np.asarray(mask.detach().cpu() if torch.is_tensor(mask) else mask, dtype=np.float32)
+    if m.shape != (INPUT_DIM,):
+        raise PcgError(f"{what} must be a name from MASKS or a ({INPUT_DIM},) vector, got shape {m.shape}")
+    return m
+
+
+def _rows_arg(x, what="x"):
+    """[N][2] rows, a tensor or an ndarray: the shape is checked on the host.  Returns (rows, given as a tensor)."""
+    given = torch.is_tensor(x)
+    if not given:
+        x = torch.as_tensor(np.asarray(x), dtype=torch.float32)
+    if x.dim() != 2 or x.shape[1] != INPUT_DIM or x.shape[0] < 1:
+        raise PcgError(f"{what} must be [N][{INPUT_DIM}] with N >= 1, got {tuple(x.shape)}")
+    return x, given
+
+
+def _eval_dims(generator, classifier):
+    if generator is not None:
+        _check_dims(generator.input_dim, generator.hidden_dim, generator.num_classes, clf_hidden=classifier.hidden_dim)
+    _check_dims(classifier.input_dim, HIDDEN_DIMS[0], classifier.num_classes, clf_hidden=classifier.hidden_dim)
+
+
+def _eval_device(*nets):
+    devs = {n.flat_params.device for n in nets}                               # (flattening refuses parameters on the CPU)
+    if len(devs) != 1:
+        raise PcgError("the generator and the classifier must be on one GPU")
+    return devs.pop()
+
+
+def _eval_launch(generator, classifier, x, group, outputs, y=None, masks=None, target=None, row_mask=None, sums=False):
+    """ONE pcg_moons_cf_eval launch.  x [N][2] float32 on the nets' device; generator None: the classifier alone.  Returns the asked
+    per-row outputs ([M][3][N]... in the sweep form, [N]... otherwise) and "sums" [M][3][n_groups][4]."""
+    dev = x.device
+    N = x.shape[0]
+    M = masks.shape[0] if masks is not None else 1
+    T = NUM_CLASSES if masks is not None else 1
+    d = _desc(generator.hidden_dim if generator is not None else HIDDEN_DIMS[0], 2, G=generator, C=classifier)
+    a = MoonsCfEvalArgs()
+    a.N, a.M, a.T, a.group = N, M, T, int(group)
+    keep = [ops._chk(x, "x")]
+    a.x, a.c_flat = x.data_ptr(), classifier.flat_params.data_ptr()
+    for name, t in (("y", y), ("masks", masks), ("target", target), ("row_mask", row_mask)):
+        if t is not None:
+            keep.append(t)
+            setattr(a, name, t.data_ptr())
+    if generator is not None:
+        a.g_flat = generator.flat_params.data_ptr()
+        for i, bn in enumerate(_bn_layers(generator)):
+            a.bn_mean[i], a.bn_var[i] = bn.running_mean.data_ptr(), bn.running_var.data_ptr()
+    lead = (M, T, N) if masks is not None else (N,)
+    out = {}
+    for name in outputs:
+        per_x = name in ("logits_x", "pred_x")
+        out[name] = torch.empty(((N,) if per_x else lead) + _OUT_SHAPE[name], dtype=torch.int64 if name.startswith("pred") else torch.float32,
+                                device=dev)
+        setattr(a, _OUT_FIELD.get(name, name), out[name].data_ptr())
+    if sums:
+        out["sums"] = torch.empty((M, T, -(-N // int(group)), 4), dtype=torch.float32, device=dev)
+        a.sums = out["sums"].data_ptr()
+    ops.check(_lib_load().pcg_moons_cf_eval(ctypes.byref(d), ctypes.byref(a), ops._stream()), "pcg_moons_cf_eval")
+    return out
+
+
+def _upload(x, dev, dtype=torch.float32):
+    return x.to(dev, dtype).contiguous()
+
+
+def _guard(nets, x, given, *others):
+    """The module forwards' guards: a tensor input must already be on the GPU (an ndarray is uploaded), the nets must be there, and
+    nothing may ask for autograd."""
+    dev = _eval_device(*nets)
+    for net in nets:
+        if given:
+            on_gpu(net, x)
+        no_autograd(net, x, *[o for o in others if torch.is_tensor(o) and o.is_floating_point()])
+    return dev
+
+
+def counterfactuals(generator, classifier, x, target, mask):
+    """gradio_app.py:79-95 for N points at once: x [N][2] (a tensor on the GPU, or an ndarray), target an int or [N], mask a name
+    from MASKS, a (2,) vector or [N][2].  The kernel always uses BatchNorm's running statistics (eval mode, as the reference's app
+    sets it).  One launch.  Returns device tensors: x_cf, masked_residual, raw_residual [N][2], logits_cf, logits_x [N][3], pred_cf,
+    pred_x [N] (int64), gain [N] = softmax(logits_cf)[target] - softmax(logits_x)[target]."""
+    _eval_dims(generator, classifier)
+    x, given = _rows_arg(x)
+    N = x.shape[0]
+    if mask is not None and not isinstance(mask, str) and np.ndim(mask) == 2:
+        row_mask = mask if torch.is_tensor(mask) else torch.as_tensor(np.asarray(mask), dtype=torch.float32)
+        if tuple(row_mask.shape) != (N, INPUT_DIM):
+            raise PcgError(f"mask must be a name from MASKS, a ({INPUT_DIM},) vector or [N][{INPUT_DIM}] (N = {N}), got {tuple(row_mask.shape)}")
+    else:
+        row_mask = torch.from_numpy(np.ascontiguousarray(np.broadcast_to(_mask_vector(mask), (N, INPUT_DIM))))
+    if isinstance(target, (int, np.integer)):
+        target = torch.full((N,), int(target), dtype=torch.int64)
+    else:
+        target = target if torch.is_tensor(target) else torch.as_tensor(np.asarray(target))
+        if tuple(target.shape) != (N,) or target.dtype.is_floating_point or target.dtype == torch.bool:
+            raise PcgError(f"target must be an int or [N] integers (N = {N}), got {tuple(target.shape)} {target.dtype}")
+    lo, hi = int(target.min()), int(target.max())                             # it selects the one-hot input: refused on the host
+    if lo < 0 or hi >= NUM_CLASSES:
+        raise PcgError(f"targets must lie in [0, {NUM_CLASSES}), got [{lo}, {hi}]")
+    dev = _guard((generator, classifier), x, given, row_mask)
+    return _eval_launch(generator, classifier, _upload(x, dev), EVAL_GROUP, ROW_OUTPUTS, target=_upload(target, dev, torch.int64),
+                        row_mask=_upload(row_mask, dev))
+
+
+def counterfactual_sweep(generator, classifier, X, y=None, masks=MASKS, batch_size=64, outputs=()):
+    """Every mask x every target class x every row in ONE launch: the loops of eval_utils.py:48-97 with the row selection (:57) folded
+    into the group sums.  masks: {name: name-or-vector} or a sequence of them; y [N] or None (every row counts); batch_size: the
+    loader's (one group of rows per workgroup), any positive integer.  Returns {"sums": [M][3][ceil(N / batch_size)][4] (included
+    rows, rows with pred_cf == target, sum of gain, sum of |masked residual| over both features), and the per-row `outputs` asked for
+    (names of ROW_OUTPUTS; [M][3][N]..., logits_x / pred_x [N]...)} as device tensors.  Eval mode is the caller's to set."""
+    _eval_dims(generator, classifier)
+    X, given = _rows_arg(X, "X")
+    N = X.shape[0]
+    vecs = [_mask_vector(m) for m in (masks.values() if isinstance(masks, dict) else masks)]
+    if not vecs:
+        raise PcgError("counterfactual_sweep: no mask")
+    group = int(batch_size)
+    if group < 1:
+        raise PcgError(f"batch_size must be positive, got {batch_size}")
+    bad = [o for o in outputs if o not in ROW_OUTPUTS]
+    if bad:
+        raise PcgError(f"outputs {bad} are not among {ROW_OUTPUTS}")
+    if y is not None:
+        y = y if torch.is_tensor(y) else torch.as_tensor(np.asarray(y))
+        if tuple(y.shape) != (N,) or y.dtype.is_floating_point:
+            raise PcgError(f"y must be [N] integers (N = {N}), got {tuple(y.shape)} {y.dtype}")
+    dev = _guard((generator, classifier), X, given)
+    return _eval_launch(generator, classifier, _upload(X, dev), group, tuple(outputs), y=None if y is None else _upload(y, dev, torch.int64),
+                        masks=_upload(torch.from_numpy(np.stack(vecs)), dev), sums=True)
+
+
+def metrics_from_sums(sums):
+    """Pure host.  sums [..., n_groups, 4] -> [..., 3] (METRIC_FIELDS) as eval_utils.py:83-103 forms them: per group with a row in
+    it the mean over its rows (actionability over both features: / (2 count)), then np.mean over those groups — the mean of the
+    per-batch means, so rows of a short batch weigh more.  No such group: nan."""
+    s = np.asarray(sums, dtype=np.float64)
+    out = np.full(s.shape[:-2] + (3,), np.nan)
+    for idx in np.ndindex(*s.shape[:-2]):
+        g = s[idx]
+        g = g[g[:, 0] > 0]
+        if len(g):
+            out[idx] = (np.mean(g[:, 1] / g[:, 0]), np.mean(g[:, 2] / g[:, 0]), np.mean(g[:, 3] / (INPUT_DIM * g[:, 0])))
+    return out
+
+
+def metric_rows(table):
+    """[3 targets][3] -> the rows of the reference's DataFrame as a list of dicts."""
+    return [dict({"target_class": t}, **{k: float(v) for k, v in zip(METRIC_FIELDS, row)}) for t, row in enumerate(table)]
+
+
+def compute_metrics_per_target(generator, classifier, X, y, config, mask=None):
+    """eval_utils.py:29-106: per target class the class-flip rate, the prediction gain and the mean |masked residual| over the rows
+    whose class differs from the target, averaged over the loader's batches (config['batch_size']).  mask: a name from MASKS or a
+    (2,) vector -> a list of dicts (the DataFrame's rows); a dict {name: mask} -> {name: rows}, all of them from ONE launch.
+    mask=None is refused, as the module forward refuses it (the reference's torch.cat fails on it, generator.py:21)."""
+    if mask is None:
+        raise PcgError("compute_metrics_per_target: mask is required (generator.py:21 concatenates it)")
+    many = isinstance(mask, dict)
+    generator.eval()                                                           # :45
+    classifier.eval()                                                          # :46
+    with torch.no_grad():                                                      # :47
+        res = counterfactual_sweep(generator, classifier, X, y, mask if many else [mask], config["batch_size"])
+    table = metrics_from_sums(res["sums"].cpu().numpy())                       # the one read
+    if many:
+        return {name: metric_rows(table[i]) for i, name in enumerate(mask)}
+    return metric_rows(table[0])
+
+
+def _classify(classifier, X):
+    X, given = _rows_arg(X, "X")
+    _eval_dims(None, classifier)
+    dev = _guard((classifier,), X, given)
+    return _eval_launch(None, classifier, _upload(X, dev), EVAL_GROUP, ("pred_x",))["pred_x"]
+
+
+def confusion_matrix(y_true, y_pred):
+    """sklearn.metrics.confusion_matrix(y_true, y_pred): labels = the sorted values that occur in either, rows true, columns predicted."""
+    y_true, y_pred = np.asarray(y_true), np.asarray(y_pred)
+    labels = np.unique(np.concatenate([y_true, y_pred]))
+    cm = np.zeros((len(labels), len(labels)), dtype=np.int64)
+    np.add.at(cm, (np.searchsorted(labels, y_true), np.searchsorted(labels, y_pred)), 1)
+    return cm
+
+
+def confusion_csv(cm):
+    """The text of eval_utils.py:21-25's DataFrame.to_csv: a header of pred_j columns, one true_i row per class."""
+    lines = ["," + ",".join(f"pred_{j}" for j in range(cm.shape[1]))]
+    lines += [f"true_{i}," + ",".join(str(int(v)) for v in row) for i, row in enumerate(cm)]
+    return "\n".join(lines) + "\n"
+
+
+def evaluate_classifier(clf, X_test, y_test, config):
+    """eval_utils.py:10-26: accuracy and confusion matrix on the test split (one classifier-only launch), classifier_confusion.csv in
+    config['out_dir'], the reference's print line.  Returns (acc, cm), which the reference computes and drops."""
+    with torch.no_grad():
+        preds = _classify(clf, X_test).cpu().numpy()
+    y_test = np.asarray(y_test)
+    acc = float(np.mean(preds == y_test))
+    cm = confusion_matrix(y_test, preds)
+    save_path = os.path.join(config["out_dir"], "classifier_confusion.csv")
+    os.makedirs(config["out_dir"], exist_ok=True)
+    with open(save_path, "w") as f:
+        f.write(confusion_csv(cm))
+    print(f"Classifier accuracy: {acc:.4f}, confusion matrix saved to {save_path}")
+    return acc, cm
+
+
+def decision_regions(classifier, X, n=200, pad=0.1):
+    """eval_utils.py:196-206 (and :114-124): the classifier's class at every point of an n x n grid over X's bounding box widened by
+    pad, in one launch.  Returns (xx, yy, Z) as numpy arrays, Z [n][n] int64 — what the reference hands to contourf."""
+    X = np.asarray(X)
+    x_min, x_max = X[:, 0].min() - pad, X[:, 0].max() + pad
+    y_min, y_max = X[:, 1].min() - pad, X[:, 1].max() + pad
+    xx, yy = np.meshgrid(np.linspace(x_min, x_max, n), np.linspace(y_min, y_max, n))
+    grid = np.c_[xx.ravel(), yy.ravel()]
+    with torch.no_grad():
+        Z = _classify(classifier, grid).cpu().numpy()
+    return xx, yy, Z.reshape(xx.shape)
+
+
+def _csv_value(v):
+    return "" if isinstance(v, float) and math.isnan(v) else (repr(v) if isinstance(v, float) else str(v))
+
+
+def save_metrics(rows, save_path, columns=("target_class",) + METRIC_FIELDS):
+    """eval_utils.py:187-190: the rows as CSV (DataFrame.to_csv(index=False): shortest float repr, nan as an empty field)."""
+    os.makedirs(os.path.dirname(save_path), exist_ok=True)
+    with open(save_path, "w") as f:
+        f.write(",".join(columns) + "\n")
+        for r in rows:
+            f.write(",".join(_csv_value(r[c]) for c in columns) + "\n")
+    print(f"Saved metrics to {save_path}")
+
+
+def evaluate_pipeline(generator, classifier, X_test, y_test, config, masks=None):
+    """eval_utils.py:227-268.  As the reference ships it (masks=None): evaluate_classifier and the decision grid of
+    plot_decision_boundaries_only — its arrays go to decision_boundaries_no_cfs.npz (xx, yy, Z) where the reference saves the
+    picture — and None is returned.  masks=MASKS (or any {name: mask}) also runs the per-mask evaluation the reference keeps
+    commented out (:242-264): mask_<name>/metrics.csv and metrics_all_masks.csv, all masks from one launch; returns {name: rows}."""
+    base_out = config["out_dir"]
+    evaluate_classifier(classifier, X_test, y_test, config)                    # :239
+    all_metrics = None
+    if masks:
+        all_metrics = compute_metrics_per_target(generator, classifier, X_test, y_test, config, mask=dict(masks))
+        summary = []
+        for name, rows in all_metrics.items():
+            print(f"Evaluating mask: {name}")
+            save_metrics(rows, os.path.join(base_out, f"mask_{name}", "metrics.csv"))
+            summary += [dict(r, mask=name) for r in rows]
+        save_metrics(summary, os.path.join(base_out, "metrics_all_masks.csv"), ("target_class",) + METRIC_FIELDS + ("mask",))
+    xx, yy, Z = decision_regions(classifier, X_test)                           # :265
+    save_path = os.path.join(base_out, "decision_boundaries_no_cfs.npz")
+    np.savez_compressed(save_path, xx=xx, yy=yy, Z=Z)
+    print(f"Saved decision regions: {save_path}")
+    return all_metrics
+
+
+def main(config=config):
+    """main.py:42-60: the data, the classifier (loaded or trained), the generator (loaded or trained, then frozen), evaluate_pipeline."""
+    X_train, X_test, y_train, y_test = load_and_preprocess(config["seed"])
+    clf = get_classifier(X_train, y_train, config)
+    num_classes = int(np.unique(y_train).size)
+    generator = ResidualGenerator(config["input_dim"], config["hidden_dim"], num_classes=num_classes).to(config["cuda"])
+    generator_path = config["generator_path"]
+    if os.path.exists(generator_path):
+        print(f"Loading pretrained generator from {generator_path}...")
+    else:
+        print("Training CounterGAN and saving generator...")
+        train_countergan(generator, config, X_train, y_train, clf)
+    generator.load_state_dict(torch.load(generator_path, map_location=config["cuda"]))
+    generator.eval()
+    for p in generator.parameters():
+        p.requires_grad = False
+    metrics = evaluate_pipeline(generator, clf, X_test, y_test, config)
+    print(metrics)
+    return metrics
+
+
+if __name__ == "__main__":
+    main()
