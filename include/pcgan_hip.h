@@ -60,6 +60,8 @@ typedef struct pcg_conv_geom {
 
 /* ---- library ------------------------------------------------------------------------------- */
 int pcg_abi_version(void);
+/* sizeof of an argument struct of this header by its typedef name (0: unknown name) — a binding checks its own layout against it */
+size_t pcg_abi_struct_bytes(const char* name);
 const char* pcg_last_error(void);
 /* "gfx950" — the only code object in the library */
 const char* pcg_target_arch(void);
@@ -539,28 +541,35 @@ int pcg_mean_bwd(const float* grad_out_dev /*nullable = 1*/, float grad_scale, i
  * Dimensions up to 256. */
 int pcg_spectral_norm_fwd(const float* w_orig, int32_t out_features, int32_t in_features, float* u, float* v, float eps,
                           int power_iteration, float* w_bar, float* sigma, float* u_used, float* v_used, pcg_stream_t stream);
-/* all (up to 8) spectral-norm layers of a net in one launch — arrays of per-layer arguments, host-side arrays of device pointers */
-int pcg_spectral_norm_fwd_batched(int32_t n, const float* const* w_orig, const int32_t* out_features, const int32_t* in_features,
-                                  float* const* u, float* const* v, float eps, int power_iteration, float* const* w_bar,
-                                  float* const* sigma, float* const* u_used, float* const* v_used, pcg_stream_t stream);
-int pcg_spectral_norm_bwd_batched(int32_t n, const float* const* dw_bar, const float* const* w_bar, const int32_t* out_features,
-                                  const int32_t* in_features, const float* const* u, const float* const* v, const float* const* sigma,
-                                  float* const* dw_orig, const int32_t* accumulate, pcg_stream_t stream);
-/* `reps` successive training-mode calls of every layer in one launch (each one power iteration from the previous call's u, v, as the
- * module's forward does: D(real) then D(fake)); the output arrays hold reps * n entries, call-major (call r of layer l: r * n + l).
- * At most 8 layers x calls. */
-int pcg_spectral_norm_fwd_batched_reps(int32_t n, int32_t reps, const float* const* w_orig, const int32_t* out_features,
-                                       const int32_t* in_features, float* const* u, float* const* v, float eps, int power_iteration,
-                                       float* const* w_bar, float* const* sigma, float* const* u_used, float* const* v_used,
-                                       pcg_stream_t stream);
-/* The backward of `passes` calls of the same n layers, applied one after the other into the same dw_orig[l] (the first writes or
+/* All (up to 8) spectral-norm layers of a net in one launch.  Every array member is a HOST array of device pointers / ints.
+ * Forward: `reps` successive calls of every layer (each one power iteration from the previous call's u, v, as the module's forward
+ * does: D(real) then D(fake)); reps > 1 needs power_iteration.  The output arrays hold reps * n entries, call-major (call r of layer
+ * l: r * n + l).  At most 8 layers x calls. */
+typedef struct pcg_sn_fwd_batch {
+  int32_t n, reps, power_iteration;
+  float eps;
+  const float* const* w_orig;                          /* [n] */
+  const int32_t* out_features; const int32_t* in_features;   /* [n] */
+  float* const* u; float* const* v;                    /* [n], updated in place when power_iteration != 0 */
+  float* const* w_bar; float* const* sigma;            /* [n * reps] */
+  float* const* u_used; float* const* v_used;          /* [n * reps], entries nullable */
+} pcg_sn_fwd_batch;
+/* Backward of `passes` calls of the same n layers, applied one after the other into the same dw_orig[l] (the first writes or
  * accumulates as accumulate[l] says, the others add — what chained launches compute); per-call arrays hold passes * n entries,
  * pass-major.  Then, where db_dst[l] is given, db_dst[l] += db_src[l] over out_features[l] values (the bias gradient of a later pass,
  * reduced into its own buffer because one grouped weight-gradient launch cannot order two writers of the same vector). */
-int pcg_spectral_norm_bwd_batched_seq(int32_t n, int32_t passes, const float* const* dw_bar, const float* const* w_bar,
-                                      const int32_t* out_features, const int32_t* in_features, const float* const* u, const float* const* v,
-                                      const float* const* sigma, float* const* dw_orig, const int32_t* accumulate, float* const* db_dst /*nullable*/,
-                                      const float* const* db_src /*nullable*/, pcg_stream_t stream);
+typedef struct pcg_sn_bwd_batch {
+  int32_t n, passes;
+  const float* const* dw_bar; const float* const* w_bar;     /* [n * passes] */
+  const int32_t* out_features; const int32_t* in_features;   /* [n] */
+  const float* const* u; const float* const* v; const float* const* sigma;   /* [n * passes] */
+  float* const* dw_orig;                               /* [n] */
+  const int32_t* accumulate;                           /* [n] */
+  float* const* db_dst;                                /* nullable; [n], entries nullable */
+  const float* const* db_src;                          /* nullable; [n], needed where db_dst[l] is given */
+} pcg_sn_bwd_batch;
+int pcg_spectral_norm_fwd_batched(const pcg_sn_fwd_batch* batch, pcg_stream_t stream);
+int pcg_spectral_norm_bwd_batched(const pcg_sn_bwd_batch* batch, pcg_stream_t stream);
 int pcg_spectral_norm_bwd(const float* dw_bar, const float* w_bar, int32_t out_features, int32_t in_features, const float* u,
                           const float* v, const float* sigma, float* dw_orig, int accumulate, pcg_stream_t stream);
 
@@ -694,36 +703,74 @@ int pcg_weighted_sum_bwd(int32_t n, const float* weights, const float* grad_out_
                          pcg_stream_t stream);
 
 /* The tabular spectral-norm critic (house_sales_kc_usa/models/discriminator.py:5-20) as one forward and one backward launch, one
- * thread per row; w_bar[l] / bias[l]: the four layers' normalised weights (from pcg_spectral_norm_fwd_batched) and biases.
- * Forward writes the concatenated input a0 [B][21] and the post-LeakyReLU activations a1 [B][32], a2 [B][64], a3 [B][128];
- * backward writes the pre-activation gradients d3, d2, d1 (the dy operands of the weight gradients; layer 4's is dout itself)
- * and, if dx != NULL, the gradient of the first D input columns.  Built for input_dim + num_classes = 21, hidden width 32. */
-int pcg_house_critic_fwd(const float* x, const float* onehot, int32_t B, int32_t D, int32_t NC, const float* const* w_bar,
-                         const float* const* bias, float slope, float* a0, float* a1, float* a2, float* a3, float* out, pcg_stream_t stream);
-int pcg_house_critic_bwd(const float* dout, int32_t B, int32_t D, const float* const* w_bar, float slope, const float* a1, const float* a2,
-                         const float* a3, float* d3, float* d2, float* d1, float* dx /*nullable*/, pcg_stream_t stream);
-/* The same for n_pass (1 or 2) independent passes in ONE launch each way — D(real) and D(fake) of the critic step (trainer.py:290-291),
- * which share the module but not the spectral-norm weights (two successive power iterations): every per-pass pointer becomes an
- * array of n_pass, w_bar has n_pass * 4 entries (pass-major).  Per pass the arithmetic is that of the one-pass calls. */
-int pcg_house_critic_fwd_n(int32_t n_pass, const float* const* x, const float* const* onehot, int32_t B, int32_t D, int32_t NC,
-                           const float* const* w_bar, const float* const* bias, float slope, float* const* a0, float* const* a1,
-                           float* const* a2, float* const* a3, float* const* out, pcg_stream_t stream);
-int pcg_house_critic_bwd_n(int32_t n_pass, const float* const* dout, int32_t B, int32_t D, const float* const* w_bar, float slope,
-                           const float* const* a1, const float* const* a2, const float* const* a3, float* const* d3, float* const* d2,
-                           float* const* d1, float* const* dx /*entries nullable*/, pcg_stream_t stream);
+ * thread per row, for n_pass (1 or 2) independent passes per launch — D(real) and D(fake) of the critic step (trainer.py:290-291)
+ * share the module but not the spectral-norm weights (two successive power iterations).  Every per-pass member is a HOST array of
+ * n_pass device pointers; w_bar has n_pass * 4 entries (pass-major): the four layers' normalised weights (from
+ * pcg_spectral_norm_fwd_batched); bias[4].  Forward writes the concatenated input a0 [B][21] and the post-LeakyReLU activations
+ * a1 [B][32], a2 [B][64], a3 [B][128]; backward writes the pre-activation gradients d3, d2, d1 (the dy operands of the weight
+ * gradients; layer 4's is dout itself) and, where dx[q] != NULL, the gradient of the first D input columns.  Built for input_dim +
+ * num_classes = 21, hidden width 32. */
+typedef struct pcg_house_critic_fwd_args {
+  int32_t n_pass, B, D, NC;
+  float slope;
+  const float* const* x; const float* const* onehot;
+  const float* const* w_bar; const float* const* bias;
+  float* const* a0; float* const* a1; float* const* a2; float* const* a3; float* const* out;
+} pcg_house_critic_fwd_args;
+typedef struct pcg_house_critic_bwd_args {
+  int32_t n_pass, B, D;
+  float slope;
+  const float* const* dout; const float* const* w_bar;
+  const float* const* a1; const float* const* a2; const float* const* a3;
+  float* const* d3; float* const* d2; float* const* d1;
+  float* const* dx;                                    /* [n_pass], entries nullable */
+} pcg_house_critic_bwd_args;
+int pcg_house_critic_fwd(const pcg_house_critic_fwd_args* args, pcg_stream_t stream);
+int pcg_house_critic_bwd(const pcg_house_critic_bwd_args* args, pcg_stream_t stream);
 
-/* The frozen tabular classifier of the counterfactual loss (house_sales_kc_usa/models/nn_classifier.py:4-32 in eval mode, each
+/* "Riders": two launches of the tabular step that do not depend on each other issued as ONE launch whose blocks split between the
+ * two kernel bodies (a HIP graph with parallel branches is launched node by node by the host; one launch is not).  Same bodies, same
+ * bits as the separate calls.  At the ABI a rider is an optional (nullable) argument struct of the launch that carries it:
+ *   pcg_house_residual_fwd   + a training-mode pcg_sn_fwd_batch: the critic step's power iterations only need the critic's weights
+ *                              (trainer.py:266-287 beside models/discriminator.py:9-16)
+ *   pcg_house_residual_bwd   + pcg_house_loss_args (+ pcg_house_diag_args): the logged scalars do not feed the backward
+ *                              (trainer.py:314 beside :292, :307-312)
+ *   pcg_house_classifier_fwd + pcg_sn_bwd_batch, and
+ *   pcg_house_classifier_bwd + a training-mode pcg_sn_fwd_batch: the frozen classifier's term (trainer.py:301-302) does not depend on
+ *                              the critic update (:290-295), so its two launches carry the critic's spectral-norm work that is on
+ *                              the chain at the same time
+ *
+ * The frozen tabular classifier of the counterfactual loss (house_sales_kc_usa/models/nn_classifier.py:4-32 in eval mode, each
  * BatchNorm1d folded into the following Linear by the caller: Linear 17->256, 256->256, 256->128, 128->64 + LeakyReLU(0.1), Linear
  * 64->4) as one launch each way on the matrix cores, 16 rows per block, activations in LDS between layers.
  *   forward:  w_kmajor[l], l = 0..3: the folded weight TRANSPOSED, [K_l][N_l] row-major, layer 0 zero-padded to K = 20;
  *             w_kmajor[4]: the last layer as stored [4][64]; bias[l]; writes the post-activation outputs a1 [B][256], a2 [B][256],
  *             a3 [B][128], a4 [B][64] (the backward's masks) and logits [B][4].
+ *             ce_target != NULL (only with a rider): the forward also evaluates the cross-entropy of its logits against ce_target
+ *             (trainer.py:302) — per row the term lse - z[target] into ce_row_loss[B] and ce_grad_scale / B * (softmax - onehot)
+ *             into ce_dlogits[B][4] (16-byte aligned), the expressions of pcg_cross_entropy_fwd_bwd; pcg_house_residual_bwd with
+ *             pcg_house_loss_args(ce_row_loss, n_ce = B) then forms the mean in that kernel's summation order (out6[5], and uses it
+ *             for G_loss instead of *g_cls): the same bits as the separate cross-entropy launch.
  *   backward: w_stored[l]: the folded weights as stored [N_l][K_l]; dx [B][17] = d(logits . dlogits)/dx.  (trainer.py:301-302;
  *             the parameters are frozen, main.py:27-30: no weight gradients.) */
-int pcg_house_classifier_fwd(const float* x, int32_t B, const float* const* w_kmajor, const float* const* bias, float* a1, float* a2,
-                             float* a3, float* a4, float* logits, pcg_stream_t stream);
-int pcg_house_classifier_bwd(const float* dlogits, int32_t B, const float* const* w_stored, const float* a1, const float* a2, const float* a3,
-                             const float* a4, float* dx, pcg_stream_t stream);
+typedef struct pcg_house_cls_fwd_args {
+  const float* x;
+  int32_t B;
+  const float* const* w_kmajor; const float* const* bias;    /* HOST arrays of 5 device pointers */
+  float* a1; float* a2; float* a3; float* a4; float* logits;
+  const int64_t* ce_target;                            /* nullable: no cross-entropy tail */
+  float ce_grad_scale;
+  float* ce_dlogits; float* ce_row_loss;               /* needed with ce_target */
+} pcg_house_cls_fwd_args;
+typedef struct pcg_house_cls_bwd_args {
+  const float* dlogits;
+  int32_t B;
+  const float* const* w_stored;                        /* HOST array of 5 device pointers */
+  const float* a1; const float* a2; const float* a3; const float* a4;
+  float* dx;
+} pcg_house_cls_bwd_args;
+int pcg_house_classifier_fwd(const pcg_house_cls_fwd_args* args, const pcg_sn_bwd_batch* rider /*nullable*/, pcg_stream_t stream);
+int pcg_house_classifier_bwd(const pcg_house_cls_bwd_args* args, const pcg_sn_fwd_batch* rider /*nullable*/, pcg_stream_t stream);
 
 /* The scalars the tabular trainer logs per step (house_sales_kc_usa/trainer.py:292, :299, :307-312, :318-330) in one launch:
  * out5 = { D_loss = mean(d_fake) - mean(d_real), G_loss = -mean(d_fake_g) + lambda_cls*g_cls + w_reg*am + lambda_mask*pen,
@@ -742,51 +789,55 @@ int pcg_house_losses(const float* d_real, const float* d_fake, const float* d_fa
  * lambda_mask, w_am = lambda_reg * D as the trainer weighs them; gx_a, gx_b: the two addends of dLoss/dx_cf (critic, classifier).
  * Bit-identical to the chain pcg_axpby, pcg_weighted_sum_bwd, 2 x pcg_abs_mean_bwd, pcg_axpby, pcg_scale_mask_bwd, add,
  * pcg_assemble_residual_bwd. */
-int pcg_house_residual_fwd(const float* cont, int32_t ncont, const float* samples, const int32_t* seg_dev, int32_t T, const float* norm,
-                           const float* x, const float* mask, const int32_t* col_src, int32_t D, int32_t B, float* res, float* masked,
-                           float* x_cf, float* partial512, int32_t* ticket, float* pen_out, float* am_out, pcg_stream_t stream);
-int pcg_house_residual_bwd(const float* res, const float* masked, const float* mask, const float* gx_a, const float* gx_b, float w_pen,
-                           float w_am, int32_t ncont, const int32_t* cont_idx_dev, const int32_t* seg_dev, int32_t S, int32_t T,
-                           const int32_t* cat_idx_dev, const float* norm, int32_t D, int32_t B, float* dcont, float* dsamples,
-                           pcg_stream_t stream);
-/* "Riders": two launches of the tabular step that do not depend on each other issued as ONE launch whose blocks split between the
- * two kernel bodies (a HIP graph with parallel branches is launched node by node by the host; one launch is not).  Same bodies, same
- * bits as the separate calls.
- *   pcg_house_residual_fwd_sn      = pcg_house_residual_fwd + pcg_spectral_norm_fwd_batched_reps (training mode: the critic step's
- *                                    power iterations only need the critic's weights; trainer.py:266-287 beside models/discriminator.py:9-16)
- *   pcg_house_residual_bwd_losses  = pcg_house_residual_bwd + pcg_house_losses (the logged scalars do not feed the backward;
- *                                    trainer.py:314 beside :292, :307-312)
- *   pcg_house_classifier_fwd_snbwd = pcg_house_classifier_fwd + pcg_spectral_norm_bwd_batched_seq, and
- *   pcg_house_classifier_bwd_snfwd = pcg_house_classifier_bwd + pcg_spectral_norm_fwd_batched_reps (training mode): the frozen
- *                                    classifier's term (trainer.py:301-302) does not depend on the critic update (:290-295), so its
- *                                    two launches carry the critic's spectral-norm work that is on the chain at the same time */
-int pcg_house_residual_fwd_sn(const float* cont, int32_t ncont, const float* samples, const int32_t* seg_dev, int32_t T, const float* norm,
-                              const float* x, const float* mask, const int32_t* col_src, int32_t D, int32_t B, float* res, float* masked,
-                              float* x_cf, float* partial512, int32_t* ticket, float* pen_out, float* am_out,
-                              int32_t n_layers, int32_t reps, const float* const* w_orig, const int32_t* out_features,
-                              const int32_t* in_features, float* const* u, float* const* v, float eps, float* const* w_bar,
-                              float* const* sigma, float* const* u_used, float* const* v_used, pcg_stream_t stream);
-int pcg_house_residual_bwd_losses(const float* res, const float* masked, const float* mask, const float* gx_a, const float* gx_b,
-                                  float w_pen, float w_am, int32_t ncont, const int32_t* cont_idx_dev, const int32_t* seg_dev, int32_t S,
-                                  int32_t T, const int32_t* cat_idx_dev, const float* norm, int32_t D, int32_t B, float* dcont,
-                                  float* dsamples, const float* d_real, const float* d_fake, const float* d_fake_g, int32_t n,
-                                  const float* g_cls, const float* am, const float* pen, float lambda_cls, float w_reg, float lambda_mask,
-                                  float w_reg_log, const float* ce_row_loss, int32_t n_ce, float* out6, pcg_stream_t stream);
-/* ce_target != NULL: the forward also evaluates the cross-entropy of its logits against ce_target (trainer.py:302) — per row the
- * term lse - z[target] into ce_row_loss[B] and ce_grad_scale / B * (softmax - onehot) into ce_dlogits[B][4], the expressions of
- * pcg_cross_entropy_fwd_bwd; pcg_house_residual_bwd_losses(ce_row_loss, n_ce = B) then forms the mean in that kernel's summation
- * order (out6[5], and uses it for G_loss instead of *g_cls): the same bits as the separate cross-entropy launch. */
-int pcg_house_classifier_fwd_snbwd(const float* x, int32_t B, const float* const* w_kmajor, const float* const* bias, float* a1, float* a2,
-                                   float* a3, float* a4, float* logits, int32_t n, int32_t passes, const float* const* dw_bar,
-                                   const float* const* w_bar, const int32_t* out_features, const int32_t* in_features,
-                                   const float* const* u, const float* const* v, const float* const* sigma, float* const* dw_orig,
-                                   const int32_t* accumulate, float* const* db_dst, const float* const* db_src,
-                                   const int64_t* ce_target, float ce_grad_scale, float* ce_dlogits, float* ce_row_loss, pcg_stream_t stream);
-int pcg_house_classifier_bwd_snfwd(const float* dlogits, int32_t B, const float* const* w_stored, const float* a1, const float* a2,
-                                   const float* a3, const float* a4, float* dx, int32_t n, int32_t reps, const float* const* w_orig,
-                                   const int32_t* out_features, const int32_t* in_features, float* const* u, float* const* v, float eps,
-                                   float* const* w_bar, float* const* sigma, float* const* u_used, float* const* v_used,
-                                   pcg_stream_t stream);
+typedef struct pcg_house_res_fwd_args {
+  const float* cont; int32_t ncont;
+  const float* samples; const int32_t* seg_dev; int32_t T;
+  const float* norm; const float* x; const float* mask;
+  const int32_t* col_src;                              /* HOST int32[D] */
+  int32_t D, B;
+  float* res; float* masked; float* x_cf; float* partial512; int32_t* ticket; float* pen_out; float* am_out;
+} pcg_house_res_fwd_args;
+typedef struct pcg_house_res_bwd_args {
+  const float* res; const float* masked; const float* mask; const float* gx_a; const float* gx_b;
+  float w_pen, w_am;
+  int32_t ncont; const int32_t* cont_idx_dev; const int32_t* seg_dev; int32_t S, T;
+  const int32_t* cat_idx_dev; const float* norm;
+  int32_t D, B;
+  float* dcont; float* dsamples;
+} pcg_house_res_bwd_args;
+/* the operands of pcg_house_losses as a rider of the backward: n <= 16384 critic outputs; out6 = the five scalars + g_cls.
+ * ce_row_loss != NULL: the [n_ce] row terms the classifier forward's cross-entropy tail left (g_cls may then be NULL). */
+typedef struct pcg_house_loss_args {
+  const float* d_real; const float* d_fake; const float* d_fake_g; int32_t n;
+  const float* g_cls;                                  /* nullable with ce_row_loss */
+  const float* am; const float* pen;
+  float lambda_cls, w_reg, lambda_mask, w_reg_log;
+  const float* ce_row_loss;                            /* nullable */
+  int32_t n_ce;
+  float* out6;
+} pcg_house_loss_args;
+/* The four per-iteration diagnostics of house_sales_kc_usa/trainer.py:318-343 in one single-block launch (pcg_house_diag) or as a
+ * rider block of pcg_house_residual_bwd:
+ *   out4 = { pred_gain, sparsity (|masked residual| > eps), reg_loss_l2, class_flip_rate }
+ * logits_orig: the frozen classifier's logits of the ORIGINAL rows (it does not change during GAN training: evaluated once for the
+ * training set), gathered through src_rows (nullable: row b).  acc (nullable, double[8]): epoch accumulators —
+ * acc[2..5] += out4 (as a rider the launch also adds D_loss, G_loss and the iteration count to acc[0], acc[1], acc[6]),
+ * read once per epoch instead of six .item() calls per iteration (trainer.py:327-353). */
+typedef struct pcg_house_diag_args {
+  const float* logits_cf; const float* logits_orig;
+  const int64_t* src_rows;                             /* nullable */
+  const int64_t* target_y; const float* masked;
+  int32_t B, nc, D;
+  float eps;
+  float* out4;
+  double* acc;                                         /* nullable */
+} pcg_house_diag_args;
+/* rider (nullable): the critic step's training-mode power iterations (see "Riders" above) */
+int pcg_house_residual_fwd(const pcg_house_res_fwd_args* args, const pcg_sn_fwd_batch* rider /*nullable*/, pcg_stream_t stream);
+/* losses (nullable): the logged scalars ride in the launch; diag (nullable, only with losses): the diagnostics too (one more block) */
+int pcg_house_residual_bwd(const pcg_house_res_bwd_args* args, const pcg_house_loss_args* losses /*nullable*/,
+                           const pcg_house_diag_args* diag /*nullable*/, pcg_stream_t stream);
+int pcg_house_diag(const pcg_house_diag_args* args, pcg_stream_t stream);
 /* The three per-iteration draws of the tabular trainer in one launch — target class != y (trainer.py:248-249, as pcg_randint with
  * exclude), feature mask (:253-255, as pcg_feature_mask), Gumbel noise [B][T] (generator.py:90, as pcg_rand_gumbel) — each from its
  * own counter offset: the values the three separate calls produce.  onehot_target / onehot_y (nullable, [B][num_classes]): the float
@@ -811,25 +862,6 @@ int pcg_house_batch_draws_counter(int64_t* target_y, int32_t B, int32_t num_clas
                                   int64_t* src_out /*nullable*/, float* mask, int32_t D, const int32_t* zero_cols, int32_t n_zero_cols,
                                   float* noise, int32_t T, uint64_t seed, float* onehot_target /*nullable*/, float* onehot_y /*nullable*/,
                                   uint64_t* counter, pcg_stream_t stream);
-/* The four per-iteration diagnostics of house_sales_kc_usa/trainer.py:318-343 in one single-block launch:
- *   out4 = { pred_gain, sparsity (|masked residual| > eps), reg_loss_l2, class_flip_rate }
- * logits_orig: the frozen classifier's logits of the ORIGINAL rows (it does not change during GAN training: evaluated once for the
- * training set), gathered through src_rows (nullable: row b).  acc (nullable, double[8]): epoch accumulators —
- * acc[2..5] += out4 (pcg_house_residual_bwd_losses_diag also adds D_loss, G_loss and the iteration count to acc[0], acc[1], acc[6]),
- * read once per epoch instead of six .item() calls per iteration (trainer.py:327-353).                                          */
-int pcg_house_diag(const float* logits_cf, const float* logits_orig, const int64_t* src_rows /*nullable*/, const int64_t* target_y,
-                   const float* masked, int32_t B, int32_t nc, int32_t D, float eps, float* out4, double* acc /*nullable*/,
-                   pcg_stream_t stream);
-/* pcg_house_residual_bwd_losses with the diagnostics riding in the same launch (one more block) and the epoch accumulators. */
-int pcg_house_residual_bwd_losses_diag(const float* res, const float* masked, const float* mask, const float* gx_a, const float* gx_b,
-                                       float w_pen, float w_am, int32_t ncont, const int32_t* cont_idx_dev, const int32_t* seg_dev,
-                                       int32_t S, int32_t T, const int32_t* cat_idx_dev, const float* norm, int32_t D, int32_t B,
-                                       float* dcont, float* dsamples, const float* d_real, const float* d_fake, const float* d_fake_g,
-                                       int32_t n, const float* g_cls, const float* am, const float* pen, float lambda_cls, float w_reg,
-                                       float lambda_mask, float w_reg_log, const float* ce_row_loss, int32_t n_ce, float* out6,
-                                       const float* logits_cf, const float* logits_orig, const int64_t* src_rows /*nullable*/,
-                                       const int64_t* target_y, int32_t nc, float eps, float* diag_out4, double* acc /*nullable*/,
-                                       pcg_stream_t stream);
 
 /* A barrier of the ranks on the library's own communicator (a 4-byte all-reduce in stream order; synchronise `stream` afterwards):
  * bench.py brackets its timed region with it, so that region uses ONE communicator — the one that carries the gradient exchange.

@@ -127,6 +127,81 @@ class DenseBnBwd(ctypes.Structure):
     _fields_ = [(n, _P) for n in ("xhat", "gamma", "invstd", "dgamma", "dbeta")] + [("accumulate", _I)]
 
 
+_PP, _PI, _F = ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_int32), ctypes.c_float
+# In the structs below _PP / _PI members are HOST arrays (of device pointers / of ints): assign the ctypes array object itself, not its
+# address — the struct then keeps the array alive for as long as it lives.
+
+
+class SnFwdBatch(ctypes.Structure):
+    """pcg_sn_fwd_batch."""
+    _fields_ = ([("n", _I), ("reps", _I), ("power_iteration", _I), ("eps", _F), ("w_orig", _PP), ("out_features", _PI), ("in_features", _PI)] +
+                [(n, _PP) for n in ("u", "v", "w_bar", "sigma", "u_used", "v_used")])
+
+
+class SnBwdBatch(ctypes.Structure):
+    """pcg_sn_bwd_batch."""
+    _fields_ = [("n", _I), ("passes", _I), ("dw_bar", _PP), ("w_bar", _PP), ("out_features", _PI), ("in_features", _PI), ("u", _PP), ("v", _PP),
+                ("sigma", _PP), ("dw_orig", _PP), ("accumulate", _PI), ("db_dst", _PP), ("db_src", _PP)]
+
+
+class HouseCriticFwdArgs(ctypes.Structure):
+    """pcg_house_critic_fwd_args."""
+    _fields_ = ([(n, _I) for n in ("n_pass", "B", "D", "NC")] + [("slope", _F)] +
+                [(n, _PP) for n in ("x", "onehot", "w_bar", "bias", "a0", "a1", "a2", "a3", "out")])
+
+
+class HouseCriticBwdArgs(ctypes.Structure):
+    """pcg_house_critic_bwd_args."""
+    _fields_ = ([(n, _I) for n in ("n_pass", "B", "D")] + [("slope", _F)] +
+                [(n, _PP) for n in ("dout", "w_bar", "a1", "a2", "a3", "d3", "d2", "d1", "dx")])
+
+
+class HouseClsFwdArgs(ctypes.Structure):
+    """pcg_house_cls_fwd_args."""
+    _fields_ = ([("x", _P), ("B", _I), ("w_kmajor", _PP), ("bias", _PP)] + [(n, _P) for n in ("a1", "a2", "a3", "a4", "logits", "ce_target")] +
+                [("ce_grad_scale", _F), ("ce_dlogits", _P), ("ce_row_loss", _P)])
+
+
+class HouseClsBwdArgs(ctypes.Structure):
+    """pcg_house_cls_bwd_args."""
+    _fields_ = [("dlogits", _P), ("B", _I), ("w_stored", _PP)] + [(n, _P) for n in ("a1", "a2", "a3", "a4", "dx")]
+
+
+class HouseResFwdArgs(ctypes.Structure):
+    """pcg_house_res_fwd_args."""
+    _fields_ = ([("cont", _P), ("ncont", _I), ("samples", _P), ("seg_dev", _P), ("T", _I), ("norm", _P), ("x", _P), ("mask", _P), ("col_src", _PI),
+                 ("D", _I), ("B", _I)] + [(n, _P) for n in ("res", "masked", "x_cf", "partial512", "ticket", "pen_out", "am_out")])
+
+
+class HouseResBwdArgs(ctypes.Structure):
+    """pcg_house_res_bwd_args."""
+    _fields_ = ([(n, _P) for n in ("res", "masked", "mask", "gx_a", "gx_b")] + [("w_pen", _F), ("w_am", _F), ("ncont", _I), ("cont_idx_dev", _P),
+                ("seg_dev", _P), ("S", _I), ("T", _I), ("cat_idx_dev", _P), ("norm", _P), ("D", _I), ("B", _I), ("dcont", _P), ("dsamples", _P)])
+
+
+class HouseLossArgs(ctypes.Structure):
+    """pcg_house_loss_args."""
+    _fields_ = ([("d_real", _P), ("d_fake", _P), ("d_fake_g", _P), ("n", _I), ("g_cls", _P), ("am", _P), ("pen", _P)] +
+                [(n, _F) for n in ("lambda_cls", "w_reg", "lambda_mask", "w_reg_log")] + [("ce_row_loss", _P), ("n_ce", _I), ("out6", _P)])
+
+
+class HouseDiagArgs(ctypes.Structure):
+    """pcg_house_diag_args."""
+    _fields_ = ([(n, _P) for n in ("logits_cf", "logits_orig", "src_rows", "target_y", "masked")] + [("B", _I), ("nc", _I), ("D", _I), ("eps", _F),
+                ("out4", _P), ("acc", _P)])
+
+
+# typedef name in include/pcgan_hip.h -> its class here (pcg_abi_struct_bytes checks the sizes: tests/test_house_abi_host.py)
+STRUCTS = {"pcg_conv_geom": ConvGeom, "pcg_in_xform": InXform, "pcg_wgrad_item": WgradItem, "pcg_sn_fwd_batch": SnFwdBatch,
+           "pcg_sn_bwd_batch": SnBwdBatch, "pcg_house_g_desc": HouseGDesc, "pcg_house_g_fwd_args": HouseGFwdArgs,
+           "pcg_house_g_bwd_args": HouseGBwdArgs, "pcg_house_critic_fwd_args": HouseCriticFwdArgs,
+           "pcg_house_critic_bwd_args": HouseCriticBwdArgs, "pcg_house_cls_fwd_args": HouseClsFwdArgs, "pcg_house_cls_bwd_args": HouseClsBwdArgs,
+           "pcg_house_res_fwd_args": HouseResFwdArgs, "pcg_house_res_bwd_args": HouseResBwdArgs, "pcg_house_loss_args": HouseLossArgs,
+           "pcg_house_diag_args": HouseDiagArgs, "pcg_moons_cf_desc": MoonsCfDesc, "pcg_moons_cf_train_args": MoonsCfTrainArgs,
+           "pcg_moons_cf_fwd_args": MoonsCfFwdArgs, "pcg_moons_cf_eval_args": MoonsCfEvalArgs, "pcg_dense_bn": DenseBn,
+           "pcg_dense_bn_bwd": DenseBnBwd, "pcg_moons_gan_desc": MoonsGanDesc, "pcg_moons_gan_train_args": MoonsGanTrainArgs,
+           "pcg_moons_gan_fwd_args": MoonsGanFwdArgs}
+
 _c = ctypes
 _vp, _f, _i, _i64, _sz = _c.c_void_p, _c.c_float, _c.c_int, _c.c_int64, _c.c_size_t
 _d = _c.c_double
@@ -137,6 +212,7 @@ _xp = _c.POINTER(InXform)
 # name -> (restype, argtypes); every symbol include/pcgan_hip.h declares
 PROTOTYPES = {
     "pcg_abi_version": (_i, []),
+    "pcg_abi_struct_bytes": (_sz, [_c.c_char_p]),
     "pcg_last_error": (_c.c_char_p, []),
     "pcg_target_arch": (_c.c_char_p, []),
     "pcg_tune_set": (_i, [_c.c_char_p, _i32]),
@@ -289,38 +365,23 @@ PROTOTYPES = {
     "pcg_linear_wgrad_workspace_bytes": (_sz, [_i32, _i32, _i32]),
     "pcg_linear_wgrad_ticket_count": (_i32, []),
     "pcg_linear_wgrad": (_i, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _i, _i, _vp, _sz, _vp, _vp]),
-    "pcg_house_residual_fwd": (_i, [_vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _c.POINTER(_i32), _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "pcg_house_residual_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _f, _f, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp]),
-    "pcg_house_residual_fwd_sn": (_i, [_vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _c.POINTER(_i32), _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
-                                       _i32, _i32, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp]),
-    "pcg_house_residual_bwd_losses": (_i, [_vp, _vp, _vp, _vp, _vp, _f, _f, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _vp,
-                                           _vp, _vp, _vp, _i32, _vp, _vp, _vp, _f, _f, _f, _f, _vp, _i32, _vp, _vp]),
+    "pcg_spectral_norm_fwd_batched": (_i, [_c.POINTER(SnFwdBatch), _vp]),
+    "pcg_spectral_norm_bwd_batched": (_i, [_c.POINTER(SnBwdBatch), _vp]),
+    "pcg_house_critic_fwd": (_i, [_c.POINTER(HouseCriticFwdArgs), _vp]),
+    "pcg_house_critic_bwd": (_i, [_c.POINTER(HouseCriticBwdArgs), _vp]),
+    "pcg_house_classifier_fwd": (_i, [_c.POINTER(HouseClsFwdArgs), _c.POINTER(SnBwdBatch), _vp]),
+    "pcg_house_classifier_bwd": (_i, [_c.POINTER(HouseClsBwdArgs), _c.POINTER(SnFwdBatch), _vp]),
+    "pcg_house_residual_fwd": (_i, [_c.POINTER(HouseResFwdArgs), _c.POINTER(SnFwdBatch), _vp]),
+    "pcg_house_residual_bwd": (_i, [_c.POINTER(HouseResBwdArgs), _c.POINTER(HouseLossArgs), _c.POINTER(HouseDiagArgs), _vp]),
+    "pcg_house_diag": (_i, [_c.POINTER(HouseDiagArgs), _vp]),
     "pcg_house_draws": (_i, [_vp, _i32, _i32, _vp, _c.c_uint64, _vp, _i32, _vp, _i32, _c.c_uint64, _vp, _i32, _c.c_uint64, _c.c_uint64, _vp, _vp, _vp]),
     "pcg_house_draws_counter": (_i, [_vp, _i32, _i32, _vp, _vp, _i32, _vp, _i32, _vp, _i32, _c.c_uint64, _vp, _vp, _vp, _vp]),
     "pcg_house_batch_draws_counter": (_i, [_vp, _i32, _i32, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _i32, _c.c_uint64,
                                            _vp, _vp, _vp, _vp]),
-    "pcg_house_diag": (_i, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _f, _vp, _vp, _vp]),
-    "pcg_house_residual_bwd_losses_diag": (_i, [_vp, _vp, _vp, _vp, _vp, _f, _f, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _vp,
-                                                _vp, _vp, _vp, _i32, _vp, _vp, _vp, _f, _f, _f, _f, _vp, _i32, _vp,
-                                                _vp, _vp, _vp, _vp, _i32, _f, _vp, _vp, _vp]),
-    "pcg_house_critic_fwd_n": (_i, [_i32, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "pcg_house_critic_bwd_n": (_i, [_i32, _vp, _i32, _i32, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "pcg_spectral_norm_fwd_batched_reps": (_i, [_i32, _i32, _vp, _vp, _vp, _vp, _vp, _f, _i, _vp, _vp, _vp, _vp, _vp]),
-    "pcg_spectral_norm_bwd_batched_seq": (_i, [_i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "pcg_house_classifier_fwd": (_i, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "pcg_house_classifier_bwd": (_i, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "pcg_house_classifier_fwd_snbwd": (_i, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
-                                            _vp, _vp, _vp, _f, _vp, _vp, _vp]),
-    "pcg_house_classifier_bwd_snfwd": (_i, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp,
-                                            _vp]),
     "pcg_linear_wgrad_grouped_slabs": (_i32, [_i32]),
     "pcg_linear_wgrad_grouped_workspace_bytes": (_sz, [_i32, _c.POINTER(WgradItem), _i32]),
-    "pcg_house_critic_fwd": (_i, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "pcg_house_critic_bwd": (_i, [_vp, _i32, _i32, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pcg_linear_wgrad_grouped": (_i, [_c.POINTER(WgradItem), _i32, _i32, _vp, _sz, _vp, _vp]),
     "pcg_gemm_act": (_i, [_i, _i, _i32, _i32, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _i, _i, _f, _vp]),
-    "pcg_spectral_norm_fwd_batched": (_i, [_i32, _vp, _vp, _vp, _vp, _vp, _f, _i, _vp, _vp, _vp, _vp, _vp]),
-    "pcg_spectral_norm_bwd_batched": (_i, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pcg_onehot": (_i, [_vp, _i32, _i32, _vp, _vp]),
     "pcg_concat_cols": (_i, [_vp, _i32, _vp, _i32, _i32, _vp, _vp]),
     "pcg_split_cols": (_i, [_vp, _i32, _i32, _i32, _vp, _vp, _vp]),

@@ -350,7 +350,7 @@ __global__ void __launch_bounds__(CL_NT) classifier_bwd_kernel(ClsBwdArgs c) {
   classifier_bwd_body(c, s, blockIdx.x);
 }
 
-// Riders (see pcg_house_residual_fwd_sn): the frozen classifier's term of the generator loss does not depend on the critic update, so
+// Riders (see include/pcgan_hip.h): the frozen classifier's term of the generator loss does not depend on the critic update, so
 // its two launches carry the critic's spectral-norm work that sits on the chain at the same time — the first n blocks one matrix
 // each (256 of the 512 threads; the other four waves end at once, and a block barrier only waits for the waves that are left), the
 // blocks behind them the classifier body.  The two bodies share the block's LDS.  Same bodies, same bits as the separate launches.
@@ -379,72 +379,59 @@ __global__ void __launch_bounds__(CL_NT) classifier_bwd_snfwd_kernel(ClsBwdArgs 
 using namespace pcg;
 
 namespace {
-int fill_cls_fwd(ClsFwdArgs& c, const float* x, int32_t B, const float* const* w_kmajor, const float* const* bias, float* a1, float* a2, float* a3,
-                 float* a4, float* logits) {
-  PCG_REQUIRE(x && B > 0 && w_kmajor && bias && a1 && a2 && a3 && a4 && logits, "pcg_house_classifier_fwd: bad arguments");
-  for (int l = 0; l < 5; ++l) { PCG_REQUIRE(w_kmajor[l] && bias[l], "pcg_house_classifier_fwd: null layer %d", l); c.w.wt[l] = w_kmajor[l]; c.w.b[l] = bias[l]; }
-  c.x = x; c.B = B; c.a1 = a1; c.a2 = a2; c.a3 = a3; c.a4 = a4; c.logits = logits;
+int fill_cls_fwd(ClsFwdArgs& c, const pcg_house_cls_fwd_args* p) {
+  PCG_REQUIRE(p, "pcg_house_classifier_fwd: null argument struct");
+  PCG_REQUIRE(p->x && p->B > 0 && p->w_kmajor && p->bias && p->a1 && p->a2 && p->a3 && p->a4 && p->logits, "pcg_house_classifier_fwd: bad arguments");
+  for (int l = 0; l < 5; ++l) {
+    PCG_REQUIRE(p->w_kmajor[l] && p->bias[l], "pcg_house_classifier_fwd: null layer %d", l);
+    c.w.wt[l] = p->w_kmajor[l]; c.w.b[l] = p->bias[l];
+  }
+  c.x = p->x; c.B = p->B; c.a1 = p->a1; c.a2 = p->a2; c.a3 = p->a3; c.a4 = p->a4; c.logits = p->logits;
   return PCG_OK;
 }
-int fill_cls_bwd(ClsBwdArgs& c, const float* dlogits, int32_t B, const float* const* w_stored, const float* a1, const float* a2, const float* a3,
-                 const float* a4, float* dx) {
-  PCG_REQUIRE(dlogits && B > 0 && w_stored && a1 && a2 && a3 && a4 && dx, "pcg_house_classifier_bwd: bad arguments");
-  for (int l = 0; l < 5; ++l) { PCG_REQUIRE(w_stored[l], "pcg_house_classifier_bwd: null layer %d", l); c.w.w[l] = w_stored[l]; }
-  c.dlogits = dlogits; c.B = B; c.a1 = a1; c.a2 = a2; c.a3 = a3; c.a4 = a4; c.dx = dx;
+int fill_cls_bwd(ClsBwdArgs& c, const pcg_house_cls_bwd_args* p) {
+  PCG_REQUIRE(p, "pcg_house_classifier_bwd: null argument struct");
+  PCG_REQUIRE(p->dlogits && p->B > 0 && p->w_stored && p->a1 && p->a2 && p->a3 && p->a4 && p->dx, "pcg_house_classifier_bwd: bad arguments");
+  for (int l = 0; l < 5; ++l) { PCG_REQUIRE(p->w_stored[l], "pcg_house_classifier_bwd: null layer %d", l); c.w.w[l] = p->w_stored[l]; }
+  c.dlogits = p->dlogits; c.B = p->B; c.a1 = p->a1; c.a2 = p->a2; c.a3 = p->a3; c.a4 = p->a4; c.dx = p->dx;
   return PCG_OK;
 }
 }  // namespace
 
-extern "C" int pcg_house_classifier_fwd(const float* x, int32_t B, const float* const* w_kmajor, const float* const* bias, float* a1, float* a2,
-                                        float* a3, float* a4, float* logits, pcg_stream_t stream) {
+// rider: pcg_spectral_norm_bwd_batched in the same launch, its n blocks first in the grid
+extern "C" int pcg_house_classifier_fwd(const pcg_house_cls_fwd_args* args, const pcg_sn_bwd_batch* rider, pcg_stream_t stream) {
   ClsFwdArgs c{};
-  if (int e = fill_cls_fwd(c, x, B, w_kmajor, bias, a1, a2, a3, a4, logits)) return e;
-  hipLaunchKernelGGL(classifier_fwd_kernel, dim3((B + CL_R - 1) / CL_R), dim3(CL_NT), 0, (hipStream_t)stream, c);
-  return launch_status("classifier_fwd_kernel");
-}
-
-extern "C" int pcg_house_classifier_bwd(const float* dlogits, int32_t B, const float* const* w_stored, const float* a1, const float* a2,
-                                        const float* a3, const float* a4, float* dx, pcg_stream_t stream) {
-  ClsBwdArgs c{};
-  if (int e = fill_cls_bwd(c, dlogits, B, w_stored, a1, a2, a3, a4, dx)) return e;
-  hipLaunchKernelGGL(classifier_bwd_kernel, dim3((B + CL_R - 1) / CL_R), dim3(CL_NT), 0, (hipStream_t)stream, c);
-  return launch_status("classifier_bwd_kernel");
-}
-
-// pcg_house_classifier_fwd + pcg_spectral_norm_bwd_batched_seq as ONE launch
-extern "C" int pcg_house_classifier_fwd_snbwd(const float* x, int32_t B, const float* const* w_kmajor, const float* const* bias, float* a1, float* a2,
-                                              float* a3, float* a4, float* logits, int32_t n, int32_t passes, const float* const* dw_bar,
-                                              const float* const* w_bar, const int32_t* out_features, const int32_t* in_features,
-                                              const float* const* u, const float* const* v, const float* const* sigma, float* const* dw_orig,
-                                              const int32_t* accumulate, float* const* db_dst, const float* const* db_src,
-                                              const int64_t* ce_target, float ce_grad_scale, float* ce_dlogits, float* ce_row_loss,
-                                              pcg_stream_t stream) {
-  ClsFwdArgs c{};
-  if (int e = fill_cls_fwd(c, x, B, w_kmajor, bias, a1, a2, a3, a4, logits)) return e;
-  if (ce_target) {
-    PCG_REQUIRE(ce_dlogits && ce_row_loss && (reinterpret_cast<uintptr_t>(ce_dlogits) & 15) == 0,
-                "pcg_house_classifier_fwd_snbwd: the cross-entropy tail needs dlogits (16-byte aligned) and row_loss");
-    c.target = ce_target; c.ce_scale = ce_grad_scale; c.dlogits = ce_dlogits; c.rowloss = ce_row_loss;
+  if (int e = fill_cls_fwd(c, args)) return e;
+  const int ncls = (args->B + CL_R - 1) / CL_R;
+  if (!rider) {
+    PCG_REQUIRE(!args->ce_target, "pcg_house_classifier_fwd: the cross-entropy tail needs a rider (the plain kernel has never run it)");
+    hipLaunchKernelGGL(classifier_fwd_kernel, dim3(ncls), dim3(CL_NT), 0, (hipStream_t)stream, c);
+    return launch_status("classifier_fwd_kernel");
+  }
+  if (args->ce_target) {
+    PCG_REQUIRE(args->ce_dlogits && args->ce_row_loss && (reinterpret_cast<uintptr_t>(args->ce_dlogits) & 15) == 0,
+                "pcg_house_classifier_fwd: the cross-entropy tail needs dlogits (16-byte aligned) and row_loss");
+    c.target = args->ce_target; c.ce_scale = args->ce_grad_scale; c.dlogits = args->ce_dlogits; c.rowloss = args->ce_row_loss;
   }
   SnBwdBatch b{};
   SnBwdExtra xx{};
-  if (int e = fill_sn_bwd_batch(b, xx, n, passes, dw_bar, w_bar, out_features, in_features, u, v, sigma, dw_orig, accumulate, db_dst, db_src)) return e;
-  const int ncls = (B + CL_R - 1) / CL_R;
-  hipLaunchKernelGGL(classifier_fwd_snbwd_kernel, dim3(ncls + n), dim3(CL_NT), 0, (hipStream_t)stream, c, b, xx, n, passes);
+  if (int e = fill_sn_bwd_batch(b, xx, rider)) return e;
+  hipLaunchKernelGGL(classifier_fwd_snbwd_kernel, dim3(ncls + rider->n), dim3(CL_NT), 0, (hipStream_t)stream, c, b, xx, rider->n, rider->passes);
   return launch_status("classifier_fwd_snbwd_kernel");
 }
 
-// pcg_house_classifier_bwd + pcg_spectral_norm_fwd_batched_reps (training mode) as ONE launch
-extern "C" int pcg_house_classifier_bwd_snfwd(const float* dlogits, int32_t B, const float* const* w_stored, const float* a1, const float* a2,
-                                              const float* a3, const float* a4, float* dx, int32_t n, int32_t reps, const float* const* w_orig,
-                                              const int32_t* out_features, const int32_t* in_features, float* const* u, float* const* v, float eps,
-                                              float* const* w_bar, float* const* sigma, float* const* u_used, float* const* v_used,
-                                              pcg_stream_t stream) {
+// rider: a training-mode pcg_spectral_norm_fwd_batched in the same launch, its n blocks first in the grid
+extern "C" int pcg_house_classifier_bwd(const pcg_house_cls_bwd_args* args, const pcg_sn_fwd_batch* rider, pcg_stream_t stream) {
   ClsBwdArgs c{};
-  if (int e = fill_cls_bwd(c, dlogits, B, w_stored, a1, a2, a3, a4, dx)) return e;
+  if (int e = fill_cls_bwd(c, args)) return e;
+  const int ncls = (args->B + CL_R - 1) / CL_R;
+  if (!rider) {
+    hipLaunchKernelGGL(classifier_bwd_kernel, dim3(ncls), dim3(CL_NT), 0, (hipStream_t)stream, c);
+    return launch_status("classifier_bwd_kernel");
+  }
   SnFwdBatch b{};
-  if (int e = fill_sn_fwd_batch(b, n, reps, w_orig, out_features, in_features, u, v, 1, w_bar, sigma, u_used, v_used)) return e;
-  const int ncls = (B + CL_R - 1) / CL_R;
-  hipLaunchKernelGGL(classifier_bwd_snfwd_kernel, dim3(ncls + n), dim3(CL_NT), 0, (hipStream_t)stream, c, b, eps, n, reps);
+  if (int e = fill_sn_fwd_batch(b, rider)) return e;
+  PCG_REQUIRE(rider->power_iteration, "pcg_house_classifier_bwd: the spectral-norm rider is a training-mode call");
+  hipLaunchKernelGGL(classifier_bwd_snfwd_kernel, dim3(ncls + rider->n), dim3(CL_NT), 0, (hipStream_t)stream, c, b, rider->eps, rider->n, rider->reps);
   return launch_status("classifier_bwd_snfwd_kernel");
 }

@@ -273,55 +273,43 @@ int set_lds(const void* fn) {
 
 using namespace pcg;
 
-extern "C" int pcg_house_critic_fwd_n(int32_t n_pass, const float* const* x, const float* const* onehot, int32_t B, int32_t D, int32_t NC,
-                                      const float* const* w_bar /*[n_pass*4]*/, const float* const* bias /*[4]*/, float slope, float* const* a0,
-                                      float* const* a1, float* const* a2, float* const* a3, float* const* out, pcg_stream_t stream) {
-  PCG_REQUIRE(n_pass >= 1 && n_pass <= CP && x && onehot && w_bar && bias && a0 && a1 && a2 && a3 && out && B > 0,
-              "pcg_house_critic_fwd_n: bad arguments (1 or 2 passes)");
-  PCG_REQUIRE(D + NC == C0 && D > 0 && NC > 0, "pcg_house_critic_fwd_n: built for input_dim + num_classes = %d and hidden width %d", C0, C1);
+extern "C" int pcg_house_critic_fwd(const pcg_house_critic_fwd_args* p, pcg_stream_t stream) {
+  PCG_REQUIRE(p, "pcg_house_critic_fwd: null argument struct");
+  const int n_pass = p->n_pass;
+  PCG_REQUIRE(n_pass >= 1 && n_pass <= CP && p->x && p->onehot && p->w_bar && p->bias && p->a0 && p->a1 && p->a2 && p->a3 && p->out && p->B > 0,
+              "pcg_house_critic_fwd: bad arguments (1 or 2 passes)");
+  PCG_REQUIRE(p->D + p->NC == C0 && p->D > 0 && p->NC > 0, "pcg_house_critic_fwd: built for input_dim + num_classes = %d and hidden width %d", C0, C1);
   CFwdArgs args{};
   for (int q = 0; q < n_pass; ++q) {
     CFwdPass& ps = args.ps[q];
-    PCG_REQUIRE(x[q] && onehot[q] && a0[q] && a1[q] && a2[q] && a3[q] && out[q], "pcg_house_critic_fwd_n: pass %d: null buffer", q);
-    ps.x = x[q]; ps.onehot = onehot[q]; ps.a0 = a0[q]; ps.a1 = a1[q]; ps.a2 = a2[q]; ps.a3 = a3[q]; ps.out = out[q];
+    PCG_REQUIRE(p->x[q] && p->onehot[q] && p->a0[q] && p->a1[q] && p->a2[q] && p->a3[q] && p->out[q], "pcg_house_critic_fwd: pass %d: null buffer", q);
+    ps.x = p->x[q]; ps.onehot = p->onehot[q]; ps.a0 = p->a0[q]; ps.a1 = p->a1[q]; ps.a2 = p->a2[q]; ps.a3 = p->a3[q]; ps.out = p->out[q];
     for (int l = 0; l < 4; ++l) {
-      PCG_REQUIRE(w_bar[q * 4 + l] && bias[l], "pcg_house_critic_fwd_n: pass %d: null layer %d", q, l);
-      ps.p.w[l] = w_bar[q * 4 + l]; ps.p.b[l] = bias[l];
+      PCG_REQUIRE(p->w_bar[q * 4 + l] && p->bias[l], "pcg_house_critic_fwd: pass %d: null layer %d", q, l);
+      ps.p.w[l] = p->w_bar[q * 4 + l]; ps.p.b[l] = p->bias[l];
     }
   }
   static int once = set_lds(reinterpret_cast<const void*>(critic_fwd_kernel));
   if (once != PCG_OK) return once;
-  hipLaunchKernelGGL(critic_fwd_kernel, dim3((B + MR - 1) / MR, n_pass), dim3(256), sizeof(CritSmem), (hipStream_t)stream, args, D, NC, B, slope);
+  hipLaunchKernelGGL(critic_fwd_kernel, dim3((p->B + MR - 1) / MR, n_pass), dim3(256), sizeof(CritSmem), (hipStream_t)stream, args, p->D, p->NC, p->B,
+                     p->slope);
   return launch_status("critic_fwd_kernel");
 }
 
-extern "C" int pcg_house_critic_fwd(const float* x, const float* onehot, int32_t B, int32_t D, int32_t NC, const float* const* w_bar,
-                                    const float* const* bias, float slope, float* a0, float* a1, float* a2, float* a3, float* out,
-                                    pcg_stream_t stream) {
-  PCG_REQUIRE(w_bar && bias, "pcg_house_critic_fwd: bad arguments");
-  return pcg_house_critic_fwd_n(1, &x, &onehot, B, D, NC, w_bar, bias, slope, &a0, &a1, &a2, &a3, &out, stream);
-}
-
-extern "C" int pcg_house_critic_bwd_n(int32_t n_pass, const float* const* dout, int32_t B, int32_t D, const float* const* w_bar /*[n_pass*4]*/,
-                                      float slope, const float* const* a1, const float* const* a2, const float* const* a3, float* const* d3,
-                                      float* const* d2, float* const* d1, float* const* dx /*entries nullable*/, pcg_stream_t stream) {
-  PCG_REQUIRE(n_pass >= 1 && n_pass <= CP && dout && w_bar && a1 && a2 && a3 && d3 && d2 && d1 && dx && B > 0 && D > 0 && D <= C0,
-              "pcg_house_critic_bwd_n: bad arguments (1 or 2 passes)");
+extern "C" int pcg_house_critic_bwd(const pcg_house_critic_bwd_args* p, pcg_stream_t stream) {
+  PCG_REQUIRE(p, "pcg_house_critic_bwd: null argument struct");
+  const int n_pass = p->n_pass;
+  PCG_REQUIRE(n_pass >= 1 && n_pass <= CP && p->dout && p->w_bar && p->a1 && p->a2 && p->a3 && p->d3 && p->d2 && p->d1 && p->dx && p->B > 0 &&
+                  p->D > 0 && p->D <= C0, "pcg_house_critic_bwd: bad arguments (1 or 2 passes)");
   CBwdArgs args{};
   for (int q = 0; q < n_pass; ++q) {
     CBwdPass& ps = args.ps[q];
-    PCG_REQUIRE(dout[q] && a1[q] && a2[q] && a3[q] && d3[q] && d2[q] && d1[q], "pcg_house_critic_bwd_n: pass %d: null buffer", q);
-    ps.dout = dout[q]; ps.a1 = a1[q]; ps.a2 = a2[q]; ps.a3 = a3[q]; ps.d3o = d3[q]; ps.d2o = d2[q]; ps.d1o = d1[q]; ps.dx = dx[q];
-    for (int l = 0; l < 4; ++l) { PCG_REQUIRE(w_bar[q * 4 + l], "pcg_house_critic_bwd_n: pass %d: null layer %d", q, l); ps.p.w[l] = w_bar[q * 4 + l]; }
+    PCG_REQUIRE(p->dout[q] && p->a1[q] && p->a2[q] && p->a3[q] && p->d3[q] && p->d2[q] && p->d1[q], "pcg_house_critic_bwd: pass %d: null buffer", q);
+    ps.dout = p->dout[q]; ps.a1 = p->a1[q]; ps.a2 = p->a2[q]; ps.a3 = p->a3[q]; ps.d3o = p->d3[q]; ps.d2o = p->d2[q]; ps.d1o = p->d1[q]; ps.dx = p->dx[q];
+    for (int l = 0; l < 4; ++l) { PCG_REQUIRE(p->w_bar[q * 4 + l], "pcg_house_critic_bwd: pass %d: null layer %d", q, l); ps.p.w[l] = p->w_bar[q * 4 + l]; }
   }
   static int once = set_lds(reinterpret_cast<const void*>(critic_bwd_kernel));
   if (once != PCG_OK) return once;
-  hipLaunchKernelGGL(critic_bwd_kernel, dim3((B + MR - 1) / MR, n_pass), dim3(256), sizeof(CritSmem), (hipStream_t)stream, args, B, slope, D);
+  hipLaunchKernelGGL(critic_bwd_kernel, dim3((p->B + MR - 1) / MR, n_pass), dim3(256), sizeof(CritSmem), (hipStream_t)stream, args, p->B, p->slope, p->D);
   return launch_status("critic_bwd_kernel");
-}
-
-extern "C" int pcg_house_critic_bwd(const float* dout, int32_t B, int32_t D, const float* const* w_bar, float slope, const float* a1,
-                                    const float* a2, const float* a3, float* d3, float* d2, float* d1, float* dx, pcg_stream_t stream) {
-  PCG_REQUIRE(w_bar, "pcg_house_critic_bwd: bad arguments");
-  return pcg_house_critic_bwd_n(1, &dout, B, D, w_bar, slope, &a1, &a2, &a3, &d3, &d2, &d1, &dx, stream);
 }

@@ -2,6 +2,7 @@
 #include "pcg_common.h"
 #include <stdarg.h>
 #include <stdio.h>
+#include <string.h>
 
 namespace pcg {
 namespace {
@@ -26,7 +27,10 @@ int launch_status(const char* what) {
 }
 }  // namespace pcg
 
-// ABI history.  v5, additive: + pcg_conv_precision_set / _get (thread-local bf16-operand mode of the implicit-GEMM convolutions).
+// ABI history.  v6: the tabular step's launches take argument structs, a rider is an optional struct pointer (eighteen entry points
+//   became nine: pcg_spectral_norm_{fwd,bwd}_batched, pcg_house_critic_{fwd,bwd}, pcg_house_classifier_{fwd,bwd},
+//   pcg_house_residual_{fwd,bwd}, pcg_house_diag); + pcg_abi_struct_bytes.
+// v5, additive: + pcg_conv_precision_set / _get (thread-local bf16-operand mode of the implicit-GEMM convolutions).
 // v5 (r04): + grouped batches (pcg_conv2d_fwd_bn_g, pcg_bn_apply_act_g, pcg_conv2d_dgrad_bn_phases, pcg_conv2d_dgrad_bnbwd_g,
 //   pcg_bn_bwd_partial_g(+_workspace_bytes), pcg_bn_act_bwd_premask_g(+pcg_bn_act_bwd_g_workspace_bytes), pcg_bce_pair),
 //   pcg_conv2d_fwd_bnbwd_thin(+_ok, +_workspace_bytes), pcg_conv_weight_adjoint_many, pcg_conv_reset_scratch, pcg_dp_barrier,
@@ -36,7 +40,23 @@ int launch_status(const char* what) {
 //   critic-stage entry points.  v3 (r02): pcg_adam_step_capturable scratch is 48 bytes; pcg_linear_wgrad_grouped takes whole layers;
 //   + the pcg_house_* / spectral-norm reps / seq entry points.  v2 (r02): + pcg_conv2d_*_xf, pcg_bn_train_stats_coef, pcg_dp_*;
 //   pcg_bn_bwd_partial takes fp64 partial rows.
-extern "C" int pcg_abi_version(void) { return 5; }
+extern "C" int pcg_abi_version(void) { return 6; }
+extern "C" size_t pcg_abi_struct_bytes(const char* name) {
+#define PCG_STRUCT(T) {#T, sizeof(T)}
+  static const struct { const char* name; size_t bytes; } table[] = {
+      PCG_STRUCT(pcg_conv_geom), PCG_STRUCT(pcg_in_xform), PCG_STRUCT(pcg_wgrad_item), PCG_STRUCT(pcg_sn_fwd_batch), PCG_STRUCT(pcg_sn_bwd_batch),
+      PCG_STRUCT(pcg_house_g_desc), PCG_STRUCT(pcg_house_g_fwd_args), PCG_STRUCT(pcg_house_g_bwd_args), PCG_STRUCT(pcg_house_critic_fwd_args),
+      PCG_STRUCT(pcg_house_critic_bwd_args), PCG_STRUCT(pcg_house_cls_fwd_args), PCG_STRUCT(pcg_house_cls_bwd_args),
+      PCG_STRUCT(pcg_house_res_fwd_args), PCG_STRUCT(pcg_house_res_bwd_args), PCG_STRUCT(pcg_house_loss_args), PCG_STRUCT(pcg_house_diag_args),
+      PCG_STRUCT(pcg_moons_cf_desc), PCG_STRUCT(pcg_moons_cf_train_args), PCG_STRUCT(pcg_moons_cf_fwd_args), PCG_STRUCT(pcg_moons_cf_eval_args),
+      PCG_STRUCT(pcg_dense_bn), PCG_STRUCT(pcg_dense_bn_bwd), PCG_STRUCT(pcg_moons_gan_desc), PCG_STRUCT(pcg_moons_gan_train_args),
+      PCG_STRUCT(pcg_moons_gan_fwd_args)};
+#undef PCG_STRUCT
+  if (name)
+    for (const auto& t : table)
+      if (!strcmp(t.name, name)) return t.bytes;
+  return 0;
+}
 extern "C" const char* pcg_last_error(void) { return pcg::g_err; }
 extern "C" const char* pcg_target_arch(void) { return "gfx950"; }
 extern "C" int pcg_conv_precision_set(int32_t precision) {

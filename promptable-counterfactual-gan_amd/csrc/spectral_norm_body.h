@@ -253,39 +253,41 @@ __device__ __forceinline__ void spectral_norm_bwd_seq_body(const SnBwdBatch& b, 
   if (x.db_dst[l])
     for (int i = threadIdx.x; i < b.O[l]; i += 256) x.db_dst[l][i] += x.db_src[l][i];
 }
-// host side: argument blocks of the batched launches from the C-ABI arrays
-inline int fill_sn_fwd_batch(SnFwdBatch& b, int32_t n, int32_t reps, const float* const* w_orig, const int32_t* out_features, const int32_t* in_features,
-                             float* const* u, float* const* v, int power_iteration, float* const* w_bar, float* const* sigma, float* const* u_used,
-                             float* const* v_used) {
-  PCG_REQUIRE(n > 0 && reps >= 1 && n * reps <= SN_MAX && w_orig && out_features && in_features && u && v && w_bar && sigma && u_used && v_used,
-              "pcg_spectral_norm_fwd_batched: bad arguments (at most %d layers x calls)", SN_MAX);
-  PCG_REQUIRE(reps == 1 || power_iteration, "pcg_spectral_norm_fwd_batched_reps: several calls only differ in training mode");
+// host side: argument blocks of the batched launches from the C-ABI structs (alone or as the rider of another launch)
+inline int fill_sn_fwd_batch(SnFwdBatch& b, const pcg_sn_fwd_batch* p) {
+  PCG_REQUIRE(p, "pcg_spectral_norm_fwd_batched: null argument struct");
+  const int n = p->n, reps = p->reps;
+  PCG_REQUIRE(n > 0 && reps >= 1 && n * reps <= SN_MAX && p->w_orig && p->out_features && p->in_features && p->u && p->v && p->w_bar && p->sigma &&
+                  p->u_used && p->v_used, "pcg_spectral_norm_fwd_batched: bad arguments (at most %d layers x calls)", SN_MAX);
+  PCG_REQUIRE(reps == 1 || p->power_iteration, "pcg_spectral_norm_fwd_batched: several calls only differ in training mode");
   for (int l = 0; l < n; ++l) {
-    PCG_REQUIRE(w_orig[l] && u[l] && v[l] && out_features[l] > 0 && out_features[l] <= 256 && in_features[l] > 0 && in_features[l] <= 256,
-                "pcg_spectral_norm_fwd_batched: layer %d: bad arguments", l);
-    b.W[l] = w_orig[l]; b.u[l] = u[l]; b.v[l] = v[l]; b.O[l] = out_features[l]; b.I[l] = in_features[l];
+    PCG_REQUIRE(p->w_orig[l] && p->u[l] && p->v[l] && p->out_features[l] > 0 && p->out_features[l] <= 256 && p->in_features[l] > 0 &&
+                    p->in_features[l] <= 256, "pcg_spectral_norm_fwd_batched: layer %d: bad arguments", l);
+    b.W[l] = p->w_orig[l]; b.u[l] = p->u[l]; b.v[l] = p->v[l]; b.O[l] = p->out_features[l]; b.I[l] = p->in_features[l];
   }
   for (int e = 0; e < n * reps; ++e) {
-    PCG_REQUIRE(w_bar[e] && sigma[e], "pcg_spectral_norm_fwd_batched: output set %d: null buffer", e);
-    b.Wbar[e] = w_bar[e]; b.sigma[e] = sigma[e]; b.uu[e] = u_used[e]; b.vu[e] = v_used[e];
+    PCG_REQUIRE(p->w_bar[e] && p->sigma[e], "pcg_spectral_norm_fwd_batched: output set %d: null buffer", e);
+    b.Wbar[e] = p->w_bar[e]; b.sigma[e] = p->sigma[e]; b.uu[e] = p->u_used[e]; b.vu[e] = p->v_used[e];
   }
   return PCG_OK;
 }
-inline int fill_sn_bwd_batch(SnBwdBatch& b, SnBwdExtra& x, int32_t n, int32_t passes, const float* const* dw_bar, const float* const* w_bar,
-                             const int32_t* out_features, const int32_t* in_features, const float* const* u, const float* const* v,
-                             const float* const* sigma, float* const* dw_orig, const int32_t* accumulate, float* const* db_dst,
-                             const float* const* db_src) {
-  PCG_REQUIRE(n > 0 && passes >= 1 && n * passes <= SN_MAX && dw_bar && w_bar && out_features && in_features && u && v && sigma && dw_orig && accumulate,
-              "pcg_spectral_norm_bwd_batched: bad arguments (at most %d layers x passes)", SN_MAX);
+inline int fill_sn_bwd_batch(SnBwdBatch& b, SnBwdExtra& x, const pcg_sn_bwd_batch* p) {
+  PCG_REQUIRE(p, "pcg_spectral_norm_bwd_batched: null argument struct");
+  const int n = p->n, passes = p->passes;
+  PCG_REQUIRE(n > 0 && passes >= 1 && n * passes <= SN_MAX && p->dw_bar && p->w_bar && p->out_features && p->in_features && p->u && p->v &&
+                  p->sigma && p->dw_orig && p->accumulate, "pcg_spectral_norm_bwd_batched: bad arguments (at most %d layers x passes)", SN_MAX);
   for (int l = 0; l < n; ++l) {
-    PCG_REQUIRE(dw_orig[l] && out_features[l] > 0 && out_features[l] <= 256 && in_features[l] > 0 && in_features[l] <= 256,
+    PCG_REQUIRE(p->dw_orig[l] && p->out_features[l] > 0 && p->out_features[l] <= 256 && p->in_features[l] > 0 && p->in_features[l] <= 256,
                 "pcg_spectral_norm_bwd_batched: layer %d: bad arguments", l);
-    b.dW[l] = dw_orig[l]; b.O[l] = out_features[l]; b.I[l] = in_features[l]; b.acc[l] = accumulate[l];
-    if (db_dst && db_dst[l]) { PCG_REQUIRE(db_src && db_src[l], "pcg_spectral_norm_bwd_batched_seq: layer %d: db_src missing", l); x.db_dst[l] = db_dst[l]; x.db_src[l] = db_src[l]; }
+    b.dW[l] = p->dw_orig[l]; b.O[l] = p->out_features[l]; b.I[l] = p->in_features[l]; b.acc[l] = p->accumulate[l];
+    if (p->db_dst && p->db_dst[l]) {
+      PCG_REQUIRE(p->db_src && p->db_src[l], "pcg_spectral_norm_bwd_batched: layer %d: db_src missing", l);
+      x.db_dst[l] = p->db_dst[l]; x.db_src[l] = p->db_src[l];
+    }
   }
   for (int e = 0; e < n * passes; ++e) {
-    PCG_REQUIRE(dw_bar[e] && w_bar[e] && u[e] && v[e] && sigma[e], "pcg_spectral_norm_bwd_batched: entry %d: null buffer", e);
-    b.dWbar[e] = dw_bar[e]; b.Wbar[e] = w_bar[e]; b.u[e] = u[e]; b.v[e] = v[e]; b.sigma[e] = sigma[e];
+    PCG_REQUIRE(p->dw_bar[e] && p->w_bar[e] && p->u[e] && p->v[e] && p->sigma[e], "pcg_spectral_norm_bwd_batched: entry %d: null buffer", e);
+    b.dWbar[e] = p->dw_bar[e]; b.Wbar[e] = p->w_bar[e]; b.u[e] = p->u[e]; b.v[e] = p->v[e]; b.sigma[e] = p->sigma[e];
   }
   return PCG_OK;
 }

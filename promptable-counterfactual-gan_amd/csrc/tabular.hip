@@ -921,37 +921,20 @@ extern "C" int pcg_gemm_act(int transA, int transB, int32_t M, int32_t N, int32_
   return launch_status("gemm_kernel");
 }
 
-extern "C" int pcg_spectral_norm_fwd_batched_reps(int32_t n, int32_t reps, const float* const* w_orig, const int32_t* out_features,
-                                                  const int32_t* in_features, float* const* u, float* const* v, float eps, int power_iteration,
-                                                  float* const* w_bar, float* const* sigma, float* const* u_used, float* const* v_used,
-                                                  pcg_stream_t stream) {
+extern "C" int pcg_spectral_norm_fwd_batched(const pcg_sn_fwd_batch* batch, pcg_stream_t stream) {
   SnFwdBatch b{};
-  if (int e = fill_sn_fwd_batch(b, n, reps, w_orig, out_features, in_features, u, v, power_iteration, w_bar, sigma, u_used, v_used)) return e;
-  hipLaunchKernelGGL(spectral_norm_fwd_batched_kernel, dim3(n), dim3(256), 0, (hipStream_t)stream, b, eps, power_iteration, n, reps);
+  if (int e = fill_sn_fwd_batch(b, batch)) return e;
+  hipLaunchKernelGGL(spectral_norm_fwd_batched_kernel, dim3(batch->n), dim3(256), 0, (hipStream_t)stream, b, batch->eps, batch->power_iteration,
+                     batch->n, batch->reps);
   return launch_status("spectral_norm_fwd_batched_kernel");
 }
 
-extern "C" int pcg_spectral_norm_fwd_batched(int32_t n, const float* const* w_orig, const int32_t* out_features, const int32_t* in_features,
-                                             float* const* u, float* const* v, float eps, int power_iteration, float* const* w_bar,
-                                             float* const* sigma, float* const* u_used, float* const* v_used, pcg_stream_t stream) {
-  return pcg_spectral_norm_fwd_batched_reps(n, 1, w_orig, out_features, in_features, u, v, eps, power_iteration, w_bar, sigma, u_used, v_used, stream);
-}
-
-extern "C" int pcg_spectral_norm_bwd_batched_seq(int32_t n, int32_t passes, const float* const* dw_bar, const float* const* w_bar,
-                                                 const int32_t* out_features, const int32_t* in_features, const float* const* u,
-                                                 const float* const* v, const float* const* sigma, float* const* dw_orig, const int32_t* accumulate,
-                                                 float* const* db_dst, const float* const* db_src, pcg_stream_t stream) {
+extern "C" int pcg_spectral_norm_bwd_batched(const pcg_sn_bwd_batch* batch, pcg_stream_t stream) {
   SnBwdBatch b{};
   SnBwdExtra x{};
-  if (int e = fill_sn_bwd_batch(b, x, n, passes, dw_bar, w_bar, out_features, in_features, u, v, sigma, dw_orig, accumulate, db_dst, db_src)) return e;
-  hipLaunchKernelGGL(spectral_norm_bwd_batched_kernel, dim3(n), dim3(256), 0, (hipStream_t)stream, b, x, n, passes);
+  if (int e = fill_sn_bwd_batch(b, x, batch)) return e;
+  hipLaunchKernelGGL(spectral_norm_bwd_batched_kernel, dim3(batch->n), dim3(256), 0, (hipStream_t)stream, b, x, batch->n, batch->passes);
   return launch_status("spectral_norm_bwd_batched_kernel");
-}
-
-extern "C" int pcg_spectral_norm_bwd_batched(int32_t n, const float* const* dw_bar, const float* const* w_bar, const int32_t* out_features,
-                                             const int32_t* in_features, const float* const* u, const float* const* v,
-                                             const float* const* sigma, float* const* dw_orig, const int32_t* accumulate, pcg_stream_t stream) {
-  return pcg_spectral_norm_bwd_batched_seq(n, 1, dw_bar, w_bar, out_features, in_features, u, v, sigma, dw_orig, accumulate, nullptr, nullptr, stream);
 }
 
 namespace {
@@ -1166,130 +1149,92 @@ extern "C" int pcg_spectral_norm_bwd(const float* dw_bar, const float* w_bar, in
 }
 
 namespace {
-int fill_res_fwd_args(ResFwdArgs& a, const float* cont, int32_t ncont, const float* samples, const int32_t* seg_dev, int32_t T, const float* norm,
-                      const float* x, const float* mask, const int32_t* col_src, int32_t D, int32_t B, float* res, float* masked, float* x_cf,
-                      float* partial512, int32_t* ticket, float* pen_out, float* am_out) {
-  PCG_REQUIRE(cont && samples && seg_dev && norm && x && mask && col_src && res && masked && x_cf && partial512 && ticket && pen_out && am_out &&
-                  B > 0 && D > 0 && D <= 32 && T > 0 && ncont >= 0, "pcg_house_residual_fwd: bad arguments (at most 32 feature columns)");
+int fill_res_fwd_args(ResFwdArgs& a, const pcg_house_res_fwd_args* p) {
+  PCG_REQUIRE(p, "pcg_house_residual_fwd: null argument struct");
+  PCG_REQUIRE(p->cont && p->samples && p->seg_dev && p->norm && p->x && p->mask && p->col_src && p->res && p->masked && p->x_cf && p->partial512 &&
+                  p->ticket && p->pen_out && p->am_out && p->B > 0 && p->D > 0 && p->D <= 32 && p->T > 0 && p->ncont >= 0,
+              "pcg_house_residual_fwd: bad arguments (at most 32 feature columns)");
   int nseg = 0;                                            // number of categorical heads = the largest -(src) among the columns
-  for (int c = 0; c < D; ++c) { a.cols.src[c] = col_src[c]; if (col_src[c] < 0 && -col_src[c] > nseg) nseg = -col_src[c]; }
+  for (int c = 0; c < p->D; ++c) { a.cols.src[c] = p->col_src[c]; if (p->col_src[c] < 0 && -p->col_src[c] > nseg) nseg = -p->col_src[c]; }
   PCG_REQUIRE(nseg <= 32, "pcg_house_residual_fwd: at most 32 categorical heads");
-  a.cont = cont; a.ncont = ncont; a.samples = samples; a.seg = seg_dev; a.nseg = nseg; a.T = T; a.norm = norm; a.x = x; a.mask = mask; a.D = D;
-  a.n = (size_t)B * D; a.inv_n = 1.0 / (double)a.n; a.res = res; a.masked = masked; a.x_cf = x_cf; a.partial = partial512; a.ticket = ticket;
-  a.pen_out = pen_out; a.am_out = am_out;
+  a.cont = p->cont; a.ncont = p->ncont; a.samples = p->samples; a.seg = p->seg_dev; a.nseg = nseg; a.T = p->T; a.norm = p->norm; a.x = p->x;
+  a.mask = p->mask; a.D = p->D; a.n = (size_t)p->B * p->D; a.inv_n = 1.0 / (double)a.n; a.res = p->res; a.masked = p->masked; a.x_cf = p->x_cf;
+  a.partial = p->partial512; a.ticket = p->ticket; a.pen_out = p->pen_out; a.am_out = p->am_out;
   return PCG_OK;
 }
-int fill_res_bwd_args(ResBwdArgs& a, const float* res, const float* masked, const float* mask, const float* gx_a, const float* gx_b, float w_pen,
-                      float w_am, int32_t ncont, const int32_t* cont_idx_dev, const int32_t* seg_dev, int32_t S, int32_t T,
-                      const int32_t* cat_idx_dev, const float* norm, int32_t D, int32_t B, float* dcont, float* dsamples) {
-  PCG_REQUIRE(res && masked && mask && gx_a && gx_b && cont_idx_dev && seg_dev && cat_idx_dev && norm && dcont && dsamples && B > 0 && D > 0 &&
-                  S >= 0 && T > 0 && ncont >= 0 && ncont + S > 0, "pcg_house_residual_bwd: bad arguments");
-  a = ResBwdArgs{res, masked, mask, gx_a, gx_b, w_pen, w_am, (size_t)B * D, ncont, cont_idx_dev, seg_dev, S, T, cat_idx_dev, norm, D, B, dcont, dsamples};
+int fill_res_bwd_args(ResBwdArgs& a, const pcg_house_res_bwd_args* p) {
+  PCG_REQUIRE(p, "pcg_house_residual_bwd: null argument struct");
+  PCG_REQUIRE(p->res && p->masked && p->mask && p->gx_a && p->gx_b && p->cont_idx_dev && p->seg_dev && p->cat_idx_dev && p->norm && p->dcont &&
+                  p->dsamples && p->B > 0 && p->D > 0 && p->S >= 0 && p->T > 0 && p->ncont >= 0 && p->ncont + p->S > 0,
+              "pcg_house_residual_bwd: bad arguments");
+  a = ResBwdArgs{p->res, p->masked, p->mask, p->gx_a, p->gx_b, p->w_pen, p->w_am, (size_t)p->B * p->D, p->ncont, p->cont_idx_dev, p->seg_dev, p->S,
+                 p->T, p->cat_idx_dev, p->norm, p->D, p->B, p->dcont, p->dsamples};
+  return PCG_OK;
+}
+int fill_diag_args(DiagArgs& d, const pcg_house_diag_args* p) {
+  PCG_REQUIRE(p, "pcg_house_diag: null argument struct");
+  PCG_REQUIRE(p->logits_cf && p->logits_orig && p->target_y && p->masked && p->out4 && p->B > 0 && p->nc > 1 && p->nc <= 64 && p->D > 0,
+              "pcg_house_diag: bad arguments (B %d, classes %d, features %d)", p->B, p->nc, p->D);
+  d = DiagArgs{p->logits_cf, p->logits_orig, p->src_rows, p->target_y, p->masked, p->B, p->nc, p->D, p->eps, p->out4, p->acc};
   return PCG_OK;
 }
 }  // namespace
 
-extern "C" int pcg_house_residual_fwd(const float* cont, int32_t ncont, const float* samples, const int32_t* seg_dev, int32_t T, const float* norm,
-                                      const float* x, const float* mask, const int32_t* col_src, int32_t D, int32_t B, float* res, float* masked,
-                                      float* x_cf, float* partial512, int32_t* ticket, float* pen_out, float* am_out, pcg_stream_t stream) {
+// rider: a training-mode pcg_spectral_norm_fwd_batched in the same launch (the two do not depend on each other)
+extern "C" int pcg_house_residual_fwd(const pcg_house_res_fwd_args* args, const pcg_sn_fwd_batch* rider, pcg_stream_t stream) {
   ResFwdArgs a{};
-  if (int e = fill_res_fwd_args(a, cont, ncont, samples, seg_dev, T, norm, x, mask, col_src, D, B, res, masked, x_cf, partial512, ticket, pen_out, am_out)) return e;
+  if (int e = fill_res_fwd_args(a, args)) return e;
   hipStream_t s = (hipStream_t)stream;
-  if (a.n <= 16 * 1024) hipLaunchKernelGGL(house_residual_fwd_kernel<true>, dim3(1), dim3(1024), 0, s, a);
-  else hipLaunchKernelGGL(house_residual_fwd_kernel<false>, dim3(RES_BLOCKS), dim3(256), 0, s, a);
-  return launch_status("house_residual_fwd_kernel");
-}
-
-// pcg_house_residual_fwd + pcg_spectral_norm_fwd_batched_reps (training mode) as ONE launch: the two do not depend on each other
-extern "C" int pcg_house_residual_fwd_sn(const float* cont, int32_t ncont, const float* samples, const int32_t* seg_dev, int32_t T, const float* norm,
-                                         const float* x, const float* mask, const int32_t* col_src, int32_t D, int32_t B, float* res, float* masked,
-                                         float* x_cf, float* partial512, int32_t* ticket, float* pen_out, float* am_out,
-                                         int32_t n_layers, int32_t reps, const float* const* w_orig, const int32_t* out_features,
-                                         const int32_t* in_features, float* const* u, float* const* v, float eps, float* const* w_bar,
-                                         float* const* sigma, float* const* u_used, float* const* v_used, pcg_stream_t stream) {
-  ResFwdArgs a{};
-  if (int e = fill_res_fwd_args(a, cont, ncont, samples, seg_dev, T, norm, x, mask, col_src, D, B, res, masked, x_cf, partial512, ticket, pen_out, am_out)) return e;
+  if (!rider) {
+    if (a.n <= 16 * 1024) hipLaunchKernelGGL(house_residual_fwd_kernel<true>, dim3(1), dim3(1024), 0, s, a);
+    else hipLaunchKernelGGL(house_residual_fwd_kernel<false>, dim3(RES_BLOCKS), dim3(256), 0, s, a);
+    return launch_status("house_residual_fwd_kernel");
+  }
   SnFwdBatch b{};
-  if (int e = fill_sn_fwd_batch(b, n_layers, reps, w_orig, out_features, in_features, u, v, 1, w_bar, sigma, u_used, v_used)) return e;
-  hipStream_t s = (hipStream_t)stream;
+  if (int e = fill_sn_fwd_batch(b, rider)) return e;
+  PCG_REQUIRE(rider->power_iteration, "pcg_house_residual_fwd: the spectral-norm rider is a training-mode call");
   if (a.n <= 16 * 1024) {                                  // the one-block form of the residual kernel: two launches
     hipLaunchKernelGGL(house_residual_fwd_kernel<true>, dim3(1), dim3(1024), 0, s, a);
     if (int e = launch_status("house_residual_fwd_kernel")) return e;
-    hipLaunchKernelGGL(spectral_norm_fwd_batched_kernel, dim3(n_layers), dim3(256), 0, s, b, eps, 1, n_layers, reps);
+    hipLaunchKernelGGL(spectral_norm_fwd_batched_kernel, dim3(rider->n), dim3(256), 0, s, b, rider->eps, 1, rider->n, rider->reps);
     return launch_status("spectral_norm_fwd_batched_kernel");
   }
-  hipLaunchKernelGGL(house_residual_fwd_sn_kernel, dim3(RES_BLOCKS + n_layers), dim3(256), 0, s, a, b, eps, 1, n_layers, reps);
+  hipLaunchKernelGGL(house_residual_fwd_sn_kernel, dim3(RES_BLOCKS + rider->n), dim3(256), 0, s, a, b, rider->eps, 1, rider->n, rider->reps);
   return launch_status("house_residual_fwd_sn_kernel");
 }
 
-extern "C" int pcg_house_residual_bwd(const float* res, const float* masked, const float* mask, const float* gx_a, const float* gx_b, float w_pen,
-                                      float w_am, int32_t ncont, const int32_t* cont_idx_dev, const int32_t* seg_dev, int32_t S, int32_t T,
-                                      const int32_t* cat_idx_dev, const float* norm, int32_t D, int32_t B, float* dcont, float* dsamples,
+// losses: pcg_house_losses in the same launch (the logged scalars do not feed the backward); diag: the diagnostics block too, and the
+// epoch accumulators (acc[8] doubles: sum D_loss, sum G_loss, sum pred_gain, sum sparsity, sum l2, sum class_flip_rate, iterations, unused)
+extern "C" int pcg_house_residual_bwd(const pcg_house_res_bwd_args* args, const pcg_house_loss_args* losses, const pcg_house_diag_args* diag,
                                       pcg_stream_t stream) {
   ResBwdArgs a{};
-  if (int e = fill_res_bwd_args(a, res, masked, mask, gx_a, gx_b, w_pen, w_am, ncont, cont_idx_dev, seg_dev, S, T, cat_idx_dev, norm, D, B, dcont, dsamples)) return e;
-  const size_t work = (size_t)B * (ncont + S);
-  hipLaunchKernelGGL(house_residual_bwd_kernel, dim3((unsigned)std::min<size_t>((work + 255) / 256, 4096)), dim3(256), 0, (hipStream_t)stream, a);
-  return launch_status("house_residual_bwd_kernel");
-}
-
-// pcg_house_residual_bwd + pcg_house_losses as ONE launch (the logged scalars do not feed the backward)
-extern "C" int pcg_house_residual_bwd_losses(const float* res, const float* masked, const float* mask, const float* gx_a, const float* gx_b,
-                                             float w_pen, float w_am, int32_t ncont, const int32_t* cont_idx_dev, const int32_t* seg_dev, int32_t S,
-                                             int32_t T, const int32_t* cat_idx_dev, const float* norm, int32_t D, int32_t B, float* dcont,
-                                             float* dsamples, const float* d_real, const float* d_fake, const float* d_fake_g, int32_t n,
-                                             const float* g_cls, const float* am, const float* pen, float lambda_cls, float w_reg, float lambda_mask,
-                                             float w_reg_log, const float* ce_row_loss, int32_t n_ce, float* out6, pcg_stream_t stream) {
-  ResBwdArgs a{};
-  if (int e = fill_res_bwd_args(a, res, masked, mask, gx_a, gx_b, w_pen, w_am, ncont, cont_idx_dev, seg_dev, S, T, cat_idx_dev, norm, D, B, dcont, dsamples)) return e;
-  PCG_REQUIRE(d_real && d_fake && d_fake_g && (g_cls || ce_row_loss) && am && pen && out6 && n > 0 && n <= 16 * 1024 && (!ce_row_loss || n_ce > 0),
-              "pcg_house_residual_bwd_losses: bad arguments (critic outputs of at most 16384 rows)");
-  const LossArgs la{d_real, d_fake, d_fake_g, (size_t)n, 1.0 / (double)n, g_cls, am, pen, lambda_cls, w_reg, lambda_mask, w_reg_log, out6, ce_row_loss, n_ce, nullptr};
-  const size_t work = (size_t)B * (ncont + S);
-  hipLaunchKernelGGL(house_residual_bwd_losses_kernel, dim3(1 + (unsigned)std::min<size_t>((work + 1023) / 1024, 4096)), dim3(1024), 0,
-                     (hipStream_t)stream, a, la);
-  return launch_status("house_residual_bwd_losses_kernel");
-}
-
-namespace {
-int fill_diag_args(pcg::DiagArgs& d, const float* logits_cf, const float* logits_orig, const int64_t* src_rows, const int64_t* target_y,
-                   const float* masked, int32_t B, int32_t nc, int32_t D, float eps, float* out4, double* acc) {
-  PCG_REQUIRE(logits_cf && logits_orig && target_y && masked && out4 && B > 0 && nc > 1 && nc <= 64 && D > 0,
-              "pcg_house_diag: bad arguments (B %d, classes %d, features %d)", B, nc, D);
-  d = pcg::DiagArgs{logits_cf, logits_orig, src_rows, target_y, masked, B, nc, D, eps, out4, acc};
-  return PCG_OK;
-}
-}  // namespace
-
-extern "C" int pcg_house_diag(const float* logits_cf, const float* logits_orig, const int64_t* src_rows, const int64_t* target_y,
-                              const float* masked, int32_t B, int32_t nc, int32_t D, float eps, float* out4, double* acc,
-                              pcg_stream_t stream) {
+  if (int e = fill_res_bwd_args(a, args)) return e;
+  PCG_REQUIRE(losses || !diag, "pcg_house_residual_bwd: the diagnostics ride with the logged scalars only");
+  const size_t work = (size_t)args->B * (args->ncont + args->S);
+  hipStream_t s = (hipStream_t)stream;
+  if (!losses) {
+    hipLaunchKernelGGL(house_residual_bwd_kernel, dim3((unsigned)std::min<size_t>((work + 255) / 256, 4096)), dim3(256), 0, s, a);
+    return launch_status("house_residual_bwd_kernel");
+  }
+  const pcg_house_loss_args& l = *losses;
+  PCG_REQUIRE(l.d_real && l.d_fake && l.d_fake_g && (l.g_cls || l.ce_row_loss) && l.am && l.pen && l.out6 && l.n > 0 && l.n <= 16 * 1024 &&
+                  (!l.ce_row_loss || l.n_ce > 0), "pcg_house_residual_bwd: bad arguments (critic outputs of at most 16384 rows)");
+  const LossArgs la{l.d_real, l.d_fake, l.d_fake_g, (size_t)l.n, 1.0 / (double)l.n, l.g_cls, l.am, l.pen, l.lambda_cls, l.w_reg, l.lambda_mask,
+                    l.w_reg_log, l.out6, l.ce_row_loss, l.n_ce, diag ? diag->acc : nullptr};
+  const unsigned blocks = (unsigned)std::min<size_t>((work + 1023) / 1024, 4096);
+  if (!diag) {
+    hipLaunchKernelGGL(house_residual_bwd_losses_kernel, dim3(1 + blocks), dim3(1024), 0, s, a, la);
+    return launch_status("house_residual_bwd_losses_kernel");
+  }
   DiagArgs d{};
-  if (int e = fill_diag_args(d, logits_cf, logits_orig, src_rows, target_y, masked, B, nc, D, eps, out4, acc)) return e;
+  if (int e = fill_diag_args(d, diag)) return e;
+  hipLaunchKernelGGL(house_residual_bwd_losses_diag_kernel, dim3(2 + blocks), dim3(1024), 0, s, a, la, d);
+  return launch_status("house_residual_bwd_losses_diag_kernel");
+}
+
+extern "C" int pcg_house_diag(const pcg_house_diag_args* args, pcg_stream_t stream) {
+  DiagArgs d{};
+  if (int e = fill_diag_args(d, args)) return e;
   hipLaunchKernelGGL(house_diag_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, d);
   return launch_status("house_diag_kernel");
-}
-
-// pcg_house_residual_bwd_losses with the diagnostics block riding along and the epoch accumulators (acc[8] doubles:
-// sum D_loss, sum G_loss, sum pred_gain, sum sparsity, sum l2, sum class_flip_rate, iterations, unused)
-extern "C" int pcg_house_residual_bwd_losses_diag(const float* res, const float* masked, const float* mask, const float* gx_a, const float* gx_b,
-                                                  float w_pen, float w_am, int32_t ncont, const int32_t* cont_idx_dev, const int32_t* seg_dev,
-                                                  int32_t S, int32_t T, const int32_t* cat_idx_dev, const float* norm, int32_t D, int32_t B,
-                                                  float* dcont, float* dsamples, const float* d_real, const float* d_fake, const float* d_fake_g,
-                                                  int32_t n, const float* g_cls, const float* am, const float* pen, float lambda_cls, float w_reg,
-                                                  float lambda_mask, float w_reg_log, const float* ce_row_loss, int32_t n_ce, float* out6,
-                                                  const float* logits_cf, const float* logits_orig, const int64_t* src_rows,
-                                                  const int64_t* target_y, int32_t nc, float eps, float* diag_out4, double* acc,
-                                                  pcg_stream_t stream) {
-  ResBwdArgs a{};
-  if (int e = fill_res_bwd_args(a, res, masked, mask, gx_a, gx_b, w_pen, w_am, ncont, cont_idx_dev, seg_dev, S, T, cat_idx_dev, norm, D, B, dcont, dsamples)) return e;
-  PCG_REQUIRE(d_real && d_fake && d_fake_g && (g_cls || ce_row_loss) && am && pen && out6 && n > 0 && n <= 16 * 1024 && (!ce_row_loss || n_ce > 0),
-              "pcg_house_residual_bwd_losses_diag: bad arguments (critic outputs of at most 16384 rows)");
-  const LossArgs la{d_real, d_fake, d_fake_g, (size_t)n, 1.0 / (double)n, g_cls, am, pen, lambda_cls, w_reg, lambda_mask, w_reg_log, out6, ce_row_loss, n_ce, acc};
-  DiagArgs d{};
-  if (int e = fill_diag_args(d, logits_cf, logits_orig, src_rows, target_y, masked, B, nc, D, eps, diag_out4, acc)) return e;
-  const size_t work = (size_t)B * (ncont + S);
-  hipLaunchKernelGGL(house_residual_bwd_losses_diag_kernel, dim3(2 + (unsigned)std::min<size_t>((work + 1023) / 1024, 4096)), dim3(1024), 0,
-                     (hipStream_t)stream, a, la, d);
-  return launch_status("house_residual_bwd_losses_diag_kernel");
 }

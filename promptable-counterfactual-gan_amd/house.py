@@ -22,7 +22,7 @@ import torch.nn as nn
 from torch.nn.utils import spectral_norm
 
 from . import ops
-from ._lib import ACT_LRELU, ACT_NONE, ACT_RELU, PcgError, load as _lib_load
+from ._lib import ACT_LRELU, ACT_NONE, ACT_RELU, PcgError
 from .countergan import CrossEntropyLoss, abs_mean, grad_norm  # noqa: F401  (same loss kernels)
 from .nn import FlatModule, affine_fwd, in_conv_precision, linear_dgrad as _lin_dgrad, linear_fwd as _lin_fwd, linear_wgrad as _lin_wgrad, mean, weighted_sum  # noqa: F401
 from .optim import Adam
@@ -148,8 +148,7 @@ class ResidualGenerator(FlatModule):
 
     @in_conv_precision
     def _fused_forward(self, x, target_onehot, mask, noise, tau, hard):
-        import ctypes
-        from ._lib import HouseGFwdArgs, load
+        from ._lib import HouseGFwdArgs
         dev = x.device
         B, T, nc = x.shape[0], self.total_cat, len(self.continuous_idx)
         x, target_onehot, mask, noise = x.contiguous(), target_onehot.contiguous(), mask.contiguous(), noise.contiguous()
@@ -172,14 +171,13 @@ class ResidualGenerator(FlatModule):
                 a.num_batches_tracked[j] = bn.num_batches_tracked.data_ptr()
         bn0 = self.blocks[0].bn1
         a.B, a.eps, a.momentum, a.tau, a.res_scale = B, bn0.eps, bn0.momentum, tau, self.residual_scaling
-        ops.check(load().pcg_house_g_fwd(ctypes.byref(self._fused_desc()), ctypes.byref(a), ops._stream()), "pcg_house_g_fwd")
+        ops.house_g_fwd(self._fused_desc(), a)
         saved = ("fused", buf, target_onehot, mask, tau, nb)
         return buf["cont"], buf["logits"], (buf["hard"] if hard else buf["soft"]), saved
 
     @in_conv_precision
     def _fused_backward(self, saved, d_cont, d_logits, d_samples):
-        import ctypes
-        from ._lib import HouseGBwdArgs, load
+        from ._lib import HouseGBwdArgs
         _, buf, onehot, mask, tau, nb = saved
         B, T, nc = onehot.shape[0], self.total_cat, len(self.continuous_idx)
         f32 = dict(dtype=torch.float32, device=onehot.device)
@@ -201,7 +199,7 @@ class ResidualGenerator(FlatModule):
         for n, t in g.items():
             setattr(a, n, t.data_ptr())
         a.B, a.accumulate, a.tau, a.res_scale = B, int(acc), tau, self.residual_scaling
-        ops.check(load().pcg_house_g_bwd(ctypes.byref(self._fused_desc()), ctypes.byref(a), ops._stream()), "pcg_house_g_bwd")
+        ops.house_g_bwd(self._fused_desc(), a)
         # weight (+ bias) gradients of all 35 Linear layers: ONE launch (deterministic slab reduction per layer)
         inp, K = buf["inp"], buf["inp"].shape[1]
         cond = inp[:, self.input_dim:]
@@ -490,9 +488,7 @@ class Discriminator(FlatModule):
 
     def _spectral_norm(self):
         """Power iteration (training mode: updates u, v in place) + W / sigma of all four layers: one launch."""
-        lins = self._linears()
-        return ops.spectral_norm_fwd_batched([l.weight_orig.data for l in lins], [l.weight_u for l in lins], [l.weight_v for l in lins],
-                                             1e-12, self.training)
+        return ops.spectral_norm_fwd_batched(*self._sn_operands(), self.training)[0]
 
     @in_conv_precision
     def _run_forward(self, x, target_onehot, keep=True, sn=None):
@@ -501,17 +497,7 @@ class Discriminator(FlatModule):
             sn = self._spectral_norm()
         if self._fused_ok(x, target_onehot):
             # the four layers as ONE launch, one thread per row (csrc/house_critic_fused.hip)
-            import ctypes
-            from ._lib import load
-            x, target_onehot = x.contiguous(), target_onehot.contiguous()
-            B = x.shape[0]
-            f32 = dict(dtype=torch.float32, device=x.device)
-            acts = [torch.empty((B, n), **f32) for n in (21, 32, 64, 128)]
-            out = torch.empty((B, 1), **f32)
-            wb = [t[0] for t in sn]
-            ops.check(load().pcg_house_critic_fwd(ops._p(x), ops._p(target_onehot), B, x.shape[1], target_onehot.shape[1], ops._ptr_array(wb),
-                                                  ops._ptr_array([l.bias.data for l in lins]), 0.2, ops._p(acts[0]), ops._p(acts[1]),
-                                                  ops._p(acts[2]), ops._p(acts[3]), ops._p(out), ops._stream()), "pcg_house_critic_fwd")
+            (acts, out), = ops.house_critic_fwd([(x.contiguous(), target_onehot.contiguous())], [t[0] for t in sn], [l.bias.data for l in lins])
             return out, (("fused", acts, sn) if keep else None)
         a = ops.concat_cols(x.contiguous(), target_onehot.contiguous())                       # :19
         layers = []
@@ -536,29 +522,18 @@ class Discriminator(FlatModule):
         takes the last one as a rider): both power iterations, both forwards, both backwards, all sixteen
         weight / bias reductions, both passes through W / sigma.  Per element the arithmetic of the chained calls (same bits).
         Returns (D(a), D(b)).  `sn`: the result of the two power iterations when the caller has already launched them;
-        defer_sn_bwd: leave the last launch (the backward through W / sigma) to the caller, as a rider."""
-        import ctypes
-        from ._lib import load
+        defer_sn_bwd: leave the last launch (the backward through W / sigma) to the caller, as a rider: returns (D(a), D(b), its
+        ops.sn_bwd_batch)."""
         lins = self._linears()
         # sn: the two power iterations already made (they rode with the residual block's launch, ops.house_residual_fwd(sn=...))
-        sn_a, sn_b = sn if sn is not None else ops.spectral_norm_fwd_batched_reps(*self._sn_operands(), 2)
+        sn_a, sn_b = sn if sn is not None else ops.spectral_norm_fwd_batched(*self._sn_operands(), True, reps=2)
         B = x_a.shape[0]
-        dev = x_a.device
-        f32 = dict(dtype=torch.float32, device=dev)
-        ins = [(x_a.contiguous(), onehot_a.contiguous()), (x_b.contiguous(), onehot_b.contiguous())]
-        acts = [[torch.empty((B, n), **f32) for n in (21, 32, 64, 128)] for _ in range(2)]
-        outs = [torch.empty((B, 1), **f32) for _ in range(2)]
         wb = [t[0] for t in sn_a] + [t[0] for t in sn_b]
-        pa = ops._ptr_array
-        ops.check(load().pcg_house_critic_fwd_n(2, pa([i[0] for i in ins]), pa([i[1] for i in ins]), B, x_a.shape[1], onehot_a.shape[1], pa(wb),
-                                                pa([l.bias.data for l in lins]), 0.2, pa([a[0] for a in acts]), pa([a[1] for a in acts]),
-                                                pa([a[2] for a in acts]), pa([a[3] for a in acts]), pa(outs), ops._stream()),
-                  "pcg_house_critic_fwd_n")
+        fwd = ops.house_critic_fwd([(x_a.contiguous(), onehot_a.contiguous()), (x_b.contiguous(), onehot_b.contiguous())], wb,
+                                   [l.bias.data for l in lins])
+        acts, outs = [f[0] for f in fwd], [f[1] for f in fwd]
         d4 = [cot_a.contiguous(), cot_b.contiguous()]
-        d3, d2, d1 = ([torch.empty((B, n), **f32) for _ in range(2)] for n in (128, 64, 32))
-        null2 = (ctypes.c_void_p * 2)(None, None)
-        ops.check(load().pcg_house_critic_bwd_n(2, pa(d4), B, self.input_dim, pa(wb), 0.2, pa([a[1] for a in acts]), pa([a[2] for a in acts]),
-                                                pa([a[3] for a in acts]), pa(d3), pa(d2), pa(d1), null2, ops._stream()), "pcg_house_critic_bwd_n")
+        d3, d2, d1 = zip(*(r[:3] for r in ops.house_critic_bwd(d4, wb, acts, self.input_dim, False)))
         # pass b is the first writer of the gradient buffer, pass a adds (bias: through its own buffer, added behind the b pass)
         items, seq_b, seq_a, dws, accs, bias_adds = [], [], [], [], [], []
         for li, lin in enumerate(lins):
@@ -572,53 +547,38 @@ class Discriminator(FlatModule):
             seq_b.append((dw_b, sn_b[li][0], sn_b[li][2], sn_b[li][3], sn_b[li][1]))
             seq_a.append((dw_a, sn_a[li][0], sn_a[li][2], sn_a[li][3], sn_a[li][1]))
             dws.append(gw); accs.append(acc); bias_adds.append((gb, gb_a))
-        ops.linear_wgrad_grouped(items, B, dev)
-        if defer_sn_bwd:      # the caller launches the backward through W / sigma as a rider: (D(a), D(b), its arguments, what they point to)
-            return outs[0], outs[1], ops.sn_bwd_seq_args([seq_b, seq_a], dws, accs, bias_adds), (seq_b, seq_a, dws, bias_adds)
-        ops.spectral_norm_bwd_batched_seq([seq_b, seq_a], dws, accs, bias_adds)
+        ops.linear_wgrad_grouped(items, B, x_a.device)
+        if defer_sn_bwd:
+            return outs[0], outs[1], ops.sn_bwd_batch([seq_b, seq_a], dws, accs, bias_adds)
+        ops.spectral_norm_bwd_batched([seq_b, seq_a], dws, accs, bias_adds)
         return outs[0], outs[1]
 
     @in_conv_precision
-    def _fused_backward(self, saved, dout, need_x, need_p, gtarget=None):
-        """gtarget: a flat buffer with the layout of flat_grads that receives this pass's parameter gradients (written, not
-        accumulated) instead of the module's gradient buffer — see FlatModule.grad_view_in."""
-        from ._lib import load
+    def _fused_backward(self, saved, dout, need_x, need_p):
         _, acts, sn = saved
         lins = self._linears()
         d4 = dout.contiguous()
-        B = d4.shape[0]
-        f32 = dict(dtype=torch.float32, device=d4.device)
-        d3, d2, d1 = (torch.empty((B, n), **f32) for n in (128, 64, 32))
-        dx = torch.empty((B, self.input_dim), **f32) if need_x else None
-        ops.check(load().pcg_house_critic_bwd(ops._p(d4), B, self.input_dim, ops._ptr_array([t[0] for t in sn]), 0.2, ops._p(acts[1]),
-                                              ops._p(acts[2]), ops._p(acts[3]), ops._p(d3), ops._p(d2), ops._p(d1), ops._p(dx),
-                                              ops._stream()), "pcg_house_critic_bwd")
+        (d3, d2, d1, dx), = ops.house_critic_bwd([d4], [t[0] for t in sn], [acts], self.input_dim, need_x)
         if need_p and lins[0].weight_orig.requires_grad:
-            items, sn_items = [], []
+            items, seq, dws, accs = [], [], [], []
             for lin, a, d, (w_bar, sigma, u, v) in zip(lins, acts, (d1, d2, d3, d4), sn):
                 dwb = torch.empty_like(w_bar)
-                if gtarget is None:
-                    gb, accb = self._grad_view(lin.bias)
-                    gw, acc = self._grad_view(lin.weight_orig)
-                else:
-                    gb, accb = self.grad_view_in(gtarget, lin.bias), False
-                    gw, acc = self.grad_view_in(gtarget, lin.weight_orig), False
+                gb, accb = self._grad_view(lin.bias)
+                gw, acc = self._grad_view(lin.weight_orig)
                 items.append((d, a, lin.out_features, lin.in_features, dwb, gb, lin.out_features, lin.in_features, False, accb))
-                sn_items.append((dwb, w_bar, u, v, sigma, gw, acc))
-            ops.linear_wgrad_grouped(items, B, d4.device)                                    # all weight + bias gradients: one launch
-            ops.spectral_norm_bwd_batched(sn_items)                                          # through W / sigma: one launch
+                seq.append((dwb, w_bar, u, v, sigma)); dws.append(gw); accs.append(acc)
+            ops.linear_wgrad_grouped(items, d4.shape[0], d4.device)                          # all weight + bias gradients: one launch
+            ops.spectral_norm_bwd_batched([seq], dws, accs)                                  # through W / sigma: one launch
         return dx
 
     @in_conv_precision
-    def _run_backward(self, layers, dout, need_x, need_p, gtarget=None):
+    def _run_backward(self, layers, dout, need_x, need_p):
         if layers[0] == "fused":
-            return self._fused_backward(layers, dout, need_x, need_p, gtarget)
-        if gtarget is not None:
-            raise PcgError("Discriminator: a separate gradient target needs the fused critic kernels")
+            return self._fused_backward(layers, dout, need_x, need_p)
         lins = self._linears()
         d = dout.contiguous()
         B = d.shape[0]
-        sn_items = []
+        seq, dws, accs = [], [], []
         for i in range(len(lins) - 1, -1, -1):
             lin = lins[i]
             a, z, w_bar, sigma, u, v = layers[i]
@@ -628,11 +588,11 @@ class Discriminator(FlatModule):
                 dwb = torch.empty_like(w_bar)
                 _lin_wgrad(self, lin, a, d, dw_out=dwb, weight_param=lin.weight_orig)
                 gw, acc = self._grad_view(lin.weight_orig)
-                sn_items.append((dwb, w_bar, u, v, sigma, gw, acc))
+                seq.append((dwb, w_bar, u, v, sigma)); dws.append(gw); accs.append(acc)
             if i > 0 or need_x:
                 d = _lin_dgrad(w_bar, d, B)
-        if sn_items:
-            ops.spectral_norm_bwd_batched(sn_items)                                          # all layers: one launch
+        if seq:
+            ops.spectral_norm_bwd_batched([seq], dws, accs)                                  # all layers: one launch
         if not need_x:
             return None
         dx, _ = ops.split_cols(d, self.input_dim, d.shape[1] - self.input_dim, need_b=False)
@@ -801,33 +761,19 @@ class NNClassifier(FlatModule):
 
     @in_conv_precision
     def _run_forward(self, x, keep=True, sn_bwd_rider=None, ce=None):
-        """sn_bwd_rider: the argument list of a spectral-norm backward (ops.sn_bwd_seq_args) that rides in the fused forward launch
-        (the scheduled tabular step: the critic's spectral-norm backward is independent of this classifier).  ce = (target, grad_scale)
-        with a rider: the launch also leaves the cross-entropy's gradient and row terms; returns (logits, acts, dlogits, row_loss)."""
+        """sn_bwd_rider: a spectral-norm backward (ops.sn_bwd_batch) that rides in the fused forward launch (the scheduled tabular
+        step: the critic's spectral-norm backward is independent of this classifier).  ce = (target, grad_scale) with a rider: the
+        launch also leaves the cross-entropy's gradient and row terms; returns (logits, acts, dlogits, row_loss)."""
         packed = self._pack()
         a = x.contiguous()
-        B = a.shape[0]
         if sn_bwd_rider is not None and not self._fused_ok(a):
             raise PcgError("NNClassifier: a rider needs the fused forward launch")
+        if ce is not None and sn_bwd_rider is None:
+            raise PcgError("NNClassifier: the cross-entropy tail needs a rider")
         if self._fused_ok(a):
             # the five layers as ONE launch on the matrix cores (csrc/house_classifier_fused.hip)
-            from ._lib import load
-            f32 = dict(dtype=torch.float32, device=a.device)
-            acts = [torch.empty((B, n), **f32) for n in (256, 256, 128, 64)]
-            logits = torch.empty((B, 4), **f32)
-            cargs = (ops._p(a), B, ops._ptr_array(self._pack_kmajor()), ops._ptr_array([b for _, b in packed]), ops._p(acts[0]), ops._p(acts[1]),
-                     ops._p(acts[2]), ops._p(acts[3]), ops._p(logits))
-            if sn_bwd_rider is None:
-                ops.check(load().pcg_house_classifier_fwd(*cargs, ops._stream()), "pcg_house_classifier_fwd")
-            elif ce is None:
-                ops.check(load().pcg_house_classifier_fwd_snbwd(*cargs, *sn_bwd_rider, None, 0.0, None, None, ops._stream()),
-                          "pcg_house_classifier_fwd_snbwd")
-            else:
-                dlog, row_loss = torch.empty((B, 4), **f32), torch.empty((B,), **f32)
-                ops.check(load().pcg_house_classifier_fwd_snbwd(*cargs, *sn_bwd_rider, ops._p(ce[0]), float(ce[1]), ops._p(dlog), ops._p(row_loss),
-                                                                ops._stream()), "pcg_house_classifier_fwd_snbwd")
-                return logits, (acts if keep else None), dlog, row_loss
-            return logits, (acts if keep else None)
+            out = ops.house_classifier_fwd(a, self._pack_kmajor(), [b for _, b in packed], sn_bwd=sn_bwd_rider, ce=ce)
+            return (out[0], out[1] if keep else None) + out[2:]
         acts = []
         for i, (w, b) in enumerate(packed):
             z = affine_fwd(a, w, b, act=ACT_LRELU if i + 1 < len(packed) else ACT_NONE, slope=0.1)
@@ -839,8 +785,8 @@ class NNClassifier(FlatModule):
 
     @in_conv_precision
     def _run_backward(self, acts, dlogits, sn_fwd_rider=None):
-        """sn_fwd_rider = (w_origs, us, vs, eps, reps): that training-mode spectral normalisation rides in the fused backward launch;
-        the return value is then (dx, its outputs)."""
+        """sn_fwd_rider: a training-mode spectral normalisation (the batch of ops.sn_fwd_batch) that rides in the fused backward
+        launch; the return value is then (dx, its outputs)."""
         packed = self._pack()
         d = dlogits.contiguous()
         B = d.shape[0]
@@ -848,15 +794,7 @@ class NNClassifier(FlatModule):
         if sn_fwd_rider is not None and not fused:
             raise PcgError("NNClassifier: a rider needs the fused backward launch")
         if fused:
-            from ._lib import load
-            dx = torch.empty((B, 17), dtype=torch.float32, device=d.device)
-            cargs = (ops._p(d), B, ops._ptr_array([w for w, _ in packed]), ops._p(acts[0]), ops._p(acts[1]), ops._p(acts[2]), ops._p(acts[3]), ops._p(dx))
-            if sn_fwd_rider is None:
-                ops.check(load().pcg_house_classifier_bwd(*cargs, ops._stream()), "pcg_house_classifier_bwd")
-                return dx
-            outs, sn_args = ops.sn_fwd_reps_args(*sn_fwd_rider)
-            ops.check(load().pcg_house_classifier_bwd_snfwd(*cargs, *sn_args, ops._stream()), "pcg_house_classifier_bwd_snfwd")
-            return dx, outs
+            return ops.house_classifier_bwd(d, [w for w, _ in packed], acts, sn_fwd=sn_fwd_rider)
         for i in range(len(packed) - 1, -1, -1):
             if i + 1 < len(packed):
                 d = ops.act_bwd(d, acts[i], ACT_LRELU, 0.1, out=d)
@@ -948,20 +886,6 @@ def _acc_losses(acc, d_loss, g_loss):
 
 
 _cot_cache = {}
-_alt_cache = {}
-
-
-def _alt_grads(net):
-    """A second, zero-initialised gradient buffer with the layout of net.flat_grads (kept per net: passes that target it WRITE
-    every parameter's gradient, the padding between parameters stays zero)."""
-    g = net.flat_grads
-    key = (id(net), g.data_ptr())
-    a = _alt_cache.get(key)
-    if a is None:
-        a = ops.fill(torch.empty_like(g), 0.0)
-        _alt_cache[key] = a
-    return a
-
 
 
 def _mean_cotangents(B, device):
@@ -1000,7 +924,6 @@ def _train_step_branch(generator, discriminator, classifier, opt_g, opt_d, x, y,
     nc, dev, B = config["num_classes"], x.device, x.shape[0]
     if classifier.training or any(p.requires_grad for p in classifier.parameters()):
         raise PcgError("train_step(branch=...): the classifier must be frozen and in eval mode (main.py:27-30)")
-    branch, branch2 = branch if isinstance(branch, (tuple, list)) else (branch, None)
     main = torch.cuda.current_stream()
     if isinstance(branch, str):        # "inline": this schedule's kernels, all on the current stream (no fork: every wait is a no-op)
         branch = main
@@ -1020,10 +943,9 @@ def _train_step_branch(generator, discriminator, classifier, opt_g, opt_d, x, y,
         # iterations ride in it (they only read the critic's weights: one launch less on the chain)
         onehot_y = onehots[1] if onehots is not None else ops.onehot(y, nc)
         # (training mode: every critic call of the step makes a power iteration — the batched / riding forms assume it)
-        pair = (branch2 is None and discriminator.training and discriminator._fused_ok(x, onehot_y) and
-                all(p.requires_grad for p in discriminator.parameters()))
+        pair = discriminator.training and discriminator._fused_ok(x, onehot_y) and all(p.requires_grad for p in discriminator.parameters())
         rf = ops.house_residual_fwd(cont.contiguous(), samples.contiguous(), seg, norm_vals, x, mask, generator.col_src(),
-                                    sn=discriminator._sn_operands() + (2,) if pair else None)
+                                    sn=ops.sn_fwd_batch(*discriminator._sn_operands(), reps=2)[1] if pair else None)
         residual_full, masked_residual, x_cf, mask_penalty_pre, am = rf[:5]
         sn_pair = rf[5] if pair else None
     # the zero-fills of the two gradient buffers are not launched: every parameter of both nets receives a gradient in this step,
@@ -1050,43 +972,20 @@ def _train_step_branch(generator, discriminator, classifier, opt_g, opt_d, x, y,
     xd = x_cf.detach()
     with torch.no_grad():
         if riders:
-            d_real, d_fake, snb_args, snb_keep = discriminator._run_pair(x, onehot_y, cot_neg, xd, target_onehot, cot_pos, sn=sn_pair,
-                                                                         defer_sn_bwd=True)                   # :290-294, three launches
+            d_real, d_fake, sn_bwd = discriminator._run_pair(x, onehot_y, cot_neg, xd, target_onehot, cot_pos, sn=sn_pair,
+                                                             defer_sn_bwd=True)                               # :290-294, three launches
             # :301 + the fourth; with the logged scalars riding below, the cross-entropy (:302) is the tail of this launch too
             ce_tail = B <= 16 * 1024
-            cf = classifier._run_forward(xc, keep=True, sn_bwd_rider=snb_args,
+            cf = classifier._run_forward(xc, keep=True, sn_bwd_rider=sn_bwd,
                                          ce=(target_y, float(config["lambda_cls"])) if ce_tail else None)
             logits_c, acts_c = cf[:2]
-            del snb_keep
         elif pair:
             d_real, d_fake = discriminator._run_pair(x, onehot_y, cot_neg, xd, target_onehot, cot_pos, sn=sn_pair)   # :290-294, four launches
-        elif branch2 is None or not discriminator._fused_ok(x, onehot_y):
+        else:
             d_real, sv_r = discriminator._run_forward(x, onehot_y, keep=True)                 # :290
             d_fake, sv_f = discriminator._run_forward(xd, target_onehot, keep=True)           # :291
             discriminator._run_backward(sv_f, cot_pos, False, True)                           # d(mean(d_fake) - mean(d_real))
             discriminator._run_backward(sv_r, cot_neg, False, True)
-        else:
-            # (Opt-in, `GraphedTrainStep(overlap="critic")`: measured r02 without gain — 0.857 vs 0.856 ms — because the classifier
-            # branch is then the longest chain, and every cross-queue edge of the graph costs ~10 us; with the zero-fills moved onto
-            # this third stream as well the step went to 1.10 ms.)
-            # The real pass and the fake pass only share the spectral-norm state: the reference's two forward calls each run a
-            # power iteration, in this order (so the passes use different sigma and cannot be batched).  After the first one the
-            # WHOLE real pass — critic forward, backward, weight gradients, the backward through W/sigma — runs on a third
-            # stream into a second gradient buffer, beside the second power iteration and the fake pass; one add joins them
-            # ((0 + a) + b either way).
-            sn_r = discriminator._spectral_norm()                                             # power iteration of the D(real) call
-            alt = _alt_grads(discriminator)
-            branch2.wait_stream(main)                                                         # (behind the zero-fills it carries)
-            with torch.cuda.stream(branch2):
-                d_real, sv_r = discriminator._run_forward(x, onehot_y, keep=True, sn=sn_r)    # :290
-                discriminator._run_backward(sv_r, cot_neg, False, True, gtarget=alt)
-            for t in (x, onehot_y, cot_neg) + tuple(tt for grp in sn_r for tt in grp):
-                t.record_stream(branch2)
-            d_fake, sv_f = discriminator._run_forward(xd, target_onehot, keep=True)           # :291 (its own power iteration)
-            discriminator._run_backward(sv_f, cot_pos, False, True)
-            main.wait_stream(branch2)
-            d_real.record_stream(main)
-            ops.axpby(1.0, discriminator.flat_grads, 1.0, alt, out=discriminator.flat_grads)
     opt_d.step()                                                                              # :295
     # ---- G step (:298-316)
     with torch.no_grad():
@@ -1098,7 +997,7 @@ def _train_step_branch(generator, discriminator, classifier, opt_g, opt_d, x, y,
                 g_cls, dlog = ops.cross_entropy_fwd_bwd(logits_c.contiguous(), target_y, need_loss=True, need_grad=True,
                                                         grad_scale=float(config["lambda_cls"]))              # :302
                 g_cls = g_cls.view(())
-            dx_cls, sn_out = classifier._run_backward(acts_c, dlog, sn_fwd_rider=discriminator._sn_operands() + (1,))
+            dx_cls, sn_out = classifier._run_backward(acts_c, dlog, sn_fwd_rider=ops.sn_fwd_batch(*discriminator._sn_operands())[1])
             sn_g = sn_out[0]                                                                  # the power iteration of the :298 call
         d_fake_for_g, sv_g = discriminator._run_forward(xd, target_onehot, keep=True, sn=sn_g)   # :298
         ride = B <= 16 * 1024  # the five logged scalars ride in the launch of the residual block's backward (same trees, same bits)
@@ -1218,9 +1117,9 @@ class GraphedTrainStep:
     section 8a row a15), and the graph removes the per-kernel host cost.  overlap="inline" (default): the scheduled step on one
     stream; True: the frozen classifier's term on a parallel graph branch (a graph with branches is launched node by node by the
     host, a chain is not: 0.28 vs 0.03 ms of host time per replay; wall 0.434 vs 0.422 ms at batch 4096 once the classifier term
-    itself was down to 47 us); "critic": a third stream for the critic's real pass (no gain); False: the reference-order autograd
-    step.  All bit-identical.  Inputs live in static device buffers (`x, y, target_y, mask, noise`): write the next
-    batch into them (`load(...)`, or draw straight into them) and call `replay()`; outputs are the static tensors in `out`.
+    itself was down to 47 us); False: the reference-order autograd step.  All bit-identical; any other value is refused.
+    Inputs live in static device buffers (`x, y, target_y, mask, noise`): write the next batch into them (`load(...)`, or draw
+    straight into them) and call `replay()`; outputs are the static tensors in `out`.
     Capture needs warm-up executions of real steps; the parameters, buffers and optimizer state are snapshotted before and
     restored after, so constructing this object does not advance training."""
 
@@ -1238,15 +1137,11 @@ class GraphedTrainStep:
         the first launch of the captured step, their Philox offsets read from a device counter that the launch advances itself — write x
         and y into the static buffers (`load_batch`) and replay(); the numbers are those draw_batch_randoms(rng, ...) would have drawn
         before each eager step, and rng.offset is kept in step on the host."""
+        if overlap not in ("inline", True, False):
+            raise PcgError(f'GraphedTrainStep: overlap must be "inline", True or False, got {overlap!r}')
         dev = norm_vals.device
-        # train_step's parallel branch: the classifier term and the logged sums; overlap="critic" adds a third stream for the
-        # critic's real pass (bit-identical, no gain measured: see _train_step_branch)
-        if overlap == "critic":
-            self.branch = (torch.cuda.Stream(device=dev), torch.cuda.Stream(device=dev))
-        elif overlap == "inline":
-            self.branch = "inline"
-        else:
-            self.branch = torch.cuda.Stream(device=dev) if overlap else None
+        # train_step's parallel branch: the classifier term and the logged sums
+        self.branch = "inline" if overlap == "inline" else (torch.cuda.Stream(device=dev) if overlap else None)
         D_in, T = config["input_dim"], generator.total_cat
         self.x = torch.zeros((batch, D_in), dtype=torch.float32, device=dev)
         self.y = torch.zeros((batch,), dtype=torch.int64, device=dev)

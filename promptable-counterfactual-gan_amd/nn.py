@@ -130,14 +130,6 @@ class FlatModule(nn.Module):
                 return gv, acc
         raise PcgError("parameter does not belong to this FlatModule")
 
-    def grad_view_in(self, buf, p):
-        """The view of parameter p's gradient inside `buf`, a flat buffer with the layout of flat_grads (a second gradient
-        accumulator: two backward passes that run on parallel streams write one buffer each and are added once)."""
-        for q, off, n in self._seg:
-            if q is p:
-                return self._views(self._flat, buf, p, off, n)[1]
-        raise PcgError("parameter does not belong to this FlatModule")
-
     def drop_grads(self):
         """Forget the gradients without touching memory: the next backward OVERWRITES (p.grad is None = 'no gradient yet', see
         _grad_view) instead of adding to a zero-filled buffer — 0 + g == g, one fill launch less.  Only for steps in which every

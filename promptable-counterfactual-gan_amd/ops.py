@@ -1145,24 +1145,37 @@ def assemble_residual_fwd(cont, cont_idx, samples, seg_offsets, cat_idx, norm_va
 def house_residual_fwd(cont, samples, seg_offsets, norm_vals, x, mask, col_src, sn=None):
     """(residual_full, masked_residual, x_cf, mask_penalty, am) of the tabular step in one launch: assemble_residual_fwd +
     scale_mask_fwd + axpby + 2 x abs_mean_fwd, bit for bit.  col_src: host list, per feature column the continuous index (>= 0) or
-    -(head + 1).  sn = (w_origs, us, vs, eps, reps): spectral_norm_fwd_batched_reps of these matrices rides in the same launch (the
-    two do not depend on each other); its result is appended to the returned tuple."""
-    import ctypes
+    -(head + 1).  sn: a training-mode batch of sn_fwd_batch — that spectral normalisation rides in the same launch (the two do not
+    depend on each other); its outputs are appended to the returned tuple."""
     _chk(cont, "cont"); _chk(samples, "samples"); _chk(x, "x"); _chk(mask, "mask"); _chk(norm_vals, "norm_vals")
     B, D = x.shape
     res, masked, x_cf = torch.empty_like(x), torch.empty_like(x), torch.empty_like(x)
     scal = torch.empty(2, dtype=torch.float32, device=x.device)
     part = torch.empty(512, dtype=torch.float32, device=x.device)
     tk = _ticket_buffer(x.device)
-    src = (ctypes.c_int32 * D)(*[int(v) for v in col_src])
-    args = (_p(cont), cont.shape[1], _p(samples), _p(seg_offsets), samples.shape[1], _p(norm_vals), _p(x), _p(mask), src, D, B, _p(res),
-            _p(masked), _p(x_cf), _p(part), tk.data_ptr() + 4 * 1024, _p(scal), scal.data_ptr() + 4)
-    if sn is None:
-        check(_lib.load().pcg_house_residual_fwd(*args, _stream()), "pcg_house_residual_fwd")
-        return res, masked, x_cf, scal[0], scal[1]
-    outs, sn_args = sn_fwd_reps_args(*sn)
-    check(_lib.load().pcg_house_residual_fwd_sn(*args, *sn_args, _stream()), "pcg_house_residual_fwd_sn")
-    return res, masked, x_cf, scal[0], scal[1], outs
+    a = _lib.HouseResFwdArgs(cont=cont.data_ptr(), ncont=cont.shape[1], samples=samples.data_ptr(), seg_dev=seg_offsets.data_ptr(),
+                             T=samples.shape[1], norm=norm_vals.data_ptr(), x=x.data_ptr(), mask=mask.data_ptr(),
+                             col_src=(ctypes.c_int32 * D)(*[int(v) for v in col_src]), D=D, B=B, res=res.data_ptr(), masked=masked.data_ptr(),
+                             x_cf=x_cf.data_ptr(), partial512=part.data_ptr(), ticket=tk.data_ptr() + 4 * 1024, pen_out=scal.data_ptr(),
+                             am_out=scal.data_ptr() + 4)
+    check(_lib.load().pcg_house_residual_fwd(a, sn, _stream()), "pcg_house_residual_fwd")
+    return (res, masked, x_cf, scal[0], scal[1]) + (() if sn is None else (sn.outputs,))
+
+
+def _diag_args(logits_cf, logits_orig, src_rows, target_y, masked, eps, out4, acc, who):
+    _chk(logits_cf, "logits_cf"); _chk(logits_orig, "logits_orig"); _chk(masked, "masked"); _chk(target_y, "target_y", torch.int64)
+    B, nc = logits_cf.shape
+    if src_rows is not None:
+        _chk(src_rows, "src_rows", torch.int64)
+    elif logits_orig.shape[0] < B:
+        raise _lib.PcgError(f"{who}: logits_orig has fewer rows than the batch and no src_rows were given")
+    if acc is not None:
+        _chk(acc, "acc", torch.float64)
+        assert acc.numel() >= 8
+    assert masked.shape[0] == B and logits_orig.shape[1] == nc and target_y.numel() == B
+    return _lib.HouseDiagArgs(logits_cf=logits_cf.data_ptr(), logits_orig=logits_orig.data_ptr(), src_rows=_p(src_rows),
+                              target_y=target_y.data_ptr(), masked=masked.data_ptr(), B=B, nc=nc, D=masked.shape[1], eps=float(eps),
+                              out4=out4.data_ptr(), acc=_p(acc))
 
 
 def house_residual_bwd(res, masked, mask, gx_a, gx_b, w_pen, w_am, ncont, cont_idx, seg_offsets, T, cat_idx, norm_vals, losses=None, diag=None):
@@ -1178,55 +1191,37 @@ def house_residual_bwd(res, masked, mask, gx_a, gx_b, w_pen, w_am, ncont, cont_i
     B, D = res.shape
     dcont = torch.empty((B, ncont), dtype=torch.float32, device=res.device)
     dsamples = torch.empty((B, T), dtype=torch.float32, device=res.device)
-    args = (_p(res), _p(masked), _p(mask), _p(gx_a), _p(gx_b), float(w_pen), float(w_am), ncont, _p(cont_idx), _p(seg_offsets), cat_idx.numel(),
-            T, _p(cat_idx), _p(norm_vals), D, B, _p(dcont), _p(dsamples))
-    if losses is None:
-        check(_lib.load().pcg_house_residual_bwd(*args, _stream()), "pcg_house_residual_bwd")
-        return dcont, dsamples
-    d_real, d_fake, d_fake_g, g_cls, am, pen, l_cls, w_reg, l_mask, w_reg_log = losses
-    out6 = torch.empty(6, dtype=torch.float32, device=res.device)
-    rows = g_cls.numel() > 1
+    a = _lib.HouseResBwdArgs(res=res.data_ptr(), masked=masked.data_ptr(), mask=mask.data_ptr(), gx_a=gx_a.data_ptr(), gx_b=gx_b.data_ptr(),
+                             w_pen=float(w_pen), w_am=float(w_am), ncont=ncont, cont_idx_dev=cont_idx.data_ptr(), seg_dev=seg_offsets.data_ptr(),
+                             S=cat_idx.numel(), T=T, cat_idx_dev=cat_idx.data_ptr(), norm=norm_vals.data_ptr(), D=D, B=B,
+                             dcont=dcont.data_ptr(), dsamples=dsamples.data_ptr())
+    la = da = None
+    outs = ()
+    if losses is not None:
+        d_real, d_fake, d_fake_g, g_cls, am, pen, l_cls, w_reg, l_mask, w_reg_log = losses
+        out6 = torch.empty(6, dtype=torch.float32, device=res.device)
+        rows = g_cls.numel() > 1
+        la = _lib.HouseLossArgs(d_real=d_real.data_ptr(), d_fake=d_fake.data_ptr(), d_fake_g=d_fake_g.data_ptr(), n=d_real.numel(),
+                                g_cls=None if rows else g_cls.data_ptr(), am=am.data_ptr(), pen=pen.data_ptr(), lambda_cls=float(l_cls),
+                                w_reg=float(w_reg), lambda_mask=float(l_mask), w_reg_log=float(w_reg_log),
+                                ce_row_loss=g_cls.data_ptr() if rows else None, n_ce=g_cls.numel() if rows else 0, out6=out6.data_ptr())
+        outs = (out6,)
     if diag is not None:
         logits_cf, logits_orig, src_rows, target_y, eps, acc = diag
-        _chk(logits_cf, "logits_cf"); _chk(logits_orig, "logits_orig"); _chk(target_y, "target_y", torch.int64)
-        if src_rows is not None:
-            _chk(src_rows, "src_rows", torch.int64)
-        elif logits_orig.shape[0] < B:
-            raise _lib.PcgError("house_residual_bwd(diag=...): logits_orig has fewer rows than the batch and no src_rows were given")
-        if acc is not None:
-            _chk(acc, "acc", torch.float64)
-            assert acc.numel() >= 8
-        nc = logits_cf.shape[1]
-        assert logits_cf.shape[0] == B and logits_orig.shape[1] == nc and target_y.numel() == B
         out4 = torch.empty(4, dtype=torch.float32, device=res.device)
-        check(_lib.load().pcg_house_residual_bwd_losses_diag(
-            *args, _p(d_real), _p(d_fake), _p(d_fake_g), d_real.numel(), None if rows else _p(g_cls), _p(am), _p(pen), float(l_cls),
-            float(w_reg), float(l_mask), float(w_reg_log), _p(g_cls) if rows else None, g_cls.numel() if rows else 0, _p(out6),
-            _p(logits_cf), _p(logits_orig), _p(src_rows), _p(target_y), nc, float(eps), _p(out4), _p(acc), _stream()),
-            "pcg_house_residual_bwd_losses_diag")
-        return dcont, dsamples, out6, out4
-    check(_lib.load().pcg_house_residual_bwd_losses(*args, _p(d_real), _p(d_fake), _p(d_fake_g), d_real.numel(), None if rows else _p(g_cls),
-                                                    _p(am), _p(pen), float(l_cls), float(w_reg), float(l_mask), float(w_reg_log),
-                                                    _p(g_cls) if rows else None, g_cls.numel() if rows else 0, _p(out6), _stream()),
-          "pcg_house_residual_bwd_losses")
-    return dcont, dsamples, out6
+        da = _diag_args(logits_cf, logits_orig, src_rows, target_y, masked, eps, out4, acc, "house_residual_bwd(diag=...)")
+        outs += (out4,)
+    check(_lib.load().pcg_house_residual_bwd(a, la, da, _stream()), "pcg_house_residual_bwd")
+    return (dcont, dsamples) + outs
 
 
 def house_diag(logits_cf, logits_orig, target_y, masked, eps=1e-3, src_rows=None, acc=None):
     """[pred_gain, sparsity, reg_loss_l2, class_flip_rate] of house_sales_kc_usa/trainer.py:318-343 in one launch (pcg_house_diag).
     logits_orig: the frozen classifier on the original rows ([B, nc], or [N, nc] for the whole training set with src_rows [B]);
     acc: float64[8] epoch accumulators (acc[2..5] += the four values)."""
-    _chk(logits_cf, "logits_cf"); _chk(logits_orig, "logits_orig"); _chk(masked, "masked"); _chk(target_y, "target_y", torch.int64)
-    B, nc = logits_cf.shape
-    if src_rows is not None:
-        _chk(src_rows, "src_rows", torch.int64)
-    elif logits_orig.shape[0] < B:
-        raise _lib.PcgError("house_diag: logits_orig has fewer rows than the batch and no src_rows were given")
-    if acc is not None:
-        _chk(acc, "acc", torch.float64)
     out = torch.empty(4, dtype=torch.float32, device=logits_cf.device)
-    check(_lib.load().pcg_house_diag(_p(logits_cf), _p(logits_orig), _p(src_rows), _p(target_y), _p(masked), B, nc, masked.shape[1], float(eps),
-                                     _p(out), _p(acc), _stream()), "pcg_house_diag")
+    check(_lib.load().pcg_house_diag(_diag_args(logits_cf, logits_orig, src_rows, target_y, masked, eps, out, acc, "house_diag"), _stream()),
+          "pcg_house_diag")
     return out
 
 
@@ -1267,83 +1262,123 @@ def spectral_norm_fwd(w_orig, u, v, eps, power_iteration):
 
 
 def _ptr_array(tensors):
-    return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+    """A host array of the tensors' device pointers (None: a null entry)."""
+    return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() if t is not None else None for t in tensors])
 
 
-def spectral_norm_fwd_batched(w_origs, us, vs, eps, power_iteration):
-    """[(w_bar, sigma, u_used, v_used)] for all layers in one launch."""
-    n = len(w_origs)
-    outs = [(torch.empty_like(w), torch.empty(1, dtype=torch.float32, device=w.device), torch.empty_like(u), torch.empty_like(v))
-            for w, u, v in zip(w_origs, us, vs)]
-    I32 = ctypes.c_int32 * n
-    check(_lib.load().pcg_spectral_norm_fwd_batched(n, _ptr_array(w_origs), I32(*[w.shape[0] for w in w_origs]), I32(*[w.shape[1] for w in w_origs]),
-                                                    _ptr_array(us), _ptr_array(vs), float(eps), int(bool(power_iteration)),
-                                                    _ptr_array([o[0] for o in outs]), _ptr_array([o[1] for o in outs]),
-                                                    _ptr_array([o[2] for o in outs]), _ptr_array([o[3] for o in outs]), _stream()),
-          "pcg_spectral_norm_fwd_batched")
-    return outs
+def _i32_array(values):
+    return (ctypes.c_int32 * len(values))(*[int(v) for v in values])
 
 
-def _sn_outputs(w_origs, us, vs, reps):
+def sn_fwd_batch(w_origs, us, vs, eps, reps=1, power_iteration=True):
+    """(outputs, batch): the pcg_sn_fwd_batch of `reps` successive calls of these layers — for spectral_norm_fwd_batched, or as the
+    rider of house_residual_fwd / house_classifier_bwd — and its freshly allocated outputs [[(w_bar, sigma, u_used, v_used)] per
+    layer] per call (also `batch.outputs`).  The batch holds every tensor it points to."""
     outs = [[(torch.empty_like(w), torch.empty(1, dtype=torch.float32, device=w.device), torch.empty_like(u), torch.empty_like(v))
              for w, u, v in zip(w_origs, us, vs)] for _ in range(reps)]
-    return outs, [o for call in outs for o in call]
+    flat = [o for call in outs for o in call]
+    b = _lib.SnFwdBatch(n=len(w_origs), reps=reps, power_iteration=int(bool(power_iteration)), eps=float(eps), w_orig=_ptr_array(w_origs),
+                        out_features=_i32_array([w.shape[0] for w in w_origs]), in_features=_i32_array([w.shape[1] for w in w_origs]),
+                        u=_ptr_array(us), v=_ptr_array(vs), w_bar=_ptr_array([o[0] for o in flat]), sigma=_ptr_array([o[1] for o in flat]),
+                        u_used=_ptr_array([o[2] for o in flat]), v_used=_ptr_array([o[3] for o in flat]))
+    b.outputs, b.tensors = outs, (list(w_origs), list(us), list(vs))
+    return outs, b
 
 
-def spectral_norm_fwd_batched_reps(w_origs, us, vs, eps, reps):
-    """`reps` successive training-mode calls in one launch: [[(w_bar, sigma, u_used, v_used)] per layer] per call."""
-    n = len(w_origs)
-    outs, flat = _sn_outputs(w_origs, us, vs, reps)
-    I32 = ctypes.c_int32 * n
-    check(_lib.load().pcg_spectral_norm_fwd_batched_reps(n, reps, _ptr_array(w_origs), I32(*[w.shape[0] for w in w_origs]),
-                                                         I32(*[w.shape[1] for w in w_origs]), _ptr_array(us), _ptr_array(vs), float(eps), 1,
-                                                         _ptr_array([o[0] for o in flat]), _ptr_array([o[1] for o in flat]),
-                                                         _ptr_array([o[2] for o in flat]), _ptr_array([o[3] for o in flat]), _stream()),
-          "pcg_spectral_norm_fwd_batched_reps")
+def sn_bwd_batch(passes, dw_origs, accumulate, bias_adds=None):
+    """The pcg_sn_bwd_batch of passes = [[(dw_bar, w_bar, u, v, sigma)] per layer] per call, applied in this order into dw_origs[l];
+    bias_adds: per layer (dst, src) or None — dst += src afterwards.  For spectral_norm_bwd_batched, or as the rider of
+    house_classifier_fwd.  The batch holds every tensor it points to."""
+    flat = [e for call in passes for e in call]
+    adds = [b if b is not None else (None, None) for b in (bias_adds or [None] * len(dw_origs))]
+    b = _lib.SnBwdBatch(n=len(dw_origs), passes=len(passes), dw_bar=_ptr_array([e[0] for e in flat]), w_bar=_ptr_array([e[1] for e in flat]),
+                        out_features=_i32_array([w.shape[0] for w in dw_origs]), in_features=_i32_array([w.shape[1] for w in dw_origs]),
+                        u=_ptr_array([e[2] for e in flat]), v=_ptr_array([e[3] for e in flat]), sigma=_ptr_array([e[4] for e in flat]),
+                        dw_orig=_ptr_array(dw_origs), accumulate=_i32_array([bool(a) for a in accumulate]),
+                        db_dst=_ptr_array([d for d, _ in adds]), db_src=_ptr_array([s_ for _, s_ in adds]))
+    b.tensors = (flat, list(dw_origs), adds)
+    return b
+
+
+def spectral_norm_fwd_batched(w_origs, us, vs, eps, power_iteration, reps=1):
+    """All layers, `reps` successive calls, in one launch: [[(w_bar, sigma, u_used, v_used)] per layer] per call."""
+    outs, b = sn_fwd_batch(w_origs, us, vs, eps, reps, power_iteration)
+    check(_lib.load().pcg_spectral_norm_fwd_batched(b, _stream()), "pcg_spectral_norm_fwd_batched")
     return outs
 
 
-def sn_bwd_seq_args(passes, dw_origs, accumulate, bias_adds=None):
-    """The argument list of pcg_spectral_norm_bwd_batched_seq (without the stream), for the launch itself or for a rider launch that
-    carries it (pcg_house_classifier_fwd_snbwd).  The tensors must stay alive until the launch."""
-    n = len(dw_origs)
-    flat = [e for call in passes for e in call]
-    I32 = ctypes.c_int32 * n
-    null = ctypes.c_void_p * n
-    dst = null(*[(b[0].data_ptr() if b is not None else None) for b in (bias_adds or [None] * n)])
-    src = null(*[(b[1].data_ptr() if b is not None else None) for b in (bias_adds or [None] * n)])
-    return (n, len(passes), _ptr_array([e[0] for e in flat]), _ptr_array([e[1] for e in flat]), I32(*[w.shape[0] for w in dw_origs]),
-            I32(*[w.shape[1] for w in dw_origs]), _ptr_array([e[2] for e in flat]), _ptr_array([e[3] for e in flat]),
-            _ptr_array([e[4] for e in flat]), _ptr_array(dw_origs), I32(*[int(bool(a)) for a in accumulate]), dst, src)
+def spectral_norm_bwd_batched(passes, dw_origs, accumulate, bias_adds=None):
+    """All layers, all passes (see sn_bwd_batch; one call's backward: a list of one pass), in one launch."""
+    check(_lib.load().pcg_spectral_norm_bwd_batched(sn_bwd_batch(passes, dw_origs, accumulate, bias_adds), _stream()),
+          "pcg_spectral_norm_bwd_batched")
 
 
-def sn_fwd_reps_args(w_origs, us, vs, eps, reps):
-    """(outputs, argument list) of a training-mode pcg_spectral_norm_fwd_batched_reps as a rider launch passes them (no
-    power_iteration flag, no stream)."""
-    n = len(w_origs)
-    outs, flat = _sn_outputs(w_origs, us, vs, reps)
-    I32 = ctypes.c_int32 * n
-    return outs, (n, reps, _ptr_array(w_origs), I32(*[w.shape[0] for w in w_origs]), I32(*[w.shape[1] for w in w_origs]), _ptr_array(us),
-                  _ptr_array(vs), float(eps), _ptr_array([o[0] for o in flat]), _ptr_array([o[1] for o in flat]),
-                  _ptr_array([o[2] for o in flat]), _ptr_array([o[3] for o in flat]))
+def house_g_fwd(desc, args):
+    """The tabular generator's fused forward (csrc/house_fused.hip): a pcg_house_g_desc and pcg_house_g_fwd_args the module filled."""
+    check(_lib.load().pcg_house_g_fwd(desc, args, _stream()), "pcg_house_g_fwd")
 
 
-def spectral_norm_bwd_batched_seq(passes, dw_origs, accumulate, bias_adds=None):
-    """passes: [[(dw_bar, w_bar, u, v, sigma)] per layer] per call, applied in this order into dw_origs[l]; bias_adds: per layer
-    (dst, src) or None — dst += src afterwards."""
-    check(_lib.load().pcg_spectral_norm_bwd_batched_seq(*sn_bwd_seq_args(passes, dw_origs, accumulate, bias_adds), _stream()),
-          "pcg_spectral_norm_bwd_batched_seq")
+def house_g_bwd(desc, args):
+    check(_lib.load().pcg_house_g_bwd(desc, args, _stream()), "pcg_house_g_bwd")
 
 
-def spectral_norm_bwd_batched(items):
-    """items: [(dw_bar, w_bar, u, v, sigma, dw_orig, accumulate)] — all layers in one launch."""
-    n = len(items)
-    I32 = ctypes.c_int32 * n
-    check(_lib.load().pcg_spectral_norm_bwd_batched(n, _ptr_array([i[0] for i in items]), _ptr_array([i[1] for i in items]),
-                                                    I32(*[i[1].shape[0] for i in items]), I32(*[i[1].shape[1] for i in items]),
-                                                    _ptr_array([i[2] for i in items]), _ptr_array([i[3] for i in items]),
-                                                    _ptr_array([i[4] for i in items]), _ptr_array([i[5] for i in items]),
-                                                    I32(*[int(bool(i[6])) for i in items]), _stream()), "pcg_spectral_norm_bwd_batched")
+def house_critic_fwd(passes, w_bars, biases, slope=0.2):
+    """The tabular critic's four layers for 1 or 2 passes in one launch (csrc/house_critic_fused.hip).  passes: [(x, onehot)];
+    w_bars: the four normalised weights of every pass (pass-major).  Returns [([a0, a1, a2, a3], out)] per pass."""
+    B = passes[0][0].shape[0]
+    f32 = dict(dtype=torch.float32, device=passes[0][0].device)
+    res = [([torch.empty((B, n), **f32) for n in (21, 32, 64, 128)], torch.empty((B, 1), **f32)) for _ in passes]
+    a = _lib.HouseCriticFwdArgs(n_pass=len(passes), B=B, D=passes[0][0].shape[1], NC=passes[0][1].shape[1], slope=slope,
+                                x=_ptr_array([_chk(x, "x") for x, _ in passes]), onehot=_ptr_array([_chk(o, "onehot") for _, o in passes]),
+                                w_bar=_ptr_array(w_bars), bias=_ptr_array(biases), out=_ptr_array([o for _, o in res]),
+                                **{f"a{i}": _ptr_array([acts[i] for acts, _ in res]) for i in range(4)})
+    check(_lib.load().pcg_house_critic_fwd(a, _stream()), "pcg_house_critic_fwd")
+    return res
+
+
+def house_critic_bwd(douts, w_bars, acts, input_dim, need_dx, slope=0.2):
+    """The backward of house_critic_fwd for the same passes (acts: their [a0..a3]) in one launch: [(d3, d2, d1, dx or None)] per pass."""
+    B = douts[0].shape[0]
+    f32 = dict(dtype=torch.float32, device=douts[0].device)
+    res = [tuple(torch.empty((B, n), **f32) for n in (128, 64, 32)) + ((torch.empty((B, input_dim), **f32) if need_dx else None),) for _ in douts]
+    a = _lib.HouseCriticBwdArgs(n_pass=len(douts), B=B, D=input_dim, slope=slope, dout=_ptr_array([_chk(d, "dout") for d in douts]),
+                                w_bar=_ptr_array(w_bars), a1=_ptr_array([a_[1] for a_ in acts]), a2=_ptr_array([a_[2] for a_ in acts]),
+                                a3=_ptr_array([a_[3] for a_ in acts]), d3=_ptr_array([r[0] for r in res]), d2=_ptr_array([r[1] for r in res]),
+                                d1=_ptr_array([r[2] for r in res]), dx=_ptr_array([r[3] for r in res]))
+    check(_lib.load().pcg_house_critic_bwd(a, _stream()), "pcg_house_critic_bwd")
+    return res
+
+
+def house_classifier_fwd(x, w_kmajor, biases, sn_bwd=None, ce=None):
+    """The frozen tabular classifier's five layers in one launch (csrc/house_classifier_fused.hip): (logits, [a1, a2, a3, a4]).
+    sn_bwd: a batch of sn_bwd_batch — that spectral-norm backward rides in the launch.  ce = (target, grad_scale), with a rider only:
+    the launch also leaves the cross-entropy's gradient and row terms: (logits, acts, dlogits, row_loss)."""
+    _chk(x, "x")
+    B = x.shape[0]
+    f32 = dict(dtype=torch.float32, device=x.device)
+    acts = [torch.empty((B, n), **f32) for n in (256, 256, 128, 64)]
+    logits = torch.empty((B, 4), **f32)
+    a = _lib.HouseClsFwdArgs(x=x.data_ptr(), B=B, w_kmajor=_ptr_array(w_kmajor), bias=_ptr_array(biases), a1=acts[0].data_ptr(),
+                             a2=acts[1].data_ptr(), a3=acts[2].data_ptr(), a4=acts[3].data_ptr(), logits=logits.data_ptr())
+    tail = ()
+    if ce is not None:
+        tail = (torch.empty((B, 4), **f32), torch.empty((B,), **f32))
+        a.ce_target, a.ce_grad_scale = _chk(ce[0], "ce target", torch.int64).data_ptr(), float(ce[1])
+        a.ce_dlogits, a.ce_row_loss = tail[0].data_ptr(), tail[1].data_ptr()
+    check(_lib.load().pcg_house_classifier_fwd(a, sn_bwd, _stream()), "pcg_house_classifier_fwd")
+    return (logits, acts) + tail
+
+
+def house_classifier_bwd(dlogits, w_stored, acts, sn_fwd=None):
+    """dx [B, 17] of the frozen classifier in one launch.  sn_fwd: a training-mode batch of sn_fwd_batch — it rides in the launch;
+    the return value is then (dx, its outputs)."""
+    _chk(dlogits, "dlogits")
+    B = dlogits.shape[0]
+    dx = torch.empty((B, 17), dtype=torch.float32, device=dlogits.device)
+    a = _lib.HouseClsBwdArgs(dlogits=dlogits.data_ptr(), B=B, w_stored=_ptr_array(w_stored), a1=acts[0].data_ptr(), a2=acts[1].data_ptr(),
+                             a3=acts[2].data_ptr(), a4=acts[3].data_ptr(), dx=dx.data_ptr())
+    check(_lib.load().pcg_house_classifier_bwd(a, sn_fwd, _stream()), "pcg_house_classifier_bwd")
+    return dx if sn_fwd is None else (dx, sn_fwd.outputs)
 
 
 def spectral_norm_bwd(dw_bar, w_bar, u, v, sigma, dw_orig, accumulate):

@@ -7,7 +7,7 @@ G, D, C = H.build(dev, seed=0)
 opt_g, opt_d = H.make_optimizers(G, D)
 norm = H.cat_norm_maps(G, H.CONFIG, dev)
 B = 4096
-ov = {"1": True, "0": False, "c": "critic", "i": "inline"}[os.environ.get("OV", "1")]
+ov = {"1": True, "0": False, "i": "inline"}[os.environ.get("OV", "1")]
 gs = H.GraphedTrainStep(G, D, C, opt_g, opt_d, norm, B, overlap=ov)
 for _ in range(20): gs.replay()
 torch.cuda.synchronize()

@@ -21,7 +21,9 @@ int main() {
   unsigned long long* ts; hipMalloc(&ts, 256 * 16 * 8); hipMemset(ts, 0, 256 * 16 * 8);
   hipMemcpyToSymbol(HIP_SYMBOL(pcg_dbg_ts), &ts, sizeof(ts));
   hipStream_t s; hipStreamCreate(&s);
-  for (int it = 0; it < 5; ++it) if (pcg_house_classifier_fwd(x, B, wk, bs, a1, a2, a3, a4, lg, s)) return 1;
+  pcg_house_cls_fwd_args args{};
+  args.x = x; args.B = B; args.w_kmajor = wk; args.bias = bs; args.a1 = a1; args.a2 = a2; args.a3 = a3; args.a4 = a4; args.logits = lg;
+  for (int it = 0; it < 5; ++it) if (pcg_house_classifier_fwd(&args, nullptr, s)) return 1;
   hipStreamSynchronize(s);
   std::vector<unsigned long long> h(256 * 16);
   hipMemcpy(h.data(), ts, 256 * 16 * 8, hipMemcpyDeviceToHost);

@@ -454,6 +454,102 @@ def test_fused_residual_block_equals_the_op_chain_bitwise(pcg, hgold, rows):
     assert torch.equal(oh[0], ops.onehot(t1, 4)) and torch.equal(oh[1], ops.onehot(y, 4))
 
 
+def _clone_nested(t):
+    return t.clone() if torch.is_tensor(t) else type(t)(_clone_nested(e) for e in t)
+
+
+def _flat_tensors(t):
+    return [t] if torch.is_tensor(t) else [f for e in t for f in _flat_tensors(e)]
+
+
+def _all_equal(a, b):
+    fa, fb = _flat_tensors(a), _flat_tensors(b)
+    return len(fa) == len(fb) and all(torch.equal(u, v) for u, v in zip(fa, fb))
+
+
+@pytest.mark.parametrize("rows", [5, 1000])
+def test_rider_launches_equal_the_separate_launches_bitwise(pcg, hgold, rows):
+    """ops.house_residual_fwd(sn=...) against the plain residual launch plus a separate spectral_norm_fwd_batched(reps=2), and
+    ops.house_residual_bwd(losses=..., diag=...) against the plain backward plus pcg_house_losses and ops.house_diag: every output,
+    the updated u / v and the epoch accumulators bit for bit, with rows * 17 on either side of 16384 (the one-block residual kernel
+    followed by the batched launch / the kernel whose blocks split between the two bodies)."""
+    H, ops = pcg.house, pcg.ops
+    G, D, _ = _load_golden_nets(pcg, hgold)
+    dev = torch.device(DEV)
+    g = torch.Generator().manual_seed(rows)
+    B, Df, T, nc = rows, 17, G.total_cat, len(G.continuous_idx)
+    x, mask = _dev(torch.rand(B, Df, generator=g)), _dev((torch.rand(B, Df, generator=g) > 0.4).float())
+    cont, samples = _dev(torch.randn(B, nc, generator=g) * 0.1), _dev(torch.softmax(torch.randn(B, T, generator=g), 1))
+    gx_a, gx_b = _dev(torch.randn(B, Df, generator=g) * 1e-3), _dev(torch.randn(B, Df, generator=g) * 1e-3)
+    norm = H.cat_norm_maps(G, H.CONFIG, dev)
+    seg, cat_idx, cont_idx = G.index_tables(dev)
+    w, u, v, eps = D._sn_operands()
+    sep_sn, rid_sn = _clone_nested((w, u, v)), _clone_nested((w, u, v))
+    # forward
+    sep = ops.house_residual_fwd(cont, samples, seg, norm, x, mask, G.col_src())
+    sep_out = ops.spectral_norm_fwd_batched(*sep_sn, eps, True, reps=2)
+    rid = ops.house_residual_fwd(cont, samples, seg, norm, x, mask, G.col_src(), sn=ops.sn_fwd_batch(*rid_sn, eps, reps=2)[1])
+    assert len(sep) == 5 and len(rid) == 6 and _all_equal(sep, rid[:5]), "residual block"
+    assert len(rid[5]) == 2 and len(rid[5][0]) == 4 and _all_equal(sep_out, rid[5]), "spectral-norm outputs"
+    assert _all_equal(sep_sn, rid_sn), "u / v after two power iterations"
+    # backward
+    res, masked, _, pen, am = sep
+    d_real, d_fake, d_fake_g = (_dev(torch.randn(B, 1, generator=g)) for _ in range(3))
+    g_cls = _dev(torch.rand(1, generator=g))
+    logits_cf, logits_orig = _dev(torch.randn(B, 4, generator=g)), _dev(torch.randn(B, 4, generator=g))
+    t = _dev(torch.randint(0, 4, (B,), generator=g))
+    lam = (0.7, 1.3 * Df, 0.9, float(Df))
+    acc_sep, acc_rid = (torch.zeros(8, dtype=torch.float64, device=dev) for _ in range(2))
+    bargs = (res, masked, mask, gx_a, gx_b, 0.9, 1.3 * Df, nc, cont_idx, seg, T, cat_idx, norm)
+    dc, ds = ops.house_residual_bwd(*bargs)
+    out5 = torch.empty(5, dtype=torch.float32, device=dev)
+    ops.check(pcg.load().pcg_house_losses(ops._p(d_real), ops._p(d_fake), ops._p(d_fake_g), B, ops._p(g_cls), ops._p(am), ops._p(pen), *lam,
+                                          ops._p(out5), ops._stream()), "pcg_house_losses")
+    out4 = ops.house_diag(logits_cf, logits_orig, t, masked, eps=1e-3, acc=acc_sep)
+    dc2, ds2, out6, out4_2 = ops.house_residual_bwd(*bargs, losses=(d_real, d_fake, d_fake_g, g_cls, am, pen) + lam,
+                                                    diag=(logits_cf, logits_orig, None, t, 1e-3, acc_rid))
+    assert torch.equal(dc, dc2) and torch.equal(ds, ds2), "d_cont / d_samples"
+    assert torch.equal(out5, out6[:5]), "logged scalars"             # (out6[5] is written only when g_cls comes as row terms)
+    assert torch.equal(out4, out4_2) and torch.equal(acc_sep[2:6], acc_rid[2:6]), "diagnostics"
+    assert torch.equal(acc_rid[[0, 1, 6]], torch.stack([out6[0].double(), out6[1].double(), out6.new_ones(()).double()])), "epoch sums"
+    dc3, ds3, out6_3 = ops.house_residual_bwd(*bargs, losses=(d_real, d_fake, d_fake_g, g_cls, am, pen) + lam)
+    assert torch.equal(dc, dc3) and torch.equal(ds, ds3) and torch.equal(out5, out6_3[:5]), "losses without diagnostics"
+
+
+def test_batch_objects_keep_their_tensors_alive(pcg, hgold):
+    """The batch of ops.sn_fwd_batch / ops.sn_bwd_batch is the only reference to its operands and outputs when it is launched (a
+    deferred rider): nothing else is kept, the freed sizes are requested again and overwritten, and the launch still computes what
+    the immediate launch does."""
+    import gc
+    ops = pcg.ops
+    _, D, _ = _load_golden_nets(pcg, hgold)
+    w, u, v, eps = D._sn_operands()
+    g = torch.Generator().manual_seed(3)
+
+    def junk():         # what a freed operand's memory would be handed to
+        return [torch.full_like(t, float("nan")) for t in list(w) + list(u) + list(v) for _ in range(3)]
+
+    ops_ref = _clone_nested((w, u, v))
+    ref = ops.spectral_norm_fwd_batched(*ops_ref, eps, True, reps=2)
+    batch = ops.sn_fwd_batch(*_clone_nested((w, u, v)), eps, reps=2)[1]
+    gc.collect()
+    keep = junk()
+    ops.check(pcg.load().pcg_spectral_norm_fwd_batched(batch, ops._stream()), "pcg_spectral_norm_fwd_batched")
+    assert _all_equal(ref, batch.outputs) and _all_equal(ops_ref, batch.tensors)
+    # backward: two passes into the same gradients, with a bias add
+    dws = [torch.randn(t.shape, generator=g) for t in w]
+    passes = [[(_dev(torch.randn(o[0].shape, generator=g)), o[0], o[2], o[3], o[1]) for o in call] for call in ref]
+    adds = [(_dev(torch.randn(t.shape[0], generator=g)), _dev(torch.randn(t.shape[0], generator=g))) for t in w]
+    want_dw, want_adds = [_dev(t) for t in dws], _clone_nested(adds)
+    ops.spectral_norm_bwd_batched(_clone_nested(passes), want_dw, [False] * len(w), want_adds)
+    bwd = ops.sn_bwd_batch(_clone_nested(passes), [_dev(t) for t in dws], [False] * len(w), _clone_nested(adds))
+    del passes, adds
+    gc.collect()
+    keep += junk()
+    ops.check(pcg.load().pcg_spectral_norm_bwd_batched(bwd, ops._stream()), "pcg_spectral_norm_bwd_batched")
+    assert _all_equal(want_dw, bwd.tensors[1]) and _all_equal(want_adds, bwd.tensors[2])
+
+
 def test_fused_critic_kernels_match_the_op_chain(pcg, hgold):
     """csrc/house_critic_fused.hip (one forward + one backward launch, one thread per row; weight gradients through the grouped
     reduction, a 128x64 layer as four tiles) against the per-op path: output, input gradient, every parameter gradient and the
@@ -517,12 +613,12 @@ def test_fused_classifier_kernels_match_the_op_chain(pcg, hgold, rows):
         _close(u, v, 2e-5, 2e-5 * float(v.abs().max()), "saved activation")
 
 
-@pytest.mark.parametrize("overlap,batch", [(True, 128), ("critic", 128), (False, 128), ("inline", 128), (True, 4096), ("inline", 4096), ("inline", 1000), ("inline", 20000)])
+@pytest.mark.parametrize("overlap,batch", [(True, 128), (False, 128), ("inline", 128), (True, 4096), ("inline", 4096), ("inline", 1000), ("inline", 20000)])
 def test_graphed_step_equals_eager(pcg, hgold, overlap, batch):
     """GraphedTrainStep (one HIP-graph replay per step) leaves the nets exactly where the eager step does, and constructing
     it (warm-up + capture) does not advance the training state.  overlap=True: the schedule with the classifier term on a parallel
-    branch and the critic passes run directly with constant cotangents (house._train_step_branch); "critic": additionally the
-    critic's real pass on a third stream into a second gradient buffer; False: the reference-order single-stream step; "inline"
+    branch and the critic passes run directly with constant cotangents (house._train_step_branch); False: the reference-order
+    single-stream step; "inline"
     (the default): the schedule on one stream, with the rider launches (spectral-norm work inside the residual block's and the
     classifier's launches, the logged scalars inside the residual block's backward, the cross-entropy as the tail of the classifier's
     forward).  All are bit-identical to the eager autograd step — parameters, buffers, D_loss, G_loss and g_cls."""
