@@ -772,6 +772,48 @@ typedef struct pcg_house_cls_bwd_args {
 int pcg_house_classifier_fwd(const pcg_house_cls_fwd_args* args, const pcg_sn_bwd_batch* rider /*nullable*/, pcg_stream_t stream);
 int pcg_house_classifier_bwd(const pcg_house_cls_bwd_args* args, const pcg_sn_fwd_batch* rider /*nullable*/, pcg_stream_t stream);
 
+/* Prompted counterfactual queries and evaluation of the trained tabular CounteRGAN in ONE launch (csrc/house_cf_eval.hip):
+ * house_sales_kc_usa/eval_utils.py:25-181 (build_counterfactuals), :185-289 (compute_metrics_per_target: every target class, every
+ * loader batch), :351-434 (analyze_class_pair_sensitivity) and gradio_app.py:144-169 (this row, that class, only these features).
+ * Both nets in eval mode (BatchNorm: the running statistics, 1 / sqrtf(var + eps)), so rows are independent; nothing of the nets is
+ * written.  Built for the descriptor's D = 17, NC = 4, hidden = 32, nblocks = 5, seg[nheads] <= 96, ncont + nheads = 17, and the
+ * classifier image of pcg_house_classifier_fwd (c_w_kmajor / c_bias).  One work item is (target slot t, row i):
+ *   generator   cond = [onehot(target), mask]; h = relu(fc_in([x, cond])); five blocks; cont = res_scale * fc_cont(h); the packed
+ *               head logits; per head the hard Gumbel-softmax sample by pcg_gumbel_softmax_fwd's rule on (logit + noise) / tau
+ *   residual    column f: cont (col_src[f] = its index >= 0) or norm_vals[seg[s] + chosen[s]] - x[f] (col_src[f] = -(s + 1));
+ *               masked = residual * mask; x_cf_raw = x + masked (two roundings); x_cf = clamp(x_cf_raw, 0, 1)
+ *   classifier  logits_x = C(x), logits_cf = C(clamp_cls ? x_cf : x_cf_raw)  (eval_utils.py:245 classifies the raw sum,
+ *               gradio_app.py:163-169 the clamped one); gain = softmax(logits_cf)[target] - softmax(logits_x)[target]; pred = the
+ *               first maximum
+ * Forms:  sweep    target NULL: slots t = 0..T-1 are the target classes (1 <= T <= 4), every row
+ *         per row  target [N] (int64, values in [0, 4)), T = 1
+ * mask: [17] broadcast (mask_rows = 0) or [N][17] (mask_rows = 1).  noise [T][N][seg[nheads]]: always an input.
+ * `group` is the loader's batch size: rows are cut into 16-row tiles that never straddle a group; tiles_per_group =
+ * ceil(min(group, N) / 16), n_tiles = ceil(N / group) * tiles_per_group, tile q holds rows of group q / tiles_per_group (possibly
+ * none).  One workgroup per tile runs all T slots.  Every per-row output is optional (NULL: not written); leading dimensions [T][N]
+ * (logits_x, pred_x: [N]).  tile_sums [T][n_tiles][4], optional: over the tile's rows with y NULL or y[i] != target
+ * (eval_utils.py:226) their count, the count with pred_cf == target, the sum of gain and the sum of |masked| over the 17 columns.
+ * class_sums [T][n_tiles][4][17] with class_counts [T][n_tiles][4] (together, optional, need y): per source class y the sum of
+ * |masked| per feature and the row count.  Fixed summation order (ascending row, ascending feature), no atomics: bitwise repeatable. */
+typedef struct pcg_house_cf_eval_args {
+  int64_t N; int32_t T, group, clamp_cls, mask_rows;
+  const float* g_flat; int32_t nG;                     /* the generator's flat parameter buffer and its element count             */
+  const float* bn_mean[10]; const float* bn_var[10];   /* running statistics, layer order bn1_0, bn2_0, bn1_1, ...                */
+  float bn_eps, tau, res_scale;
+  int32_t col_src[17];
+  const float* norm_vals;                              /* [seg[nheads]] normalised category values, head order                    */
+  const float* const* c_w_kmajor; const float* const* c_bias;   /* HOST arrays of 5 device pointers (pcg_house_cls_fwd_args)      */
+  const float* x; const int64_t* y;                    /* [N][17]; [N] or NULL                                                    */
+  const int64_t* target; const float* mask; const float* noise;
+  float* cont; float* logits; int32_t* chosen;         /* [T][N][ncont], [T][N][seg[nheads]], [T][N][nheads]                      */
+  float* masked; float* x_cf; float* x_cf_raw;         /* [T][N][17]                                                              */
+  float* logits_cf; float* logits_x;                   /* [T][N][4]; [N][4]                                                       */
+  int64_t* pred_cf; int64_t* pred_x;                   /* [T][N]; [N]                                                             */
+  float* gain;                                         /* [T][N]                                                                  */
+  float* tile_sums; float* class_sums; float* class_counts;
+} pcg_house_cf_eval_args;
+int pcg_house_cf_eval(const pcg_house_g_desc* desc, const pcg_house_cf_eval_args* args, pcg_stream_t stream);
+
 /* The scalars the tabular trainer logs per step (house_sales_kc_usa/trainer.py:292, :299, :307-312, :318-330) in one launch:
  * out5 = { D_loss = mean(d_fake) - mean(d_real), G_loss = -mean(d_fake_g) + lambda_cls*g_cls + w_reg*am + lambda_mask*pen,
  *          g_adv = -mean(d_fake_g), g_reg = w_reg_log*am, mean(d_fake_g) } — the same reduction trees and fma chains as

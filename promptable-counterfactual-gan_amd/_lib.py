@@ -99,6 +99,15 @@ class MoonsCfEvalArgs(ctypes.Structure):
                 [(n, _P) for n in ("raw", "masked", "x_cf", "logits_cf", "logits_x", "pred_cf", "pred_x", "gain", "sums")])
 
 
+class HouseCfEvalArgs(ctypes.Structure):
+    """pcg_house_cf_eval_args."""
+    _fields_ = ([("N", ctypes.c_int64)] + [(n, _I) for n in ("T", "group", "clamp_cls", "mask_rows")] + [("g_flat", _P), ("nG", _I)] +
+                [("bn_mean", _P * 10), ("bn_var", _P * 10)] + [(n, ctypes.c_float) for n in ("bn_eps", "tau", "res_scale")] +
+                [("col_src", _I * 17), ("norm_vals", _P), ("c_w_kmajor", ctypes.POINTER(ctypes.c_void_p)), ("c_bias", ctypes.POINTER(ctypes.c_void_p))] +
+                [(n, _P) for n in ("x", "y", "target", "mask", "noise", "cont", "logits", "chosen", "masked", "x_cf", "x_cf_raw", "logits_cf",
+                                   "logits_x", "pred_cf", "pred_x", "gain", "tile_sums", "class_sums", "class_counts")])
+
+
 class MoonsGanDesc(ctypes.Structure):
     """pcg_moons_gan_desc."""
     _fields_ = ([(n, _I) for n in ("hidden", "z_dim", "label_dim", "B", "N", "nG", "nD", "nG_adam", "nD_adam")] +
@@ -198,7 +207,8 @@ STRUCTS = {"pcg_conv_geom": ConvGeom, "pcg_in_xform": InXform, "pcg_wgrad_item":
            "pcg_house_critic_bwd_args": HouseCriticBwdArgs, "pcg_house_cls_fwd_args": HouseClsFwdArgs, "pcg_house_cls_bwd_args": HouseClsBwdArgs,
            "pcg_house_res_fwd_args": HouseResFwdArgs, "pcg_house_res_bwd_args": HouseResBwdArgs, "pcg_house_loss_args": HouseLossArgs,
            "pcg_house_diag_args": HouseDiagArgs, "pcg_moons_cf_desc": MoonsCfDesc, "pcg_moons_cf_train_args": MoonsCfTrainArgs,
-           "pcg_moons_cf_fwd_args": MoonsCfFwdArgs, "pcg_moons_cf_eval_args": MoonsCfEvalArgs, "pcg_dense_bn": DenseBn,
+           "pcg_moons_cf_fwd_args": MoonsCfFwdArgs, "pcg_moons_cf_eval_args": MoonsCfEvalArgs,
+           "pcg_house_cf_eval_args": HouseCfEvalArgs, "pcg_dense_bn": DenseBn,
            "pcg_dense_bn_bwd": DenseBnBwd, "pcg_moons_gan_desc": MoonsGanDesc, "pcg_moons_gan_train_args": MoonsGanTrainArgs,
            "pcg_moons_gan_fwd_args": MoonsGanFwdArgs}
 
@@ -371,6 +381,7 @@ PROTOTYPES = {
     "pcg_house_critic_bwd": (_i, [_c.POINTER(HouseCriticBwdArgs), _vp]),
     "pcg_house_classifier_fwd": (_i, [_c.POINTER(HouseClsFwdArgs), _c.POINTER(SnBwdBatch), _vp]),
     "pcg_house_classifier_bwd": (_i, [_c.POINTER(HouseClsBwdArgs), _c.POINTER(SnFwdBatch), _vp]),
+    "pcg_house_cf_eval": (_i, [_c.POINTER(HouseGDesc), _c.POINTER(HouseCfEvalArgs), _vp]),
     "pcg_house_residual_fwd": (_i, [_c.POINTER(HouseResFwdArgs), _c.POINTER(SnFwdBatch), _vp]),
     "pcg_house_residual_bwd": (_i, [_c.POINTER(HouseResBwdArgs), _c.POINTER(HouseLossArgs), _c.POINTER(HouseDiagArgs), _vp]),
     "pcg_house_diag": (_i, [_c.POINTER(HouseDiagArgs), _vp]),

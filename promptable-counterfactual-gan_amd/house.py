@@ -10,6 +10,10 @@
     trainer.py  cat_norm_maps :205-223                      cat_norm_maps
     trainer.py  train_countergan loop body :241-316         make_optimizers + train_step
     trainer.py  train_countergan :186-378                   train_countergan(generator, config, X_train, y_train, clf_model)
+    gradio_app.py  :144-169                                 prompt_mask + counterfactuals (this row, that class, these features)
+    eval_utils.py  :185-289, :351-434, :673-728             compute_metrics_per_target(one_launch=True), analyze_class_pair_sensitivity,
+                                                            evaluate_pipeline: ONE launch of pcg_house_cf_eval each
+    eval_utils.py  :292-348, :436-493                       analyze_feature_shift_importance, evaluate_classifier (tables; no plots)
 
 Every network is one autograd node that sequences C-ABI calls (csrc/tabular.hip + the BatchNorm / activation / loss kernels)
 and accumulates parameter gradients straight into the FlatModule's flat gradient buffer.  The categorical heads are packed
@@ -112,6 +116,14 @@ class ResidualGenerator(FlatModule):
         self._fdesc = None
 
     # -- fused path -------------------------------------------------------------------------------------------------------------
+    def _eval_dims_ok(self):
+        """The dimensions of _fused_ok (below) without its training clause: what the one-launch evaluation kernel is built for."""
+        bn = self.blocks[0].bn1 if len(self.blocks) else None
+        return (self.hidden_dim == 32 and len(self.blocks) == 5 and bn is not None
+                and self.input_dim == 17 and self.num_classes == 4 and self.total_cat <= 96 and len(self.cat_idx) <= 8
+                and self.total_cat + len(self.continuous_idx) <= 96 and all(b_ - a_ <= 32 for a_, b_ in zip(self.seg, self.seg[1:]))
+                and len(self.continuous_idx) <= 32 and all(b_.bn1.eps == bn.eps and b_.bn2.eps == bn.eps for b_ in self.blocks))
+
     def _fused_ok(self):
         bn = self.blocks[0].bn1 if len(self.blocks) else None
         return (self.use_fused and self.hidden_dim == 32 and len(self.blocks) == 5 and self.training and bn is not None
@@ -1069,11 +1081,16 @@ def build_counterfactuals(G, x, target_onehot, config, gumbel=None, norm_vals=No
     return masked, x_cf
 
 
-def compute_metrics_per_target(generator, classifier, X, y, config, gumbel_per_call=None, rng=None, max_vis=500):
+def compute_metrics_per_target(generator, classifier, X, y, config, gumbel_per_call=None, rng=None, max_vis=500, one_launch=False):
     """eval_utils.py:185-289 — per target class: class-flip rate, prediction gain, mean |masked residual| over the samples whose
     class differs from the target, averaged over batches.  X, y: numpy arrays (already MinMax-scaled).  `gumbel_per_call`: an
-    iterator of packed noise tensors, one per generator call, for runs that must reproduce given draws; otherwise `rng`."""
+    iterator of packed noise tensors, one per generator call, for runs that must reproduce given draws; otherwise `rng`.
+    one_launch=True: every target class and every loader batch in ONE launch of pcg_house_cf_eval (csrc/house_cf_eval.hip, DESIGN.md
+    §3.12) on the same draws — the per-call noise laid into [T][N][Tcat] at the rows each call would have selected — and one read of
+    the tile sums; same return type."""
     import numpy as np
+    if one_launch:
+        return _metrics_one_launch(generator, classifier, X, y, config, gumbel_per_call, rng, max_vis)
     device = next(generator.parameters()).device
     bs_cfg = int(config.get("batch_size", 128))
     X_t, y_t = torch.as_tensor(X, dtype=torch.float32), torch.as_tensor(y, dtype=torch.long)
@@ -1109,6 +1126,451 @@ def compute_metrics_per_target(generator, classifier, X, y, config, gumbel_per_c
     originals = torch.cat(originals, 0).numpy() if originals else np.empty((0, X_t.shape[1]))
     cfs = torch.cat(cfs, 0).numpy() if cfs else np.empty((0, X_t.shape[1]))
     return results, originals, cfs
+
+
+# ---- prompted queries and evaluation in ONE launch (csrc/house_cf_eval.hip) -------------------------------------
+CF_ROW_OUTPUTS = ("cont", "logits", "chosen", "masked_residual", "x_cf", "x_cf_raw", "logits_cf", "logits_x", "pred_cf", "pred_x", "gain")
+METRIC_FIELDS = ("class_flip", "prediction_gain", "avg_actionability")
+CF_TILE_ROWS = 16           # rows per workgroup of pcg_house_cf_eval: tiles never straddle a group
+CF_QUERY_GROUP = 256        # the group where the caller names no batch size (queries: no sums are read)
+_CF_FIELD = {"masked_residual": "masked"}                                     # the argument struct's names where they differ
+_CF_CLS_DIMS = [17, 256, 256, 128, 64, 4]
+
+
+def prompt_mask(config, allowed=None, feature_names=FEATURES):
+    """gradio_app.py:150-155 — the feature mask of one request: 1 for the features the prompt allows to move (`allowed`: names from
+    feature_names and / or column indices; None: all of them), 0 for the rest and ALWAYS 0 for config['immutable_idx'].
+    Returns a float32 ndarray [len(feature_names)]."""
+    names = list(feature_names)
+    D = len(names)
+    mask = np.zeros(D, dtype=np.float32)
+    if allowed is None:
+        mask[:] = 1.0
+    else:
+        if isinstance(allowed, (str, int, np.integer)):
+            allowed = [allowed]
+        for a_ in allowed:
+            if isinstance(a_, str):
+                if a_ not in names:
+                    raise PcgError(f"prompt_mask: unknown feature {a_!r} (known: {names})")
+                mask[names.index(a_)] = 1.0
+            elif isinstance(a_, (int, np.integer)) and not isinstance(a_, bool):
+                if not 0 <= int(a_) < D:
+                    raise PcgError(f"prompt_mask: feature index {int(a_)} outside [0, {D})")
+                mask[int(a_)] = 1.0
+            else:
+                raise PcgError(f"prompt_mask: allowed entries are feature names or column indices, got {a_!r}")
+    for i in config.get("immutable_idx", []):
+        mask[int(i)] = 0.0
+    return mask
+
+
+def _cf_nets(generator, classifier):
+    """Host guards of the one-launch evaluation, before anything touches the GPU."""
+    if generator.training or classifier.training:
+        raise PcgError("the one-launch evaluation uses BatchNorm's running statistics: put the generator and the classifier in eval mode (.eval())")
+    if not generator._eval_dims_ok():
+        raise PcgError("pcg_house_cf_eval is built for input_dim 17, 4 classes, hidden_dim 32, 5 blocks, at most 8 heads of at most 32 "
+                       "categories (96 in all) and one BatchNorm eps; this generator is outside that")
+    dims = [m.in_features for m in classifier.net if isinstance(m, nn.Linear)] + [classifier.net[-1].out_features]
+    if dims != _CF_CLS_DIMS:
+        raise PcgError(f"pcg_house_cf_eval is built for the classifier widths {_CF_CLS_DIMS}, got {dims}")
+
+
+def _cf_rows(x, what="x"):
+    if not torch.is_tensor(x):
+        x = torch.as_tensor(np.asarray(x), dtype=torch.float32)
+    if x.dim() != 2 or x.shape[1] != 17 or x.shape[0] < 1 or not x.dtype.is_floating_point:
+        raise PcgError(f"{what} must be [N][17] floats with N >= 1, got {tuple(x.shape)} {x.dtype}")
+    return x.detach()
+
+
+def _cf_mask(mask, config, N):
+    """None: prompt_mask(config); a [17] vector (broadcast) or [N][17] (one mask per row).  Returns (float32 tensor, per-row flag)."""
+    if mask is None:
+        mask = prompt_mask(config)
+    m = mask.detach() if torch.is_tensor(mask) else torch.as_tensor(np.asarray(mask, dtype=np.float32))
+    if tuple(m.shape) not in ((17,), (N, 17)):
+        raise PcgError(f"mask must be [17] or [N][17] (N = {N}), got {tuple(m.shape)}")
+    return m.to(torch.float32), m.dim() == 2
+
+
+def _cf_given_noise(generator, gumbel, T, N):
+    """Shape check of supplied Gumbel noise: [T][N][Tcat] (or [N][Tcat] / a dict idx -> [N][n] where T = 1).  None stays None."""
+    if gumbel is None:
+        return None
+    Tc = generator.total_cat
+    if isinstance(gumbel, dict):
+        gumbel = generator.pack_noise(gumbel)
+    if not torch.is_tensor(gumbel):
+        gumbel = torch.as_tensor(np.asarray(gumbel, dtype=np.float32))
+    if T == 1 and tuple(gumbel.shape) == (N, Tc):
+        gumbel = gumbel.reshape(1, N, Tc)
+    if tuple(gumbel.shape) != (T, N, Tc):
+        raise PcgError(f"gumbel noise must be [{T}][{N}][{Tc}]" + (f" or [{N}][{Tc}]" if T == 1 else "") + f", got {tuple(gumbel.shape)}")
+    return gumbel.detach().to(torch.float32)
+
+
+def _cf_device(generator, classifier):
+    devs = {next(generator.parameters()).device, next(classifier.parameters()).device}
+    if len(devs) != 1:
+        raise PcgError("the generator and the classifier must be on one GPU")
+    dev = devs.pop()
+    if dev.type != "cuda":
+        raise PcgError(f"the generator and the classifier are on {dev}; libpcgan_hip has no CPU path")
+    return dev
+
+
+def _cf_launch(generator, classifier, x, config, T, group, outputs, noise, mask, mask_rows, target=None, y=None, clamp_cls=False,
+               tile_sums=False, class_sums=False):
+    """ONE pcg_house_cf_eval launch.  x [N][17], noise [T][N][Tcat], mask [17] / [N][17], target / y [N] int64: contiguous tensors on
+    the nets' device.  Returns the asked per-row outputs ([T][N]...; logits_x / pred_x [N]...) and the asked sums."""
+    import ctypes
+    from ._lib import HouseCfEvalArgs, load as _lib_load
+    dev, N = x.device, x.shape[0]
+    generator._ensure_flat()
+    a = HouseCfEvalArgs()
+    a.N, a.T, a.group, a.clamp_cls, a.mask_rows = N, T, int(group), int(bool(clamp_cls)), int(bool(mask_rows))
+    a.g_flat, a.nG = generator._flat.data_ptr(), generator._flat.numel()
+    for k, blk in enumerate(generator.blocks):
+        for j, bn in ((2 * k, blk.bn1), (2 * k + 1, blk.bn2)):
+            a.bn_mean[j] = ops._chk(bn.running_mean, "running_mean").data_ptr()
+            a.bn_var[j] = ops._chk(bn.running_var, "running_var").data_ptr()
+    tau = config.get("gumbel_tau", None)                                       # eval_utils.py:76-77
+    a.bn_eps, a.tau, a.res_scale = generator.blocks[0].bn1.eps, generator.tau if tau is None else float(tau), generator.residual_scaling
+    for f, v in enumerate(generator.col_src()):
+        a.col_src[f] = v
+    norm_vals = cat_norm_maps(generator, config, dev)                          # :56-67
+    if norm_vals.numel() != generator.total_cat:
+        raise PcgError(f"config['categorical_info'] lists {norm_vals.numel()} category values, the generator's heads have {generator.total_cat}")
+    biases = [b for _, b in classifier._pack()]
+    wk, bk = ops._ptr_array(classifier._pack_kmajor()), ops._ptr_array(biases)
+    a.norm_vals, a.c_w_kmajor, a.c_bias = norm_vals.data_ptr(), wk, bk
+    a.x, a.mask, a.noise = ops._chk(x, "x").data_ptr(), ops._chk(mask, "mask").data_ptr(), ops._chk(noise, "gumbel noise").data_ptr()
+    if target is not None:
+        a.target = ops._chk(target, "target", torch.int64).data_ptr()
+    if y is not None:
+        a.y = ops._chk(y, "y", torch.int64).data_ptr()
+    shape = {"cont": (len(generator.continuous_idx),), "logits": (generator.total_cat,), "chosen": (len(generator.cat_idx),),
+             "masked_residual": (17,), "x_cf": (17,), "x_cf_raw": (17,), "logits_cf": (4,), "logits_x": (4,), "pred_cf": (), "pred_x": (), "gain": ()}
+    out = {}
+    for name in outputs:
+        lead = (N,) if name in ("logits_x", "pred_x") else (T, N)
+        dt = torch.int32 if name == "chosen" else (torch.int64 if name.startswith("pred") else torch.float32)
+        out[name] = torch.empty(lead + shape[name], dtype=dt, device=dev)
+        setattr(a, _CF_FIELD.get(name, name), out[name].data_ptr())
+    n_tiles = -(-N // int(group)) * -(-min(int(group), N) // CF_TILE_ROWS)
+    if tile_sums:
+        out["tile_sums"] = torch.empty((T, n_tiles, 4), dtype=torch.float32, device=dev)
+        a.tile_sums = out["tile_sums"].data_ptr()
+    if class_sums:
+        out["class_sums"] = torch.empty((T, n_tiles, 4, 17), dtype=torch.float32, device=dev)
+        out["class_counts"] = torch.empty((T, n_tiles, 4), dtype=torch.float32, device=dev)
+        a.class_sums, a.class_counts = out["class_sums"].data_ptr(), out["class_counts"].data_ptr()
+    ops.check(_lib_load().pcg_house_cf_eval(ctypes.byref(generator._fused_desc()), ctypes.byref(a), ops._stream()), "pcg_house_cf_eval")
+    return out
+
+
+def _cf_draw(generator, rng, shape, dev):
+    """The Gumbel noise of a call that was given none: ONE DeviceRNG.gumbel launch (rng, else generator.rng, else a fresh seed-0 one)."""
+    if rng is None:
+        if generator.rng is None:
+            generator.rng = ops.DeviceRNG(seed=0)
+        rng = generator.rng
+    return rng.gumbel(shape, dev)
+
+
+def _cf_group(batch_size, config):
+    group = int(config.get("batch_size", 128) if batch_size is None else batch_size)
+    if not 1 <= group < 2 ** 31:
+        raise PcgError(f"batch_size must be a positive 32-bit integer, got {group}")
+    return group
+
+
+def counterfactuals(generator, classifier, x, target, config, mask=None, gumbel=None, rng=None):
+    """gradio_app.py:144-169 for N rows at once — this house, that price class, only these features may move: x [N][17] (a tensor
+    or an ndarray), target an int or [N] integers in [0, 4), mask None (prompt_mask(config): everything but the immutable columns),
+    [17] or [N][17] (one prompt per row).  The classifier sees the clamped counterfactual, as the app's query does (:163-169).
+    gumbel: the hard Gumbel-softmax noise [N][Tcat] (or a dict idx -> [N][n]); None: one draw from rng / generator.rng.  Both nets
+    must be in eval mode.  ONE launch.  Returns a dict of device tensors, the names of CF_ROW_OUTPUTS, leading dimension N."""
+    _cf_nets(generator, classifier)
+    x = _cf_rows(x)
+    N = x.shape[0]
+    if isinstance(target, (int, np.integer)) and not isinstance(target, bool):
+        target = torch.full((N,), int(target), dtype=torch.int64)
+    else:
+        target = target.detach() if torch.is_tensor(target) else torch.as_tensor(np.asarray(target))
+        if tuple(target.shape) != (N,) or target.dtype.is_floating_point or target.dtype == torch.bool:
+            raise PcgError(f"target must be an int or [N] integers (N = {N}), got {tuple(target.shape)} {target.dtype}")
+    lo, hi = int(target.min()), int(target.max())                              # it selects the one-hot input: refused on the host
+    if lo < 0 or hi >= generator.num_classes:
+        raise PcgError(f"targets must lie in [0, {generator.num_classes}), got [{lo}, {hi}]")
+    mask, mask_rows = _cf_mask(mask, config, N)
+    noise = _cf_given_noise(generator, gumbel, 1, N)
+    dev = _cf_device(generator, classifier)
+    with torch.no_grad():
+        if noise is None:
+            noise = _cf_draw(generator, rng, (1, N, generator.total_cat), dev)
+        out = _cf_launch(generator, classifier, x.to(dev, torch.float32).contiguous(), config, 1, CF_QUERY_GROUP, CF_ROW_OUTPUTS,
+                         noise.to(dev).contiguous(), mask.to(dev).contiguous(), mask_rows, target=target.to(dev, torch.int64).contiguous(),
+                         clamp_cls=True)
+    return {k: (v if k in ("logits_x", "pred_x") else v[0]) for k, v in out.items()}
+
+
+def counterfactual_sweep(generator, classifier, X, y=None, config=CONFIG, mask=None, batch_size=None, gumbel=None, rng=None, outputs=(),
+                         clamp_cls=False, class_sums=False):
+    """Every target class x every row in ONE launch: the loops of eval_utils.py:219-267 with the row selection (:226) folded into
+    the sums.  y [N] or None (every row counts); mask as in `counterfactuals`; batch_size: the loader's (default
+    config['batch_size']); gumbel [4][N][Tcat] or None (one draw); clamp_cls False: the classifier sees x + masked_residual as the
+    metrics do (:245).  Returns {"tile_sums": [4][n_tiles][4] (included rows, rows with pred_cf == target, sum of gain, sum of
+    |masked_residual| over the 17 columns; metrics_from_sums folds them), with class_sums=True also "class_sums" [4][n_tiles][4][17]
+    and "class_counts" [4][n_tiles][4] (per source class; needs y), and the per-row `outputs` asked for ([4][N]...; logits_x,
+    pred_x [N]...)} as device tensors."""
+    _cf_nets(generator, classifier)
+    X = _cf_rows(X, "X")
+    N, T = X.shape[0], generator.num_classes
+    group = _cf_group(batch_size, config)
+    bad = [o for o in outputs if o not in CF_ROW_OUTPUTS]
+    if bad:
+        raise PcgError(f"outputs {bad} are not among {CF_ROW_OUTPUTS}")
+    if y is not None:
+        y = y.detach() if torch.is_tensor(y) else torch.as_tensor(np.asarray(y))
+        if tuple(y.shape) != (N,) or y.dtype.is_floating_point:
+            raise PcgError(f"y must be [N] integers (N = {N}), got {tuple(y.shape)} {y.dtype}")
+    elif class_sums:
+        raise PcgError("class_sums splits the rows by their class: y is required")
+    mask, mask_rows = _cf_mask(mask, config, N)
+    noise = _cf_given_noise(generator, gumbel, T, N)
+    dev = _cf_device(generator, classifier)
+    with torch.no_grad():
+        if noise is None:
+            noise = _cf_draw(generator, rng, (T, N, generator.total_cat), dev)
+        return _cf_launch(generator, classifier, X.to(dev, torch.float32).contiguous(), config, T, group, tuple(outputs),
+                          noise.to(dev).contiguous(), mask.to(dev).contiguous(), mask_rows,
+                          y=None if y is None else y.to(dev, torch.int64).contiguous(), clamp_cls=clamp_cls, tile_sums=True,
+                          class_sums=class_sums)
+
+
+def fold_tiles(sums, group):
+    """Pure host.  sums [T][n_tiles]... -> [T][n_groups]... in float64: the tiles of each group added in ascending order.  A group
+    has ceil(group / 16) tiles; fewer tiles than that in all means the rows did not fill one group."""
+    s = np.asarray(sums, dtype=np.float64)
+    group = int(group)
+    if s.ndim < 2 or group < 1:
+        raise PcgError(f"fold_tiles: sums must be [T][n_tiles]... and group positive, got {s.shape}, {group}")
+    tpg = -(-group // CF_TILE_ROWS)
+    n_tiles = s.shape[1]
+    if n_tiles <= tpg:
+        tpg = max(n_tiles, 1)
+    elif n_tiles % tpg:
+        raise PcgError(f"fold_tiles: {n_tiles} tiles are no whole number of groups of {group} rows ({tpg} tiles each)")
+    out = np.zeros((s.shape[0], n_tiles // tpg) + s.shape[2:])
+    for j in range(tpg):                                                       # ascending tile order inside every group
+        out += s[:, j::tpg][:, :out.shape[1]]
+    return out
+
+
+def metrics_from_sums(tile_sums, group):
+    """Pure host.  tile_sums [T][n_tiles][4] of pcg_house_cf_eval -> [T][3] (METRIC_FIELDS) as eval_utils.py:253-278 forms them:
+    per group with a row in it the mean over its rows (actionability over all 17 columns: / (17 count)), then the mean over those
+    groups — the mean of the per-batch means.  A target without such a group: nan."""
+    g = fold_tiles(tile_sums, group)
+    if g.ndim != 3 or g.shape[2] != 4:
+        raise PcgError(f"metrics_from_sums: tile_sums must be [T][n_tiles][4], got {np.shape(tile_sums)}")
+    out = np.full((g.shape[0], 3), np.nan)
+    for t in range(g.shape[0]):
+        r = g[t][g[t][:, 0] > 0]
+        if len(r):
+            out[t] = (np.mean(r[:, 1] / r[:, 0]), np.mean(r[:, 2] / r[:, 0]), np.mean(r[:, 3] / (17 * r[:, 0])))
+    return out
+
+
+def metric_rows(table):
+    """[T][3] -> the rows of the reference's DataFrame (eval_utils.py:274-279) as a list of dicts."""
+    return [dict({"target_class": t}, **{k: float(v) for k, v in zip(METRIC_FIELDS, row)}) for t, row in enumerate(table)]
+
+
+def _metrics_one_launch(generator, classifier, X, y, config, gumbel_per_call, rng, max_vis):
+    """compute_metrics_per_target(one_launch=True): the chain's (target, batch) calls become rows of one sweep.  Call (t, batch) of
+    the chain selects the batch's rows with y != t in ascending order, and the calls of a target come in ascending batch order, so
+    their noise tensors, concatenated, are the noise of the included rows of slot t in ascending row order."""
+    X_t, y_np = torch.as_tensor(np.asarray(X), dtype=torch.float32), np.asarray(y)
+    num_classes = int(np.unique(y_np).size)
+    generator.eval(); classifier.eval()
+    _cf_nets(generator, classifier)
+    X_t = _cf_rows(X_t, "X")
+    N, Tc = X_t.shape[0], generator.total_cat
+    if y_np.shape != (N,) or num_classes != generator.num_classes or y_np.min() < 0 or y_np.max() >= num_classes:
+        raise PcgError(f"y must be [N] labels covering the generator's {generator.num_classes} classes, got shape {y_np.shape}, "
+                       f"{num_classes} distinct values")
+    bs = _cf_group(None, config)
+    dev = _cf_device(generator, classifier)
+    if gumbel_per_call is None and generator.rng is None:
+        generator.rng = rng if rng is not None else ops.DeviceRNG(seed=0)
+    noise_it = iter(gumbel_per_call) if gumbel_per_call is not None else None
+    vis, seen = [], 0
+    with torch.no_grad():
+        noise = ops.fill(torch.empty((num_classes, N, Tc), dtype=torch.float32, device=dev), 0.0)   # excluded rows: not read back
+        for t in range(num_classes):
+            rows_t, parts = np.nonzero(y_np != t)[0], []
+            stage = torch.empty((len(rows_t), Tc), dtype=torch.float32, device=dev) if noise_it is None else None
+            done = 0
+            for i in range(0, N, bs):
+                n_sel = int((y_np[i:i + bs] != t).sum())
+                if n_sel == 0:
+                    continue
+                if noise_it is not None:
+                    part = next(noise_it)
+                    part = generator.pack_noise(part) if isinstance(part, dict) else part
+                    if tuple(part.shape) != (n_sel, Tc):
+                        raise PcgError(f"gumbel noise of call (target {t}, rows {i}..) must be [{n_sel}, {Tc}], got {tuple(part.shape)}")
+                    parts.append(part.to(dev, torch.float32))
+                else:
+                    generator.rng.gumbel(None, dev, out=stage[done:done + n_sel])   # the chain's draw of this call
+                if seen < max_vis:                                             # :270-272 (whole calls, while under max_vis)
+                    vis.append(t * N + rows_t[done:done + n_sel])
+                    seen += n_sel
+                done += n_sel
+            if len(rows_t):
+                noise[t].index_copy_(0, torch.from_numpy(rows_t).to(dev), torch.cat(parts) if noise_it is not None else stage)
+        res = _cf_launch(generator, classifier, X_t.to(dev).contiguous(), config, num_classes, bs, ("x_cf_raw",), noise,
+                         torch.from_numpy(prompt_mask(config)).to(dev), False, y=torch.from_numpy(y_np.astype(np.int64)).to(dev),
+                         tile_sums=True)
+        table = metrics_from_sums(res["tile_sums"].cpu().numpy(), bs)          # the one read of the sums
+        if vis:
+            idx = np.concatenate(vis)
+            cfs = res["x_cf_raw"].view(num_classes * N, 17).index_select(0, torch.from_numpy(idx).to(dev)).cpu().numpy()
+            originals = X_t[torch.from_numpy(idx % N)].numpy()
+        else:
+            originals, cfs = np.empty((0, X_t.shape[1])), np.empty((0, X_t.shape[1]))
+    return metric_rows(table), originals, cfs
+
+
+def analyze_class_pair_sensitivity(G, clf, X, y, config, gumbel=None, rng=None):
+    """eval_utils.py:351-434 — deltas [NC][NC][17]: for every source class s and target t != s the mean |masked residual| per
+    feature over the rows of class s (diagonal and absent classes: 0), from ONE sweep launch (the reference makes NC (NC - 1)
+    generator passes).  gumbel: [NC][N][Tcat] — the noise of pass (s, t) at the rows of class s in slot t — or None (one draw).
+    The heat maps are plotting: left out."""
+    G.eval(); clf.eval()
+    y_np = np.asarray(y.detach().cpu() if torch.is_tensor(y) else y)
+    N = len(y_np)
+    res = counterfactual_sweep(G, clf, X, y_np, config, batch_size=max(N, 1), gumbel=gumbel, rng=rng, class_sums=True)
+    sums = fold_tiles(res["class_sums"].cpu().numpy(), N)[:, 0]                # [t][s][17]
+    counts = fold_tiles(res["class_counts"].cpu().numpy(), N)[:, 0]            # [t][s]
+    NC = sums.shape[0]
+    deltas = np.zeros((NC, NC, sums.shape[2]), dtype=float)
+    for s_ in range(NC):
+        for t in range(NC):
+            if s_ != t and counts[t, s_] > 0:
+                deltas[s_, t] = sums[t, s_] / counts[t, s_]
+    return deltas
+
+
+def analyze_feature_shift_importance(X_orig, X_cf, feature_names, scaler=None):
+    """eval_utils.py:292-324 — the table of the global feature-shift plot as a list of dicts, sorted by mean_abs_change_norm
+    descending (ties keep the feature order): feature, mean_abs_change_norm = mean |X_cf - X_orig| per feature,
+    mean_pct_of_range = 100 x that, and with a scaler mean_abs_change_denorm = that x (data_max_ - data_min_) of the row's own
+    feature (the reference assigns this column after the sort, in unsorted order: not repeated here).  Empty inputs: the
+    reference's zero table (:305-307)."""
+    X_orig, X_cf, names = np.asarray(X_orig), np.asarray(X_cf), list(feature_names)
+    if X_orig.size == 0 or X_cf.size == 0:
+        return [{"feature": f, "mean_abs_change_norm": 0.0} for f in names]
+    if X_orig.shape != X_cf.shape or X_orig.ndim != 2 or X_orig.shape[1] != len(names):
+        raise PcgError(f"analyze_feature_shift_importance: X_orig {X_orig.shape} and X_cf {X_cf.shape} must be [n][{len(names)}]")
+    delta = np.mean(np.abs(X_cf - X_orig), axis=0)                             # :309
+    rng_ = None
+    if scaler is not None and hasattr(scaler, "data_min_") and hasattr(scaler, "data_max_"):
+        rng_ = (np.asarray(scaler.data_max_) - np.asarray(scaler.data_min_)).astype(float)   # :319
+    rows = []
+    for i in np.argsort(-delta, kind="stable"):                                # :314
+        row = {"feature": names[i], "mean_abs_change_norm": float(delta[i]), "mean_pct_of_range": float(delta[i] * 100.0)}
+        if rng_ is not None:
+            row["mean_abs_change_denorm"] = float(delta[i] * rng_[i])
+        rows.append(row)
+    return rows
+
+
+def confusion_matrix(y_true, y_pred):
+    """sklearn.metrics.confusion_matrix(y_true, y_pred): labels = the sorted values that occur in either, rows true, columns predicted."""
+    y_true, y_pred = np.asarray(y_true), np.asarray(y_pred)
+    labels = np.unique(np.concatenate([y_true, y_pred]))
+    cm = np.zeros((len(labels), len(labels)), dtype=np.int64)
+    np.add.at(cm, (np.searchsorted(labels, y_true), np.searchsorted(labels, y_pred)), 1)
+    return cm
+
+
+def weighted_scores(cm):
+    """Pure host.  accuracy and sklearn's precision / recall / f1 with average='weighted', zero_division=0, from a confusion matrix
+    (rows true, columns predicted): per class tp / column sum, tp / row sum and their harmonic mean (0 where a denominator is 0),
+    weighted by the class's support (its row sum)."""
+    cm = np.asarray(cm, dtype=np.float64)
+    tp, support, predicted = np.diag(cm), cm.sum(1), cm.sum(0)
+    total = support.sum()
+    if cm.ndim != 2 or cm.shape[0] != cm.shape[1] or total <= 0:
+        raise PcgError(f"weighted_scores: a square confusion matrix with at least one sample is required, got {cm.shape}")
+    prec = np.divide(tp, predicted, out=np.zeros_like(tp), where=predicted > 0)
+    rec = np.divide(tp, support, out=np.zeros_like(tp), where=support > 0)
+    f1 = np.divide(2 * prec * rec, prec + rec, out=np.zeros_like(tp), where=(prec + rec) > 0)
+    w = support / total
+    return {"accuracy": float(tp.sum() / total), "precision": float((w * prec).sum()), "recall": float((w * rec).sum()),
+            "f1": float((w * f1).sum()), "per_class": {"precision": prec, "recall": rec, "f1": f1, "support": support.astype(np.int64)}}
+
+
+def evaluate_classifier(classifier, X_test, y_test, class_names=None):
+    """eval_utils.py:436-493 — accuracy, weighted precision / recall / F1 (zero_division=0), the confusion matrix and a text report
+    of the per-class scores; one fused classifier launch, the scores on the host without scikit-learn.  The confusion-matrix
+    picture is plotting: left out."""
+    classifier.eval()
+    dev = next(classifier.parameters()).device
+    with torch.no_grad():
+        logits = classifier(torch.as_tensor(np.asarray(X_test), dtype=torch.float32).to(dev).contiguous())
+        preds = logits.argmax(1).cpu().numpy()                                # :455
+    y_true = np.asarray(y_test, dtype=int)
+    cm = confusion_matrix(y_true, preds)
+    sc = weighted_scores(cm)
+    labels = np.unique(np.concatenate([y_true, preds]))
+    names = [str(n) for n in class_names] if class_names is not None else [str(v) for v in labels]
+    pc = sc.pop("per_class")
+    lines = [f"{'':>12} {'precision':>9} {'recall':>9} {'f1-score':>9} {'support':>9}"]
+    lines += [f"{names[i] if i < len(names) else labels[i]:>12} {pc['precision'][i]:9.4f} {pc['recall'][i]:9.4f} {pc['f1'][i]:9.4f} {pc['support'][i]:9d}"
+              for i in range(len(labels))]
+    lines.append(f"{'weighted avg':>12} {sc['precision']:9.4f} {sc['recall']:9.4f} {sc['f1']:9.4f} {int(pc['support'].sum()):9d}")
+    return dict(sc, confusion_matrix=cm, report="\n".join(lines) + "\n")
+
+
+def _csv_value(v):
+    return "" if isinstance(v, float) and np.isnan(v) else (repr(v) if isinstance(v, float) else str(v))
+
+
+def save_table(rows, save_path, columns):
+    """DataFrame.to_csv(index=False) of a list of dicts: shortest float repr, nan as an empty field (eval_utils.py:667-670)."""
+    import os
+    os.makedirs(os.path.dirname(save_path) or ".", exist_ok=True)
+    with open(save_path, "w") as f:
+        f.write(",".join(columns) + "\n")
+        for r in rows:
+            f.write(",".join(_csv_value(r[c]) for c in columns) + "\n")
+
+
+def evaluate_pipeline(generator, classifier, X_test, y_test, config):
+    """eval_utils.py:673-728 — compute_metrics_per_target on the one-launch path -> <out_dir>/countergan_metrics.csv (the
+    reference's layout); the feature-shift table -> feature_shift_importance.csv and the class-pair sensitivity array ->
+    class_pair_sensitivity/deltas.npy, where the reference saves their pictures.  Plots, the case-study HTML and t-SNE stay out
+    (DESIGN.md §7).  Returns the metric rows."""
+    import os
+    out = config.get("out_dir", ".")
+    os.makedirs(out, exist_ok=True)
+    print("[pipeline] Computing per-target CounterGAN metrics ...")
+    rows, originals, cfs = compute_metrics_per_target(generator, classifier, X_test, y_test, config, one_launch=True)   # :687
+    save_table(rows, os.path.join(out, "countergan_metrics.csv"), ("target_class",) + METRIC_FIELDS)                     # :688
+    print(f"[metrics] Saved metrics to {os.path.join(out, 'countergan_metrics.csv')}")
+    names = config.get("feature_names", [f"feat_{i}" for i in range(np.asarray(X_test).shape[1])])
+    shift = analyze_feature_shift_importance(originals, cfs, names, scaler=config.get("scaler", None))                   # :691-697
+    save_table(shift, os.path.join(out, "feature_shift_importance.csv"), tuple(shift[0].keys()) if shift else ("feature",))
+    deltas = analyze_class_pair_sensitivity(generator, classifier, X_test, y_test, config)                               # :700-708
+    os.makedirs(os.path.join(out, "class_pair_sensitivity"), exist_ok=True)
+    np.save(os.path.join(out, "class_pair_sensitivity", "deltas.npy"), deltas)
+    return rows
 
 
 class GraphedTrainStep:
