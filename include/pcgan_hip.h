@@ -814,6 +814,80 @@ typedef struct pcg_house_cf_eval_args {
 } pcg_house_cf_eval_args;
 int pcg_house_cf_eval(const pcg_house_g_desc* desc, const pcg_house_cf_eval_args* args, pcg_stream_t stream);
 
+/* Prompted queries and per-target evaluation of the MNIST CounteRGAN (csrc/mnist_cf_eval.hip): what surrounds the
+ * generator's and the classifier's convolutions when ONE pass carries every (target class, row) query of a loader batch.
+ * A query is q = t * B + b (target-major) for B rows and T targets per row:
+ *   sweep    target NULL, T <= K: query (t, b) asks for target class t
+ *   per row  target [B] (int64, values in [0, K)), T = 1
+ * Every launch works on a window [q0, q0 + nq) of the T * B queries so that the host can chunk; per-QUERY inputs and outputs
+ * (out, c, x_cf, raw, masked, sums, logits_cf, tail_sums, pred ... flip) are indexed by q - q0, per-ROW ones (x, y_true, target,
+ * logits_orig) by b.  x is never replicated T times, neither is the mask: mask_mode says which row of `mask` a query reads.
+ * fp32, no atomics, every sum in one fixed order (two calls give the same bits). */
+enum { PCG_MASK_SHARED = 0,      /* mask [HW]        one mask for every query                                                  */
+       PCG_MASK_PER_ROW = 1,     /* mask [B][HW]     query (t, b) reads row b                                                  */
+       PCG_MASK_PER_QUERY = 2 }; /* mask [T*B][HW]   query q reads row q (NOT window-relative)                                  */
+
+/* eval_utils.py:247-256 create_mask_from_indices / gradio_app.py:234-240 make_mask_from_patch_list: bit p of bits[m] set = patch
+ * p = (i, j) = divmod(p, W / ps) of mask m is modifiable: mask[m][i*ps .. (i+1)*ps)[j*ps .. (j+1)*ps) = 1, everything else 0 (the
+ * pixels outside the (H/ps)*ps x (W/ps)*ps grid included).  Needs (H/ps) * (W/ps) <= 64. */
+typedef struct pcg_patch_mask_bits_args {
+  const uint64_t* bits;   /* [n]        */
+  float* mask;            /* [n][H][W]  */
+  int32_t n, H, W, ps;
+} pcg_patch_mask_bits_args;
+int pcg_patch_mask_bits(const pcg_patch_mask_bits_args* args, pcg_stream_t stream);
+
+/* generator.py:73-74 `torch.cat([x, embed(target).view(B,1,H,W), mask], 1)` for the window's queries, NHWC:
+ * out[q - q0][p] = (x[b][p], table[target(q)][p], mask[row(q)][p]) — pcg_embed_concat_fwd with the broadcast done by indexing. */
+typedef struct pcg_mnist_cf_entry_args {
+  const float* x;          /* [B][HW]                              */
+  const float* table;      /* [K][HW]  the label embedding         */
+  const float* mask;       /* see mask_mode                        */
+  const int64_t* target;   /* NULL (sweep) or [B]                  */
+  float* out;              /* [nq][HW][3]                          */
+  int32_t B, T, HW, K, mask_mode, q0, nq;
+} pcg_mnist_cf_entry_args;
+int pcg_mnist_cf_entry(const pcg_mnist_cf_entry_args* args, pcg_stream_t stream);
+
+/* generator.py:80,82 + eval_utils.py:57,66,325,330 from conv_out's result c: raw = scale * c, masked = raw * m,
+ * x_cf = clamp(x[b] + masked, -1, 1), each product and sum rounded on its own as the reference's tensor expressions are.  x_cf is
+ * always written (rows of HW floats: the classifier's input), raw and masked only when given.  sums[q - q0] =
+ * { sum |x_cf - x|, sum |raw * m|, sum |raw * (1 - m)| } over the HW pixels: the numerators of actionability,
+ * Residual_L1_norm_in_allowed_patches and mask_penalty_pre.  One wave per query, 16-byte loads (HW % 4 == 0, 16-byte aligned
+ * pointers), the wave's partial sums combined by a fixed butterfly. */
+typedef struct pcg_mnist_cf_tail_args {
+  const float* c;          /* [nq][HW]                             */
+  const float* x;          /* [B][HW]                              */
+  const float* mask;       /* see mask_mode                        */
+  float* x_cf;             /* [nq][HW]                             */
+  float* raw; float* masked;   /* [nq][HW] or NULL                 */
+  float* sums;             /* [nq][3]                              */
+  float scale;
+  int32_t B, T, HW, mask_mode, q0, nq;
+} pcg_mnist_cf_tail_args;
+int pcg_mnist_cf_tail(const pcg_mnist_cf_tail_args* args, pcg_stream_t stream);
+
+/* eval_utils.py:58-64 (evaluate_counterfactuals) and :305-321 (compute_masked_metrics) from the classifier's logits (rows of ld >= K
+ * floats, K <= 16 read): max-subtracted softmax; pred = the first maximum (torch.argmax), conf = its probability; p_target =
+ * p_cf[target(q)], p_true = p_cf[y_true[b]], p_orig_true = softmax(logits_orig[b])[y_true[b]] (0 without logits_orig), flip =
+ * (pred == target).  Every per-query output is optional.  group_sums [T][ceil(B / group_rows)][8], optional: for group (t, j), j =
+ * b / group_rows the loader batch, over its rows inside the window in ascending b, by one workgroup:
+ *   { sum flip, max flip, sum (p_target - p_true)  [:63-64, both from the counterfactual's softmax],
+ *     sum (p_target - p_orig_true)  [:314-316; 0 without logits_orig], the three sums of pcg_mnist_cf_tail (0 without tail_sums), count }
+ * Without y_true both gains are 0.  A ragged last batch has its own count. */
+#define PCG_MNIST_CF_GROUP_SUMS 8
+typedef struct pcg_mnist_cf_score_args {
+  const float* logits_cf;     /* [nq][ld]                          */
+  const float* logits_orig;   /* [B][ld] or NULL                   */
+  const int64_t* target;      /* NULL (sweep) or [B]               */
+  const int64_t* y_true;      /* [B] or NULL                       */
+  const float* tail_sums;     /* [nq][3] or NULL                   */
+  int64_t* pred; float* conf; float* p_target; float* p_true; float* p_orig_true; float* flip;   /* [nq] or NULL */
+  float* group_sums;
+  int32_t B, T, K, ld, group_rows, q0, nq;
+} pcg_mnist_cf_score_args;
+int pcg_mnist_cf_score(const pcg_mnist_cf_score_args* args, pcg_stream_t stream);
+
 /* The scalars the tabular trainer logs per step (house_sales_kc_usa/trainer.py:292, :299, :307-312, :318-330) in one launch:
  * out5 = { D_loss = mean(d_fake) - mean(d_real), G_loss = -mean(d_fake_g) + lambda_cls*g_cls + w_reg*am + lambda_mask*pen,
  *          g_adv = -mean(d_fake_g), g_reg = w_reg_log*am, mean(d_fake_g) } — the same reduction trees and fma chains as

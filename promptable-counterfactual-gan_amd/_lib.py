@@ -108,6 +108,32 @@ class HouseCfEvalArgs(ctypes.Structure):
                                    "logits_x", "pred_cf", "pred_x", "gain", "tile_sums", "class_sums", "class_counts")])
 
 
+class PatchMaskBitsArgs(ctypes.Structure):
+    """pcg_patch_mask_bits_args."""
+    _fields_ = [("bits", _P), ("mask", _P)] + [(n, _I) for n in ("n", "H", "W", "ps")]
+
+
+class MnistCfEntryArgs(ctypes.Structure):
+    """pcg_mnist_cf_entry_args."""
+    _fields_ = [(n, _P) for n in ("x", "table", "mask", "target", "out")] + [(n, _I) for n in ("B", "T", "HW", "K", "mask_mode", "q0", "nq")]
+
+
+class MnistCfTailArgs(ctypes.Structure):
+    """pcg_mnist_cf_tail_args."""
+    _fields_ = ([(n, _P) for n in ("c", "x", "mask", "x_cf", "raw", "masked", "sums")] + [("scale", ctypes.c_float)] +
+                [(n, _I) for n in ("B", "T", "HW", "mask_mode", "q0", "nq")])
+
+
+class MnistCfScoreArgs(ctypes.Structure):
+    """pcg_mnist_cf_score_args."""
+    _fields_ = ([(n, _P) for n in ("logits_cf", "logits_orig", "target", "y_true", "tail_sums", "pred", "conf", "p_target", "p_true",
+                                   "p_orig_true", "flip", "group_sums")] + [(n, _I) for n in ("B", "T", "K", "ld", "group_rows", "q0", "nq")])
+
+
+MASK_SHARED, MASK_PER_ROW, MASK_PER_QUERY = 0, 1, 2      # PCG_MASK_* (include/pcgan_hip.h)
+MNIST_CF_GROUP_SUMS = 8                                  # PCG_MNIST_CF_GROUP_SUMS
+
+
 class MoonsGanDesc(ctypes.Structure):
     """pcg_moons_gan_desc."""
     _fields_ = ([(n, _I) for n in ("hidden", "z_dim", "label_dim", "B", "N", "nG", "nD", "nG_adam", "nD_adam")] +
@@ -208,7 +234,9 @@ STRUCTS = {"pcg_conv_geom": ConvGeom, "pcg_in_xform": InXform, "pcg_wgrad_item":
            "pcg_house_res_fwd_args": HouseResFwdArgs, "pcg_house_res_bwd_args": HouseResBwdArgs, "pcg_house_loss_args": HouseLossArgs,
            "pcg_house_diag_args": HouseDiagArgs, "pcg_moons_cf_desc": MoonsCfDesc, "pcg_moons_cf_train_args": MoonsCfTrainArgs,
            "pcg_moons_cf_fwd_args": MoonsCfFwdArgs, "pcg_moons_cf_eval_args": MoonsCfEvalArgs,
-           "pcg_house_cf_eval_args": HouseCfEvalArgs, "pcg_dense_bn": DenseBn,
+           "pcg_house_cf_eval_args": HouseCfEvalArgs, "pcg_patch_mask_bits_args": PatchMaskBitsArgs,
+           "pcg_mnist_cf_entry_args": MnistCfEntryArgs, "pcg_mnist_cf_tail_args": MnistCfTailArgs,
+           "pcg_mnist_cf_score_args": MnistCfScoreArgs, "pcg_dense_bn": DenseBn,
            "pcg_dense_bn_bwd": DenseBnBwd, "pcg_moons_gan_desc": MoonsGanDesc, "pcg_moons_gan_train_args": MoonsGanTrainArgs,
            "pcg_moons_gan_fwd_args": MoonsGanFwdArgs}
 
@@ -382,6 +410,10 @@ PROTOTYPES = {
     "pcg_house_classifier_fwd": (_i, [_c.POINTER(HouseClsFwdArgs), _c.POINTER(SnBwdBatch), _vp]),
     "pcg_house_classifier_bwd": (_i, [_c.POINTER(HouseClsBwdArgs), _c.POINTER(SnFwdBatch), _vp]),
     "pcg_house_cf_eval": (_i, [_c.POINTER(HouseGDesc), _c.POINTER(HouseCfEvalArgs), _vp]),
+    "pcg_patch_mask_bits": (_i, [_c.POINTER(PatchMaskBitsArgs), _vp]),
+    "pcg_mnist_cf_entry": (_i, [_c.POINTER(MnistCfEntryArgs), _vp]),
+    "pcg_mnist_cf_tail": (_i, [_c.POINTER(MnistCfTailArgs), _vp]),
+    "pcg_mnist_cf_score": (_i, [_c.POINTER(MnistCfScoreArgs), _vp]),
     "pcg_house_residual_fwd": (_i, [_c.POINTER(HouseResFwdArgs), _c.POINTER(SnFwdBatch), _vp]),
     "pcg_house_residual_bwd": (_i, [_c.POINTER(HouseResBwdArgs), _c.POINTER(HouseLossArgs), _c.POINTER(HouseDiagArgs), _vp]),
     "pcg_house_diag": (_i, [_c.POINTER(HouseDiagArgs), _vp]),

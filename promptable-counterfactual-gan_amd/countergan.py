@@ -42,6 +42,11 @@ class Config:
     num_modifiable_patches = 10
     img_shape = (1, 28, 28)
     num_classes = 10
+    min_modifiable_patches = 6                       # config.py:18-20: the evaluation's patch prompts
+    max_modifiable_patches = 15
+    user_input_patches = [1, 5, 10, 12, 13, 14]
+    device = "cuda"
+    save_dir = "./results"
 
 
 # ---- conv helpers on NHWC activations ------------------------------------------------------------------------------
@@ -233,7 +238,87 @@ class ResidualGenerator(FlatModule):
         self.conv_out = nn.Conv2d(base_ch, 1, kernel_size=3, padding=1)
         self.residual_scaling = residual_scaling
         self._hw = (H, W)
+        self._fold_cache = None
         self._init_weights()
+
+    # -- eval-mode BatchNorm folded into conv1 of every block (forward_queries) ----------------------------------
+    def train(self, mode=True):
+        # as CNNClassifier.train: the optimizer kernel updates parameters without touching torch's version counters
+        self._fold_cache = None
+        return super().train(mode)
+
+    def load_state_dict(self, *args, **kwargs):
+        self._fold_cache = None
+        return super().load_state_dict(*args, **kwargs)
+
+    def _apply(self, fn, *args, **kwargs):
+        self._fold_cache = None
+        return super()._apply(fn, *args, **kwargs)
+
+    def _fold_key(self):
+        ts = [t for blk in self.resblocks for t in (blk.conv1.weight, blk.conv1.bias, blk.bn1.weight, blk.bn1.bias, blk.bn1.running_mean,
+                                                    blk.bn1.running_var) if t is not None]
+        return tuple((t.data_ptr(), t._version) for t in ts)
+
+    def folded_conv1(self):
+        """Per block (w' OHWI, b') with bn1's eval-mode affine folded into conv1: w' = w * s, b' = (b - mean) * s + beta,
+        s = gamma / sqrt(var + eps) per output channel, computed in float64 and rounded once.  Cached on the module; the cache is
+        dropped by train() / eval(), load_state_dict(), .to() and any change of a parameter's or buffer's storage or version."""
+        if any(blk.bn1.training for blk in self.resblocks):
+            raise PcgError("ResidualGenerator.folded_conv1: BatchNorm in training mode has no fixed affine to fold; call .eval()")
+        key = self._fold_key()
+        if self._fold_cache is not None and self._fold_cache[0] == key:
+            return self._fold_cache[1]
+        folded = []
+        with torch.no_grad():
+            for blk in self.resblocks:
+                conv, bn = blk.conv1, blk.bn1
+                s = bn.weight.double() / torch.sqrt(bn.running_var.double() + bn.eps)
+                w = (conv.weight.permute(0, 2, 3, 1).double() * s.view(-1, 1, 1, 1)).float().contiguous()
+                b0 = conv.bias.double() if conv.bias is not None else torch.zeros_like(s)
+                folded.append((w, ((b0 - bn.running_mean.double()) * s + bn.bias.double()).float().contiguous()))
+        self._fold_cache = (key, folded)
+        return folded
+
+    @in_conv_precision
+    def forward_queries(self, x, targets, mask, mask_mode="row", T=None, q0=0, nq=None, fold_eval_bn=True, want_residuals=True, out=None):
+        """The eval-mode forward over the window [q0, q0 + nq) of the queries q = t * B + b (generator.py:71-84 + eval_utils.py:57).
+        x [B,1,H,W] / [B,HW]; targets None: the sweep, query (t, b) asks for class t of T (default num_classes), or [B] int64 with
+        T = 1; mask per mask_mode: "shared" [HW], "row" [B][HW], "query" [T*B][HW] — neither x nor the mask is replicated.
+        One entry launch, the convolutions, one tail launch.  bn1 of every block runs folded into conv1's weights and LeakyReLU
+        epilogue (fold_eval_bn=False: the conv + bn_apply_act chain of _run_forward); bn2 + skip stays one bn_apply_act pass.
+        Returns {"x_cf" [nq,HW], "raw", "masked" ([nq,HW] or None), "sums" [nq,3]: sum |x_cf - x|, |raw * m|, |raw * (1 - m)|};
+        `out`: preallocated tensors under those names."""
+        if self.training or any(blk.bn1.training or blk.bn2.training for blk in self.resblocks):
+            raise PcgError("ResidualGenerator.forward_queries is the eval-mode forward: call .eval() first")
+        if not (torch.is_tensor(x) and x.is_cuda):
+            raise PcgError(f"ResidualGenerator.forward_queries: x is on {getattr(x, 'device', type(x))}; libpcgan_hip has no CPU path")
+        self._ensure_flat()
+        H, W = self._hw
+        B = x.shape[0]
+        xr = _as_rows(x, B)
+        if xr.shape[1] != H * W:
+            raise PcgError(f"x: expected {H * W} pixels per row, got shape {tuple(x.shape)}")
+        T = (self.embed.num_embeddings if targets is None else 1) if T is None else int(T)
+        slope = float(self.act.negative_slope)
+        if not torch.is_tensor(mask):
+            raise PcgError("ResidualGenerator.forward_queries: a mask tensor is required")
+        mk = mask.contiguous()
+        inp = ops.mnist_cf_entry(xr, targets, self.embed.weight.data, mk, mask_mode, T, q0, nq)
+        n = inp.shape[0]
+        h = _conv_fwd(self.conv_in, inp.view(n, H, W, 3), ACT_LRELU, slope)[1]
+        folded = self.folded_conv1() if fold_eval_bn else None
+        for i, blk in enumerate(self.resblocks):
+            if folded is not None:
+                a1 = ops.conv2d_fwd(_geom(blk.conv1, n, H, W), h, folded[i][0], folded[i][1], act=ACT_LRELU, slope=slope)
+            else:
+                a1 = self._conv_bn(blk.conv1, blk.bn1, h, ACT_LRELU, slope)[2]
+            h = self._conv_bn(blk.conv2, blk.bn2, a1, ACT_NONE, 0.0, residual=h, alpha=0.1)[2]                     # x + 0.1*out (:20)
+        hm = _conv_fwd(self.conv_mid, h, ACT_LRELU, slope)[1]
+        c = _conv_fwd(self.conv_out, hm)[1]
+        x_cf, raw, masked, sums = ops.mnist_cf_tail(c.view(n, H * W), xr, mk, mask_mode, self.residual_scaling, T, q0, n,
+                                                    want_residuals=want_residuals, out=out)
+        return {"x_cf": x_cf, "raw": raw, "masked": masked, "sums": sums}
 
     def _init_weights(self):
         """generator.py:58-69."""
@@ -919,3 +1004,370 @@ def train_countergan(generator, discriminator, classifier, train_loader, cfg, de
         if verbose:
             print(f"Generator saved to {cfg.generator_path}")
     return hist
+
+
+# ---- the promptable half: patch prompts, queries and per-target evaluation (eval_utils.py, gradio_app.py:234-259) ----
+SUM_FIELDS = ("flips", "flip_max", "gain_cf", "gain_orig", "abs_change", "abs_allowed", "abs_forbidden", "count")   # pcg_mnist_cf_score's group sums
+PER_CLASS_FIELDS = ("class_flip_rate", "prediction_gain", "actionability")
+MASKED_METRIC_KEYS = ("Class_flip_rate_mean", "Class_flip_rate_max", "Residual_L1_norm_in_allowed_patches", "Prediction_gain",
+                      "Actionability (overall L1 norm)", "mask_penalty_pre")
+
+
+def patch_bits(patches, total):
+    """One 64-bit word (as a signed Python int, the value an int64 tensor holds) with bit p set for every patch p of `patches` inside
+    [0, total); an index outside is ignored, as create_mask_from_indices does (eval_utils.py:251-252)."""
+    if not 1 <= total <= 64:
+        raise PcgError(f"patch_bits: {total} patches do not fit a 64-bit word")
+    word = 0
+    for p in patches:
+        p = int(p)
+        if 0 <= p < total:
+            word |= 1 << p
+    return word - (1 << 64) if word >= 1 << 63 else word
+
+
+def _patch_grid(H, W, patch_size):
+    patch_size = int(patch_size)
+    if patch_size < 1 or H // patch_size < 1 or W // patch_size < 1:
+        raise PcgError(f"patch size {patch_size} gives no patch on a {H} x {W} image")
+    return H // patch_size, W // patch_size
+
+
+def _masks_from_lists(lists, H, W, patch_size, device):
+    """[len(lists), 1, H, W] masks on the GPU from lists of patch indices: the host packs bits, the device expands them
+    (pcg_patch_mask_bits).  More than 64 patches do not fit a word: those masks are built on the host and uploaded."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise PcgError(f"patch masks are built on the GPU, got device {device}; libpcgan_hip has no CPU path")
+    nph, npw = _patch_grid(H, W, patch_size)
+    total = nph * npw
+    if total <= 64:
+        bits = torch.tensor([patch_bits(c, total) for c in lists], dtype=torch.int64).to(device)
+        return ops.patch_mask_bits(bits, H, W, patch_size)
+    import numpy as np
+    m = np.zeros((len(lists), 1, H, W), np.float32)
+    for r, chosen in enumerate(lists):
+        for idx in chosen:
+            if 0 <= idx < total:
+                i, j = divmod(int(idx), npw)
+                m[r, 0, i * patch_size:(i + 1) * patch_size, j * patch_size:(j + 1) * patch_size] = 1.0
+    return torch.from_numpy(m).to(device)
+
+
+def choose_patches(bs, total_patches, shared_per_batch=False, modifiable_patches=None, randomize_per_sample=True, min_patches=5,
+                   max_patches=None):
+    """The patch selection of build_patch_mask_for_batch (eval_utils.py:239-282) on the host, with the same np.random calls in the
+    same order: one list for a shared mask, else one per sample.  Pure host."""
+    import numpy as np
+    if max_patches is None:
+        max_patches = total_patches // 2                                                       # :240-241
+    min_patches = max(1, int(min_patches))
+    max_patches = min(total_patches, int(max_patches))
+    if min_patches > max_patches:
+        min_patches = max_patches
+    use_random = (modifiable_patches is None) or randomize_per_sample                          # :260
+
+    def draw():
+        if not use_random:
+            return list(modifiable_patches)                                                    # :269, :281
+        k = np.random.randint(min_patches, max_patches + 1)                                    # :265, :277
+        return np.random.choice(range(total_patches), size=k, replace=False).tolist()          # :266, :278
+    return [draw() for _ in range(1 if shared_per_batch else bs)]
+
+
+def build_patch_mask_for_batch(x, patch_size=5, device=None, shared_per_batch=False, modifiable_patches=None, return_single_mask=True,
+                               randomize_per_sample=True, min_patches=5, max_patches=None):
+    """eval_utils.py:204-288, the reference's signature and draws (choose_patches); the masks are expanded on the GPU.  Returns
+    (batch_mask [B,C,H,W], single_mask [1,C,H,W]) or batch_mask; a shared mask and C > 1 are broadcast views, not copies."""
+    device = x.device if device is None else device
+    bs, C, H, W = x.shape
+    nph, npw = _patch_grid(H, W, patch_size)
+    chosen = choose_patches(bs, nph * npw, shared_per_batch, modifiable_patches, randomize_per_sample, min_patches, max_patches)
+    masks = _masks_from_lists(chosen, H, W, patch_size, device)
+    batch_mask = masks.expand(bs, C, H, W)
+    single_mask = masks[0:1].expand(1, C, H, W)
+    return (batch_mask, single_mask) if return_single_mask else batch_mask
+
+
+def make_mask_from_patch_list(x_batch, patch_size, allowed_patches, device=None):
+    """gradio_app.py:234-240: the single mask [1,C,H,W] of a user's patch list."""
+    return build_patch_mask_for_batch(x_batch, patch_size=patch_size, device=device, shared_per_batch=True, modifiable_patches=allowed_patches,
+                                      return_single_mask=True, randomize_per_sample=False)[1]
+
+
+def _padded_logits(classifier, rows, out=None):
+    """The frozen classifier's logits [n, kp] (kp = num_classes padded to a multiple of 4) of image rows [n, 784]: CNNClassifier's
+    eval forward with the padded columns kept (the score kernel reads rows of kp floats) and an optional destination."""
+    with ops.conv_precision(classifier.conv_precision):
+        cw, w1, b1, w2, b2, kp = classifier._pack()
+        n = rows.shape[0]
+        a = rows.view(n, 28, 28, 1)
+        for conv, w, b in cw:
+            a = ops.conv2d_fwd(_geom(conv, n, a.shape[1], a.shape[2]), a, w, b, act=ACT_RELU)
+        feat = a.numel() // n
+        h = ops.conv2d_fwd(ops.conv_geom(n, 1, 1, feat, w1.shape[0], 1, 1, 1, 0), a.view(n, 1, 1, feat), w1, b1, act=ACT_RELU)
+        logits = ops.conv2d_fwd(ops.conv_geom(n, 1, 1, w1.shape[0], kp, 1, 1, 1, 0), h, w2, b2, out=out)
+    return logits.view(n, kp)
+
+
+def _prompt_mask(x, T, patches, mask, patch_size):
+    """(mask tensor, mask_mode, the mask in the shape the caller gets back) from a patch prompt or a dense mask."""
+    B, H, W = x.shape[0], x.shape[-2], x.shape[-1]
+    HW = H * W
+    if patches is not None and mask is not None:
+        raise PcgError("give the prompt as `patches` or as `mask`, not both")
+    if patches is not None:
+        patches = list(patches)
+        per_row = len(patches) > 0 and isinstance(patches[0], (list, tuple))
+        if per_row and len(patches) != B:
+            raise PcgError(f"patches: {len(patches)} lists for {B} rows")
+        m = _masks_from_lists(patches if per_row else [patches], H, W, patch_size, x.device)
+        return m, ("row" if per_row else "shared"), m
+    if mask is None:                                       # no prompt: every pixel may change (eval_utils.py:55)
+        m = torch.empty((1, 1, H, W), dtype=torch.float32, device=x.device)
+        ops.fill(m, 1.0)
+        return m, "shared", m
+    if not torch.is_tensor(mask) or not mask.is_cuda:
+        raise PcgError(f"mask: expected a tensor on the GPU, got {getattr(mask, 'device', type(mask))}")
+    modes = {}                                             # the smaller reading wins where two sizes coincide (B == 1 or T == 1)
+    for n, v in ((T * B * HW, ("query", (T, B, 1, H, W))), (B * HW, ("row", (B, 1, H, W))), (HW, ("shared", (1, 1, H, W)))):
+        modes[n] = v
+    if mask.numel() not in modes or mask.shape[-1] != W:
+        raise PcgError(f"mask: expected {HW} (shared), {B * HW} (per row) or {T * B * HW} (per query) values of [.., {H}, {W}], got {tuple(mask.shape)}")
+    mode, shape = modes[mask.numel()]
+    m = mask.contiguous()
+    return m, mode, m.view(shape)
+
+
+def _run_queries(generator, classifier, x, targets, T, m, mode, y_true=None, group_rows=None, query_chunk=2048, keep=True, with_orig=True,
+                 fold_eval_bn=True, outputs=ops.SCORE_FIELDS):
+    """All T * B queries of a batch: generator + classifier over windows of `query_chunk` queries, then ONE score launch."""
+    if not (torch.is_tensor(x) and x.is_cuda):
+        raise PcgError(f"x is on {getattr(x, 'device', type(x))}; libpcgan_hip has no CPU path")
+    if int(query_chunk) < 1:
+        raise PcgError(f"query_chunk {query_chunk}")
+    B = x.shape[0]
+    xr = _as_rows(x, B)
+    HW, K, TB, dev = xr.shape[1], classifier.num_classes, T * B, x.device
+    kp = (K + 3) // 4 * 4
+    f32 = dict(dtype=torch.float32, device=dev)
+    logits, sums = torch.empty((TB, kp), **f32), torch.empty((TB, 3), **f32)
+    full = {k: torch.empty((TB, HW), **f32) for k in ("x_cf", "raw", "masked")} if keep else None
+    for q0 in range(0, TB, int(query_chunk)):
+        nq = min(int(query_chunk), TB - q0)
+        out = {"sums": sums[q0:q0 + nq]}
+        if keep:
+            out.update({k: v[q0:q0 + nq] for k, v in full.items()})
+        r = generator.forward_queries(xr, targets, m, mode, T=T, q0=q0, nq=nq, fold_eval_bn=fold_eval_bn, want_residuals=keep, out=out)
+        _padded_logits(classifier, r["x_cf"], out=logits[q0:q0 + nq])
+    logits_orig = _padded_logits(classifier, xr) if (with_orig and y_true is not None) else None
+    res = ops.mnist_cf_score(logits, K, B, T, target=targets, y_true=y_true, logits_orig=logits_orig, tail_sums=sums, group_rows=group_rows,
+                             outputs=outputs)
+    res.update(sums=sums, logits=logits)
+    if keep:
+        res.update(full)
+    return res
+
+
+def _labels(v, B, device, name):
+    if v is None:
+        return None
+    t = torch.full((B,), int(v), dtype=torch.int64) if not torch.is_tensor(v) else v.reshape(-1).to(torch.int64)
+    if t.numel() != B:
+        raise PcgError(f"{name}: expected {B} labels, got {t.numel()}")
+    return t.to(device).contiguous()
+
+
+def counterfactuals(generator, classifier, x, target, patches=None, mask=None, patch_size=Config.patch_size, query_chunk=2048, y_true=None):
+    """The prompted query (gradio_app.py:242-259 run_transformation / eval_utils.py:498-530 without the plot): "turn these images
+    into `target` (an int or one class per row), touching only `patches`" — a list of patch indices for every row, one list per row,
+    or a dense `mask`; neither: every pixel may change.  Both nets must be in eval mode.  Returns device tensors: x_cf, raw_residual,
+    masked_residual [B,1,H,W], mask (as used), pred (int64), conf, p_target, p_true / p_orig_true (with y_true) [B], and sums [B,3]:
+    sum |x_cf - x|, sum |raw * mask|, sum |raw * (1 - mask)| over the pixels."""
+    if not (torch.is_tensor(x) and x.is_cuda and x.dim() == 4):
+        raise PcgError(f"x: expected a [B,1,H,W] tensor on the GPU, got {getattr(x, 'device', type(x))}")
+    B, _, H, W = x.shape
+    m, mode, m_out = _prompt_mask(x, 1, patches, mask, patch_size)
+    res = _run_queries(generator, classifier, x, _labels(target, B, x.device, "target"), 1, m, mode, y_true=_labels(y_true, B, x.device, "y_true"),
+                       query_chunk=query_chunk)
+    shp = (B, 1, H, W)
+    out = {"x_cf": res["x_cf"].view(shp), "raw_residual": res["raw"].view(shp), "masked_residual": res["masked"].view(shp), "mask": m_out,
+           "sums": res["sums"], "group_sums": res["group_sums"]}
+    out.update({k: res[k] for k in ops.SCORE_FIELDS})
+    return out
+
+
+def counterfactual_sweep(generator, classifier, x, y_true=None, patches=None, mask=None, patch_size=Config.patch_size, query_chunk=2048,
+                         group_rows=None):
+    """counterfactuals() for ALL num_classes targets of every row in one pass: results shaped [T,B,...] (x_cf, raw_residual,
+    masked_residual [T,B,1,H,W]; pred ... flip [T,B]; sums [T,B,3]) and group_sums [T, ceil(B / group_rows), 8] (SUM_FIELDS)."""
+    if not (torch.is_tensor(x) and x.is_cuda and x.dim() == 4):
+        raise PcgError(f"x: expected a [B,1,H,W] tensor on the GPU, got {getattr(x, 'device', type(x))}")
+    B, _, H, W = x.shape
+    T = generator.embed.num_embeddings
+    m, mode, m_out = _prompt_mask(x, T, patches, mask, patch_size)
+    res = _run_queries(generator, classifier, x, None, T, m, mode, y_true=_labels(y_true, B, x.device, "y_true"), group_rows=group_rows,
+                       query_chunk=query_chunk)
+    shp = (T, B, 1, H, W)
+    out = {"x_cf": res["x_cf"].view(shp), "raw_residual": res["raw"].view(shp), "masked_residual": res["masked"].view(shp), "mask": m_out,
+           "sums": res["sums"].view(T, B, 3), "group_sums": res["group_sums"]}
+    out.update({k: res[k].view(T, B) for k in ops.SCORE_FIELDS})
+    return out
+
+
+def metrics_from_sums(sums, hw):
+    """Pure host.  Group sums [..., 8] (SUM_FIELDS) -> the per-group means in float64: class_flip_rate, class_flip_max, prediction_gain
+    (eval_utils.py:63-64, both probabilities from the counterfactual's softmax), prediction_gain_orig (:314-316), actionability,
+    allowed_l1, mask_penalty_pre (per pixel) and count.  An empty group gives nan."""
+    import numpy as np
+    s = np.asarray(sums, np.float64)
+    if s.shape[-1] != len(SUM_FIELDS):
+        raise PcgError(f"metrics_from_sums: expected [..., {len(SUM_FIELDS)}] sums, got {s.shape}")
+    n = s[..., 7]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        rows, pix = np.where(n > 0, n, np.nan), np.where(n > 0, n, np.nan) * float(hw)
+        return {"class_flip_rate": s[..., 0] / rows, "class_flip_max": np.where(n > 0, s[..., 1], np.nan), "prediction_gain": s[..., 2] / rows,
+                "prediction_gain_orig": s[..., 3] / rows, "actionability": s[..., 4] / pix, "allowed_l1": s[..., 5] / pix,
+                "mask_penalty_pre": s[..., 6] / pix, "count": n}
+
+
+def fold_groups(group_sums, hw):
+    """Pure host.  [T][J][8] group sums (J loader batches) -> per target the mean over the batches of the per-batch means, the order
+    of eval_utils.py:97-102 (a ragged last batch weighs as much as a full one), in float64.  Empty groups are left out."""
+    import numpy as np
+    per = metrics_from_sums(group_sums, hw)
+    if per["count"].ndim != 2:
+        raise PcgError(f"fold_groups: expected [T][J][8] sums, got {np.asarray(group_sums).shape}")
+    live = per["count"] > 0
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return {k: np.where(live, v, 0.0).sum(axis=1) / live.sum(axis=1) for k, v in per.items() if k != "count"}
+
+
+def compute_masked_metrics(raw_residual, masked_residual, x, x_cf, mask, classifier, y_true, y_target, device=None):
+    """eval_utils.py:292-344, the reference's signature and six keys.  The sums over the allowed and the forbidden pixels come from
+    the tail kernel on `raw_residual`, the flip rate and the prediction gain (p_cf[target] - p_orig[y_true], :314-316) from the score
+    kernel; two host reads."""
+    B = x.shape[0]
+    xr, rr = _as_rows(x, B), _as_rows(raw_residual, B)
+    HW = xr.shape[1]
+    mr = mask if mask.numel() == HW else _as_rows(mask, B)
+    _, _, _, sums = ops.mnist_cf_tail(rr, xr, mr.contiguous(), "shared" if mask.numel() == HW else "row", 1.0, want_residuals=False)
+    xc = _as_rows(x_cf, B)
+    res = ops.mnist_cf_score(_padded_logits(classifier, xc), classifier.num_classes, B, 1, target=_labels(y_target, B, x.device, "y_target"),
+                             y_true=_labels(y_true, B, x.device, "y_true"), logits_orig=_padded_logits(classifier, xr), tail_sums=sums, outputs=())
+    m = metrics_from_sums(res["group_sums"].cpu().numpy()[0, 0], HW)
+    actionability = abs_mean(ops.axpby(1.0, xc, -1.0, xr)).item()                                                   # :335, of the x_cf given
+    return dict(zip(MASKED_METRIC_KEYS, (float(m["class_flip_rate"]), float(m["class_flip_max"]), float(m["allowed_l1"]),
+                                         float(m["prediction_gain_orig"]), actionability, float(m["mask_penalty_pre"]))))
+
+
+def per_class_csv(avg_results, fields=PER_CLASS_FIELDS):
+    """The text of DataFrame.from_dict(avg_results, orient="index").to_csv() (eval_utils.py:104-107): an empty first header cell, one
+    row per target class, floats in their shortest repr."""
+    lines = ["," + ",".join(fields)]
+    for cls in avg_results:
+        lines.append(f"{cls}," + ",".join(repr(float(avg_results[cls][f])) for f in fields))
+    return "\n".join(lines) + "\n"
+
+
+def evaluate_generator_per_target(generator, classifier, test_loader, config, one_pass=True, query_chunk=2048, fold_eval_bn=True, verbose=True):
+    """eval_utils.py:78-110: class flip rate, prediction gain and actionability per target class, the mean over the loader's batches of
+    the per-batch means; countergan_metrics_per_class.csv under config.save_dir.  one_pass: all num_classes targets of a loader batch
+    in ONE generator pass (chunked by query_chunk) with the all-ones mask shared, the sums read once at the end; one_pass=False: one
+    evaluate_counterfactuals call per (batch, target), the reference's own loop.  Host arithmetic in float64.  Returns
+    {target class: {metric: value}}."""
+    import numpy as np
+    device, T = torch.device(config.device), config.num_classes
+    generator.eval(); classifier.eval()                                                                             # :81-82
+    if one_pass:
+        ones, groups = None, []
+        with torch.no_grad():
+            for x, y in test_loader:                                                                                    # :87
+                x, y = x.to(device), y.to(device)
+                B = x.shape[0]
+                if ones is None:
+                    ones = torch.empty(x[0].numel(), dtype=torch.float32, device=device)
+                    ops.fill(ones, 1.0)
+                res = _run_queries(generator, classifier, x, None, T, ones, "shared", y_true=_labels(y, B, device, "y"), group_rows=B,
+                                   query_chunk=query_chunk, keep=False, with_orig=False, fold_eval_bn=fold_eval_bn, outputs=())
+                groups.append(res["group_sums"])
+        if not groups:
+            raise PcgError("evaluate_generator_per_target: the loader yielded no batch")
+        sums = np.stack([g.cpu().numpy()[:, 0, :] for g in groups], axis=1)                                             # [T][J][8]
+        folded = fold_groups(sums, ones.numel())
+        avg_results = {cls: {k: float(folded[k][cls]) for k in PER_CLASS_FIELDS} for cls in range(T)}
+    else:
+        results = {cls: {k: [] for k in PER_CLASS_FIELDS} for cls in range(T)}
+        for x, y in test_loader:
+            x, y = x.to(device), y.to(device)
+            for cls in range(T):                                                                                        # :91-95
+                metrics, _ = evaluate_counterfactuals(generator, classifier, x, y, torch.full_like(y, cls), device)
+                for k in PER_CLASS_FIELDS:
+                    results[cls][k].append(metrics[k])
+        avg_results = {cls: {k: float(np.mean(np.asarray(v, np.float64))) for k, v in m.items()} for cls, m in results.items()}   # :98-102
+    if getattr(config, "save_dir", None):
+        os.makedirs(config.save_dir, exist_ok=True)
+        csv_path = os.path.join(config.save_dir, "countergan_metrics_per_class.csv")
+        with open(csv_path, "w") as f:
+            f.write(per_class_csv(avg_results))
+        if verbose:
+            print(f"Saved per-class CounterGAN metrics to {csv_path}")
+    if verbose:
+        print(per_class_csv(avg_results), end="")
+    return avg_results
+
+
+def evaluate_classifier(classifier, dataloader, device, save_dir=None, prefix="classifier", verbose=True):
+    """eval_utils.py:15-43 without the heat map: accuracy and confusion matrix [true][pred] over the loader; the predictions are the
+    score kernel's first maxima, read once at the end.  With save_dir the matrix goes to <prefix>_confusion_matrix.csv."""
+    import numpy as np
+    classifier.eval()
+    K = classifier.num_classes
+    preds, labels = [], []
+    with torch.no_grad():
+        for x, y in dataloader:
+            x = x.to(device)
+            B = x.shape[0]
+            preds.append(ops.mnist_cf_score(_padded_logits(classifier, _as_rows(x, B)), K, B, 1, target=None, outputs=("pred",), group_sums=False)["pred"])
+            labels.append(y)
+    if not preds:
+        raise PcgError("evaluate_classifier: the loader yielded no batch")
+    all_preds = np.concatenate([p.cpu().numpy() for p in preds])
+    all_labels = np.concatenate([np.asarray(t.cpu().numpy(), np.int64).reshape(-1) for t in labels])
+    acc = float((all_preds == all_labels).mean())
+    cm = np.zeros((K, K), np.int64)
+    np.add.at(cm, (all_labels, all_preds), 1)
+    if save_dir:
+        os.makedirs(save_dir, exist_ok=True)
+        with open(os.path.join(save_dir, f"{prefix}_confusion_matrix.csv"), "w") as f:
+            f.write("," + ",".join(f"pred_{j}" for j in range(K)) + "\n")
+            for i in range(K):
+                f.write(f"true_{i}," + ",".join(str(int(v)) for v in cm[i]) + "\n")
+    if verbose:
+        print(f"{prefix} Test Accuracy: {acc:.4f}")
+    return acc, cm
+
+
+def evaluate_pipeline(generator, classifier, full_dataset, test_loader, config, verbose=True):
+    """eval_utils.py:572-647, the live lines (:577-610, :643): a patch prompt per sample of the first test batch, targets that differ
+    from the labels, the counterfactuals, evaluate_counterfactuals on that batch (countergan_metrics.csv) and the per-target table.
+    The plots (cf_grid.png, the heat maps) are left out; `full_dataset` is what they would read.  Returns (metrics, per-target table)."""
+    device = torch.device(config.device)
+    x, y = next(iter(test_loader))                                                                                  # :577
+    x, y = x.to(device), y.to(device)
+    batch_mask, single_mask = build_patch_mask_for_batch(                                                           # :585-595
+        x, patch_size=config.patch_size, device=device, shared_per_batch=False, modifiable_patches=None, return_single_mask=True,
+        randomize_per_sample=(config.user_input_patches is None), min_patches=config.min_modifiable_patches,
+        max_patches=config.max_modifiable_patches)
+    y_target = torch.randint(0, config.num_classes, y.shape, device=device)                                         # :598
+    y_target[y_target == y] = (y_target[y_target == y] + 1) % config.num_classes                                    # :599
+    generate_counterfactuals(generator, classifier, x, y, y_target, batch_mask.contiguous(), device)                # :602-604
+    metrics_without_mask = evaluate_counterfactuals(generator, classifier, x, y, y_target, device)[0]               # :609
+    table = evaluate_generator_per_target(generator, classifier, test_loader, config, verbose=verbose)              # :610
+    os.makedirs(config.save_dir, exist_ok=True)
+    path = os.path.join(config.save_dir, "countergan_metrics.csv")
+    with open(path, "w") as f:
+        f.write(per_class_csv({0: metrics_without_mask}))                                                           # :643
+    if verbose:
+        print(f"Countergan metrics: {metrics_without_mask}\nSaved to: {path}")
+    return metrics_without_mask, table

@@ -1705,3 +1705,124 @@ def calibrate(device, mfma_ms=20.0, copy_mb=512, rounds=2, warm_ms=30.0):
         times.append(e[0].elapsed_time(e[1]))
     out["hbm_gbs"] = round(2.0 * n / (min(times[1:]) * 1e-3) / 1e9, 1)
     return out
+
+
+# ---- MNIST CounteRGAN: prompted queries and per-target evaluation (csrc/mnist_cf_eval.hip) ------------------------
+MASK_MODES = {"shared": _lib.MASK_SHARED, "row": _lib.MASK_PER_ROW, "query": _lib.MASK_PER_QUERY}
+
+
+def _mask_mode(mask, mode, B, T, HW):
+    """The PCG_MASK_* code of `mode`, after checking that `mask` holds what that mode reads."""
+    if mode not in MASK_MODES:
+        raise _lib.PcgError(f"mask_mode {mode!r} is not one of {sorted(MASK_MODES)}")
+    want = {"shared": HW, "row": B * HW, "query": T * B * HW}[mode]
+    _chk(mask, "mask")
+    if mask.numel() != want:
+        raise _lib.PcgError(f"mask: mask_mode {mode!r} reads {want} values ({B} rows x {T} targets of {HW} pixels), got shape {tuple(mask.shape)}")
+    return MASK_MODES[mode]
+
+
+def _window(B, T, q0, nq):
+    nq = T * B - q0 if nq is None else nq
+    if q0 < 0 or nq < 1 or q0 + nq > T * B:
+        raise _lib.PcgError(f"query window [{q0}, {q0} + {nq}) is not inside the {T} x {B} queries")
+    return int(q0), int(nq)
+
+
+def _targets(target, B, T, K):
+    if target is None:
+        if not 1 <= T <= K:
+            raise _lib.PcgError(f"the sweep form takes 1 <= T <= {K} target classes, got {T}")
+        return None
+    _chk_idx(target, K, "target")
+    if T != 1 or target.numel() != B:
+        raise _lib.PcgError(f"the per-row form takes T = 1 and one target per row ({B}), got T = {T} and {target.numel()} targets")
+    return target
+
+
+def patch_mask_bits(bits, H, W, ps):
+    """bits [n] int64 on the GPU (bit p = patch p is modifiable) -> masks [n, 1, H, W] of whole ps x ps patches."""
+    _chk(bits, "bits", torch.int64)
+    n = bits.numel()
+    if ps < 1 or H // ps < 1 or W // ps < 1:
+        raise _lib.PcgError(f"patch size {ps} gives no patch on a {H} x {W} image")
+    mask = torch.empty((n, 1, H, W), dtype=torch.float32, device=bits.device)
+    a = _lib.PatchMaskBitsArgs(bits.data_ptr(), mask.data_ptr(), n, H, W, ps)
+    check(_lib.load().pcg_patch_mask_bits(ctypes.byref(a), _stream()), "pcg_patch_mask_bits")
+    return mask
+
+
+def mnist_cf_entry(x, target, table, mask, mask_mode, T=1, q0=0, nq=None):
+    """[nq, HW, 3] with channels (x[b], table[target(q)], mask[row(q)]) for the queries q = t * B + b of the window; x [B, HW]."""
+    _chk(x, "x"); _chk(table, "table")
+    K, HW = table.shape
+    B = x.numel() // HW
+    target = _targets(target, B, T, K)
+    mode = _mask_mode(mask, mask_mode, B, T, HW)
+    q0, nq = _window(B, T, q0, nq)
+    out = torch.empty((nq, HW, 3), dtype=torch.float32, device=x.device)
+    a = _lib.MnistCfEntryArgs(x.data_ptr(), table.data_ptr(), mask.data_ptr(), target.data_ptr() if target is not None else None,
+                              out.data_ptr(), B, T, HW, K, mode, q0, nq)
+    check(_lib.load().pcg_mnist_cf_entry(ctypes.byref(a), _stream()), "pcg_mnist_cf_entry")
+    return out
+
+
+def mnist_cf_tail(c, x, mask, mask_mode, scale, T=1, q0=0, nq=None, want_residuals=True, out=None):
+    """conv_out's result c [nq, HW] -> (x_cf [nq, HW], raw, masked ([nq, HW] or None), sums [nq, 3]); `out`: a dict of preallocated
+    tensors under those names (a given "raw" / "masked" is written whatever want_residuals says)."""
+    _chk(c, "c"); _chk(x, "x")
+    nq_c = c.shape[0]
+    HW = c.numel() // nq_c
+    B = x.numel() // HW
+    mode = _mask_mode(mask, mask_mode, B, T, HW)
+    q0, nq = _window(B, T, q0, nq_c if nq is None else nq)
+    if nq != nq_c:
+        raise _lib.PcgError(f"c holds {nq_c} queries, the window {nq}")
+    out = dict(out or {})
+
+    def buf(name, shape, need=True):
+        t = out.get(name)
+        if t is None:
+            return torch.empty(shape, dtype=torch.float32, device=c.device) if need else None
+        _chk(t, name)
+        if t.numel() != shape[0] * shape[1]:
+            raise _lib.PcgError(f"out[{name!r}]: expected {shape[0] * shape[1]} values, got shape {tuple(t.shape)}")
+        return t
+    x_cf, sums = buf("x_cf", (nq, HW)), buf("sums", (nq, 3))
+    raw, masked = buf("raw", (nq, HW), want_residuals), buf("masked", (nq, HW), want_residuals)
+    a = _lib.MnistCfTailArgs(c.data_ptr(), x.data_ptr(), mask.data_ptr(), x_cf.data_ptr(), raw.data_ptr() if raw is not None else None,
+                             masked.data_ptr() if masked is not None else None, sums.data_ptr(), float(scale), B, T, HW, mode, q0, nq)
+    check(_lib.load().pcg_mnist_cf_tail(ctypes.byref(a), _stream()), "pcg_mnist_cf_tail")
+    return x_cf, raw, masked, sums
+
+
+SCORE_FIELDS = ("pred", "conf", "p_target", "p_true", "p_orig_true", "flip")
+
+
+def mnist_cf_score(logits_cf, K, B, T=1, target=None, y_true=None, logits_orig=None, tail_sums=None, group_rows=None, q0=0, nq=None,
+                   outputs=SCORE_FIELDS, group_sums=True):
+    """logits_cf [nq, ld] (ld >= K) -> {name: [nq] tensor for name in outputs} (+ "group_sums" [T, ceil(B / group_rows), 8])."""
+    _chk(logits_cf, "logits_cf")
+    nq_l, ld = logits_cf.shape
+    target = _targets(target, B, T, K)
+    q0, nq = _window(B, T, q0, nq_l if nq is None else nq)
+    if nq != nq_l:
+        raise _lib.PcgError(f"logits_cf holds {nq_l} queries, the window {nq}")
+    if y_true is not None and (_chk_idx(y_true, K, "y_true").numel() != B):
+        raise _lib.PcgError(f"y_true: expected {B} labels, got {y_true.numel()}")
+    if logits_orig is not None and (tuple(_chk(logits_orig, "logits_orig").shape) != (B, ld) or y_true is None):
+        raise _lib.PcgError(f"logits_orig: expected [{B}, {ld}] and y_true, got {tuple(logits_orig.shape)}")
+    if tail_sums is not None and _chk(tail_sums, "tail_sums").numel() != nq * 3:
+        raise _lib.PcgError(f"tail_sums: expected [{nq}, 3], got {tuple(tail_sums.shape)}")
+    group_rows = B if group_rows is None else int(group_rows)
+    if group_rows < 1:
+        raise _lib.PcgError(f"group_rows {group_rows}")
+    dev = logits_cf.device
+    res = {n: torch.empty(nq, dtype=torch.int64 if n == "pred" else torch.float32, device=dev) for n in outputs}
+    if group_sums:
+        res["group_sums"] = torch.empty((T, (B + group_rows - 1) // group_rows, _lib.MNIST_CF_GROUP_SUMS), dtype=torch.float32, device=dev)
+    ptr = lambda t: t.data_ptr() if t is not None else None     # noqa: E731
+    a = _lib.MnistCfScoreArgs(logits_cf.data_ptr(), ptr(logits_orig), ptr(target), ptr(y_true), ptr(tail_sums),
+                              *(ptr(res.get(n)) for n in SCORE_FIELDS), ptr(res.get("group_sums")), B, T, K, ld, group_rows, q0, nq)
+    check(_lib.load().pcg_mnist_cf_score(ctypes.byref(a), _stream()), "pcg_mnist_cf_score")
+    return res
