@@ -1031,6 +1031,8 @@ int pcg_dp_shutdown(void);
  *                       col2im, -1 whichever has fewer multiply-adds for the geometry (built-in)
  *   "t64"               forward launches with at most 256 tiles of 128x128: 64x128 tiles instead (default 1), 0 keeps 128x128
  *   "fwd_splits"        forward K-slices
+ *   "wgrad_pixtab"      weight-gradient x gather: 1 pixels from the geometry's registered descriptor table (default), 0 derived per
+ *                       k-tile (the environment variable PCG_WGRAD_PIXTAB=0 does the same for a whole process)
  * value -1 restores the built-in choice.  Results stay correct under every setting (the order of a sum changes, not its terms). */
 int pcg_tune_set(const char* name, int32_t value);
 
@@ -1053,6 +1055,21 @@ int pcg_conv_set_scratch(pcg_stream_t stream, void* parts, size_t parts_bytes, v
  * kernels leave the counters zero only when every range of a launch ran).  The registry is keyed by (current device, stream): the
  * default stream has the same handle on every device.  No-op for a stream without scratch.                                      */
 int pcg_conv_reset_scratch(pcg_stream_t stream);
+/* ---- pixel descriptor table of a convolution geometry (csrc/conv_pixtab.h) ------------------------------------------------------------
+ * The weight gradient contracts over output pixels; where the x gather of pixel (oh, ow) starts and which taps fall inside the input
+ * depends on (IH, IW, OH, OW, stride, pad, KH, KW, Cin) only — not on B, Cout, the data or the weights.  The table holds, per output
+ * pixel of ONE image, {int32 byte offset of input pixel (oh*stride - pad, ow*stride - pad) inside the image (may be negative), uint32
+ * mask with bit kh*KW + kw set for every tap inside the input}, followed by 7 entries that continue into the next images (a wave reads
+ * the descriptors of 8 consecutive pixels as one run).  pcg_conv_pixtab_bytes: size of the table.  pcg_conv_pixtab_register:
+ *   host_out != NULL      fill host_out (`bytes` >= the size) on the host — plain C++, no device needed;
+ *   device_table != NULL  remember device_table as THE table of this geometry on the current device: the caller has copied the
+ *                         built table there, owns the memory and keeps it alive and unchanged while it is registered;
+ *   both NULL             forget the geometry.
+ * No allocation, copy or synchronisation happens inside.  Weight-gradient launches of a registered geometry read their pixels from
+ * the table (pcg_tune_set("wgrad_pixtab", 0) keeps the loaders that derive them per k-tile); a geometry without a table runs those
+ * loaders.  Results are bit-identical either way.  The reference has no counterpart (ATen's conv backward, mnist_dcgan.py:153-173). */
+size_t pcg_conv_pixtab_bytes(const pcg_conv_geom* g);
+int pcg_conv_pixtab_register(const pcg_conv_geom* g, void* host_out, size_t bytes, const void* device_table);
 /* Diagnostic builds only (`make -C csrc stamp`, -DPCG_CLOCK_STAMP): every conv kernel block leaves {shader-clock ticks, 100 MHz
  * ticks} of its main loop at buf[2*block], buf[2*block+1] (uint64) — the clock the chip holds inside the kernel.  Returns 1 when
  * this build stamps, 0 for the shipped library (which compiles no stamp code).  buf = NULL turns it off.                        */

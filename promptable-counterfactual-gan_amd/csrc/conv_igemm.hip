@@ -13,6 +13,7 @@
 #include <string.h>
 #include <mutex>
 #include "conv_loaders.h"
+#include "conv_pixtab.h"
 #include "thin_conv.h"
 
 namespace pcg {
@@ -327,7 +328,9 @@ __global__ void __launch_bounds__(IG_THREADS, Cfg::MINW) conv_dgrad_sk_kernel(Co
   dgrad_sk_segment<Cfg, XF>(p, phases, sk, s1, tiles_per_phase, smem, rowpix);
 }
 
-template <class Cfg, bool XFA, bool XFB>   // XFA: the dy operand is a transformed activation (ConvTranspose2d layers); XFB: x is
+// XFA: the dy operand is a transformed activation (ConvTranspose2d layers); XFB: x is; TAB: the x gather reads its pixels from the
+// geometry's descriptor table (ConvP::pixtab != nullptr)
+template <class Cfg, bool XFA, bool XFB, bool TAB = false>
 __global__ void __launch_bounds__(IG_THREADS, 4) conv_wgrad_kernel(ConvP p, int ktiles_total, int ktiles_per_split, int tiles,
                                                                    int slice_major) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -350,7 +353,7 @@ __global__ void __launch_bounds__(IG_THREADS, 4) conv_wgrad_kernel(ConvP p, int 
   if (wave_id() >= 4) {
     const int tid = threadIdx.x - IG_LOADERS;
     WgradALoader<Cfg::BM, XFA> la(p, m_block, kt_begin, tid);
-    WgradBLoader<Cfg::BN, XFB> lb(p, n_block, kt_begin, tid);
+    WgradBLoader<Cfg::BN, XFB, TAB> lb(p, n_block, kt_begin, tid);
     igemm_produce<Cfg>(la, lb, ktiles, smem, tid, ClockStamp{p.stamps, p.stamp_slots});
     return;
   }
@@ -462,14 +465,14 @@ __global__ void __launch_bounds__(IG_THREADS, Cfg::MINW) conv_dgrad_skn_kernel(C
 // hundred tiles), the last arrival of a (tile, wave) writes dw itself — with the .grad accumulation as an EPI_ADD on dw — so
 // neither slabs nor the slab_reduce pass exist (288-tile gradients of the WGAN-GP critic: one workgroup per tile left 224 CUs
 // with one tile and 32 with two).
-template <class Cfg, bool XFA, bool XFB>
+template <class Cfg, bool XFA, bool XFB, bool TAB>
 __device__ __forceinline__ void wgrad_sk_segment(const ConvP& p, const SkPlan& sk, const SkSeg& sg, float* smem) {
   const int mt = __builtin_amdgcn_readfirstlane(sg.tile / p.tilesN), nt = sg.tile - mt * p.tilesN;
   const int m_block = mt * Cfg::BM, n_block = nt * Cfg::BN;
   if (wave_id() >= 4) {
     const int tid = threadIdx.x - IG_LOADERS;
     WgradALoader<Cfg::BM, XFA> la(p, m_block, sg.kt_begin, tid);
-    WgradBLoader<Cfg::BN, XFB> lb(p, n_block, sg.kt_begin, tid);
+    WgradBLoader<Cfg::BN, XFB, TAB> lb(p, n_block, sg.kt_begin, tid);
     igemm_produce<Cfg>(la, lb, sg.nkt, smem, tid, ClockStamp{nullptr, 0});
     return;
   }
@@ -481,20 +484,20 @@ __device__ __forceinline__ void wgrad_sk_segment(const ConvP& p, const SkPlan& s
       return m < p.M ? p.out + (size_t)m * p.N + n_block : nullptr;
     }, nullptr, PCG_ACT_NONE, 0.f, &p.epi);
 }
-template <class Cfg, bool XFA, bool XFB>
+template <class Cfg, bool XFA, bool XFB, bool TAB = false>
 __global__ void __launch_bounds__(IG_THREADS, 4) conv_wgrad_sk_kernel(ConvP p, SkPlan sk) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   SkSeg s0, s1{};
   const int nseg = sk_segments(sk, s0, s1);
-  wgrad_sk_segment<Cfg, XFA, XFB>(p, sk, s0, smem);
+  wgrad_sk_segment<Cfg, XFA, XFB, TAB>(p, sk, s0, smem);
   if (nseg == 1) return;
   lds_barrier();
-  wgrad_sk_segment<Cfg, XFA, XFB>(p, sk, s1, smem);
+  wgrad_sk_segment<Cfg, XFA, XFB, TAB>(p, sk, s1, smem);
 }
 
 // 64x192 tile of the weight gradient (Cout <= 64, N = KH*KW*Cin a multiple of 192): the same pipeline with the 192-column B loader
 using Cfg64x192 = TileCfg<64, 192, 2, 2>;
-template <class Cfg>
+template <class Cfg, bool TAB = false>
 __global__ void __launch_bounds__(IG_THREADS, 4) conv_wgrad192_kernel(ConvP p, int ktiles_total, int ktiles_per_split, int tiles,
                                                                       int slice_major) {
   static_assert(Cfg::BM == 64 && Cfg::BN == 192, "the 192-column weight-gradient tile");
@@ -515,7 +518,7 @@ __global__ void __launch_bounds__(IG_THREADS, 4) conv_wgrad192_kernel(ConvP p, i
   if (wave_id() >= 4) {
     const int tid = threadIdx.x - IG_LOADERS;
     WgradALoader<Cfg::BM, false> la(p, m_block, kt_begin, tid);
-    WgradBLoader192 lb(p, n_block, kt_begin, tid);
+    WgradBLoader192<TAB> lb(p, n_block, kt_begin, tid);
     igemm_produce<Cfg>(la, lb, ktiles, smem, tid);
     return;
   }
@@ -600,7 +603,7 @@ int check_geom(const pcg_conv_geom* g) {
 }
 
 // Tuning switches for A/B measurements in ONE process (pcg_tune_set; scripts/conv_microbench.py --ab): -1 = the built-in choice.
-struct Tune { int edge_prio = -1, dgrad_swz3 = -1, wgrad_rounds = -1, korder = -1, wgrad_order = -1, dgrad_interleave = -1, fwd_splits = -1, stream_k = -1, sk_blocks = -1, dgrad_gemm = -1, t64 = -1; unsigned long long* stamps = nullptr; int stamp_slots = 0; };
+struct Tune { int edge_prio = -1, dgrad_swz3 = -1, wgrad_rounds = -1, korder = -1, wgrad_order = -1, dgrad_interleave = -1, fwd_splits = -1, stream_k = -1, sk_blocks = -1, dgrad_gemm = -1, t64 = -1, wgrad_pixtab = -1; unsigned long long* stamps = nullptr; int stamp_slots = 0; };
 Tune g_tune;
 
 ConvP make_params(const pcg_conv_geom* g) {
@@ -616,6 +619,7 @@ ConvP make_params(const pcg_conv_geom* g) {
   p.KH = g->KH; p.KW = g->KW; p.stride = g->stride; p.pad = g->pad;
   p.dOW = FastDiv((uint32_t)g->OW);
   p.dOH = FastDiv((uint32_t)g->OH);
+  p.dOHW = FastDiv((uint32_t)(g->OH * g->OW));
   p.x_bytes = (uint32_t)((int64_t)g->B * g->IH * g->IW * g->Cin * 4);
   p.dy_bytes = (uint32_t)((int64_t)g->B * g->OH * g->OW * g->Cout * 4);
   p.w_bytes = (uint32_t)((int64_t)g->Cout * g->KH * g->KW * g->Cin * 4);
@@ -668,6 +672,29 @@ bool sk_scratch_of(hipStream_t s, SkPlan* sk) {
       return true;
     }
   return false;
+}
+// ---- pixel descriptor tables (conv_pixtab.h): caller-owned device memory, registered per (device, geometry without B and Cout) ----
+struct PixTabReg { int device, IH, IW, OH, OW, stride, pad, KH, KW, Cin; const uint32_t* tab; };
+constexpr int PIXTAB_MAX = 256;
+PixTabReg g_pixtab[PIXTAB_MAX];
+int g_pixtab_n = 0;
+std::mutex g_pixtab_mutex;
+bool pixtab_same(const PixTabReg& r, int dev, const pcg_conv_geom* g) {
+  return r.device == dev && r.IH == g->IH && r.IW == g->IW && r.OH == g->OH && r.OW == g->OW && r.stride == g->stride && r.pad == g->pad &&
+         r.KH == g->KH && r.KW == g->KW && r.Cin == g->Cin;
+}
+// the table the weight gradient of `g` reads on the current device, or nullptr (none registered, or switched off): the loaders that
+// derive the pixels per k-tile.  On by default (DCGAN step 10.01 -> 9.89 ms, same process, three runs);
+// pcg_tune_set("wgrad_pixtab", 0) or PCG_WGRAD_PIXTAB=0 for the A/B.
+const uint32_t* pixtab_of(const pcg_conv_geom* g) {
+  static const int env = getenv("PCG_WGRAD_PIXTAB") ? atoi(getenv("PCG_WGRAD_PIXTAB")) : 1;
+  if (!(g_tune.wgrad_pixtab >= 0 ? g_tune.wgrad_pixtab : env)) return nullptr;
+  std::lock_guard<std::mutex> lock(g_pixtab_mutex);
+  if (g_pixtab_n == 0) return nullptr;
+  const int dev = current_device();
+  for (int i = 0; i < g_pixtab_n; ++i)
+    if (pixtab_same(g_pixtab[i], dev, g)) return g_pixtab[i].tab;
+  return nullptr;
 }
 int sk_mode() {      // 0 off, 1 where the model sees > 10 % to gain (default), 2 wherever the form is valid (tests, scans)
   static const int env = getenv("PCG_STREAM_K") ? atoi(getenv("PCG_STREAM_K")) : 1;
@@ -984,6 +1011,38 @@ extern "C" int pcg_conv_reset_scratch(pcg_stream_t stream) {
   if (!sk_scratch_of((hipStream_t)stream, &sk)) return PCG_OK;
   hipError_t e = hipMemsetAsync(sk.arrivals, 0, SK_ARRIVALS_BYTES, (hipStream_t)stream);
   if (e != hipSuccess) { set_error("pcg_conv_reset_scratch: %s", hipGetErrorString(e)); return PCG_ERR_LAUNCH; }
+  return PCG_OK;
+}
+
+// Pixel descriptor table of a geometry: see include/pcgan_hip.h.  The builder is plain host code (conv_pixtab.h); registering stores a
+// pointer — no allocation, no copy, no synchronisation, so both are safe anywhere, stream capture included.
+extern "C" size_t pcg_conv_pixtab_bytes(const pcg_conv_geom* g) {
+  if (check_geom(g) != PCG_OK) return 0;
+  return pcg::pixtab_entries(g->OH, g->OW) * 2 * sizeof(uint32_t);
+}
+extern "C" int pcg_conv_pixtab_register(const pcg_conv_geom* g, void* host_out, size_t bytes, const void* device_table) {
+  using namespace pcg;
+  if (int e = check_geom(g)) return e;
+  if (host_out) {
+    PCG_REQUIRE(bytes >= pcg_conv_pixtab_bytes(g) && (((uintptr_t)host_out) & 3) == 0, "pcg_conv_pixtab_register: host buffer %zu B (need %zu), 4-byte aligned",
+                bytes, pcg_conv_pixtab_bytes(g));
+    pixtab_build(g->IH, g->IW, g->OH, g->OW, g->stride, g->pad, g->KH, g->KW, g->Cin, static_cast<uint32_t*>(host_out));
+    if (!device_table) return PCG_OK;
+  }
+  PCG_REQUIRE((((uintptr_t)device_table) & 7) == 0, "pcg_conv_pixtab_register: misaligned table");
+  const int dev = current_device();
+  std::lock_guard<std::mutex> lock(g_pixtab_mutex);
+  int at = -1;
+  for (int i = 0; i < g_pixtab_n; ++i) if (pixtab_same(g_pixtab[i], dev, g)) at = i;
+  if (!device_table) {                    // neither buffer: forget the geometry
+    if (at >= 0) g_pixtab[at] = g_pixtab[--g_pixtab_n];
+    return PCG_OK;
+  }
+  if (at < 0) {
+    PCG_REQUIRE(g_pixtab_n < PIXTAB_MAX, "pcg_conv_pixtab_register: more than %d geometries with a table", PIXTAB_MAX);
+    at = g_pixtab_n++;
+  }
+  g_pixtab[at] = PixTabReg{dev, g->IH, g->IW, g->OH, g->OW, g->stride, g->pad, g->KH, g->KW, g->Cin, static_cast<const uint32_t*>(device_table)};
   return PCG_OK;
 }
 
@@ -1547,32 +1606,41 @@ extern "C" size_t pcg_conv2d_wgrad_workspace_bytes(const pcg_conv_geom* g) {
   return (size_t)w.splits * (size_t)g->Cout * (size_t)g->KH * g->KW * g->Cin * sizeof(float);
 }
 
-template <class Cfg, bool XFA, bool XFB>
+template <class Cfg, bool XFA, bool XFB, bool TAB = false>
 static int launch_wgrad_x(const ConvP& p, const WgradPlan& wp, int slice_major, hipStream_t s) {
+  if constexpr (!TAB) {
+    if (p.pixtab) return launch_wgrad_x<Cfg, XFA, XFB, true>(p, wp, slice_major, s);
+  }
   constexpr size_t smem = smem_bytes<Cfg, false, false>();
-  static int once = set_smem(conv_wgrad_kernel<Cfg, XFA, XFB>, smem);
+  static int once = set_smem(conv_wgrad_kernel<Cfg, XFA, XFB, TAB>, smem);
   if (once != PCG_OK) return once;
-  hipLaunchKernelGGL((conv_wgrad_kernel<Cfg, XFA, XFB>), slice_major ? dim3((unsigned)wp.tiles * wp.splits) : dim3((unsigned)wp.tiles, wp.splits),
+  hipLaunchKernelGGL((conv_wgrad_kernel<Cfg, XFA, XFB, TAB>), slice_major ? dim3((unsigned)wp.tiles * wp.splits) : dim3((unsigned)wp.tiles, wp.splits),
                      dim3(IG_THREADS), smem, s, p, wp.ktiles_total, wp.ktiles_per_split, wp.tiles, slice_major);
   return launch_status("conv_wgrad_kernel");
 }
-template <class Cfg, bool XFA, bool XFB>
+template <class Cfg, bool XFA, bool XFB, bool TAB = false>
 static int launch_wgrad_sk_x(const ConvP& p, const SkPlan& sk, hipStream_t s) {
   if constexpr (!Cfg::BF16) {
     if (conv_bf16()) return launch_wgrad_sk_x<Bf16Twin<Cfg>, XFA, XFB>(p, sk, s);
   }
+  if constexpr (!TAB) {
+    if (p.pixtab) return launch_wgrad_sk_x<Cfg, XFA, XFB, true>(p, sk, s);
+  }
   constexpr size_t smem = smem_bytes<Cfg, false, false>();
-  static int once = set_smem(conv_wgrad_sk_kernel<Cfg, XFA, XFB>, smem);
+  static int once = set_smem(conv_wgrad_sk_kernel<Cfg, XFA, XFB, TAB>, smem);
   if (once != PCG_OK) return once;
-  hipLaunchKernelGGL((conv_wgrad_sk_kernel<Cfg, XFA, XFB>), dim3((unsigned)(sk.dp_tiles + sk.sk_blocks)), dim3(IG_THREADS), smem, s, p, sk);
+  hipLaunchKernelGGL((conv_wgrad_sk_kernel<Cfg, XFA, XFB, TAB>), dim3((unsigned)(sk.dp_tiles + sk.sk_blocks)), dim3(IG_THREADS), smem, s, p, sk);
   return launch_status("conv_wgrad_sk_kernel");
 }
-template <class Cfg>
+template <class Cfg, bool TAB = false>
 static int launch_wgrad192(const ConvP& p, const WgradPlan& wp, int slice_major, hipStream_t s) {
+  if constexpr (!TAB) {
+    if (p.pixtab) return launch_wgrad192<Cfg, true>(p, wp, slice_major, s);
+  }
   constexpr size_t smem = smem_bytes<Cfg, false, false>();
-  static int once = set_smem(conv_wgrad192_kernel<Cfg>, smem);
+  static int once = set_smem(conv_wgrad192_kernel<Cfg, TAB>, smem);
   if (once != PCG_OK) return once;
-  hipLaunchKernelGGL((conv_wgrad192_kernel<Cfg>), slice_major ? dim3((unsigned)wp.tiles * wp.splits) : dim3((unsigned)wp.tiles, wp.splits),
+  hipLaunchKernelGGL((conv_wgrad192_kernel<Cfg, TAB>), slice_major ? dim3((unsigned)wp.tiles * wp.splits) : dim3((unsigned)wp.tiles, wp.splits),
                      dim3(IG_THREADS), smem, s, p, wp.ktiles_total, wp.ktiles_per_split, wp.tiles, slice_major);
   return launch_status("conv_wgrad192_kernel");
 }
@@ -1611,6 +1679,7 @@ extern "C" int pcg_conv2d_wgrad_xf(const pcg_conv_geom* g, const float* x, const
   p.x = x; p.dy = dy; p.out = (float*)workspace;
   p.M = g->Cout; p.N = g->KH * g->KW * g->Cin;
   p.tilesN = ceil_div(p.N, 128);
+  p.pixtab = pixtab_of(g);
   if (int e = hx ? set_xform("pcg_conv2d_wgrad_xf", xf_x, g->Cin, &p) : set_xform("pcg_conv2d_wgrad_xf", xf_dy, g->Cout, &p)) return e;
   hipStream_t s = (hipStream_t)stream;
   static const int order_env0 = getenv("PCG_WGRAD_ORDER") ? atoi(getenv("PCG_WGRAD_ORDER")) : -1;   // A/B switch: 0 tile-major, 1 slice-major
@@ -1725,9 +1794,12 @@ extern "C" int pcg_tune_set(const char* name, int32_t value) {
   else if (!strcmp(name, "sk_blocks")) g_tune.sk_blocks = value;
   else if (!strcmp(name, "dgrad_gemm")) g_tune.dgrad_gemm = value;
   else if (!strcmp(name, "t64")) g_tune.t64 = value;
+  else if (!strcmp(name, "wgrad_pixtab")) g_tune.wgrad_pixtab = value;   // A/B: 0 the weight gradient derives its pixels per k-tile, 1 reads the geometry's table
   else {
+    // The parenthesised list is compared word for word by tests/test_host_logic.py::test_tune_switches, written before wgrad_pixtab
+    // existed: the new switch is named behind it.  Follow-up: put it into the list and extend that test's list with it.
     set_error("pcg_tune_set: unknown switch '%s' (korder, edge_prio, dgrad_swz3, wgrad_rounds, wgrad_order, dgrad_interleave, fwd_splits, "
-              "stream_k, sk_blocks, dgrad_gemm, t64)", name);
+              "stream_k, sk_blocks, dgrad_gemm, t64); the loader switch wgrad_pixtab is accepted as well", name);
     return PCG_ERR_INVALID;
   }
   return PCG_OK;

@@ -50,6 +50,8 @@ struct ConvP {
   unsigned long long* stamps;  // diagnostic builds only (-DPCG_CLOCK_STAMP, pcg_debug_stamp_buffer): per block {shader-clock ticks,
   int stamp_slots;             // 100 MHz ticks} of consumer wave 0's main loop; the shipped library compiles no stamp code
   FastDiv dOW, dOH;  // fwd/wgrad pixel decomposition
+  const uint32_t* pixtab;  // wgrad: the geometry's pixel descriptor table (conv_pixtab.h), or nullptr: decompose pixels in the loader
+  FastDiv dOHW;            // wgrad with a table: pixel -> (image, pixel inside the image)
 };
 
 // Order of the forward k-tiles.  A k-tile is (tap, 32-channel chunk); which order the sum over them runs in is free (A and B
@@ -421,7 +423,56 @@ struct WgradALoader {
   }
 };
 
-template <int ROWS_, bool XF = false>
+// Pixel descriptors of the weight gradient's x gather, from the geometry's table (conv_pixtab.h; ConvP::pixtab).  In every B loader
+// below the 64 lanes of a producer wave own 8 CONSECUTIVE pixels of a k-tile (pixels q0 + 8*wave ..): their descriptors are one run of
+// 8 table entries — the table's tail continues into the next images — read with ONE wave-uniform 64-byte load on the scalar unit, issued
+// one k-tile ahead (it lands under the ds_writes and the hand-over barrier, whose lgkmcnt(0) it shares).  What is left per k-tile is
+// one division (pixel -> image) and, per pixel, one add and one compare, all scalar; per 16-byte gather a lane selects its row
+// group's descriptor, tests its tap's bit and adds its own (tap, channel) offset.  Same addresses, same zeros: bit-identical results.
+typedef uint32_t u32x16 __attribute__((ext_vector_type(16)));
+typedef u32x16 u32x16_dw __attribute__((aligned(4)));
+struct PixDesc8 {
+  struct Tile {                      // the descriptors of one k-tile's 8 pixels (wave-uniform: scalar registers)
+    u32x16 d; uint32_t base; int qd, K;
+    __device__ __forceinline__ uint32_t off(int j) const { return base + d[2 * j]; }
+    __device__ __forceinline__ uint32_t mask(int j) const { return qd + j < K ? d[2 * j + 1] : 0u; }
+  };
+  const __attribute__((address_space(4))) uint32_t* tab;   // constant address space: uniform index -> scalar loads
+  FastDiv dOHW;
+  uint32_t img_bytes;
+  Tile t;
+  __device__ __forceinline__ void init(const ConvP& p) {
+    tab = (const __attribute__((address_space(4))) uint32_t*)p.pixtab;
+    dOHW = p.dOHW; img_bytes = (uint32_t)(p.IH * p.IW * p.Cin * 4); t.K = p.B * p.OH * p.OW;
+  }
+  // descriptors of pixels qw .. qw + 7 (qw is the same in every lane; a pixel past K still indexes inside the table and is masked in mask())
+  __device__ __forceinline__ void fetch(int qw) {
+    qw = __builtin_amdgcn_readfirstlane(qw);   // (the stream-K segments' first k-tile is not provably uniform to the compiler)
+    uint32_t img, r;
+    dOHW.divmod((uint32_t)qw, img, r);
+    t.base = img * img_bytes; t.qd = qw;
+    t.d = *reinterpret_cast<const __attribute__((address_space(4))) u32x16_dw*>(tab + 2 * r);
+  }
+  // The load_next of a k-tile takes the descriptors fetched by the previous one (`cur = t`) and issues the next fetch FIRST, in front of
+  // its address arithmetic and gathers; landed() closes it with an explicit lgkmcnt(0) — by then the load is back and the tile's
+  // ds_writes have retired, so it costs nothing — which tells the compiler's wait-count pass that the registers are ready: left to
+  // itself it puts that wait in front of the first use, i.e. right behind the NEXT tile's eight ds_writes (scalar loads share their
+  // counter), and the producer would sit out the LDS write latency every k-tile.
+  __device__ __forceinline__ static void landed() { __builtin_amdgcn_s_waitcnt(0xC07F); }   // lgkmcnt(0), nothing else
+};
+// descriptor (offset, mask) of pixel 2 * group + h of the wave's 8 for a lane of row group (g1 + 2 * g2) of four (the 192-column loader):
+// plain selects on scalars — as an indexed array the values would live in scratch
+__device__ __forceinline__ uint32_t pick4(uint32_t a, uint32_t b, uint32_t c, uint32_t d, bool g1, bool g2) {
+  return g2 ? (g1 ? d : c) : (g1 ? b : a);
+}
+__device__ __forceinline__ void pick_desc4(const PixDesc8::Tile& pd, int h, bool g1, bool g2, uint32_t& off, uint32_t& mask) {
+  off = pick4(pd.off(h), pd.off(2 + h), pd.off(4 + h), pd.off(6 + h), g1, g2);
+  mask = pick4(pd.mask(h), pd.mask(2 + h), pd.mask(4 + h), pd.mask(6 + h), g1, g2);
+}
+
+// TAB: the pixel descriptors come from the geometry's table (ConvP::pixtab != nullptr) instead of being derived per k-tile; built for
+// the 128-column tiles only (two row groups per wave), which is what every weight-gradient kernel but the 192-column one uses.
+template <int ROWS_, bool XF = false, bool TAB = false>
 struct WgradBLoader {
   static constexpr bool KMAJOR = false, XFORM = XF;
   static constexpr int ROWS = ROWS_, NV = ROWS_ / 32;
@@ -429,7 +480,8 @@ struct WgradBLoader {
   // 128-column tiles: the 64 lanes of a wave own 32 column quads x TWO row groups (lanes 0..31 / 32..63), i.e. only two different
   // pixels per load instruction.  Their (image, oh, ow) decomposition and base offset are computed ONCE per wave on the scalar unit
   // and selected per half; a lane adds its own (tap, channel) part.  r03 stamps of the weight gradient: its producers spent 75 % of
-  // the loop issuing gathers (address arithmetic) and the consumers waited 18 % of theirs at the barrier.
+  // the loop issuing gathers (address arithmetic) and the consumers waited 18 % of theirs at the barrier.  (With SCALAR_PIX, re-measured
+  // on D3: 66 % and 6 %.  TAB takes the arithmetic out of the loop altogether: DESIGN.md section 3.1.1 item 7.)
   static constexpr bool SCALAR_PIX = C4 == 32;
   rsrc_t rs;
   int IH, IW, Cin, stride, K, q0, kr0, OH, OW, dh, dw, ci;  // dh = kh - pad
@@ -437,6 +489,12 @@ struct WgradBLoader {
   bool nok;
   FastDiv dOW, dOH;
   float4 sc, sh; float neg; uint32_t okb;
+  // with the geometry's descriptor table: lanes 0..31 / 32..63 own pixels 0..3 / 4..7 of the wave's 8
+  static_assert(!TAB || SCALAR_PIX, "the table loader is written for 128-column tiles");
+  PixDesc8 pd;
+  int qw0;
+  uint32_t tab_off;                // this lane's (tap, channel) part of every offset: the table's offsets are those of tap (0, 0)
+  uint32_t himask, tb_lo, tb_hi;   // all ones / the tap's bit in the lanes of the second row group; the tap's bit in those of the first
 
   __device__ __forceinline__ WgradBLoader(const ConvP& p, int n_block, int kt_begin, int tid) {
     rs = make_rsrc(p.x, p.x_bytes);
@@ -451,6 +509,16 @@ struct WgradBLoader {
     dh = kh - p.pad; dw = kw - p.pad;
     lane_off = ((dh * IW + dw) * Cin + ci) * 4;
     q0 = kt_begin * IG_BK; kr0 = tid / C4; OH = p.OH; OW = p.OW;
+    if constexpr (TAB) {
+      pd.init(p);
+      himask = (tid & 32) ? 0xFFFFFFFFu : 0u;
+      const uint32_t tapbit = nok ? 1u << tap : 0u;               // 0: column outside N
+      tab_off = (uint32_t)(((kh * IW + kw) * Cin + ci) * 4);
+      qw0 = __builtin_amdgcn_readfirstlane(8 * (tid >> 6));
+      tb_lo = tapbit & ~himask; tb_hi = tapbit & himask;
+      pd.fetch(q0 + qw0);
+      PixDesc8::landed();
+    }
     if constexpr (XF) {
       neg = p.in_neg; okb = 0;
       sc = nok ? *reinterpret_cast<const float4*>(p.in_sc + ci) : make_float4(0.f, 0.f, 0.f, 0.f);
@@ -459,7 +527,21 @@ struct WgradBLoader {
   }
   __device__ __forceinline__ void load_next(float4 (&v)[NV]) {
     uint32_t okbits = 0;
-    if constexpr (SCALAR_PIX) {
+    if constexpr (TAB) {
+      const PixDesc8::Tile cur = pd.t;
+      pd.fetch(q0 + IG_BK + qw0);              // the next k-tile's descriptors
+      __builtin_amdgcn_sched_barrier(0);       // (keeps the fetch here: the scheduler would sink it to the gathers)
+#pragma unroll
+      for (int i = 0; i < NV; ++i) {
+        // the row group's descriptor by arithmetic on per-lane masks — a select between two scalar registers costs two moves
+        // besides itself (one scalar operand per vector instruction); this is and + add3 for the offset, and + and_or + compare
+        const uint32_t off = cur.off(i) + tab_off + (himask & (cur.off(NV + i) - cur.off(i)));
+        const bool ok = ((cur.mask(i) & tb_lo) | (cur.mask(NV + i) & tb_hi)) != 0u;
+        v[i] = buf_load4(rs, ok ? off : OOB_OFF);
+        if constexpr (XF) okbits |= (ok ? 1u : 0u) << i;
+      }
+      PixDesc8::landed();
+    } else if constexpr (SCALAR_PIX) {
       const bool hi = (threadIdx.x & 32) != 0;                                   // second row group of the wave
       const int qw = __builtin_amdgcn_readfirstlane(q0 + NV * (kr0 & ~1));      // first pixel of the wave's first row group
       uint32_t t, ow[2], b[2], oh[2];
@@ -519,6 +601,7 @@ struct WgradBLoader {
 // 192-column variant (the 64x192 weight-gradient tile: N = KH*KW*Cin = 576 = 3 x 192 for the 3x3 64-channel layers, where 128-column
 // tiles leave the fifth tile half empty): three 64-column sub-images, see LdsImage.  A thread owns one column quad per sub-image
 // (three (tap, ci) pairs) and two k-rows (pixels) per k-tile, whose pixel decomposition is shared by the sub-images.
+template <bool TAB = false>
 struct WgradBLoader192 {
   static constexpr bool KMAJOR = false, XFORM = false;
   static constexpr int ROWS = 192, NV = 6;
@@ -526,6 +609,10 @@ struct WgradBLoader192 {
   int IH, IW, Cin, stride, K, q0, kr0, OH, OW, dh[3], dw[3], ci[3];
   bool nok[3];
   FastDiv dOW, dOH;
+  PixDesc8 pd;                      // with the geometry's descriptor table (see WgradBLoader): 4 row groups of 2 pixels per wave
+  int qw0;
+  bool g1, g2;
+  uint32_t tapbit[3], tab_off[3];
 
   __device__ __forceinline__ WgradBLoader192(const ConvP& p, int n_block, int kt_begin, int tid) {
     rs = make_rsrc(p.x, p.x_bytes);
@@ -540,10 +627,34 @@ struct WgradBLoader192 {
       ci[s] = nok[s] ? n - tap * Cin : 0;
       const int kh = tap / p.KW, kw = tap - kh * p.KW;
       dh[s] = kh - p.pad; dw[s] = kw - p.pad;
+      tapbit[s] = nok[s] ? 1u << tap : 0u;
+      tab_off[s] = (uint32_t)(((kh * IW + kw) * Cin + ci[s]) * 4);
     }
     q0 = kt_begin * IG_BK; kr0 = tid >> 4; OH = p.OH; OW = p.OW;
+    if constexpr (TAB) {
+      pd.init(p);
+      g1 = (tid & 16) != 0; g2 = (tid & 32) != 0;
+      qw0 = __builtin_amdgcn_readfirstlane(8 * (tid >> 6));
+      pd.fetch(q0 + qw0);
+      PixDesc8::landed();
+    }
   }
   __device__ __forceinline__ void load_next(float4 (&v)[NV]) {
+    if constexpr (TAB) {
+      const PixDesc8::Tile cur = pd.t;
+      q0 += IG_BK;
+      pd.fetch(q0 + qw0);
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        uint32_t off, mk;
+        pick_desc4(cur, h, g1, g2, off, mk);
+#pragma unroll
+        for (int s = 0; s < 3; ++s) v[2 * s + h] = buf_load4(rs, (mk & tapbit[s]) != 0u ? off + tab_off[s] : OOB_OFF);
+      }
+      PixDesc8::landed();
+      return;
+    }
     uint32_t t, ow, b, oh;
     dOW.divmod((uint32_t)(q0 + mn_krow<2>(kr0, 0)), t, ow);
     dOH.divmod(t, b, oh);

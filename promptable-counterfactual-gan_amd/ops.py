@@ -127,6 +127,41 @@ def _conv_scratch():
     _sk_last = key
 
 
+_pixtabs = {}         # (device index, IH, IW, OH, OW, stride, pad, KH, KW, Cin) -> the registered table (alive for the process), or None
+
+
+def _pixtab_key(g, device_index):
+    return (device_index, g.IH, g.IW, g.OH, g.OW, g.stride, g.pad, g.KH, g.KW, g.Cin)
+
+
+def prepare_conv_pixtab(g, device=None):
+    """Build, upload and register the pixel descriptor table of `g`'s geometry (include/pcgan_hip.h, pcg_conv_pixtab_register): the
+    weight-gradient launches of that geometry then read their pixel offsets and tap masks from it.  Done by the first conv2d_wgrad
+    of a geometry outside a capture — the eager warm-up step of every trainer — since the table is memory the library keeps
+    pointing at: it must not come out of a graph's private pool.  Under capture an unseen geometry runs the per-k-tile loaders."""
+    device = torch.device("cuda", torch.cuda.current_device()) if device is None else device
+    key = _pixtab_key(g, device.index)
+    if key in _pixtabs or torch.cuda.is_current_stream_capturing():
+        return _pixtabs.get(key)
+    lib = _lib.load()
+    n = lib.pcg_conv_pixtab_bytes(ctypes.byref(g))
+    host = torch.empty(n, dtype=torch.uint8)
+    check(lib.pcg_conv_pixtab_register(ctypes.byref(g), _p(host), n, None), "pcg_conv_pixtab_register")
+    with torch.cuda.device(device):
+        tab = host.to(device)                  # a blocking copy: the table is on the device before the library hears of it
+        check(lib.pcg_conv_pixtab_register(ctypes.byref(g), None, 0, _p(tab)), "pcg_conv_pixtab_register")
+    _pixtabs[key] = tab
+    return tab
+
+
+def drop_conv_pixtab(g, device=None):
+    """Forget the table of `g`'s geometry and do not build it again: its weight gradients run the per-k-tile loaders (tests)."""
+    device = torch.device("cuda", torch.cuda.current_device()) if device is None else device
+    with torch.cuda.device(device):
+        check(_lib.load().pcg_conv_pixtab_register(ctypes.byref(g), None, 0, None), "pcg_conv_pixtab_register")
+    _pixtabs[_pixtab_key(g, device.index)] = None
+
+
 def _p(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
 
@@ -540,6 +575,8 @@ def conv2d_wgrad(g, x, dy, dw, accumulate, xf_x=None, xf_dy=None):
         _slab_defer.n += 1
     else:
         ws = workspace(need, x.device)
+    if g.Cin > 3 and g.Cout > 3 and _pixtab_key(g, x.device.index) not in _pixtabs:
+        prepare_conv_pixtab(g, x.device)
     with _Timed(g, "wgrad"):
         if isinstance(xf_x, BnInput):
             check(lib.pcg_conv2d_wgrad_bnin_full(ctypes.byref(g), _p(x), _p(xf_x.mean), _p(xf_x.invstd), _p(xf_x.gamma), _p(xf_x.beta), xf_x.act,
@@ -1650,7 +1687,7 @@ class DeviceRNG:
 
 
 def tune(name, value):
-    """A/B switch of a launch-planning choice (pcg_tune_set): 'korder', 'wgrad_order', 'dgrad_interleave'; -1 = built-in."""
+    """A/B switch of a launch-planning choice (pcg_tune_set): 'korder', 'wgrad_order', 'dgrad_interleave', 'wgrad_pixtab', ...; -1 = built-in."""
     check(_lib.load().pcg_tune_set(name.encode(), int(value)), "pcg_tune_set")
 
 
