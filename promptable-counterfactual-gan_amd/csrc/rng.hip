@@ -4,8 +4,11 @@
 //                            — the reference's Python loop of B randperm calls costs 18-125 ms per batch on the host
 //   * target classes         trainer.py:94     torch.randint(0, num_classes, (bs,))
 //   * latent noise           mnist_dcgan.py:156 torch.randn(b_size, z_dim, 1, 1)
-// The streams differ from torch's generators (RNG parity is by supplied tensors — SURVEY.md §7 "RNG parity"); what is
-// tested is the distribution: exact patch counts, uniform marginals, N(0,1) moments, determinism in (seed, offset).
+// The streams differ from torch's generators (RNG parity is by supplied tensors — SURVEY.md §7 "RNG parity").  What is
+// tested: every draw against the host Philox model oracle/rng_np.py (tests/test_hip_rng_exact.py: the integer-valued draws bit
+// for bit, randn / gumbel within a derived ulp bound of float64 from the same bits; counter layout and spans in DESIGN.md §3.14),
+// the stream bookkeeping of ops.DeviceRNG against the model's counter ranges (tests/test_rng_model_host.py), and the
+// distribution: exact patch counts, uniform marginals, N(0,1) moments, determinism in (seed, offset).
 #include <algorithm>
 #include "pcg_common.h"
 
