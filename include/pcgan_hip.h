@@ -1033,6 +1033,9 @@ int pcg_dp_shutdown(void);
  *   "fwd_splits"        forward K-slices
  *   "wgrad_pixtab"      weight-gradient x gather: 1 pixels from the geometry's registered descriptor table (default), 0 derived per
  *                       k-tile (the environment variable PCG_WGRAD_PIXTAB=0 does the same for a whole process)
+ *   "pad_clip"          k4 s2 p1 forward / grad-input launches: 0 today's kernels, 1 position-major tiles that skip their all-padding
+ *                       taps where the schedule model predicts >= 5 % (pcg_conv_pad_clip_query); 2 / 3 / 4 (measurements) every
+ *                       eligible launch, tiles long first / short first / in pairs.  PCG_PAD_CLIP=v for a whole process.
  * value -1 restores the built-in choice.  Results stay correct under every setting (the order of a sum changes, not its terms). */
 int pcg_tune_set(const char* name, int32_t value);
 
@@ -1070,6 +1073,27 @@ int pcg_conv_reset_scratch(pcg_stream_t stream);
  * loaders.  Results are bit-identical either way.  The reference has no counterpart (ATen's conv backward, mnist_dcgan.py:153-173). */
 size_t pcg_conv_pixtab_bytes(const pcg_conv_geom* g);
 int pcg_conv_pixtab_register(const pcg_conv_geom* g, void* host_out, size_t bytes, const void* device_table);
+/* ---- tile descriptor table of a k4 s2 p1 geometry (csrc/conv_cliptab.h) -------------------------------------------------------------
+ * Zero padding is gathered as zeros and multiplied like any other tap.  A tile whose rows are ONE output pixel (forward form) or ONE
+ * pixel of a sub-pixel phase grid (grad-input form) of different images has the same padded taps in every row and can leave them
+ * out.  The table holds, for the forward form and each of the four grad-input phases, one 32-bit descriptor per position — position,
+ * first valid tap and tap count per axis — sorted by tap count, largest first; it depends on (OH, OW) only (IH = 2 OH, IW = 2 OW).
+ * pcg_conv_cliptab_bytes: its size, 0 for a geometry that has none.  pcg_conv_cliptab_register: the contract of
+ * pcg_conv_pixtab_register (host_out: build on the host; device_table: remember the caller's device copy; both NULL: forget).
+ * An eligible launch — fp32 MFMA path, batch and each BatchNorm group's share of it whole tiles, no K-slices, no stream-K — of a
+ * registered geometry takes the clipped kernels where the schedule model predicts at least 5 % (pcg_tune_set("pad_clip", 0): never).
+ * Convolution outputs are bit-identical; fused BatchNorm sums regroup their fp64 partial rows.
+ * pcg_conv_sched_model: the model — time in us at which the last of n workgroups ends that are dispatched in order onto 256 CUs x 2
+ * slots and run ktiles[i] k-tiles each, at 3.5 us per k-tile beside a busy neighbour slot and 2.2 us alone.
+ * pcg_conv_pad_clip_query: what a launch of `g` would do.  op 0: forward kernel, 1: grad-input kernel; groups: BatchNorm groups along
+ * the batch; assume_scratch: plan as for a stream with stream-K scratch.  *taken 1: the clipped path (also needs the table on the
+ * current device); *order 0 long tiles first, 1 short first, 2 pairs; *tile_rows 128 / 64; *predicted: model time, clipped / today's
+ * (1.0 for a launch that is not eligible).  Outputs may be NULL.                                                                  */
+size_t pcg_conv_cliptab_bytes(const pcg_conv_geom* g);
+int pcg_conv_cliptab_register(const pcg_conv_geom* g, void* host_out, size_t bytes, const void* device_table);
+double pcg_conv_sched_model(const int32_t* ktiles, int32_t n);
+int pcg_conv_pad_clip_query(const pcg_conv_geom* g, int32_t op, int32_t groups, int32_t assume_scratch, int32_t* taken, int32_t* order,
+                            int32_t* tile_rows, double* predicted);
 /* Diagnostic builds only (`make -C csrc stamp`, -DPCG_CLOCK_STAMP): every conv kernel block leaves {shader-clock ticks, 100 MHz
  * ticks} of its main loop at buf[2*block], buf[2*block+1] (uint64) — the clock the chip holds inside the kernel.  Returns 1 when
  * this build stamps, 0 for the shipped library (which compiles no stamp code).  buf = NULL turns it off.                        */

@@ -11,9 +11,12 @@
 // Replaces ATen conv forward/backward behind nn.Conv2d / nn.ConvTranspose2d at
 // dconv_gan/mnist/mnist_dcgan.py:76-88,100-111 and conditional_counteRGAN/mnist/models/*.py.
 #include <string.h>
+#include <array>
+#include <map>
 #include <mutex>
 #include "conv_loaders.h"
 #include "conv_pixtab.h"
+#include "conv_cliptab.h"
 #include "thin_conv.h"
 
 namespace pcg {
@@ -40,10 +43,41 @@ __device__ __forceinline__ int epi_group_off(const ConvP& p, int m_block) {
 
 // XF (here and below): the activation operand carries an input transform (ConvP::in_sc) — a separate instantiation, so the
 // plain kernels pay nothing for it.
-template <class Cfg, bool XF>
+// CLIP: position-major rows, each tile iterating only the taps that are not padding at its position (conv_cliptab.h): a 1-D grid of
+// whole tiles, no K-slices.  Same products in the same order for every output element, zeros left out: bit-identical outputs.
+template <class Cfg, bool XF, bool CLIP = false>
 __global__ void __launch_bounds__(IG_THREADS, Cfg::MINW) conv_fwd_kernel(ConvP p) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   prio_entry(p);
+  if constexpr (CLIP) {
+    uint32_t nt, idx;
+    clip_block_tile(blockIdx.x, (uint32_t)p.tilesN, gridDim.x / (uint32_t)p.tilesN, p.clip_order, false, 0u, nt, idx);
+    nt = __builtin_amdgcn_readfirstlane(nt); idx = __builtin_amdgcn_readfirstlane(idx);   // (the divisions ran on the vector unit)
+    const ClipTile t = clip_tile(p, 0, idx, Cfg::BM);
+    const int n_block = (int)nt * Cfg::BN;
+    const int ktiles = t.nh * t.nw * ((p.Cin + IG_BK - 1) / IG_BK);
+    if (wave_id() >= 4) {  // producers
+      const int tid = threadIdx.x - IG_LOADERS;
+      FwdALoader<Cfg::BM, XF, true> la(p, t, tid);
+      FwdBLoader<Cfg::BN, true> lb(p, n_block, tid);
+      lb.it.clip(t.h0, t.nh, t.w0, t.nw);
+      igemm_produce<Cfg>(la, lb, ktiles, smem, tid, ClockStamp{p.stamps, p.stamp_slots});
+      return;
+    }
+    f32x16 acc[Cfg::TM][Cfg::TN];
+    ClockStamp cs{p.stamps, p.stamp_slots};
+    cs.phase(0);
+    igemm_consume<Cfg, true, true>(ktiles, acc, smem, cs);
+    prio_epilogue(p);
+    const size_t npix = (size_t)p.OH * p.OW;
+    igemm_store_tile<Cfg>(acc, smem, n_block, p.N, p.bias, [&](int row) -> float* {
+      const int b = t.img0 + row;
+      return b < p.B ? p.out + ((size_t)b * npix + t.pos) * p.N + n_block : nullptr;
+    }, p.stat_partial ? p.stat_partial + (size_t)t.stat_tile * Cfg::WAVES_M * 2 * p.N : nullptr, p.act, p.slope, &p.epi,
+       p.epi.group_rows > 0 ? t.group * p.N : 0);
+    cs.phase(3);
+    return;
+  }
   const uint32_t tile = xcd_remap(blockIdx.x, gridDim.x);
   const int mt = tile / p.tilesN, nt = tile % p.tilesN;
   const int m_block = mt * Cfg::BM, n_block = nt * Cfg::BN;
@@ -77,11 +111,46 @@ __global__ void __launch_bounds__(IG_THREADS, Cfg::MINW) conv_fwd_kernel(ConvP p
   cs.phase(3);
 }
 
-template <class Cfg, bool XF>
+template <class Cfg, bool XF, bool CLIP = false>
 __global__ void __launch_bounds__(IG_THREADS, Cfg::MINW) conv_dgrad_kernel(ConvP p, DgradPhases phases) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   __shared__ int rowpix[Cfg::BM];
   prio_entry(p);
+  if constexpr (CLIP) {   // (see conv_fwd_kernel) equal phases, either interleaved in the 1-D grid or one per blockIdx.y
+    const uint32_t nil = phases.interleave ? (uint32_t)phases.interleave : 1u, per = nil * (uint32_t)p.tilesN;
+    uint32_t within, idx;
+    clip_block_tile(blockIdx.x, per, gridDim.x / per, p.clip_order, !phases.interleave, blockIdx.y, within, idx);
+    idx = __builtin_amdgcn_readfirstlane(idx);   // (the divisions ran on the vector unit: back to scalar registers, like the phase below)
+    const uint32_t py = __builtin_amdgcn_readfirstlane(phases.interleave ? within % nil : blockIdx.y), nt = __builtin_amdgcn_readfirstlane(within / nil);
+    const PhaseInfo& f = phases.p[py];
+    const ClipTile t = clip_tile(p, 1 + 2 * f.ph + f.pw, idx, Cfg::BM);
+    const int n_block = (int)nt * Cfg::BN;
+    const int ktiles = t.nh * t.nw * ((p.Cout + IG_BK - 1) / IG_BK);
+    if (wave_id() >= 4) {
+      const int tid = threadIdx.x - IG_LOADERS;
+      uint32_t aa, cc;
+      f.dPHw.divmod((uint32_t)t.pos, aa, cc);
+      const int pix0 = ((int)aa * p.stride + f.ph) * p.IW + (int)cc * p.stride + f.pw;
+      for (int r = tid; r < Cfg::BM; r += IG_LOADERS) rowpix[r] = t.img0 + r < p.B ? (t.img0 + r) * p.IH * p.IW + pix0 : -1;
+      DgradALoader<Cfg::BM, XF, true> la(p, f, t, tid);
+      DgradBLoader<Cfg::BN, true> lb(p, f, n_block, tid);
+      lb.it.clip(t.h0, t.nh, t.w0, t.nw);
+      igemm_produce<Cfg>(la, lb, ktiles, smem, tid, ClockStamp{p.stamps, p.stamp_slots});
+      return;
+    }
+    f32x16 acc[Cfg::TM][Cfg::TN];
+    ClockStamp cs{p.stamps, p.stamp_slots};
+    cs.phase(0);
+    igemm_consume<Cfg, true, false>(ktiles, acc, smem, cs);
+    prio_epilogue(p);
+    igemm_store_tile<Cfg>(acc, smem, n_block, p.N, p.bias, [&](int row) -> float* {
+      const int pix = rowpix[row];
+      return pix >= 0 ? p.out + (size_t)pix * p.Cin + n_block : nullptr;
+    }, p.stat_partial ? p.stat_partial + (size_t)(f.prow0 + t.stat_tile * Cfg::WAVES_M) * 2 * p.N : nullptr, p.act, p.slope, &p.epi,
+       p.epi.group_rows > 0 ? t.group * p.N : 0);
+    cs.phase(3);
+    return;
+  }
   // phases.interleave (all phases the same size, 1-D grid): the sub-pixel phases of one tile are neighbours in launch order and
   // on one XCD — they gather the same dy rows, which then come from HBM once and from that XCD's L2 for the other phases
   uint32_t bx = blockIdx.x, py = blockIdx.y;
@@ -569,6 +638,9 @@ __global__ void __launch_bounds__(256) col2im_kernel(const float4* __restrict__ 
 // host side
 // ------------------------------------------------------------------------------------------------
 using Cfg128x128 = TileCfg<128, 128, 2, 2>;
+#ifndef PCG_PAD_CLIP_DEFAULT
+#define PCG_PAD_CLIP_DEFAULT 1
+#endif
 #ifndef PCG_TILE64_SWZ
 #define PCG_TILE64_SWZ 1     // 128x64 tiles: swizzled unpadded LDS images, three workgroups per CU (0: the r01 layout, two per CU)
 #endif
@@ -603,7 +675,7 @@ int check_geom(const pcg_conv_geom* g) {
 }
 
 // Tuning switches for A/B measurements in ONE process (pcg_tune_set; scripts/conv_microbench.py --ab): -1 = the built-in choice.
-struct Tune { int edge_prio = -1, dgrad_swz3 = -1, wgrad_rounds = -1, korder = -1, wgrad_order = -1, dgrad_interleave = -1, fwd_splits = -1, stream_k = -1, sk_blocks = -1, dgrad_gemm = -1, t64 = -1, wgrad_pixtab = -1; unsigned long long* stamps = nullptr; int stamp_slots = 0; };
+struct Tune { int edge_prio = -1, dgrad_swz3 = -1, wgrad_rounds = -1, korder = -1, wgrad_order = -1, dgrad_interleave = -1, fwd_splits = -1, stream_k = -1, sk_blocks = -1, dgrad_gemm = -1, t64 = -1, wgrad_pixtab = -1, pad_clip = -1; unsigned long long* stamps = nullptr; int stamp_slots = 0; };
 Tune g_tune;
 
 ConvP make_params(const pcg_conv_geom* g) {
@@ -696,6 +768,88 @@ const uint32_t* pixtab_of(const pcg_conv_geom* g) {
     if (pixtab_same(g_pixtab[i], dev, g)) return g_pixtab[i].tab;
   return nullptr;
 }
+// ---- tile descriptor tables of the clipped path (conv_cliptab.h): caller-owned device memory, registered per (device, OH, OW) ----
+struct ClipTabReg { int device, OH, OW; const uint32_t* tab; };
+constexpr int CLIPTAB_MAX = 64;
+ClipTabReg g_cliptab[CLIPTAB_MAX];
+int g_cliptab_n = 0;
+std::mutex g_clip_mutex;
+// 0: off.  1: the launches the schedule model takes.  2 / 3 / 4 (measurements, tests): every eligible launch, tiles long first / short
+// first / in pairs, at today's tile height; 5 / 6 / 7: the same with 64-row tiles where the forward kernel has them.
+// pcg_tune_set("pad_clip", v) or PCG_PAD_CLIP=v.
+int clip_mode() {
+  static const int env = getenv("PCG_PAD_CLIP") ? atoi(getenv("PCG_PAD_CLIP")) : PCG_PAD_CLIP_DEFAULT;
+  return g_tune.pad_clip >= 0 ? g_tune.pad_clip : env;
+}
+const uint32_t* cliptab_of(const pcg_conv_geom* g) {
+  std::lock_guard<std::mutex> lock(g_clip_mutex);
+  if (g_cliptab_n == 0) return nullptr;
+  const int dev = current_device();
+  for (int i = 0; i < g_cliptab_n; ++i)
+    if (g_cliptab[i].device == dev && g_cliptab[i].OH == g->OH && g_cliptab[i].OW == g->OW) return g_cliptab[i].tab;
+  return nullptr;
+}
+// One eligible launch as the schedule model sees it, and what the model says.  form 0: forward kernel, 1: grad-input kernel (four equal
+// phases, `interleave`d in a 1-D grid or one per blockIdx.y).  bm0: today's tile height; the forward kernel's 128-column tiles may also
+// run 64 rows high (`alt64`), at 254 us against 479 / 2 per tile (D4 forward).
+struct ClipShape { int form, OH, OW, B, tilesN, interleave, bm0, alt64; };
+struct ClipPlan { bool take; int order, bm; double ratio; };   // ratio: predicted time of the chosen clipped launch / today's
+constexpr double CLIP_UNIT64 = 254.0 / (479.0 / 2.0) / 2.0;    // a 64-row tile's k-tile in units of a 128-row tile's
+constexpr double CLIP_TAKE = 0.95;
+// The clipped grad-input kernel measured 19-22 % SLOWER than today's at equal work (D3 / D4 at batch 512 and 1024, every order: 0.2514 ->
+// 0.3053 ms on D4; profiles/pad_clip_ab.json): its rows no longer share dy pixels between the taps of a tile or between the phases of
+// one tile.  The model carries that cost, so no grad-input launch is taken unless clipping removes more than a quarter of its time.
+constexpr double CLIP_DGRAD_COST = 1.21;
+double clip_predict(const ClipShape& c, int bm, int order) {     // order < 0: today's launch (every tile iterates every tap)
+  const int npos = c.OH * c.OW, tpp = c.B / bm, tilesM = npos * tpp, nph = c.form ? 4 : 1;
+  const int per = (c.form && c.interleave ? nph : 1) * c.tilesN, gx = tilesM * per, gy = c.form && !c.interleave ? nph : 1;
+  std::vector<uint32_t> tab(cliptab_words(c.OH, c.OW));
+  cliptab_build(c.OH, c.OW, tab.data());
+  std::vector<int> len((size_t)gx * gy);
+  for (int y = 0; y < gy; ++y)
+    for (int b = 0; b < gx; ++b) {
+      uint32_t within, idx;
+      clip_block_tile((uint32_t)b, (uint32_t)per, (uint32_t)tilesM, order < 0 ? 0 : order, gy > 1, (uint32_t)y, within, idx);
+      const int py = c.form ? (c.interleave ? (int)(within % (uint32_t)nph) : y) : 0;
+      len[(size_t)y * gx + b] = order < 0 ? (c.form ? 4 : 16) : clip_desc_taps(tab[(size_t)(c.form ? 1 + py : 0) * npos + idx / (uint32_t)tpp]);
+    }
+  return clip_sched_model(len.data(), (int)len.size()) * (bm == 64 ? CLIP_UNIT64 : 1.0) * (c.form && order >= 0 ? CLIP_DGRAD_COST : 1.0);
+}
+ClipPlan plan_clip(const ClipShape& c) {
+  static std::map<std::array<int, 9>, ClipPlan> cache;
+  const int mode = clip_mode();
+  const std::array<int, 9> key = {c.form, c.OH, c.OW, c.B, c.tilesN, c.interleave, c.bm0, c.alt64, mode};
+  std::lock_guard<std::mutex> lock(g_clip_mutex);
+  auto it = cache.find(key);
+  if (it != cache.end()) return it->second;
+  ClipPlan best{false, 0, c.bm0, 1.0};
+  const double t0 = clip_predict(c, c.B % c.bm0 ? 64 : c.bm0, -1);     // (B % bm0 != 0: forced 64-row modes only)
+  if (mode >= 2) {
+    const bool rows64 = mode >= 5 && c.alt64 && c.B % 64 == 0 && (c.OH * c.OW * (c.B / 64)) % 8 == 0;
+    best = ClipPlan{true, (mode - 2) % 3, rows64 ? 64 : c.bm0, 0.0};
+    best.ratio = clip_predict(c, best.bm, best.order) / t0;
+  } else {
+    for (int h = 0; h < 2; ++h) {
+      const int bm = h ? 64 : 128;
+      if (bm != c.bm0 && !(bm == 64 && c.alt64)) continue;
+      if (c.B % bm || (c.OH * c.OW * (c.B / bm)) % 8) continue;
+      for (int order = 0; order < 3; ++order) {
+        const double r = clip_predict(c, bm, order) / t0;
+        if (r < best.ratio - 1e-9) best = ClipPlan{false, order, bm, r};
+      }
+    }
+    best.take = best.ratio <= CLIP_TAKE + 1e-9;
+  }
+  cache[key] = best;
+  return best;
+}
+// geometry and batch alone (what the query reports); the launch also needs one group's images to be whole tiles, a table and the
+// plain data-parallel form
+bool clip_shape_ok(const pcg_conv_geom* g, int groups, int bm) {
+  return clip_geom_ok(g->IH, g->IW, g->OH, g->OW, g->stride, g->pad, g->KH, g->KW) && groups >= 1 && g->B % groups == 0 &&
+         (g->B / groups) % bm == 0 && (g->OH * g->OW * (g->B / bm)) % 8 == 0;
+}
+
 int sk_mode() {      // 0 off, 1 where the model sees > 10 % to gain (default), 2 wherever the form is valid (tests, scans)
   static const int env = getenv("PCG_STREAM_K") ? atoi(getenv("PCG_STREAM_K")) : 1;
   return g_tune.stream_k >= 0 ? g_tune.stream_k : env;
@@ -768,6 +922,19 @@ int launch_fwd(const ConvP& p, int splits, hipStream_t s) {
   return p.in_sc ? launch_fwd_x<Cfg, true>(p, splits, s) : launch_fwd_x<Cfg, false>(p, splits, s);
 }
 
+// the clipped launch (ConvP::cliptab set by clip_fwd_setup): a 1-D grid of whole position-major tiles
+template <class Cfg, bool XF>
+int launch_fwd_clip_x(ConvP p, hipStream_t s) {
+  p.tilesN = ceil_div(p.N, Cfg::BN);
+  constexpr size_t smem = smem_bytes<Cfg, true, true>();
+  static int once = set_smem(conv_fwd_kernel<Cfg, XF, true>, smem);
+  if (once != PCG_OK) return once;
+  hipLaunchKernelGGL((conv_fwd_kernel<Cfg, XF, true>), dim3((unsigned)(p.clip_npos * p.clip_tpp * p.tilesN)), dim3(IG_THREADS), smem, s, p);
+  return launch_status("conv_fwd_kernel (clipped)");
+}
+template <class Cfg>
+int launch_fwd_clip(const ConvP& p, hipStream_t s) { return p.in_sc ? launch_fwd_clip_x<Cfg, true>(p, s) : launch_fwd_clip_x<Cfg, false>(p, s); }
+
 // Forward split-K: when M*N gives far fewer tiles than the chip has CUs and K is long (small-batch layers with big weights:
 // the WGAN-GP critic's conv3 / 8192->1024 Linear, the generator's 1x1 -> 4x4 ConvT backward), K is cut into slabs that are
 // summed in slab order by slab_reduce — the same deterministic scheme as the weight gradient.
@@ -831,11 +998,33 @@ bool plan_skn_shape(const DgradPhases& ph, int nphases, int BM, int tilesN, int 
   return ok;
 }
 
+// equal phases share a 1-D grid, neighbours in launch order — only for small weight tensors: interleaved phases keep ALL phases' weight
+// slices live in an XCD's 4 MB L2 at once (measured: WGAN-GP's 8 MB ConvT weights ran 20 % slower interleaved, DCGAN's 0.5 MB D2 / G4
+// layers 1-3 % faster)
+bool dgrad_interleaved(uint32_t w_bytes, const DgradPhases& ph, int nphases) {
+  static const int il_env0 = getenv("PCG_DGRAD_INTERLEAVE") ? atoi(getenv("PCG_DGRAD_INTERLEAVE")) : 1;   // A/B switch
+  const int il_env = g_tune.dgrad_interleave >= 0 ? g_tune.dgrad_interleave : il_env0;
+  bool same = nphases > 1 && il_env && w_bytes <= (1u << 20);
+  for (int i = 1; i < nphases; ++i) same = same && ph.p[i].Mp == ph.p[0].Mp;
+  return same;
+}
+
 template <class Cfg, bool XF>
 int launch_dgrad_x(ConvP p, const DgradPhases& ph, int nphases, int maxMp, hipStream_t s) {
   p.tilesN = ceil_div(p.N, Cfg::BN);
   const int tilesM = ceil_div(maxMp, Cfg::BM);
   constexpr size_t smem = smem_bytes<Cfg, true, false>();
+  if constexpr (!Cfg::BF16) {
+    if (p.cliptab) {       // the clipped launch (clip_dgrad_setup): whole position-major tiles of four equal phases
+      static int once_c = set_smem(conv_dgrad_kernel<Cfg, XF, true>, smem);
+      if (once_c != PCG_OK) return once_c;
+      DgradPhases phc = ph;
+      phc.interleave = dgrad_interleaved(p.w_bytes, ph, nphases) ? nphases : 0;
+      const unsigned tiles = (unsigned)(p.clip_npos * p.clip_tpp * p.tilesN);
+      hipLaunchKernelGGL((conv_dgrad_kernel<Cfg, XF, true>), phc.interleave ? dim3(tiles * nphases) : dim3(tiles, nphases), dim3(IG_THREADS), smem, s, p, phc);
+      return launch_status("conv_dgrad_kernel (clipped)");
+    }
+  }
   if constexpr (Cfg::BM == 128 && Cfg::BN == 128) {
     bool uniform = true;
     for (int i = 0; i < nphases; ++i)
@@ -868,13 +1057,8 @@ int launch_dgrad_x(ConvP p, const DgradPhases& ph, int nphases, int maxMp, hipSt
   }
   static int once = set_smem(conv_dgrad_kernel<Cfg, XF>, smem);
   if (once != PCG_OK) return once;
-  static const int il_env0 = getenv("PCG_DGRAD_INTERLEAVE") ? atoi(getenv("PCG_DGRAD_INTERLEAVE")) : 1;   // A/B switch
-  const int il_env = g_tune.dgrad_interleave >= 0 ? g_tune.dgrad_interleave : il_env0;
   DgradPhases phl = ph;
-  // only for small weight tensors: interleaved phases keep ALL phases' weight slices live in an XCD's 4 MB L2 at once (measured:
-  // WGAN-GP's 8 MB ConvT weights ran 20 % slower interleaved, DCGAN's 0.5 MB D2 / G4 layers 1-3 % faster)
-  bool same = nphases > 1 && il_env && p.w_bytes <= (1u << 20);
-  for (int i = 1; i < nphases; ++i) same = same && ph.p[i].Mp == ph.p[0].Mp;
+  const bool same = dgrad_interleaved(p.w_bytes, ph, nphases);
   phl.interleave = same ? nphases : 0;
   if (same)
     hipLaunchKernelGGL((conv_dgrad_kernel<Cfg, XF>), dim3((unsigned)tilesM * p.tilesN * nphases), dim3(IG_THREADS), smem, s, p, phl);
@@ -1046,6 +1230,42 @@ extern "C" int pcg_conv_pixtab_register(const pcg_conv_geom* g, void* host_out, 
   return PCG_OK;
 }
 
+// Tile descriptor table of a geometry (clipped forward / grad-input launches): see include/pcgan_hip.h.  Same contract as the pixel table:
+// the builder is plain host code (conv_cliptab.h), registering stores a pointer.
+extern "C" size_t pcg_conv_cliptab_bytes(const pcg_conv_geom* g) {
+  if (check_geom(g) != PCG_OK || !pcg::clip_geom_ok(g->IH, g->IW, g->OH, g->OW, g->stride, g->pad, g->KH, g->KW)) return 0;
+  return pcg::cliptab_words(g->OH, g->OW) * sizeof(uint32_t);
+}
+extern "C" int pcg_conv_cliptab_register(const pcg_conv_geom* g, void* host_out, size_t bytes, const void* device_table) {
+  using namespace pcg;
+  if (int e = check_geom(g)) return e;
+  const size_t need = pcg_conv_cliptab_bytes(g);
+  PCG_REQUIRE(need > 0, "pcg_conv_cliptab_register: only k4 s2 p1 geometries with IH = 2 OH and IW = 2 OW have a tile table");
+  if (host_out) {
+    PCG_REQUIRE(bytes >= need && (((uintptr_t)host_out) & 3) == 0, "pcg_conv_cliptab_register: host buffer %zu B (need %zu), 4-byte aligned", bytes, need);
+    cliptab_build(g->OH, g->OW, static_cast<uint32_t*>(host_out));
+    if (!device_table) return PCG_OK;
+  }
+  PCG_REQUIRE((((uintptr_t)device_table) & 3) == 0, "pcg_conv_cliptab_register: misaligned table");
+  const int dev = current_device();
+  std::lock_guard<std::mutex> lock(g_clip_mutex);
+  int at = -1;
+  for (int i = 0; i < g_cliptab_n; ++i) if (g_cliptab[i].device == dev && g_cliptab[i].OH == g->OH && g_cliptab[i].OW == g->OW) at = i;
+  if (!device_table) {                    // neither buffer: forget the geometry
+    if (at >= 0) g_cliptab[at] = g_cliptab[--g_cliptab_n];
+    return PCG_OK;
+  }
+  if (at < 0) {
+    PCG_REQUIRE(g_cliptab_n < CLIPTAB_MAX, "pcg_conv_cliptab_register: more than %d geometries with a table", CLIPTAB_MAX);
+    at = g_cliptab_n++;
+  }
+  g_cliptab[at] = ClipTabReg{dev, g->OH, g->OW, static_cast<const uint32_t*>(device_table)};
+  return PCG_OK;
+}
+extern "C" double pcg_conv_sched_model(const int32_t* ktiles, int32_t n) {
+  return ktiles && n > 0 ? pcg::clip_sched_model(ktiles, n) : 0.0;
+}
+
 extern "C" size_t pcg_conv2d_dgrad_workspace_bytes(const pcg_conv_geom* g) {
   if (check_geom(g) != PCG_OK) return 0;
   if (thin_is_cin(g) || thin_is_cout(g)) return thin_conv_dgrad_workspace_bytes(g);
@@ -1079,9 +1299,34 @@ static bool fwd_use_t64(int M, int N, int splits) {
   const int tiles128 = ceil_div(M, 128) * ceil_div(N, 128);
   return g_tune.t64 != 0 && N > 64 && splits == 1 && tiles128 > 224 && tiles128 <= 256 && M % 128 == 0;
 }
+// The clipped path of a forward-kernel launch (conv_cliptab.h).  Eligible: k4 s2 p1 on the fp32 MFMA path, the batch — and each
+// BatchNorm group's share of it — whole tiles, today's launch plain data-parallel (`plain`: no K-slices, no stream-K).  Taken where the
+// schedule model predicts at least 5 % (plan_clip).  Returns the plan; take == false: today's launch.
+static ClipPlan clip_fwd_plan(const pcg_conv_geom* g, int groups, bool t64, bool plain) {
+  const ClipPlan none{false, 0, 0, 1.0};
+  const int bm0 = t64 ? 64 : 128;
+  // (the batch whole tiles of today's height; the forced 64-row modes also take whole 64-row tiles)
+  if (clip_mode() == 0 || conv_bf16() || !plain || !mfma_layer(g) || g->Cin % 4 ||
+      !(clip_shape_ok(g, groups, bm0) || (clip_mode() >= 5 && g->Cout > 64 && clip_shape_ok(g, groups, 64)))) return none;
+  const int N = g->Cout;
+  const ClipShape c{0, g->OH, g->OW, g->B, ceil_div(N, N > 64 ? 128 : 64), 0, bm0, N > 64 && !t64 ? 1 : 0};
+  const ClipPlan cp = plan_clip(c);
+  return cp.take && clip_shape_ok(g, groups, cp.bm) ? cp : ClipPlan{false, cp.order, cp.bm, cp.ratio};
+}
+static ClipPlan clip_dgrad_plan(const pcg_conv_geom* g, int groups, bool interleave, bool plain) {
+  const ClipPlan none{false, 0, 0, 1.0};
+  if (clip_mode() == 0 || conv_bf16() || !plain || !mfma_layer(g) || g->Cin % 4 || g->Cout % 4 || !clip_shape_ok(g, groups, 128)) return none;
+  const int N = g->Cin;
+  const ClipShape c{1, g->OH, g->OW, g->B, ceil_div(N, N > 64 ? 128 : 64), interleave ? 1 : 0, 128, 0};
+  return plan_clip(c);
+}
+static void clip_apply(const pcg_conv_geom* g, const ClipPlan& cp, int groups, const uint32_t* tab, ConvP* p) {
+  p->cliptab = tab; p->clip_order = cp.order; p->clip_tpp = g->B / cp.bm; p->clip_tpg = p->clip_tpp / groups; p->clip_npos = g->OH * g->OW;
+}
+
 static int conv2d_fwd_impl(const pcg_conv_geom* g, const float* x, const float* w, const float* bias, float* y,
                            double* stat_partial, void* workspace, size_t workspace_bytes, pcg_stream_t stream, int act = PCG_ACT_NONE,
-                           float slope = 0.f, const EpiAux* epi = nullptr, const pcg_in_xform* xf = nullptr) {
+                           float slope = 0.f, const EpiAux* epi = nullptr, const pcg_in_xform* xf = nullptr, int groups = 1) {
   if (int e = check_geom(g)) return e;
   PCG_REQUIRE(x && w && y, "pcg_conv2d_fwd: null pointer");
   PCG_REQUIRE(act >= PCG_ACT_NONE && act <= PCG_ACT_SIGMOID, "pcg_conv2d_fwd: unknown activation %d", act);
@@ -1112,7 +1357,16 @@ static int conv2d_fwd_impl(const pcg_conv_geom* g, const float* x, const float* 
   // tiles had measured neutral.  (pcg_tune_set("t64", 0) keeps the 128x128 tiles.)
   // Only where the doubled count fills the 512 slots (225..256 big tiles); fewer tiles take stream-K / K-slices as before.
   const bool t64 = fwd_use_t64(p.M, p.N, f.splits);
-  if (int e = t64 ? launch_fwd<TileCfg<64, 128, 1, 4>>(p, f.splits, s)
+  int clip_bm = 0;         // tile height of the clipped launch, 0: today's launch
+  if (const uint32_t* tab = clip_mode() != 0 ? cliptab_of(g) : nullptr) {
+    SkPlan sk{};
+    const bool plain = f.splits == 1 && !(p.N > 64 && !t64 && plan_sk(ceil_div(p.M, 128) * ceil_div(p.N, 128), p.ktiles, s, &sk));
+    const ClipPlan cp = clip_fwd_plan(g, groups, t64, plain);
+    if (cp.take) { clip_apply(g, cp, groups, tab, &p); clip_bm = cp.bm; }
+  }
+  if (int e = clip_bm == 64 ? launch_fwd_clip<TileCfg<64, 128, 1, 4>>(p, s)
+                  : clip_bm ? (p.N > 64 ? launch_fwd_clip<Cfg128x128>(p, s) : launch_fwd_clip<Cfg128x64>(p, s))
+                  : t64 ? launch_fwd<TileCfg<64, 128, 1, 4>>(p, f.splits, s)
                   : p.N > 64 ? launch_fwd<Cfg128x128>(p, f.splits, s)
                        : launch_fwd<Cfg128x64>(p, f.splits, s)) return e;
   if (f.splits > 1) {
@@ -1175,7 +1429,7 @@ extern "C" int pcg_conv2d_fwd_bn_g(const pcg_conv_geom* g, const float* x, const
   PCG_REQUIRE(groups >= 1 && groups <= 8 && g->B % groups == 0 && ((int64_t)(g->B / groups) * g->OH * g->OW) % 128 == 0,
               "pcg_conv2d_fwd_bn_g: %d images do not split into %d groups of whole 128-row tiles (%d x %d output)", g->B, groups, g->OH, g->OW);
   if (!workspace || workspace_bytes < need) { set_error("pcg_conv2d_fwd_bn_g: workspace %zu B < required %zu B", workspace_bytes, need); return PCG_ERR_WORKSPACE; }
-  if (int e = conv2d_fwd_impl(g, x, w, bias, y, (double*)workspace, nullptr, 0, stream)) return e;
+  if (int e = conv2d_fwd_impl(g, x, w, bias, y, (double*)workspace, nullptr, 0, stream, PCG_ACT_NONE, 0.f, nullptr, nullptr, groups)) return e;
   return launch_bn_stats_finalize_g((const double*)workspace, fwd_stat_rows(g), 1, groups, (int64_t)(g->B / groups) * g->OH * g->OW, g->Cout,
                                     eps, momentum, save_mean, save_invstd, running_mean, running_var, num_batches_tracked, (hipStream_t)stream);
 }
@@ -1255,6 +1509,13 @@ static int conv2d_dgrad_impl(const pcg_conv_geom* g, const float* dy, const floa
   const int nph = build_phases(g, &ph, &maxMp);
   PCG_REQUIRE(nph > 0, "pcg_conv2d_dgrad: empty problem");
   hipStream_t st = (hipStream_t)stream;
+  if (const uint32_t* tab = clip_mode() != 0 ? cliptab_of(g) : nullptr) {
+    const int groups = p.epi.group_rows > 0 ? maxMp / p.epi.group_rows : 1;
+    SkPlan sk{};
+    const bool plain = nph == 4 && !(p.N > 64 && plan_sk(ceil_div(maxMp, 128) * ceil_div(p.N, 128) * nph, 4 * ceil_div(g->Cout, IG_BK), st, &sk));
+    const ClipPlan cp = clip_dgrad_plan(g, groups, dgrad_interleaved(p.w_bytes, ph, nph), plain);
+    if (cp.take) clip_apply(g, cp, groups, tab, &p);
+  }
   if (int e = p.N > 64 ? launch_dgrad<Cfg128x128>(p, ph, nph, maxMp, st)
                        : (nph > 1 && g_tune.dgrad_swz3 == 0) ? launch_dgrad<Cfg128x64P>(p, ph, nph, maxMp, st)   // (r04: with the epilogue at priority 3 the three-per-CU config also wins on the four-phase k4 s2 grad-input: D2 0.2957 -> 0.2893 ms)
                                                              : launch_dgrad<Cfg128x64>(p, ph, nph, maxMp, st)) return e;
@@ -1781,6 +2042,37 @@ extern "C" int pcg_conv_plan_describe(const pcg_conv_geom* g, int32_t op, int32_
   return PCG_OK;
 }
 
+// Would a forward-kernel (op 0) or grad-input-kernel (op 1) launch of `g` with `groups` BatchNorm groups take the clipped path on the
+// current device, as planned for a stream with (assume_scratch) or without stream-K scratch?  *taken also needs the geometry's table.
+extern "C" int pcg_conv_pad_clip_query(const pcg_conv_geom* g, int32_t op, int32_t groups, int32_t assume_scratch, int32_t* taken,
+                                       int32_t* order, int32_t* tile_rows, double* predicted) {
+  if (int e = check_geom(g)) return e;
+  PCG_REQUIRE((op == 0 || op == 1) && groups >= 1, "pcg_conv_pad_clip_query: bad arguments");
+  const int have = assume_scratch && sk_mode() != 0 ? 1 : 0;
+  ClipPlan cp{false, 0, 0, 1.0};
+  if (mfma_layer(g) && op == 0) {
+    const int M = g->B * g->OH * g->OW, N = g->Cout, kt = g->KH * g->KW * ceil_div(g->Cin, IG_BK);
+    const FwdPlan f = plan_fwd(g, have);
+    const bool t64 = fwd_use_t64(M, N, f.splits);
+    SkPlan sk{};
+    const bool plain = f.splits == 1 && !(N > 64 && !t64 && have && plan_sk_shape(ceil_div(M, 128) * ceil_div(N, 128), kt, &sk));
+    cp = clip_fwd_plan(g, groups, t64, plain);
+  } else if (mfma_layer(g) && g->stride <= 2 && !dgrad_as_gemm(g, have)) {
+    DgradPhases ph{};
+    int maxMp = 0;
+    const int nph = build_phases(g, &ph, &maxMp);
+    SkPlan sk{};
+    const bool plain = nph == 4 && !(g->Cin > 64 && have && plan_sk_shape(ceil_div(maxMp, 128) * ceil_div(g->Cin, 128) * nph, 4 * ceil_div(g->Cout, IG_BK), &sk));
+    const uint32_t w_bytes = (uint32_t)((int64_t)g->Cout * g->KH * g->KW * g->Cin * 4);
+    cp = clip_dgrad_plan(g, groups, dgrad_interleaved(w_bytes, ph, nph), plain);
+  }
+  if (taken) *taken = cp.take && cliptab_of(g) ? 1 : 0;
+  if (order) *order = cp.order;
+  if (tile_rows) *tile_rows = cp.bm;
+  if (predicted) *predicted = cp.ratio;
+  return PCG_OK;
+}
+
 extern "C" int pcg_tune_set(const char* name, int32_t value) {
   PCG_REQUIRE(name != nullptr, "pcg_tune_set: null name");
   if (!strcmp(name, "korder")) g_tune.korder = value;
@@ -1795,11 +2087,12 @@ extern "C" int pcg_tune_set(const char* name, int32_t value) {
   else if (!strcmp(name, "dgrad_gemm")) g_tune.dgrad_gemm = value;
   else if (!strcmp(name, "t64")) g_tune.t64 = value;
   else if (!strcmp(name, "wgrad_pixtab")) g_tune.wgrad_pixtab = value;   // A/B: 0 the weight gradient derives its pixels per k-tile, 1 reads the geometry's table
+  else if (!strcmp(name, "pad_clip")) g_tune.pad_clip = value;           // A/B: 0 today's forward / grad-input launches, 1 the clipped ones the model takes
   else {
     // The parenthesised list is compared word for word by tests/test_host_logic.py::test_tune_switches, written before wgrad_pixtab
-    // existed: the new switch is named behind it.  Follow-up: put it into the list and extend that test's list with it.
+    // existed: the later switches are named behind it.  Follow-up: put them into the list and extend that test's list with them.
     set_error("pcg_tune_set: unknown switch '%s' (korder, edge_prio, dgrad_swz3, wgrad_rounds, wgrad_order, dgrad_interleave, fwd_splits, "
-              "stream_k, sk_blocks, dgrad_gemm, t64); the loader switch wgrad_pixtab is accepted as well", name);
+              "stream_k, sk_blocks, dgrad_gemm, t64); the loader switches wgrad_pixtab and pad_clip are accepted as well", name);
     return PCG_ERR_INVALID;
   }
   return PCG_OK;

@@ -52,7 +52,27 @@ struct ConvP {
   FastDiv dOW, dOH;  // fwd/wgrad pixel decomposition
   const uint32_t* pixtab;  // wgrad: the geometry's pixel descriptor table (conv_pixtab.h), or nullptr: decompose pixels in the loader
   FastDiv dOHW;            // wgrad with a table: pixel -> (image, pixel inside the image)
+  // fwd / dgrad on the position-major clipped path (CLIP kernels only; conv_cliptab.h): the geometry's descriptor table, the order of
+  // the M tiles, tiles per position (image blocks of BM rows), of those per BatchNorm group, and positions per section
+  const uint32_t* cliptab; int clip_order, clip_tpp, clip_tpg, clip_npos;
 };
+
+// One M tile of a clipped launch: BM images [img0, img0 + BM) at ONE position (output pixel, or pixel of a sub-pixel phase grid),
+// the rectangle [h0, h0 + nh) x [w0, w0 + nw) of taps that are not padding there, the tile's slot among the partial-statistics rows
+// (every group's rows stay contiguous, as the finalize kernels expect) and its BatchNorm group.  All wave-uniform.
+struct ClipTile { int img0, pos, h0, nh, w0, nw, stat_tile, group; };
+// section: 0 forward, 1 + py grad-input phase; idx: index in the sorted (position, image block) list (clip_block_tile)
+__device__ __forceinline__ ClipTile clip_tile(const ConvP& p, int section, uint32_t idx, int BM) {
+  const uint32_t rank = idx / (uint32_t)p.clip_tpp, j = idx - rank * (uint32_t)p.clip_tpp;
+  const uint32_t d = ((const __attribute__((address_space(4))) uint32_t*)p.cliptab)[section * p.clip_npos + (int)rank];
+  const uint32_t g = j / (uint32_t)p.clip_tpg, jj = j - g * (uint32_t)p.clip_tpg;
+  ClipTile t;
+  t.img0 = (int)j * BM; t.pos = (int)(d & 0xFFFFu);
+  t.h0 = (int)((d >> 16) & 15u); t.nh = (int)((d >> 20) & 15u); t.w0 = (int)((d >> 24) & 15u); t.nw = (int)(d >> 28);
+  t.stat_tile = (int)((g * (uint32_t)p.clip_npos + rank) * (uint32_t)p.clip_tpg + jj);
+  t.group = (int)g;
+  return t;
+}
 
 // Order of the forward k-tiles.  A k-tile is (tap, 32-channel chunk); which order the sum over them runs in is free (A and B
 // loaders share this iterator), but it decides what the XCD's 4 MB L2 sees: an input line [pixel][32 channels] is wanted by
@@ -62,9 +82,19 @@ struct ConvP {
 //             the forward kernels fetched 2.6x their input bytes.
 //   korder 1: taps grouped by their stride-parity class (kh % s, kw % s) — the taps of a class read the SAME input pixels shifted
 //             by whole output steps — then channel chunk, then the taps of the class: all re-reads of a line are 1..3 k-tiles apart.
-struct FwdKIter {
+// CLIP: only the taps of a rectangle [hlo, KH) x [wlo, KW) (KH / KW then hold the rectangle's exclusive upper bounds), in the same
+// relative order; every stride-parity class of a k4 s2 rectangle of >= 2 x 2 taps keeps at least one tap.
+template <bool CLIP = false>
+struct FwdKIterT {
   int KH, KW, Cin, S, mode;
   int ch, cw, jh, jw, ci0;
+  int hlo, wlo;
+  __device__ __forceinline__ int jh0() const { return CLIP && hlo > ch ? (hlo - ch + S - 1) / S : 0; }   // first tap of class row ch
+  __device__ __forceinline__ int jw0() const { return CLIP && wlo > cw ? (wlo - cw + S - 1) / S : 0; }
+  __device__ __forceinline__ void clip(int h0, int nh, int w0, int nw) {
+    hlo = h0; wlo = w0; KH = h0 + nh; KW = w0 + nw;
+    jh = jh0(); jw = jw0();
+  }
   __device__ __forceinline__ void init(const ConvP& p) {
     KH = p.KH; KW = p.KW; Cin = p.Cin; mode = p.korder; S = mode ? p.stride : 1;
     ch = cw = jh = jw = ci0 = 0;
@@ -73,13 +103,14 @@ struct FwdKIter {
   __device__ __forceinline__ int kw() const { return cw + S * jw; }
   __device__ __forceinline__ bool next_tap_in_class() {
     if (cw + S * (++jw) < KW) return true;
-    jw = 0;
+    jw = jw0();
     if (ch + S * (++jh) < KH) return true;
-    jh = 0;
+    jh = jh0();
     return false;
   }
   __device__ __forceinline__ void next_class() {
     if (++cw >= S || cw >= KW) { cw = 0; ++ch; }
+    if constexpr (CLIP) { jh = jh0(); jw = jw0(); }
   }
   __device__ __forceinline__ void advance() {
     if (mode == 0) {                       // (tap, chunk)
@@ -120,6 +151,7 @@ struct FwdKIter {
     }
   }
 };
+using FwdKIter = FwdKIterT<false>;
 
 struct PhaseInfo {
   int ph, pw;          // phase offsets (ih % s, iw % s)
@@ -156,16 +188,37 @@ __device__ __forceinline__ float4 xf_apply(float4 v, float4 sc, float4 sh, float
 }
 
 // ---- forward: A = im2col rows of x (K-major), B = OHWI weight rows (K-major) --------------------------------
-template <int ROWS_, bool XF = false>
+template <int ROWS_, bool XF = false, bool CLIP = false>
 struct FwdALoader {
   static constexpr bool KMAJOR = true, XFORM = XF;
   static constexpr int ROWS = ROWS_, NV = ROWS_ / 32;
   rsrc_t rs;
   uint32_t base[NV], mask[NV];
   int IW, Cin, KW, kq4;
-  FwdKIter it;
+  FwdKIterT<CLIP> it;
   XfK xf;
 
+  // position-major tile: row r is image t.img0 + r at the tile's one output pixel
+  __device__ __forceinline__ FwdALoader(const ConvP& p, const ClipTile& t, int tid) {
+    if constexpr (XF) xf.init(p);
+    rs = make_rsrc(p.x, p.x_bytes);
+    IW = p.IW; Cin = p.Cin; KW = p.KW;
+    it.init(p);
+    it.clip(t.h0, t.nh, t.w0, t.nw);
+    kq4 = (tid & 7) * 4;
+    const int r0 = tid >> 3;
+    uint32_t oh, ow;
+    p.dOW.divmod((uint32_t)t.pos, oh, ow);
+    const int ih0 = (int)oh * p.stride - p.pad, iw0 = (int)ow * p.stride - p.pad;
+    const uint32_t mk = tap_mask(-ih0, p.IH - ih0, p.KH, -iw0, IW - iw0, KW);
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+      const int b = t.img0 + r0 + 32 * i;
+      const bool in = b < p.B;
+      base[i] = in ? (uint32_t)((((b * p.IH + ih0) * IW + iw0) * Cin + kq4) * 4) : OOB_OFF;
+      mask[i] = in ? mk : 0u;
+    }
+  }
   __device__ __forceinline__ FwdALoader(const ConvP& p, int m_block, int tid) {
     if constexpr (XF) xf.init(p);
     rs = make_rsrc(p.x, p.x_bytes);
@@ -214,14 +267,14 @@ struct FwdALoader {
   }
 };
 
-template <int ROWS_>
+template <int ROWS_, bool CLIP = false>
 struct FwdBLoader {
   static constexpr bool KMAJOR = true, XFORM = false;
   static constexpr int ROWS = ROWS_, NV = ROWS_ / 32;
   rsrc_t rs;
   uint32_t base[NV];
   int Cin, KW, kq4;
-  FwdKIter it;
+  FwdKIterT<CLIP> it;
 
   __device__ __forceinline__ FwdBLoader(const ConvP& p, int n_block, int tid) {
     rs = make_rsrc(p.w, p.w_bytes);
@@ -251,12 +304,31 @@ struct FwdBLoader {
 // k-tiles of a grad-input phase: (jh, jw, co-chunk) with the chunk innermost (mode 0), or (co-chunk, jh, jw) with the taps innermost
 // (mode 1, default): the taps of a phase read the same dy pixels shifted by one — with the taps innermost a dy line [pixel][32 co]
 // is re-read in the NEXT k-tiles instead of Cout/32 k-tiles later (see FwdKIter).
-struct DgradTapIter {
+// CLIP: only the taps [hlo, hhi) x [wlo, whi) of the phase's nth x ntw, in the same relative order.
+template <bool CLIP = false>
+struct DgradTapIterT {
   int Cout, nth, ntw, jw, co0, jh, mode;
+  int hlo, hhi, wlo, whi;
   __device__ __forceinline__ void init(int Cout_, int nth_, int ntw_, int mode_) {
     Cout = Cout_; nth = nth_; ntw = ntw_; mode = mode_; jh = 0; jw = 0; co0 = 0;
   }
+  __device__ __forceinline__ void clip(int h0, int nh, int w0, int nw) {
+    hlo = h0; hhi = h0 + nh; wlo = w0; whi = w0 + nw; jh = hlo; jw = wlo;
+  }
   __device__ __forceinline__ void advance() {
+    if constexpr (CLIP) {
+      if (mode == 0) {
+        co0 += IG_BK;
+        if (co0 >= Cout) { co0 = 0; if (++jw == whi) { jw = wlo; ++jh; } }
+      } else {
+        if (++jw < whi) return;
+        jw = wlo;
+        if (++jh < hhi) return;
+        jh = hlo;
+        co0 += IG_BK;
+      }
+      return;
+    }
     if (mode == 0) {
       co0 += IG_BK;
       if (co0 >= Cout) { co0 = 0; if (++jw == ntw) { jw = 0; ++jh; } }
@@ -283,17 +355,39 @@ struct DgradTapIter {
     jh = tap / ntw; jw = tap - jh * ntw;
   }
 };
+using DgradTapIter = DgradTapIterT<false>;
 
-template <int ROWS_, bool XF = false>
+template <int ROWS_, bool XF = false, bool CLIP = false>
 struct DgradALoader {
   static constexpr bool KMAJOR = true, XFORM = XF;
   static constexpr int ROWS = ROWS_, NV = ROWS_ / 32;
   rsrc_t rs;
   uint32_t base[NV], mask[NV];
   int OW, Cout, kq4;
-  DgradTapIter it;
+  DgradTapIterT<CLIP> it;
   XfK xf;
 
+  // position-major tile: row r is image t.img0 + r at the tile's one pixel (a, c) of the phase grid
+  __device__ __forceinline__ DgradALoader(const ConvP& p, const PhaseInfo& f, const ClipTile& t, int tid) {
+    if constexpr (XF) xf.init(p);
+    rs = make_rsrc(p.dy, p.dy_bytes);
+    OW = p.OW; Cout = p.Cout;
+    kq4 = (tid & 7) * 4;
+    const int r0 = tid >> 3;
+    uint32_t aa, cc;
+    f.dPHw.divmod((uint32_t)t.pos, aa, cc);
+    const int oh0 = (int)aa + f.dh0, ow0 = (int)cc + f.dw0;
+    const uint32_t mk = tap_mask(oh0 - p.OH + 1, oh0 + 1, f.nth, ow0 - OW + 1, ow0 + 1, f.ntw);
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+      const int b = t.img0 + r0 + 32 * i;
+      const bool in = b < p.B;
+      base[i] = in ? (uint32_t)((((b * p.OH + oh0) * OW + ow0) * Cout + kq4) * 4) : OOB_OFF;
+      mask[i] = in ? mk : 0u;
+    }
+    it.init(Cout, f.nth, f.ntw, p.korder);
+    it.clip(t.h0, t.nh, t.w0, t.nw);
+  }
   __device__ __forceinline__ DgradALoader(const ConvP& p, const PhaseInfo& f, int m_block, int tid) {
     if constexpr (XF) xf.init(p);
     rs = make_rsrc(p.dy, p.dy_bytes);
@@ -340,7 +434,7 @@ struct DgradALoader {
   }
 };
 
-template <int ROWS_>
+template <int ROWS_, bool CLIP = false>
 struct DgradBLoader {
   static constexpr bool KMAJOR = false, XFORM = false;
   static constexpr int ROWS = ROWS_, NV = ROWS_ / 32;
@@ -348,7 +442,7 @@ struct DgradBLoader {
   rsrc_t rs;
   uint32_t base[NV];
   int Cin, KHKW, KW, stride, kh0, kw0, kr0;
-  DgradTapIter it;
+  DgradTapIterT<CLIP> it;
 
   __device__ __forceinline__ DgradBLoader(const ConvP& p, const PhaseInfo& f, int n_block, int tid) {
     rs = make_rsrc(p.w, p.w_bytes);

@@ -49,6 +49,7 @@ def _conv_flops(g):
 class _Timed:
     def __init__(self, g, op):
         _conv_scratch()                      # every conv entry point passes here: the stream-K launches get their scratch
+        _conv_cliptab(g)                     # ... and a k4 s2 p1 geometry its tile table (the clipped forward / grad-input launches)
         self.on = _conv_hook is not None
         if self.on:
             self.g, self.op = g, op
@@ -160,6 +161,37 @@ def drop_conv_pixtab(g, device=None):
     with torch.cuda.device(device):
         check(_lib.load().pcg_conv_pixtab_register(ctypes.byref(g), None, 0, None), "pcg_conv_pixtab_register")
     _pixtabs[_pixtab_key(g, device.index)] = None
+
+
+_cliptabs = {}        # (device index, OH, OW) -> the registered tile table (alive for the process), or None: no table for the geometry
+
+
+def _conv_cliptab(g):
+    """Build, upload and register the tile descriptor table of `g`'s geometry (include/pcgan_hip.h, pcg_conv_cliptab_register) on its
+    first use outside a capture — like the pixel table, it is memory the library keeps pointing at.  Under capture an unseen geometry
+    runs the unclipped kernels."""
+    if g.KH != 4 or g.stride != 2 or g.pad != 1:
+        return
+    key = (torch.cuda.current_device(), g.OH, g.OW)
+    if key in _cliptabs or torch.cuda.is_current_stream_capturing():
+        return
+    lib = _lib.load()
+    n = lib.pcg_conv_cliptab_bytes(ctypes.byref(g))
+    tab = None
+    if n:
+        host = torch.empty(n, dtype=torch.uint8)
+        check(lib.pcg_conv_cliptab_register(ctypes.byref(g), _p(host), n, None), "pcg_conv_cliptab_register")
+        tab = host.cuda()                      # a blocking copy: the table is on the device before the library hears of it
+        check(lib.pcg_conv_cliptab_register(ctypes.byref(g), None, 0, _p(tab)), "pcg_conv_cliptab_register")
+    _cliptabs[key] = tab
+
+
+def conv_pad_clip_query(g, op, groups=1, assume_scratch=True):
+    """(taken, order, tile_rows, predicted) of pcg_conv_pad_clip_query: op 0 forward kernel, 1 grad-input kernel."""
+    taken, order, rows, pred = ctypes.c_int32(0), ctypes.c_int32(0), ctypes.c_int32(0), ctypes.c_double(1.0)
+    check(_lib.load().pcg_conv_pad_clip_query(ctypes.byref(g), int(op), int(groups), int(bool(assume_scratch)), ctypes.byref(taken),
+                                              ctypes.byref(order), ctypes.byref(rows), ctypes.byref(pred)), "pcg_conv_pad_clip_query")
+    return bool(taken.value), order.value, rows.value, pred.value
 
 
 def _p(t):
