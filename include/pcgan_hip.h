@@ -1287,6 +1287,37 @@ typedef struct pcg_moons_gan_fwd_args {
 } pcg_moons_gan_fwd_args;
 int pcg_moons_gan_forward(const pcg_moons_gan_desc* desc, const pcg_moons_gan_fwd_args* args, pcg_stream_t stream);
 
+/* ---- moons CounteRGAN: the classifier fit in one launch, one workgroup (csrc/moons_clf.hip) --------------------------------------
+ * conditional_counteRGAN/moons/trainer.py:13-29 (train_classifier) and main.py:14-40 (get_classifier) fit
+ * NNClassifier = Linear(2 -> 32), ReLU, Linear(32 -> 32), ReLU, Linear(32 -> 3) with full-batch Adam steps of the mean cross-entropy
+ * over the N training rows (trainer.py:22-25).  hidden 32 and 1 <= N <= 4096 only; anything else is refused with PCG_ERR_INVALID and
+ * pcg_last_error() names the field.  Parameters live in the module's flat buffer of nC floats:
+ *   c_off: net.0.weight [32][2], net.0.bias, net.2.weight [32][32], net.2.bias, net.4.weight [3][32], net.4.bias   (floats, in this
+ *          order, each a multiple of 4, not overlapping)
+ * Adam as in pcg_moons_cf_desc: pcg_adam_step_capturable's arithmetic over the first nC_adam floats, weight decay 0, the device step
+ * counter advanced by one per iteration.                                                                                        */
+typedef struct pcg_moons_clf_fit_desc {
+  int32_t hidden, N, nC, nC_adam;          /* 32; rows 1..4096; flat length; Adam span (floats)           */
+  int32_t c_off[6];                        /* net.{0,2,4}.weight/bias offsets (floats) in the flat buffer */
+  double lr, beta1, beta2, adam_eps;
+} pcg_moons_clf_fit_desc;
+typedef struct pcg_moons_clf_fit_args {
+  const float* X; const int64_t* Y;        /* [N][2], [N] in HBM (labels 0..2: the caller checks)                            */
+  float* c_flat; float* exp_avg; float* exp_avg_sq; int64_t* step;
+  float* losses;                           /* [n_steps]: the loss before the update of each iteration (trainer.py:23)        */
+  int32_t* correct;                        /* optional [1]: rows with argmax(logits) == Y under the final weights             */
+  float* scratch; size_t scratch_bytes;    /* pcg_moons_clf_fit_scratch_bytes of them, 16-byte aligned (may be NULL with 0)  */
+} pcg_moons_clf_fit_args;
+/* Bytes of global scratch a launch with this descriptor needs.  0 for every valid descriptor: the rows are walked in chunks whose
+ * activations live in LDS.  (0 for an invalid one as well; pcg_moons_clf_fit refuses it.)                                        */
+size_t pcg_moons_clf_fit_scratch_bytes(const pcg_moons_clf_fit_desc* desc);
+/* n_steps consecutive iterations of trainer.py:22-25 in ONE launch of one workgroup: forward of all N rows, loss = mean
+ * cross-entropy (log-softmax with the row maximum subtracted), d logits = (softmax - onehot) / N, backward through both ReLUs, the
+ * six gradient tensors, Adam, step counter + 1.  fp32, every sum in an order fixed by N alone: n steps in one launch are
+ * bit-identical to any split into several launches.  Weights and moments are read once and written once per launch.  With
+ * `correct` the launch ends with one more forward under the final weights (ties of the argmax go to the lower index).          */
+int pcg_moons_clf_fit(const pcg_moons_clf_fit_desc* desc, const pcg_moons_clf_fit_args* args, int32_t n_steps, pcg_stream_t stream);
+
 /* ---- calibration (diagnostics; not on the step's path) -----------------------------------------------------------------------
  * What THIS box's fp32 matrix pipe and HBM sustain right now — bench.py prints it next to the step (`calib`) so that a run on a
  * slower-clocked box can be told from a slower kernel (the reference has nothing comparable: it publishes no performance numbers,

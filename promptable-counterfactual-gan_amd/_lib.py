@@ -151,6 +151,18 @@ class MoonsGanFwdArgs(ctypes.Structure):
     _fields_ = [("which", _I), ("R", ctypes.c_int64)] + [(n, _P) for n in ("x", "onehot", "params", "out")]
 
 
+class MoonsClfFitDesc(ctypes.Structure):
+    """pcg_moons_clf_fit_desc."""
+    _fields_ = ([(n, _I) for n in ("hidden", "N", "nC", "nC_adam")] + [("c_off", _I * 6)] +
+                [(n, ctypes.c_double) for n in ("lr", "beta1", "beta2", "adam_eps")])
+
+
+class MoonsClfFitArgs(ctypes.Structure):
+    """pcg_moons_clf_fit_args."""
+    _fields_ = ([(n, _P) for n in ("X", "Y", "c_flat", "exp_avg", "exp_avg_sq", "step", "losses", "correct", "scratch")] +
+                [("scratch_bytes", ctypes.c_size_t)])
+
+
 class DenseBn(ctypes.Structure):
     """pcg_dense_bn."""
     _fields_ = ([(n, _P) for n in ("gamma", "beta", "running_mean", "running_var", "num_batches_tracked", "save_mean", "save_invstd", "xhat")] +
@@ -238,7 +250,8 @@ STRUCTS = {"pcg_conv_geom": ConvGeom, "pcg_in_xform": InXform, "pcg_wgrad_item":
            "pcg_mnist_cf_entry_args": MnistCfEntryArgs, "pcg_mnist_cf_tail_args": MnistCfTailArgs,
            "pcg_mnist_cf_score_args": MnistCfScoreArgs, "pcg_dense_bn": DenseBn,
            "pcg_dense_bn_bwd": DenseBnBwd, "pcg_moons_gan_desc": MoonsGanDesc, "pcg_moons_gan_train_args": MoonsGanTrainArgs,
-           "pcg_moons_gan_fwd_args": MoonsGanFwdArgs}
+           "pcg_moons_gan_fwd_args": MoonsGanFwdArgs, "pcg_moons_clf_fit_desc": MoonsClfFitDesc,
+           "pcg_moons_clf_fit_args": MoonsClfFitArgs}
 
 _c = ctypes
 _vp, _f, _i, _i64, _sz = _c.c_void_p, _c.c_float, _c.c_int, _c.c_int64, _c.c_size_t
@@ -452,6 +465,8 @@ PROTOTYPES = {
     "pcg_moons_gan_scratch_bytes": (_sz, [_c.POINTER(MoonsGanDesc)]),
     "pcg_moons_gan_train_steps": (_i, [_c.POINTER(MoonsGanDesc), _c.POINTER(MoonsGanTrainArgs), _i32, _vp]),
     "pcg_moons_gan_forward": (_i, [_c.POINTER(MoonsGanDesc), _c.POINTER(MoonsGanFwdArgs), _vp]),
+    "pcg_moons_clf_fit_scratch_bytes": (_sz, [_c.POINTER(MoonsClfFitDesc)]),
+    "pcg_moons_clf_fit": (_i, [_c.POINTER(MoonsClfFitDesc), _c.POINTER(MoonsClfFitArgs), _i32, _vp]),
     "pcg_dense_rows_fwd": (_i, [_vp, _vp, _vp, _i32, _i32, _i32, _c.POINTER(DenseBn), _i, _f, _vp, _vp]),
     "pcg_dense_rows_dgrad": (_i, [_vp, _vp, _i32, _i32, _i32, _i, _f, _vp, _c.POINTER(DenseBnBwd), _vp, _vp]),
     "pcg_dense_rows_wgrad": (_i, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _i, _vp]),

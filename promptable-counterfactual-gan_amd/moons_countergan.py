@@ -5,7 +5,9 @@
     models/generator.py:4-24    -> ResidualGenerator      (Linear-BatchNorm1d-ReLU x3, Linear; state_dict keys net.{0,1,3,4,6,7,9})
     models/discriminator.py:6-22-> Discriminator          (four spectral-norm Linears, LeakyReLU 0.2; net.{0,2,4,6}.weight_orig/_u/_v/bias)
     models/nn_classifier.py:3-15-> NNClassifier           (Linear-ReLU-Linear-ReLU-Linear; net.{0,2,4})
-    trainer.py:13-29, main.py:14-40 -> train_classifier / get_classifier
+    trainer.py:13-29, main.py:14-40 -> train_classifier / get_classifier; with one_launch=True the 1000 Adam steps of trainer.py:22-25
+                                   run in ONE launch of pcg_moons_clf_fit (csrc/moons_clf.hip): fit_classifier /
+                                   ClassifierFit.  The default stays the op chain (_fit_classifier)
     trainer.py:31-128           -> train_countergan: one epoch = ONE launch of pcg_moons_cf_train_steps (csrc/moons_cf.hip), which
                                    runs every iteration of the batch loop (:58-113) inside one workgroup
 
@@ -31,7 +33,8 @@ from torch.nn.utils import spectral_norm
 
 from . import _epoch, ops
 from ._epoch import no_autograd, on_gpu
-from ._lib import MoonsCfDesc, MoonsCfEvalArgs, MoonsCfFwdArgs, MoonsCfTrainArgs, PcgError, load as _lib_load
+from ._lib import (MoonsCfDesc, MoonsCfEvalArgs, MoonsCfFwdArgs, MoonsCfTrainArgs, MoonsClfFitArgs, MoonsClfFitDesc, PcgError,
+                   load as _lib_load)
 from .countergan import CrossEntropyLoss
 from .data import MinMax, _split_indices
 from .house import epoch_permutation
@@ -59,6 +62,7 @@ config = {                                                                    # 
 HIDDEN_DIMS = (32, 64)          # the kernel's instantiations
 INPUT_DIM, NUM_CLASSES, CLF_HIDDEN = 2, 3, 32
 MAX_BATCH = 512
+MAX_FIT_ROWS = 4096             # pcg_moons_clf_fit: one workgroup walks the whole training set
 LOG_FIELDS = ("D_loss", "G_loss", "D_real_p", "D_fake_p", "g_adv", "g_cls", "reg_l1", "reg_l2", "mask_pen")
 
 
@@ -276,18 +280,104 @@ def _fit_classifier(clf, X_train, y_train, device):
     return clf
 
 
-def train_classifier(X_train, y_train, config):
-    """trainer.py:13-29: a fresh NNClassifier trained and saved as {"model_state_dict": ...} at config['clf_model_path']."""
+class ClassifierFit:
+    """Runs iterations of trainer.py:22-25 (full-batch cross-entropy, Adam) on the GPU, n per launch (pcg_moons_clf_fit).  Holds the
+    training set in HBM.  run(n, count_correct=False) -> losses [n] (the loss before each update, a device tensor), and with
+    count_correct the number of training rows the final weights classify as their label ([1] int32 on the device).
+
+    After a run `clf` and `opt` hold what the reference's objects hold after n iterations: weights, exp_avg / exp_avg_sq / step, so
+    an eager opt.step() continues at step n + 1.  The contents of the parameters' .grad are NOT specified after a run."""
+
+    def __init__(self, clf, X_train, y_train, lr=1e-2, opt=None):
+        _check_dims(clf.input_dim, HIDDEN_DIMS[0], clf.num_classes, clf_hidden=clf.hidden_dim)
+        if any(not p.requires_grad for p in clf.parameters()):
+            raise PcgError("ClassifierFit: every parameter of the classifier must have requires_grad=True (the kernel updates all of them)")
+        X, y = np.asarray(X_train), np.asarray(y_train)
+        if X.ndim != 2 or X.shape[1] != INPUT_DIM or y.shape != (X.shape[0],):
+            raise PcgError(f"ClassifierFit: X_train must be [N][{INPUT_DIM}] and y_train [N], got {X.shape} and {y.shape}")
+        if not 1 <= X.shape[0] <= MAX_FIT_ROWS:
+            raise PcgError(f"ClassifierFit: N = {X.shape[0]} rows; one launch takes 1..{MAX_FIT_ROWS}")
+        if y.dtype.kind not in "iu" or y.min() < 0 or y.max() >= NUM_CLASSES:
+            raise PcgError(f"ClassifierFit: labels must be integers in [0, {NUM_CLASSES})")
+        if opt is None:
+            opt = Adam(clf.parameters(), lr=lr)
+        if type(opt) is not Adam:
+            raise PcgError("ClassifierFit: the fused step implements pcgan_amd.optim.Adam only")
+        if len(opt.param_groups) != 1 or opt.param_groups[0]["weight_decay"] != 0.0 or opt.param_groups[0].get("amsgrad", False):
+            raise PcgError("ClassifierFit: the optimizer must be one parameter group with weight decay 0 and no amsgrad")
+        if any(not p.is_cuda for p in clf.parameters()):
+            raise PcgError("ClassifierFit: the classifier is on the CPU; libpcgan_hip has no CPU path")
+        dev = _epoch.one_gpu(clf)
+        self.clf, self.device, self.N = clf, dev, X.shape[0]
+        self.X, self.Y = _epoch.resident(X, torch.float32, dev), _epoch.resident(y, torch.int64, dev)
+        self.opt, self.seg = opt, opt.flat_segment(clf, "ClassifierFit")
+        self.scratch, self.scratch_bytes = _epoch.alloc_scratch(_lib_load().pcg_moons_clf_fit_scratch_bytes(ctypes.byref(self._make_desc())), dev)
+
+    def _make_desc(self):
+        d = MoonsClfFitDesc()
+        d.hidden, d.N, d.nC, d.nC_adam = self.clf.hidden_dim, self.N, self.clf.flat_params.numel(), self.seg["n"]
+        d.c_off[:] = _offsets(self.clf, _C_NAMES)
+        g = self.opt.param_groups[0]              # read per launch: a changed learning rate takes effect at the next one
+        d.lr, d.beta1, d.beta2, d.adam_eps = float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"])
+        return d
+
+    def run(self, n, count_correct=False):
+        n = int(n)
+        if n < 1:
+            raise PcgError(f"ClassifierFit.run: n = {n} steps")
+        losses = torch.empty(n, dtype=torch.float32, device=self.device)
+        correct = torch.zeros(1, dtype=torch.int32, device=self.device) if count_correct else None
+        a = MoonsClfFitArgs()
+        a.X, a.Y, a.c_flat = self.X.data_ptr(), self.Y.data_ptr(), self.clf.flat_params.data_ptr()
+        a.exp_avg, a.exp_avg_sq, a.step = self.seg["exp_avg"].data_ptr(), self.seg["exp_avg_sq"].data_ptr(), self.seg["step"].data_ptr()
+        a.losses = losses.data_ptr()
+        a.correct = correct.data_ptr() if count_correct else None
+        a.scratch, a.scratch_bytes = (self.scratch.data_ptr() if self.scratch_bytes else None), self.scratch_bytes
+        ops.check(_lib_load().pcg_moons_clf_fit(ctypes.byref(self._make_desc()), ctypes.byref(a), n, ops._stream()), "pcg_moons_clf_fit")
+        return (losses, correct) if count_correct else losses
+
+
+def fit_classifier(clf, X_train, y_train, steps=1000, lr=1e-2, steps_per_launch=None):
+    """trainer.py:22-25, `steps` iterations in one launch (or in launches of steps_per_launch: bit-identical).  Returns
+    {"losses": [steps] device tensor, "optimizer": the Adam that holds the moments, "train_correct": rows of the training set the
+    final weights classify as their label (an int; the one host read)}."""
+    steps = int(steps)
+    per = steps if steps_per_launch is None else int(steps_per_launch)
+    if steps < 1 or per < 1:
+        raise PcgError(f"fit_classifier: steps = {steps}, steps_per_launch = {steps_per_launch}")
+    fit = ClassifierFit(clf, X_train, y_train, lr=lr)
+    losses, correct = [], None
+    for done in range(0, steps, per):
+        n = min(per, steps - done)
+        if done + n == steps:
+            part, correct = fit.run(n, count_correct=True)
+        else:
+            part = fit.run(n)
+        losses.append(part)
+    return {"losses": torch.cat(losses) if len(losses) > 1 else losses[0], "optimizer": fit.opt, "train_correct": int(correct.item())}
+
+
+def _fit(clf, X_train, y_train, device, one_launch):
+    if one_launch:
+        fit_classifier(clf, X_train, y_train)
+        return clf
+    return _fit_classifier(clf, X_train, y_train, device)
+
+
+def train_classifier(X_train, y_train, config, one_launch=False):
+    """trainer.py:13-29: a fresh NNClassifier trained and saved as {"model_state_dict": ...} at config['clf_model_path'].
+    one_launch=True: the 1000 steps in one launch (fit_classifier) instead of the op chain."""
     device = config["cuda"]
     clf = NNClassifier(config["input_dim"]).to(device)
-    _fit_classifier(clf, X_train, y_train, device)
+    _fit(clf, X_train, y_train, device, one_launch)
     os.makedirs(config["out_dir"], exist_ok=True)
     torch.save({"model_state_dict": clf.state_dict()}, config["clf_model_path"])
     return clf
 
 
-def get_classifier(X_train, y_train, config):
-    """main.py:14-40: load config['clf_model_path'] if it exists, else train 1000 steps and save the state_dict there."""
+def get_classifier(X_train, y_train, config, one_launch=False):
+    """main.py:14-40: load config['clf_model_path'] if it exists, else train 1000 steps and save the state_dict there.
+    one_launch=True: the 1000 steps in one launch (fit_classifier) instead of the op chain."""
     device = config["cuda"]
     clf = NNClassifier(config["input_dim"]).to(device)
     clf_path = config["clf_model_path"]
@@ -297,7 +387,7 @@ def get_classifier(X_train, y_train, config):
         clf.eval()
         return clf
     print("Training new classifier...")
-    _fit_classifier(clf, X_train, y_train, device)
+    _fit(clf, X_train, y_train, device, one_launch)
     os.makedirs(os.path.dirname(clf_path), exist_ok=True)
     torch.save(clf.state_dict(), clf_path)
     print(f"Saved classifier to {clf_path}")
@@ -734,10 +824,11 @@ def evaluate_pipeline(generator, classifier, X_test, y_test, config, masks=None)
     return all_metrics
 
 
-def main(config=config):
-    """main.py:42-60: the data, the classifier (loaded or trained), the generator (loaded or trained, then frozen), evaluate_pipeline."""
+def main(config=config, one_launch=False):
+    """main.py:42-60: the data, the classifier (loaded or trained), the generator (loaded or trained, then frozen), evaluate_pipeline.
+    one_launch: the classifier's fit in one launch (get_classifier)."""
     X_train, X_test, y_train, y_test = load_and_preprocess(config["seed"])
-    clf = get_classifier(X_train, y_train, config)
+    clf = get_classifier(X_train, y_train, config, one_launch=one_launch)
     num_classes = int(np.unique(y_train).size)
     generator = ResidualGenerator(config["input_dim"], config["hidden_dim"], num_classes=num_classes).to(config["cuda"])
     generator_path = config["generator_path"]
