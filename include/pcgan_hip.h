@@ -979,6 +979,34 @@ int pcg_house_batch_draws_counter(int64_t* target_y, int32_t B, int32_t num_clas
                                   float* noise, int32_t T, uint64_t seed, float* onehot_target /*nullable*/, float* onehot_y /*nullable*/,
                                   uint64_t* counter, pcg_stream_t stream);
 
+/* ---- classifier pre-training of the tabular pipeline as a replayed step (house_sales_kc_usa/trainer.py:18-180) ----------------------
+ * pcg_house_clf_batch: the batch and the forward's three Dropout masks (models/nn_classifier.py:11,16,22) in one launch.  Rows
+ * perm[cursor .. cursor+B) of the resident X [n_rows][D] / Y [n_rows] go to x_out [B][D] / y_out [B]; m0 [B][w0], m1 [B][w1], m2 [B][w2]
+ * are 0/1 with P(1) = keep0 / keep1 / keep2: exactly what three pcg_rand_bernoulli calls write at offset, offset + (B*w0+3)/4,
+ * offset + (B*w0+3)/4 + (B*w1+3)/4.  Refused: cursor + B > n_perm.
+ * pcg_house_clf_batch_counter: the same launch with offset and cursor read from a DEVICE counter uint64[4] = [Philox offset, ticket
+ * (zero before first use, left zero), row cursor, unused], which the launch advances itself (offset by the three spans, cursor by B):
+ * captured in a HIP graph, every replay takes the next rows and the next numbers.  The caller keeps cursor + B <= n_perm (the kernel
+ * clamps its reads, it cannot report). */
+int pcg_house_clf_batch(const float* X, const int64_t* Y, const int64_t* perm, int64_t n_perm, int64_t n_rows, float* x_out, int64_t* y_out,
+                        int32_t B, int32_t D, float* m0, int32_t w0, float keep0, float* m1, int32_t w1, float keep1, float* m2, int32_t w2,
+                        float keep2, uint64_t seed, uint64_t offset, int64_t cursor, pcg_stream_t stream);
+int pcg_house_clf_batch_counter(const float* X, const int64_t* Y, const int64_t* perm, int64_t n_perm, int64_t n_rows, float* x_out,
+                                int64_t* y_out, int32_t B, int32_t D, float* m0, int32_t w0, float keep0, float* m1, int32_t w1, float keep1,
+                                float* m2, int32_t w2, float keep2, uint64_t seed, uint64_t* counter, pcg_stream_t stream);
+/* The weighted cross-entropy head with its bookkeeping, one launch, one workgroup, fixed summation order.  For each run of `seg`
+ * consecutive rows of logits [B][K] (the last run may be shorter; seg >= B: one run) L_s = sum_r w[y_r] nll_r / sum_r w[y_r] -- the
+ * value (bit for bit) of pcg_cross_entropy_weighted_fwd_bwd on those rows -- and adds to the device tally double[3]:
+ *   tally[0] += sum_s L_s n_s   (trainer.py:89 running_loss += loss.item() * n; :110 over the validation loader's batches)
+ *   tally[1] += rows whose argmax equals the target (first maximum: a tie counts for the lower index)
+ *   tally[2] += B
+ * dlogits (nullable; needs seg >= B, refused otherwise): the gradient of that single mean, as pcg_cross_entropy_weighted_fwd_bwd
+ * writes it with grad_scale 1.  dbias (nullable, [K], needs dlogits): the column sums of dlogits, the bias gradient of the Linear that
+ * made the logits.  seg_loss (nullable, one float per segment): the L_s themselves. */
+int pcg_ce_weighted_tally(const float* logits, const int64_t* target, const float* class_weight, int32_t B, int32_t K, int32_t seg,
+                          double* tally /*[3], accumulated*/, float* dlogits /*nullable*/, float* dbias /*nullable*/,
+                          float* seg_loss /*nullable*/, pcg_stream_t stream);
+
 /* A barrier of the ranks on the library's own communicator (a 4-byte all-reduce in stream order; synchronise `stream` afterwards):
  * bench.py brackets its timed region with it, so that region uses ONE communicator — the one that carries the gradient exchange.
  * pcg_dp_rccl_version: ncclGetVersion of the RCCL the library bound (22105 = 2.21.5; 0 = unknown).                              */
@@ -1234,6 +1262,30 @@ int pcg_dense_rows_dgrad(const float* dz, const float* W, int32_t R, int32_t O, 
                          pcg_stream_t stream);
 int pcg_dense_rows_wgrad(const float* dz, const float* x, int32_t R, int32_t O, int32_t I, float* dW, float* db /*nullable*/,
                          int accumulate, pcg_stream_t stream);
+/* The post-activation stage Linear -> activation -> BatchNorm1d (batch statistics) -> Dropout of the tabular classifier in training mode
+ * (house_sales_kc_usa/models/nn_classifier.py:8-25), same workgroup shape and summation order as the two kernels above; training mode
+ * only (evaluation folds the BatchNorm into the next Linear).  2 <= R <= 128; act: PCG_ACT_NONE or PCG_ACT_LRELU; anything else, or a
+ * null a / save_mean / save_invstd (forward), a / mean / invstd / gamma / dgamma / dbeta (backward), is refused with PCG_ERR_INVALID.
+ *   pcg_dense_rows_fwd_post    a = act(x W^T + bias) is written to a[R][O], the ONLY saved activation; mean and biased variance of a per
+ *                              column -> save_mean / save_invstd, running statistics (momentum, unbiased variance; nullable) and
+ *                              num_batches_tracked (nullable) as pcg_dense_rows_fwd updates them; xhat = (a - mean) invstd;
+ *                              y = (gamma xhat + beta) * mask * scale with mask[R][O] of 0/1 (nullable: no Dropout), scale = 1/(1-p).
+ *                              in_features % 4 != 0 or unaligned x / W rows (the first layer's 17 columns) take guarded scalar operand
+ *                              loads; aligned shapes the 16-byte loads.
+ *   pcg_dense_rows_dgrad_post  g = dz[R][O] W[O][I], then the backward of the stage below: dn = g * mask * scale; xhat recomputed from
+ *                              (a, mean, invstd) with the forward's expression; dbeta (+)= sum_r dn, dgamma (+)= sum_r dn xhat;
+ *                              da = gamma invstd (dn - dbeta/R - xhat dgamma/R); dx = da * act'(a), act' from the sign of a;
+ *                              db[I] (nullable) (+)= sum_r dx, the bias gradient of the stage's Linear: the columns are complete here.
+ * The weight gradients are pcg_dense_rows_wgrad (x = the stage's input, dz = the dx written here; db NULL when taken here: its own
+ * bias sum is a loop over the rows by one thread per column, three quarters of that launch at 128 rows). */
+int pcg_dense_rows_fwd_post(const float* x, const float* W, const float* bias /*nullable*/, int32_t R, int32_t I, int32_t O, int act,
+                            float slope, const float* gamma, const float* beta, float* running_mean /*nullable*/,
+                            float* running_var /*nullable*/, int64_t* num_batches_tracked /*nullable*/, float eps, float momentum,
+                            const float* mask /*nullable*/, float scale, float* a, float* save_mean, float* save_invstd, float* y,
+                            pcg_stream_t stream);
+int pcg_dense_rows_dgrad_post(const float* dz, const float* W, int32_t R, int32_t O, int32_t I, const float* mask /*nullable*/, float scale,
+                              const float* a, const float* mean, const float* invstd, const float* gamma, int act, float slope,
+                              float* dgamma, float* dbeta, float* db /*nullable*/, int accumulate, float* dx, pcg_stream_t stream);
 
 /* ---- moons GAN and conditional GAN: whole training iterations in one launch, one workgroup (csrc/moons_gan.hip) ----------------
  * simple_gan/moons/make_moons_gan.py (build_generator :33-38, build_discriminator :40-46, the batch loop :61-88) and

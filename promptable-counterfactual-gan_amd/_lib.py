@@ -470,6 +470,13 @@ PROTOTYPES = {
     "pcg_dense_rows_fwd": (_i, [_vp, _vp, _vp, _i32, _i32, _i32, _c.POINTER(DenseBn), _i, _f, _vp, _vp]),
     "pcg_dense_rows_dgrad": (_i, [_vp, _vp, _i32, _i32, _i32, _i, _f, _vp, _c.POINTER(DenseBnBwd), _vp, _vp]),
     "pcg_dense_rows_wgrad": (_i, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _i, _vp]),
+    "pcg_dense_rows_fwd_post": (_i, [_vp, _vp, _vp, _i32, _i32, _i32, _i, _f, _vp, _vp, _vp, _vp, _vp, _f, _f, _vp, _f, _vp, _vp, _vp, _vp, _vp]),
+    "pcg_dense_rows_dgrad_post": (_i, [_vp, _vp, _i32, _i32, _i32, _vp, _f, _vp, _vp, _vp, _vp, _i, _f, _vp, _vp, _vp, _i, _vp, _vp]),
+    "pcg_ce_weighted_tally": (_i, [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "pcg_house_clf_batch": (_i, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _i32, _i32, _vp, _i32, _f, _vp, _i32, _f, _vp, _i32, _f, _c.c_uint64,
+                                 _c.c_uint64, _i64, _vp]),
+    "pcg_house_clf_batch_counter": (_i, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _i32, _i32, _vp, _i32, _f, _vp, _i32, _f, _vp, _i32, _f, _c.c_uint64,
+                                         _vp, _vp]),
     "pcg_spectral_norm_fwd": (_i, [_vp, _i32, _i32, _vp, _vp, _f, _i, _vp, _vp, _vp, _vp, _vp]),
     "pcg_spectral_norm_bwd": (_i, [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _i, _vp]),
 }

@@ -274,6 +274,60 @@ __global__ void __launch_bounds__(256) bernoulli_kernel(float* __restrict__ out,
   }
 }
 
+// The classifier fit's batch (house_sales_kc_usa/trainer.py:78-80: DataLoader(shuffle=True), drop_last=False) and the three Dropout
+// masks of its forward (nn_classifier.py:11,16,22) in one launch: rows perm[cur .. cur+B) of the resident training set into x_out /
+// y_out, and m[q] = what bernoulli_kernel writes for (n[q], keep[q]) at consecutive offsets of (n + 3) / 4.  ctr != nullptr: offset
+// and cursor come from the device counter [Philox offset, ticket, row cursor, unused], which the block that takes the last ticket
+// advances (house_batch_draws_kernel's scheme), so a captured launch takes the next rows and the next numbers on every replay.
+struct ClfMasks { float* m[3]; int64_t n[3]; float keep[3]; };
+__global__ void __launch_bounds__(256) house_clf_batch_kernel(const float* __restrict__ X, const int64_t* __restrict__ Y,
+                                                              const int64_t* __restrict__ perm, int64_t n_perm, int64_t n_rows,
+                                                              float* __restrict__ x_out, int64_t* __restrict__ y_out, int B, int D, ClfMasks mk,
+                                                              uint64_t seed, uint64_t offset, int64_t cursor, unsigned long long* ctr) {
+  if (ctr) {                                                 // kernel-uniform
+    offset = ctr[0];
+    cursor = (int64_t)ctr[2];
+  }
+  const int64_t tid = (int64_t)blockIdx.x * 256 + threadIdx.x, nthr = (int64_t)gridDim.x * 256;
+  auto src_row = [&](int64_t b) -> int64_t {
+    int64_t p = cursor + b;
+    p = p < 0 ? 0 : (p < n_perm ? p : n_perm - 1);           // the host guarantees cursor + B <= n_perm; never read past the buffers
+    const int64_t r = perm[p];
+    return r < 0 ? 0 : (r < n_rows ? r : n_rows - 1);
+  };
+  uint64_t off = offset;
+#pragma unroll
+  for (int q = 0; q < 3; ++q) {
+    const int64_t n = mk.n[q];
+    float* __restrict__ out = mk.m[q];
+    const float keep = mk.keep[q];
+    for (int64_t i = tid; i < (n + 3) / 4; i += nthr) {
+      const U4 r = draw(seed, off, (uint64_t)i);
+      const uint32_t v[4] = {r.x, r.y, r.z, r.w};
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int64_t j = i * 4 + e;
+        if (j < n) out[j] = (float)(v[e] >> 8) * (1.0f / 16777216.0f) < keep ? 1.f : 0.f;
+      }
+    }
+    off += (uint64_t)((n + 3) / 4);
+  }
+  for (int64_t i = tid; i < (int64_t)B * D; i += nthr) {
+    const int64_t b = i / D;
+    const int c = (int)(i - b * D);
+    x_out[i] = X[src_row(b) * D + c];
+  }
+  for (int64_t b = tid; b < B; b += nthr) y_out[b] = Y[src_row(b)];
+  if (ctr) {
+    __syncthreads();                                         // every thread of this block has read the counters
+    if (threadIdx.x == 0 && atomicAdd(reinterpret_cast<int*>(ctr + 1), 1) == (int)gridDim.x - 1) {
+      ctr[0] = off;
+      ctr[2] = (unsigned long long)(cursor + B);
+      *reinterpret_cast<int*>(ctr + 1) = 0;
+    }
+  }
+}
+
 unsigned grid_for(int64_t n) {
   int64_t b = (n + 255) / 256;
   if (b > 4096) b = 4096;
@@ -383,4 +437,46 @@ extern "C" int pcg_house_batch_draws_counter(int64_t* target_y, int32_t B, int32
                      x_out, y_out, src_out, mask, D, zero_cols, n_zero_cols, noise, (int64_t)B * T, seed, onehot_target, onehot_y,
                      reinterpret_cast<unsigned long long*>(counter));
   return launch_status("house_batch_draws_kernel");
+}
+
+namespace {
+int house_clf_batch_launch(const char* who, const float* X, const int64_t* Y, const int64_t* perm, int64_t n_perm, int64_t n_rows, float* x_out,
+                           int64_t* y_out, int32_t B, int32_t D, float* m0, int32_t w0, float keep0, float* m1, int32_t w1, float keep1, float* m2,
+                           int32_t w2, float keep2, uint64_t seed, uint64_t offset, int64_t cursor, unsigned long long* counter,
+                           pcg_stream_t stream) {
+  PCG_REQUIRE(X && Y && perm && x_out && y_out && m0 && m1 && m2 && B > 0 && D > 0 && w0 > 0 && w1 > 0 && w2 > 0 && n_rows > 0,
+              "%s: bad arguments", who);
+  PCG_REQUIRE(n_perm >= B && cursor >= 0 && cursor + B <= n_perm, "%s: rows %lld .. +%d of a permutation of %lld entries", who,
+              (long long)cursor, B, (long long)n_perm);
+  PCG_REQUIRE(keep0 >= 0.f && keep0 <= 1.f && keep1 >= 0.f && keep1 <= 1.f && keep2 >= 0.f && keep2 <= 1.f,
+              "%s: keep probabilities must lie in [0, 1]", who);
+  ClfMasks mk{};
+  mk.m[0] = m0; mk.m[1] = m1; mk.m[2] = m2;
+  mk.n[0] = (int64_t)B * w0; mk.n[1] = (int64_t)B * w1; mk.n[2] = (int64_t)B * w2;
+  mk.keep[0] = keep0; mk.keep[1] = keep1; mk.keep[2] = keep2;
+  const int64_t quads = std::max(std::max((mk.n[0] + 3) / 4, (mk.n[1] + 3) / 4), std::max((mk.n[2] + 3) / 4, ((int64_t)B * D + 3) / 4));
+  unsigned blocks = grid_for(quads);
+  if (blocks > 256u) blocks = 256u;                           // one same-address ticket per block
+  hipLaunchKernelGGL(house_clf_batch_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, X, Y, perm, n_perm, n_rows, x_out, y_out, B, D, mk,
+                     seed, offset, cursor, counter);
+  return launch_status("house_clf_batch_kernel");
+}
+}  // namespace
+
+extern "C" int pcg_house_clf_batch(const float* X, const int64_t* Y, const int64_t* perm, int64_t n_perm, int64_t n_rows, float* x_out,
+                                   int64_t* y_out, int32_t B, int32_t D, float* m0, int32_t w0, float keep0, float* m1, int32_t w1, float keep1,
+                                   float* m2, int32_t w2, float keep2, uint64_t seed, uint64_t offset, int64_t cursor, pcg_stream_t stream) {
+  return house_clf_batch_launch("pcg_house_clf_batch", X, Y, perm, n_perm, n_rows, x_out, y_out, B, D, m0, w0, keep0, m1, w1, keep1, m2, w2, keep2,
+                                seed, offset, cursor, nullptr, stream);
+}
+
+// counter: uint64[4] on the device = [Philox offset, ticket, row cursor into perm, unused]; the launch advances offset and cursor itself
+// (the host keeps cursor + B <= n_perm: the kernel clamps, it cannot report).
+extern "C" int pcg_house_clf_batch_counter(const float* X, const int64_t* Y, const int64_t* perm, int64_t n_perm, int64_t n_rows, float* x_out,
+                                           int64_t* y_out, int32_t B, int32_t D, float* m0, int32_t w0, float keep0, float* m1, int32_t w1,
+                                           float keep1, float* m2, int32_t w2, float keep2, uint64_t seed, uint64_t* counter,
+                                           pcg_stream_t stream) {
+  PCG_REQUIRE(counter, "pcg_house_clf_batch_counter: null counter");
+  return house_clf_batch_launch("pcg_house_clf_batch_counter", X, Y, perm, n_perm, n_rows, x_out, y_out, B, D, m0, w0, keep0, m1, w1, keep1, m2, w2,
+                                keep2, seed, 0, 0, reinterpret_cast<unsigned long long*>(counter), stream);
 }

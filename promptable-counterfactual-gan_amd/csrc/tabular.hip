@@ -1238,3 +1238,102 @@ extern "C" int pcg_house_diag(const pcg_house_diag_args* args, pcg_stream_t stre
   hipLaunchKernelGGL(house_diag_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, d);
   return launch_status("house_diag_kernel");
 }
+
+// ---- weighted cross-entropy head of the classifier fit: loss, gradient, accuracy and the epoch bookkeeping in one launch ------------
+// (house_sales_kc_usa/trainer.py:84-91 per training batch, :104-115 over the validation loader).  One workgroup; per segment of `seg`
+// consecutive rows the two reductions of cross_entropy_weighted_kernel (csrc/cf_ops.hip) in its order -- thread t takes rows t, t + 256,
+// ..., then the 256 partial sums fold in halves -- so a segment's loss and gradient carry that kernel's bits.
+namespace pcg { namespace {
+__global__ void __launch_bounds__(256) ce_weighted_tally_kernel(const float* __restrict__ z, const int64_t* __restrict__ target,
+                                                                const float* __restrict__ w, int B, int K, int seg, double* tally,
+                                                                float* __restrict__ dz, float* __restrict__ dbias,
+                                                                float* __restrict__ seg_loss) {
+  __shared__ float red[256];
+  __shared__ int hits[256];
+  __shared__ float s_wsum;
+  double t_loss = 0.0, t_hits = 0.0;                         // thread 0's
+  int si = 0;
+  for (int s0 = 0; s0 < B; s0 += seg, ++si) {
+    const int n = B - s0 < seg ? B - s0 : seg;
+    float ws = 0.f;
+    for (int b = threadIdx.x; b < n; b += 256) {
+      int64_t t = target[s0 + b];
+      t = t < 0 ? 0 : (t >= K ? K - 1 : t);
+      ws += w[t];
+    }
+    red[threadIdx.x] = ws;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+      if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+      __syncthreads();
+    }
+    if (threadIdx.x == 0) s_wsum = red[0];
+    __syncthreads();
+    const float wsum = s_wsum;
+    const float g = 1.f / wsum;
+    float acc = 0.f;
+    int hit = 0;
+    for (int b = threadIdx.x; b < n; b += 256) {
+      const float* r = z + (size_t)(s0 + b) * K;
+      float mx = r[0];
+      int arg = 0;
+      for (int k = 1; k < K; ++k)
+        if (r[k] > mx) { mx = r[k]; arg = k; }               // first maximum, as torch.argmax: a tie counts for the lower index
+      float se = 0.f;
+      for (int k = 0; k < K; ++k) se += expf(r[k] - mx);
+      const float lse = mx + logf(se);
+      int64_t t = target[s0 + b];
+      t = t < 0 ? 0 : (t >= K ? K - 1 : t);
+      const float wt = w[t];
+      acc += wt * (lse - r[t]);
+      hit += arg == (int)t ? 1 : 0;
+      if (dz)
+        for (int k = 0; k < K; ++k) dz[(size_t)(s0 + b) * K + k] = g * wt * (expf(r[k] - lse) - (k == (int)t ? 1.f : 0.f));
+    }
+    __syncthreads();
+    red[threadIdx.x] = acc;
+    hits[threadIdx.x] = hit;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+      if ((int)threadIdx.x < s) { red[threadIdx.x] += red[threadIdx.x + s]; hits[threadIdx.x] += hits[threadIdx.x + s]; }
+      __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+      const float loss = red[0] / wsum;
+      if (seg_loss) seg_loss[si] = loss;
+      t_loss += (double)loss * (double)n;                    // running_loss += loss.item() * n
+      t_hits += (double)hits[0];
+    }
+    __syncthreads();                                         // red / hits / s_wsum are free for the next segment
+  }
+  if (dz && dbias) {                                         // one segment (the host checks): the bias gradient of the logits layer,
+    for (int k = 0; k < K; ++k) {                            // the column sums of dz -- every thread re-reads the rows it wrote
+      float s = 0.f;
+      for (int b = threadIdx.x; b < B; b += 256) s += dz[(size_t)b * K + k];
+      red[threadIdx.x] = s;
+      __syncthreads();
+      for (int h = 128; h > 0; h >>= 1) {
+        if ((int)threadIdx.x < h) red[threadIdx.x] += red[threadIdx.x + h];
+        __syncthreads();
+      }
+      if (threadIdx.x == 0) dbias[k] = red[0];
+      __syncthreads();
+    }
+  }
+  if (threadIdx.x == 0) {
+    tally[0] += t_loss;
+    tally[1] += t_hits;
+    tally[2] += (double)B;
+  }
+}
+} }
+
+extern "C" int pcg_ce_weighted_tally(const float* logits, const int64_t* target, const float* class_weight, int32_t B, int32_t K, int32_t seg,
+                                     double* tally, float* dlogits, float* dbias, float* seg_loss, pcg_stream_t stream) {
+  PCG_REQUIRE(logits && target && class_weight && tally && B > 0 && K > 0 && seg > 0, "pcg_ce_weighted_tally: bad arguments");
+  PCG_REQUIRE(!dlogits || seg >= B, "pcg_ce_weighted_tally: the gradient is that of ONE mean; %d rows in segments of %d have several", B, seg);
+  PCG_REQUIRE(!dbias || dlogits, "pcg_ce_weighted_tally: dbias is the column sum of dlogits, which is null");
+  hipLaunchKernelGGL(ce_weighted_tally_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, logits, target, class_weight, B, K,
+                     seg < B ? seg : B, tally, dlogits, dbias, seg_loss);
+  return launch_status("ce_weighted_tally_kernel");
+}

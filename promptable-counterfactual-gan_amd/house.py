@@ -10,6 +10,8 @@
     trainer.py  cat_norm_maps :205-223                      cat_norm_maps
     trainer.py  train_countergan loop body :241-316         make_optimizers + train_step
     trainer.py  train_countergan :186-378                   train_countergan(generator, config, X_train, y_train, clf_model)
+    trainer.py  train_classifier :18-180                    train_classifier(..., fused=False); fused=True: ClassifierFit, 16 whole-batch
+                                                            launches as one graph replay + AdamW per step
     gradio_app.py  :144-169                                 prompt_mask + counterfactuals (this row, that class, these features)
     eval_utils.py  :185-289, :351-434, :673-728             compute_metrics_per_target(one_launch=True), analyze_class_pair_sensitivity,
                                                             evaluate_pipeline: ONE launch of pcg_house_cf_eval each
@@ -1753,9 +1755,212 @@ class _WCEFn(torch.autograd.Function):
         return dz, None, None
 
 
-def train_classifier(X_train_all, X_test, y_train_all, y_test, scaler, config, device=None, verbose=True):
+_fused_fallback_warned = False
+
+
+def _warn_fused_fallback(why):
+    global _fused_fallback_warned
+    if not _fused_fallback_warned:
+        import warnings
+        warnings.warn(f"train_classifier(fused=True): {why}; running the op chain instead", RuntimeWarning, stacklevel=3)
+        _fused_fallback_warned = True
+
+
+class ClassifierFit:
+    """The classifier pre-training step (trainer.py:78-91) as whole-batch dense launches (csrc/dense_rows.hip): the batch
+    gather with the three Dropout masks, four post-activation forward stages, the logits, the loss head with its tally, four stage
+    backwards, five weight gradients -- 16 launches captured once as a single-stream, strictly linear HIP graph -- and AdamW, launched
+    eagerly after each replay (its lr is a by-value argument that ReduceLROnPlateau changes).  The training set, the epoch's
+    permutation, the saved activations and the tally (sum of loss * rows, correct rows, rows) live on the device; nothing is read
+    back inside an epoch.  One graph for the full batch, one for the tail N % batch_size; a tail of one row is refused, as
+    BatchNorm1d refuses it.  graph=False: the same entries called eagerly with by-value draws (what the replays must equal)."""
+
+    DIMS = [17, 256, 256, 128, 64, 4]
+
+    @staticmethod
+    def unsupported(model, batch_size):
+        """None, or why this net / batch cannot take the fused path."""
+        dims = [m.in_features for m in model.net if isinstance(m, nn.Linear)] + [model.net[-1].out_features]
+        if dims != ClassifierFit.DIMS:
+            return f"layer widths {dims} are not {ClassifierFit.DIMS}"
+        if batch_size > 128:
+            return f"batch size {batch_size} is above the 128 rows one workgroup holds"
+        return None
+
+    def __init__(self, model, X_train, y_train, class_weight, batch_size, lr=1e-3, weight_decay=1e-4, rng=None, graph=True):
+        from .optim import AdamW
+        why = self.unsupported(model, batch_size)
+        if why is not None:
+            raise PcgError(f"ClassifierFit: {why}")
+        dev = next(model.parameters()).device
+        if dev.type != "cuda":
+            raise PcgError(f"ClassifierFit: the model is on {dev}; libpcgan_hip has no CPU path")
+        self.model, self.B = model, int(batch_size)
+        self.X = torch.as_tensor(np.asarray(X_train), dtype=torch.float32).to(dev).contiguous()
+        self.Y = torch.as_tensor(np.asarray(y_train), dtype=torch.int64).to(dev).contiguous()
+        self.N = int(self.X.shape[0])
+        if self.X.dim() != 2 or self.X.shape[1] != self.DIMS[0] or self.Y.shape != (self.N,):
+            raise PcgError(f"ClassifierFit: need X [N, {self.DIMS[0]}] and y [N]")
+        self.tail = self.N % self.B
+        if self.B < 2 or self.N < 2 or self.tail == 1:
+            raise PcgError(f"ClassifierFit: {self.N} rows in batches of {self.B} leave a batch of one row; training-mode BatchNorm1d "
+                           "needs more than 1 row per batch")
+        self.cw = class_weight.to(dev, torch.float32).contiguous()
+        self.rng = rng if rng is not None else ops.DeviceRNG(seed=0)
+        model.train()
+        model._ensure_flat()
+        model.zero_grad()                                     # attaches the .grad views; every step OVERWRITES them (no zero_grad)
+        self.optimizer = AdamW(model.parameters(), lr=lr, weight_decay=weight_decay)
+        self._stages, self._last = model._stages()
+        self._slopes = [m.negative_slope for m in model.net if isinstance(m, nn.LeakyReLU)]
+        self._tallies = torch.zeros(6, dtype=torch.float64, device=dev)
+        self.tally, self.val_tally = self._tallies[:3], self._tallies[3:]
+        self.perm = torch.arange(self.N, dtype=torch.int64, device=dev)               # identity until new_epoch()
+        self._cur = 0
+        self._ctr = self.rng.device_counter(dev, cursor=True)
+        f32 = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev)      # noqa: E731
+        widths = self.DIMS[1:5]
+        self._bufs = {}
+        for R in sorted({self.B if self.N >= self.B else 0, self.tail} - {0}):
+            self._bufs[R] = {"x": f32(R, self.DIMS[0]), "y": torch.zeros((R,), dtype=torch.int64, device=dev),
+                             "m": [f32(R, w) for w in widths[:3]], "a": [f32(R, w) for w in widths], "h": [f32(R, w) for w in widths],
+                             "mean": [f32(w) for w in widths], "invstd": [f32(w) for w in widths], "d": [f32(R, w) for w in widths],
+                             "logits": f32(R, self.DIMS[5]), "dl": f32(R, self.DIMS[5]), "loss": f32(1)}
+        self._graphs = self._capture() if graph else None
+
+    def _span(self, R):
+        return ops.DeviceRNG.house_clf_batch_span(R, self.DIMS[1:4])
+
+    def _launches(self, b, cursor=None):
+        """One step without AdamW over the buffer set b; cursor None: offsets and rows from the device counter (the captured form)."""
+        st, last = self._stages, self._last
+        keeps = [1.0 - p for _, _, p in st if p is not None]
+        self.rng.house_clf_batch(self.X, self.Y, self.perm, (b["x"], b["y"]), b["m"], keeps, counter=self._ctr if cursor is None else None,
+                                 cursor=cursor or 0)
+        self._forward_backward(b)
+
+    def _forward_backward(self, b):
+        st, last = self._stages, self._last
+        h = b["x"]
+        for s, (lin, bn, p) in enumerate(st):
+            dbn = ops.DenseBN(bn.weight.data, bn.bias.data, bn.running_mean, bn.running_var, bn.num_batches_tracked, bn.eps, bn.momentum, True,
+                              b["mean"][s], b["invstd"][s])
+            ops.dense_rows_fwd_post(h, lin.weight.data, lin.bias.data, dbn, ACT_LRELU, self._slopes[s], mask=b["m"][s] if p is not None else None,
+                                    p=p or 0.0, a=b["a"][s], out=b["h"][s])
+            h = b["h"][s]
+        ops.dense_rows_fwd(h, last.weight.data, last.bias.data, out=b["logits"])
+        ops.ce_weighted_tally(b["logits"], b["y"], self.cw, self.tally, dlogits=b["dl"], seg_loss=b["loss"], dbias=last.bias.grad)
+        d, upper = b["dl"], last
+        for s in range(len(st) - 1, -1, -1):
+            lin, bn, p = st[s]
+            d = ops.dense_rows_dgrad_post(d, upper.weight.data, b["a"][s], b["mean"][s], b["invstd"][s], bn.weight.data, bn.weight.grad, bn.bias.grad,
+                                          ACT_LRELU, self._slopes[s], mask=b["m"][s] if p is not None else None, p=p or 0.0, out=b["d"][s],
+                                          db=lin.bias.grad)
+            upper = lin
+        # the bias gradients came from the epilogues above, which hold complete columns: the weight-gradient launches skip theirs
+        ops.dense_rows_wgrad(b["dl"], b["h"][-1], last.weight.grad, None)
+        for s in range(len(st) - 1, -1, -1):
+            ops.dense_rows_wgrad(b["d"][s], b["x"] if s == 0 else b["h"][s - 1], st[s][0].weight.grad, None)
+
+    def _capture(self):
+        """Capture needs one real execution of every launch first; the BatchNorm buffers, the tally and the counter are put back."""
+        bufs = [t.clone() for t in self.model.buffers()]
+        ctr0, tal0 = self._ctr.clone(), self._tallies.clone()
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            for R, b in self._bufs.items():
+                self._launches(b)
+                self._ctr.copy_(ctr0)
+        torch.cuda.current_stream().wait_stream(side)
+        # no finalizer may run while the stream captures (see nn._HipGraphCapture.begin): the cyclic collector is held off.  It is not
+        # run first: what is garbage now stays so until the collector is back on, and a collection costs 60 ms, more than two epochs.
+        import gc
+        gc_on = gc.isenabled()
+        gc.disable()
+        graphs = {}
+        try:
+            for R, b in self._bufs.items():
+                graphs[R] = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(graphs[R]):
+                    self._launches(b)
+        finally:
+            if gc_on:
+                gc.enable()
+        for t, t0 in zip(self.model.buffers(), bufs):
+            t.copy_(t0)
+        self._ctr.copy_(ctr0); self._tallies.copy_(tal0)
+        return graphs
+
+    def new_epoch(self, perm):
+        """Upload this epoch's row order (N entries) and rewind the cursor: one small copy per EPOCH."""
+        if perm.numel() != self.N:
+            raise PcgError(f"ClassifierFit.new_epoch: permutation of {perm.numel()} entries, {self.N} needed")
+        self.perm.copy_(perm.to(torch.int64))
+        self._ctr[2:3].zero_()
+        self._cur = 0
+
+    @property
+    def steps_per_epoch(self):
+        return self.N // self.B + (1 if self.tail else 0)
+
+    def step(self, record=None):
+        """The next batch of the epoch: one replay, then AdamW.  record (a dict): receives clones of the batch's rows ("x", "y"), its
+        masks ("masks") and its loss ("loss", a [1] device tensor)."""
+        left = self.N - self._cur
+        if left <= 0:
+            raise PcgError("ClassifierFit.step: the epoch is used up; call new_epoch(perm)")
+        R = self.B if left >= self.B else left
+        b = self._bufs[R]
+        if self._graphs is not None:
+            self._graphs[R].replay()
+            self.rng.offset += self._span(R)                  # the host-side mirror of the device counter
+        else:
+            self._launches(b, cursor=self._cur)
+        self.optimizer.step()
+        self._cur += R
+        if record is not None:
+            record.update(x=b["x"].clone(), y=b["y"].clone(), masks=[m.clone() for m in b["m"]], loss=b["loss"].clone())
+        return R
+
+    def run_batch(self, x, y, masks):
+        """Forward, loss and backward of one GIVEN batch with GIVEN Dropout masks (runs that must reproduce recorded draws), called
+        eagerly: the gradients land in the flat gradient buffer, the tally counts the batch; no AdamW.  Returns the loss ([1], device)."""
+        R = int(x.shape[0])
+        if R not in self._bufs:
+            raise PcgError(f"ClassifierFit.run_batch: {R} rows; this fit holds buffers for {sorted(self._bufs)}")
+        b = self._bufs[R]
+        b["x"].copy_(x); b["y"].copy_(y)
+        for dst, src in zip(b["m"], masks):
+            dst.copy_(src)
+        self._forward_backward(b)
+        return b["loss"]
+
+    def epoch(self, perm):
+        """All steps of one epoch in the order perm, with no host read."""
+        self.new_epoch(perm)
+        for _ in range(self.steps_per_epoch):
+            self.step()
+
+    def read_tally(self):
+        """(sum of loss * rows, correct rows, rows) of the training steps since the last read; clears it.  One host read."""
+        t = self.tally.cpu().tolist()
+        self.tally.zero_()
+        return tuple(t)
+
+    def read_tallies(self):
+        """The training tally and val_tally (same layout; train_classifier's validation launch adds to it) in ONE host read; clears both."""
+        t = self._tallies.cpu().tolist()
+        self._tallies.zero_()
+        return tuple(t)
+
+
+def train_classifier(X_train_all, X_test, y_train_all, y_test, scaler, config, device=None, verbose=True, fused=False):
     """trainer.py:18-180 without the plotting tail: stratified validation split, class-weighted CrossEntropyLoss, AdamW,
-    ReduceLROnPlateau(factor 0.5, patience 4), early stopping on the validation loss; returns the model with its best state."""
+    ReduceLROnPlateau(factor 0.5, patience 4), early stopping on the validation loss; returns the model with its best state.
+    fused=True: the batches run through ClassifierFit (one graph replay + one AdamW launch per step, no host read inside an epoch),
+    the validation is one eval-mode forward over the whole split and one segmented tally launch, and both tallies are read once per
+    epoch; the host logic is the same.  A net of other widths or a batch above 128 rows falls back to the op chain with a warning."""
     import copy
     import numpy as np
     from sklearn.model_selection import train_test_split
@@ -1775,7 +1980,20 @@ def train_classifier(X_train_all, X_test, y_train_all, y_test, scaler, config, d
     model = NNClassifier(config["input_dim"], output_dim=num_classes).to(device)              # :50
     cw = compute_class_weight("balanced", classes=np.arange(num_classes), y=y_train)          # :53
     criterion = WeightedCrossEntropyLoss(torch.tensor(cw, dtype=torch.float32, device=device))
-    optimizer = AdamW(model.parameters(), lr=config.get("clf_lr", 1e-3), weight_decay=config.get("clf_wd", 1e-4))   # :58
+    fit = None
+    if fused:
+        why = ClassifierFit.unsupported(model, bs)
+        if why is None:
+            if model.rng is None:
+                model.rng = ops.DeviceRNG(seed=0)                                             # the stream NNClassifier.forward draws from
+            fit = ClassifierFit(model, X_train, y_train, criterion.weight, bs, lr=config.get("clf_lr", 1e-3),
+                                weight_decay=config.get("clf_wd", 1e-4), rng=model.rng)
+            X_val_dev = torch.tensor(X_val, dtype=torch.float32).to(device).contiguous()
+            y_val_dev = torch.tensor(y_val, dtype=torch.long).to(device)
+        else:
+            _warn_fused_fallback(why)
+    optimizer = fit.optimizer if fit is not None else \
+        AdamW(model.parameters(), lr=config.get("clf_lr", 1e-3), weight_decay=config.get("clf_wd", 1e-4))           # :58
     scheduler = torch.optim.lr_scheduler.ReduceLROnPlateau(optimizer, mode="min", factor=0.5, patience=4)           # :59
     best_val, best_state, wait = float("inf"), None, 0
     patience, epochs = config.get("clf_early_stopping", 15), config.get("clf_epochs", 100)
@@ -1783,7 +2001,7 @@ def train_classifier(X_train_all, X_test, y_train_all, y_test, scaler, config, d
     for epoch in range(1, epochs + 1):
         model.train()
         run_loss, correct, total = 0.0, 0.0, 0
-        for xb, yb in train_loader:
+        for xb, yb in (train_loader if fit is None else ()):
             xb, yb = xb.to(device), yb.to(device)
             optimizer.zero_grad()
             logits = model(xb)
@@ -1796,8 +2014,15 @@ def train_classifier(X_train_all, X_test, y_train_all, y_test, scaler, config, d
             total += n
         model.eval()
         v_loss, v_correct, v_total = 0.0, 0.0, 0
+        if fit is not None:
+            fit.epoch(epoch_permutation(fit.N))                                               # the order train_loader walks
         with torch.no_grad():
-            for xb, yb in val_loader:
+            if fit is not None:
+                model._packed = None             # the in-place optimizer kernel bumps no tensor version: _pack would serve the old image
+                torch.empty((), dtype=torch.int64).random_()                                  # val_loader's iterator: its base seed
+                ops.ce_weighted_tally(model(X_val_dev).contiguous(), y_val_dev, criterion.weight, fit.val_tally, seg=bs)
+                run_loss, correct, total, v_loss, v_correct, v_total = fit.read_tallies()     # the epoch's one host read
+            for xb, yb in (val_loader if fit is None else ()):
                 xb, yb = xb.to(device), yb.to(device)
                 logits = model(xb).contiguous()
                 n = xb.size(0)

@@ -1125,6 +1125,61 @@ def dense_rows_wgrad(dz, x, dW, db=None, accumulate=False):
     return dW
 
 
+def dense_rows_fwd_post(x, w, bias, bn, act=_lib.ACT_LRELU, slope=0.0, mask=None, p=0.0, a=None, out=None):
+    """y = Dropout(BN_train(act(x[R][I] w^T + bias))) in one launch, 2 <= R <= 128 (pcg_dense_rows_fwd_post): the post-activation
+    stage of the tabular classifier.  bn: a DenseBN in training mode; its save_mean / save_invstd are allocated here when absent.
+    mask [R][O] of 0/1 (None: no Dropout), p the Dropout probability.  Returns (y, a): a = act(z) is all the backward needs."""
+    _chk(x, "x"); _chk(w, "w")
+    R, I = x.shape
+    O = w.shape[0]
+    if w.shape[1] != I:
+        raise _lib.PcgError(f"dense_rows_fwd_post: x has {I} features, the weight takes {w.shape[1]}")
+    if bn is None or not bn.training:
+        raise _lib.PcgError("dense_rows_fwd_post: training-mode BatchNorm only (evaluation folds it into the next Linear)")
+    dev = x.device
+    y = out if out is not None else torch.empty((R, O), dtype=torch.float32, device=dev)
+    a = a if a is not None else torch.empty((R, O), dtype=torch.float32, device=dev)
+    _chk(y, "out"); _chk(a, "a")
+    if tuple(y.shape) != (R, O) or tuple(a.shape) != (R, O) or (mask is not None and tuple(_chk(mask, "mask").shape) != (R, O)):
+        raise _lib.PcgError(f"dense_rows_fwd_post: out, a and mask must be [{R}, {O}]")
+    if bn.save_mean is None:
+        bn.save_mean = torch.empty(O, dtype=torch.float32, device=dev)
+    if bn.save_invstd is None:
+        bn.save_invstd = torch.empty(O, dtype=torch.float32, device=dev)
+    nbt = bn.num_batches_tracked
+    if nbt is not None and nbt.dtype != torch.int64:
+        raise _lib.PcgError(f"dense_rows_fwd_post: num_batches_tracked must be int64, got {nbt.dtype}")
+    check(_lib.load().pcg_dense_rows_fwd_post(_p(x), _p(w), _p(bias), R, I, O, int(act), float(slope), _p(bn.gamma), _p(bn.beta),
+                                              _p(bn.running_mean), _p(bn.running_var), _p(nbt), bn.eps, bn.momentum, _p(mask),
+                                              1.0 / (1.0 - p), _p(a), _p(bn.save_mean), _p(bn.save_invstd), _p(y), _stream()),
+          "pcg_dense_rows_fwd_post")
+    return y, a
+
+
+def dense_rows_dgrad_post(dz, w, a, mean, invstd, gamma, dgamma, dbeta, act=_lib.ACT_LRELU, slope=0.0, mask=None, p=0.0, accumulate=False,
+                          out=None, db=None):
+    """dx = the whole backward of the post-activation stage below (Dropout, BatchNorm1d, activation, in this order) applied to
+    dz[R][O] w[O][I], in one launch (pcg_dense_rows_dgrad_post); a, mean, invstd as dense_rows_fwd_post left them; dgamma / dbeta are
+    written (accumulate: added to); db ([I], optional): so is the column sum of dx, the bias gradient of the stage's Linear."""
+    _chk(dz, "dz"); _chk(w, "w")
+    R, O = dz.shape
+    I = w.shape[1]
+    if w.shape[0] != O:
+        raise _lib.PcgError(f"dense_rows_dgrad_post: dz has {O} features, the weight has {w.shape[0]} rows")
+    dx = out if out is not None else torch.empty((R, I), dtype=torch.float32, device=dz.device)
+    _chk(dx, "out")
+    if tuple(dx.shape) != (R, I) or (a is not None and tuple(_chk(a, "a").shape) != (R, I)) or \
+            (mask is not None and tuple(_chk(mask, "mask").shape) != (R, I)):
+        raise _lib.PcgError(f"dense_rows_dgrad_post: out, a and mask must be [{R}, {I}]")
+    for t, name in ((mean, "mean"), (invstd, "invstd"), (gamma, "gamma"), (dgamma, "dgamma"), (dbeta, "dbeta"), (db, "db")):
+        if t is not None and (_chk(t, name).numel() != I):
+            raise _lib.PcgError(f"dense_rows_dgrad_post: {name} must have {I} entries")
+    check(_lib.load().pcg_dense_rows_dgrad_post(_p(dz), _p(w), R, O, I, _p(mask), 1.0 / (1.0 - p), _p(a), _p(mean), _p(invstd), _p(gamma),
+                                                int(act), float(slope), _p(dgamma), _p(dbeta), _p(db), int(bool(accumulate)), _p(dx), _stream()),
+          "pcg_dense_rows_dgrad_post")
+    return dx
+
+
 def linear_wgrad_grouped(items, B, device):
     """items: list of (dy, x, O, I, dW, db or None, ldy, ldx, accumulate_w, accumulate_b) — layers that reduce over the same B rows,
     all in one launch (the library tiles them for the matrix cores)."""
@@ -1466,6 +1521,29 @@ def cross_entropy_weighted_fwd_bwd(logits, target, class_weight, need_loss=True,
     return loss, dz
 
 
+def ce_weighted_tally(logits, target, class_weight, tally, seg=None, dlogits=None, seg_loss=None, dbias=None):
+    """nn.CrossEntropyLoss(weight=class_weight) per run of `seg` rows (None: one run) with the epoch bookkeeping in one launch
+    (pcg_ce_weighted_tally): tally (float64[3] on the device) += (sum of loss * rows, rows whose argmax is the target, rows).
+    dlogits ([B, K], one run only): the gradient of the mean; dbias ([K], with dlogits): its column sums, the bias gradient of the
+    logits layer; seg_loss (float32, one entry per run): the losses themselves."""
+    _chk(logits, "logits"); _chk_idx(target, logits.shape[-1], "target"); _chk(class_weight, "class_weight")
+    B, K = logits.shape
+    seg = B if seg is None else int(seg)
+    _chk(tally, "tally", torch.float64)
+    if tally.numel() < 3 or target.numel() != B or class_weight.numel() != K:
+        raise _lib.PcgError("ce_weighted_tally: tally must be float64[3], target [B], class_weight [K]")
+    if dlogits is not None and tuple(_chk(dlogits, "dlogits").shape) != (B, K):
+        raise _lib.PcgError(f"ce_weighted_tally: dlogits must be [{B}, {K}]")
+    if dbias is not None and _chk(dbias, "dbias").numel() != K:
+        raise _lib.PcgError(f"ce_weighted_tally: dbias must have {K} entries")
+    if seg_loss is not None and (seg < 1 or _chk(seg_loss, "seg_loss").numel() < (B + min(seg, B) - 1) // min(seg, B)):
+        raise _lib.PcgError("ce_weighted_tally: seg_loss needs one entry per segment")
+    check(_lib.load().pcg_ce_weighted_tally(_p(logits), _p(target), _p(class_weight), B, K, seg, _p(tally), _p(dlogits), _p(dbias),
+                                            _p(seg_loss), _stream()),
+          "pcg_ce_weighted_tally")
+    return tally
+
+
 def dropout_apply(x, mask, p, inner=1, C=None, out=None):
     """y = x * mask / (1 - p); mask one entry per element (inner=1) or per (sample, channel) of an NHWC activation (inner=HW)."""
     _chk(x, "x"); _chk(mask, "mask")
@@ -1682,6 +1760,38 @@ class DeviceRNG:
                                                         _p(src_out), _p(o_m), D, _p(zero_cols), nz, _p(o_n), T, self.seed, _p(oh_t), _p(oh_y),
                                                         _p(counter), _stream()), "pcg_house_batch_draws_counter")
         return out
+
+    def house_clf_batch(self, X, Y, perm, out, masks, keeps, counter=None, cursor=0):
+        """The classifier fit's batch and its three Dropout masks in ONE launch: rows perm[cursor .. cursor+B) of the resident training
+        set (X [N, D] float32, Y [N] int64) into out = (x [B, D], y [B]), and masks = (m0, m1, m2) ([B, width] each) with P(1) =
+        keeps[i] -- the values three bernoulli() calls give in this order.  By value (counter None): `cursor` is the first row and the
+        host offset advances.  counter (device_counter(device, cursor=True)): offset and cursor come from the device and the launch
+        advances them itself -- the form a HIP graph can capture; the host-side offset is not touched."""
+        o_x, o_y = out
+        B, D = o_x.shape
+        _chk(X, "X"); _chk(Y, "Y", torch.int64); _chk(perm, "perm", torch.int64); _chk(o_x, "x"); _chk(o_y, "y", torch.int64)
+        if len(masks) != 3 or len(keeps) != 3 or any(_chk(m, "mask").dim() != 2 or m.shape[0] != B for m in masks):
+            raise _lib.PcgError(f"house_clf_batch: three masks of {B} rows and three keep probabilities")
+        if X.shape[1] != D or Y.numel() != X.shape[0] or o_y.numel() != B or perm.numel() < B:
+            raise _lib.PcgError("house_clf_batch: X [N, D], Y [N], x [B, D], y [B], perm >= B entries")
+        args = [a for m, k in zip(masks, keeps) for a in (_p(m), m.shape[1], float(k))]
+        if counter is not None:
+            if counter.numel() < 4 or counter.dtype != torch.int64 or not counter.is_cuda:
+                raise _lib.PcgError("house_clf_batch: counter must be int64[4] on the device (device_counter(cursor=True))")
+            check(_lib.load().pcg_house_clf_batch_counter(_p(X), _p(Y), _p(perm), perm.numel(), X.shape[0], _p(o_x), _p(o_y), B, D, *args, self.seed,
+                                                          _p(counter), _stream()), "pcg_house_clf_batch_counter")
+            return out, masks
+        if cursor < 0 or cursor + B > perm.numel():
+            raise _lib.PcgError(f"house_clf_batch: rows {cursor} .. +{B} of a permutation of {perm.numel()} entries")
+        off = self._advance(self.house_clf_batch_span(B, [m.shape[1] for m in masks]))
+        check(_lib.load().pcg_house_clf_batch(_p(X), _p(Y), _p(perm), perm.numel(), X.shape[0], _p(o_x), _p(o_y), B, D, *args, self.seed, off,
+                                              int(cursor), _stream()), "pcg_house_clf_batch")
+        return out, masks
+
+    @staticmethod
+    def house_clf_batch_span(B, widths):
+        """Counter values one house_clf_batch call consumes."""
+        return sum((B * w + 3) // 4 for w in widths)
 
     @staticmethod
     def house_draws_span(B, D, T):
