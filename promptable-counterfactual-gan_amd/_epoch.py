@@ -32,12 +32,15 @@ def check_adam_pair(opt_G, opt_D):
         raise PcgError("TrainSteps: opt_G and opt_D must share betas and eps")
 
 
-def one_gpu(*nets):
-    """Flattens the nets; their common device."""
-    devs = {net.flat_params.device for net in nets}
-    if len(devs) != 1 or next(iter(devs)).type != "cuda":
-        raise PcgError("TrainSteps: the nets must be on one GPU")
-    return devs.pop()
+def one_gpu(*nets, who="TrainSteps"):
+    """The nets' common device, read from their parameters (nothing is flattened or moved): one GPU, or a refusal in `who`'s name."""
+    devs = {next(net.parameters()).device for net in nets}
+    if len(devs) != 1:
+        raise PcgError(f"{who}: the nets must be on one GPU, got {sorted(map(str, devs))}")
+    dev = devs.pop()
+    if dev.type != "cuda":
+        raise PcgError(f"{who}: the nets are on {dev}; libpcgan_hip has no CPU path")
+    return dev
 
 
 def resident(a, dtype, dev):

@@ -21,8 +21,9 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import ops
+from ._cfeval import confusion_csv
 from ._lib import ACT_LRELU, ACT_NONE, ACT_RELU, PcgError
-from .nn import weighted_sum, FlatModule, in_conv_precision
+from .nn import weighted_sum, FlatModule, FrozenClassifier, in_conv_precision
 from .optim import Adam
 
 
@@ -603,32 +604,7 @@ class Discriminator(FlatModule):
 
 
 # ---- frozen classifier -----------------------------------------------------------------------------------------------
-class _CFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, net, x):
-        logits, saved = net._run_forward(x)
-        ctx.net, ctx.saved = net, saved
-        return logits
-
-    @staticmethod
-    def backward(ctx, dlogits):
-        return None, ctx.net._run_backward(ctx.saved, dlogits)
-
-
-class _CTrainFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, net, x, masks, *params):
-        logits, saved = net._train_forward(x, masks)
-        ctx.net, ctx.saved = net, saved
-        return logits
-
-    @staticmethod
-    def backward(ctx, dlogits):
-        ctx.net._train_backward(ctx.saved, dlogits)
-        return (None,) * len(ctx.needs_input_grad)
-
-
-class CNNClassifier(FlatModule):
+class CNNClassifier(FrozenClassifier):
     """classifier.py:4-28.  In the GAN step it is frozen and in eval mode (main.py:30-33): forward and the gradient with
     respect to the input image, on packed weights.  In training mode (pre-training, trainer.py:8-39 — SURVEY.md section 8f
     item 3) it is a regular trainable net: Dropout2d(0.25) / Dropout(0.5) masks come from `self.rng` (a device Philox
@@ -638,8 +614,6 @@ class CNNClassifier(FlatModule):
 
     def __init__(self, num_classes=10):
         super().__init__()
-        self.rng = None
-        self.dropout_masks = None
         self.conv = nn.Sequential(
             nn.Conv2d(1, 32, 3, 1, 1), nn.ReLU(),
             nn.Conv2d(32, 64, 3, 2, 1), nn.ReLU(),
@@ -648,7 +622,6 @@ class CNNClassifier(FlatModule):
         )
         self.fc = nn.Sequential(nn.Flatten(), nn.Linear(128 * 7 * 7, 256), nn.ReLU(), nn.Dropout(0.5), nn.Linear(256, num_classes))
         self.num_classes = num_classes
-        self._packed = None
 
     def _pack(self):
         """NHWC / 4-aligned images of the frozen weights (rebuilt if the parameters change): conv weights OHWI; fc1 columns
@@ -673,29 +646,9 @@ class CNNClassifier(FlatModule):
         self._packed = (key, packed)
         return packed
 
-    def train(self, mode=True):
-        # the optimizer kernel updates parameters in place without touching torch's version counters: drop the packed eval
-        # image whenever the mode changes so that eval after training sees the new weights
-        self._packed = None
-        return super().train(mode)
-
-    def forward(self, x):
-        if not x.is_cuda:
-            raise PcgError(f"CNNClassifier: input is on {x.device}; libpcgan_hip has no CPU path")
-        if self.training:
-            self._ensure_flat()
-            B = x.shape[0]
-            masks = self.dropout_masks
-            if masks is None:
-                if self.rng is None:
-                    self.rng = ops.DeviceRNG(seed=0)
-                masks = [self.rng.bernoulli((B, 128), x.device, 0.75), self.rng.bernoulli((B, 256), x.device, 0.5)]
-            if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
-                return _CTrainFn.apply(self, x, masks, *self.parameters())
-            return self._train_forward(x, masks)[0]
-        if torch.is_grad_enabled() and x.requires_grad:
-            return _CFn.apply(self, x)
-        return self._run_forward(x, keep=False)[0]
+    def _draw_dropout_masks(self, x):
+        B = x.shape[0]
+        return [self.rng.bernoulli((B, 128), x.device, 0.75), self.rng.bernoulli((B, 256), x.device, 0.5)]
 
     # -- training mode (trainer.py:15-20) ------------------------------------------------------------------------------------
     @in_conv_precision
@@ -1340,9 +1293,7 @@ def evaluate_classifier(classifier, dataloader, device, save_dir=None, prefix="c
     if save_dir:
         os.makedirs(save_dir, exist_ok=True)
         with open(os.path.join(save_dir, f"{prefix}_confusion_matrix.csv"), "w") as f:
-            f.write("," + ",".join(f"pred_{j}" for j in range(K)) + "\n")
-            for i in range(K):
-                f.write(f"true_{i}," + ",".join(str(int(v)) for v in cm[i]) + "\n")
+            f.write(confusion_csv(cm))
     if verbose:
         print(f"{prefix} Test Accuracy: {acc:.4f}")
     return acc, cm

@@ -27,10 +27,11 @@ import torch
 import torch.nn as nn
 from torch.nn.utils import spectral_norm
 
-from . import ops
+from . import _cfeval, ops
+from ._cfeval import confusion_matrix, metric_rows, save_table, upload  # noqa: F401  (public here: the host side is _cfeval's)
 from ._lib import ACT_LRELU, ACT_NONE, ACT_RELU, PcgError
 from .countergan import CrossEntropyLoss, abs_mean, grad_norm  # noqa: F401  (same loss kernels)
-from .nn import FlatModule, affine_fwd, in_conv_precision, linear_dgrad as _lin_dgrad, linear_fwd as _lin_fwd, linear_wgrad as _lin_wgrad, mean, weighted_sum  # noqa: F401
+from .nn import FlatModule, FrozenClassifier, affine_fwd, in_conv_precision, linear_dgrad as _lin_dgrad, linear_fwd as _lin_fwd, linear_wgrad as _lin_wgrad, mean, weighted_sum  # noqa: F401
 from .optim import Adam
 
 FEATURES = ["bedrooms", "bathrooms", "sqft_living", "sqft_lot", "floors", "waterfront", "view", "condition", "grade",
@@ -614,32 +615,7 @@ class Discriminator(FlatModule):
 
 
 # ---- frozen classifier ------------------------------------------------------------------------------------------------
-class _CFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, net, x):
-        logits, saved = net._run_forward(x)
-        ctx.net, ctx.saved = net, saved
-        return logits
-
-    @staticmethod
-    def backward(ctx, dlogits):
-        return None, ctx.net._run_backward(ctx.saved, dlogits)
-
-
-class _CTrainFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, net, x, masks, *params):
-        logits, saved = net._train_forward(x, masks)
-        ctx.net, ctx.saved = net, saved
-        return logits
-
-    @staticmethod
-    def backward(ctx, dlogits):
-        ctx.net._train_backward(ctx.saved, dlogits)
-        return (None,) * len(ctx.needs_input_grad)
-
-
-class NNClassifier(FlatModule):
+class NNClassifier(FrozenClassifier):
     """nn_classifier.py:4-32.  In the GAN step: eval mode, parameters frozen (main.py:27-30) — forward and the gradient with
     respect to the input row; each BatchNorm1d is then a per-column affine map folded into the following Linear once (fp64 at
     pack time): 5 GEMMs and 4 LeakyReLUs.  In training mode (pre-training, trainer.py:18-180 — SURVEY.md section 8f item 3):
@@ -648,15 +624,12 @@ class NNClassifier(FlatModule):
 
     def __init__(self, input_dim, output_dim=4):
         super().__init__()
-        self.rng = None
-        self.dropout_masks = None
         self.net = nn.Sequential(
             nn.Linear(input_dim, 256), nn.LeakyReLU(0.1), nn.BatchNorm1d(256), nn.Dropout(0.3),
             nn.Linear(256, 256), nn.LeakyReLU(0.1), nn.BatchNorm1d(256), nn.Dropout(0.2),
             nn.Linear(256, 128), nn.LeakyReLU(0.1), nn.BatchNorm1d(128), nn.Dropout(0.1),
             nn.Linear(128, 64), nn.LeakyReLU(0.1), nn.BatchNorm1d(64),
             nn.Linear(64, output_dim))
-        self._packed = None
 
     def _pack(self):
         key = tuple((t.data_ptr(), t._version) for t in list(self.parameters()) + list(self.buffers()))
@@ -697,28 +670,8 @@ class NNClassifier(FlatModule):
             self._kmajor = km
         return self._kmajor
 
-    def train(self, mode=True):
-        # the optimizer kernel updates parameters in place without touching torch's version counters: drop the packed eval
-        # image whenever the mode changes so that eval after training sees the new weights
-        self._packed = None
-        return super().train(mode)
-
-    def forward(self, x):
-        if not x.is_cuda:
-            raise PcgError(f"NNClassifier: input is on {x.device}; libpcgan_hip has no CPU path")
-        if self.training:
-            self._ensure_flat()
-            masks = self.dropout_masks
-            if masks is None:
-                if self.rng is None:
-                    self.rng = ops.DeviceRNG(seed=0)
-                masks = [self.rng.bernoulli((x.shape[0], m_.out_features), x.device, 1.0 - p_) for m_, p_ in self._dropout_sites()]
-            if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
-                return _CTrainFn.apply(self, x, masks, *self.parameters())
-            return self._train_forward(x, masks)[0]
-        if torch.is_grad_enabled() and x.requires_grad:
-            return _CFn.apply(self, x)
-        return self._run_forward(x, keep=False)[0]
+    def _draw_dropout_masks(self, x):
+        return [self.rng.bernoulli((x.shape[0], m_.out_features), x.device, 1.0 - p_) for m_, p_ in self._dropout_sites()]
 
     # -- training mode ------------------------------------------------------------------------------------------------------------
     def _stages(self):
@@ -1132,7 +1085,7 @@ def compute_metrics_per_target(generator, classifier, X, y, config, gumbel_per_c
 
 # ---- prompted queries and evaluation in ONE launch (csrc/house_cf_eval.hip) -------------------------------------
 CF_ROW_OUTPUTS = ("cont", "logits", "chosen", "masked_residual", "x_cf", "x_cf_raw", "logits_cf", "logits_x", "pred_cf", "pred_x", "gain")
-METRIC_FIELDS = ("class_flip", "prediction_gain", "avg_actionability")
+METRIC_FIELDS = _cfeval.METRIC_FIELDS
 CF_TILE_ROWS = 16           # rows per workgroup of pcg_house_cf_eval: tiles never straddle a group
 CF_QUERY_GROUP = 256        # the group where the caller names no batch size (queries: no sums are read)
 _CF_FIELD = {"masked_residual": "masked"}                                     # the argument struct's names where they differ
@@ -1179,14 +1132,6 @@ def _cf_nets(generator, classifier):
         raise PcgError(f"pcg_house_cf_eval is built for the classifier widths {_CF_CLS_DIMS}, got {dims}")
 
 
-def _cf_rows(x, what="x"):
-    if not torch.is_tensor(x):
-        x = torch.as_tensor(np.asarray(x), dtype=torch.float32)
-    if x.dim() != 2 or x.shape[1] != 17 or x.shape[0] < 1 or not x.dtype.is_floating_point:
-        raise PcgError(f"{what} must be [N][17] floats with N >= 1, got {tuple(x.shape)} {x.dtype}")
-    return x.detach()
-
-
 def _cf_mask(mask, config, N):
     """None: prompt_mask(config); a [17] vector (broadcast) or [N][17] (one mask per row).  Returns (float32 tensor, per-row flag)."""
     if mask is None:
@@ -1211,16 +1156,6 @@ def _cf_given_noise(generator, gumbel, T, N):
     if tuple(gumbel.shape) != (T, N, Tc):
         raise PcgError(f"gumbel noise must be [{T}][{N}][{Tc}]" + (f" or [{N}][{Tc}]" if T == 1 else "") + f", got {tuple(gumbel.shape)}")
     return gumbel.detach().to(torch.float32)
-
-
-def _cf_device(generator, classifier):
-    devs = {next(generator.parameters()).device, next(classifier.parameters()).device}
-    if len(devs) != 1:
-        raise PcgError("the generator and the classifier must be on one GPU")
-    dev = devs.pop()
-    if dev.type != "cuda":
-        raise PcgError(f"the generator and the classifier are on {dev}; libpcgan_hip has no CPU path")
-    return dev
 
 
 def _cf_launch(generator, classifier, x, config, T, group, outputs, noise, mask, mask_rows, target=None, y=None, clamp_cls=False,
@@ -1296,26 +1231,17 @@ def counterfactuals(generator, classifier, x, target, config, mask=None, gumbel=
     gumbel: the hard Gumbel-softmax noise [N][Tcat] (or a dict idx -> [N][n]); None: one draw from rng / generator.rng.  Both nets
     must be in eval mode.  ONE launch.  Returns a dict of device tensors, the names of CF_ROW_OUTPUTS, leading dimension N."""
     _cf_nets(generator, classifier)
-    x = _cf_rows(x)
+    x = _cfeval.rows_arg(x, 17, floats_only=True, detach=True)[0]
     N = x.shape[0]
-    if isinstance(target, (int, np.integer)) and not isinstance(target, bool):
-        target = torch.full((N,), int(target), dtype=torch.int64)
-    else:
-        target = target.detach() if torch.is_tensor(target) else torch.as_tensor(np.asarray(target))
-        if tuple(target.shape) != (N,) or target.dtype.is_floating_point or target.dtype == torch.bool:
-            raise PcgError(f"target must be an int or [N] integers (N = {N}), got {tuple(target.shape)} {target.dtype}")
-    lo, hi = int(target.min()), int(target.max())                              # it selects the one-hot input: refused on the host
-    if lo < 0 or hi >= generator.num_classes:
-        raise PcgError(f"targets must lie in [0, {generator.num_classes}), got [{lo}, {hi}]")
+    target = _cfeval.targets_arg(target, N, generator.num_classes, refuse_bool=True)
     mask, mask_rows = _cf_mask(mask, config, N)
     noise = _cf_given_noise(generator, gumbel, 1, N)
-    dev = _cf_device(generator, classifier)
+    dev = _cfeval.one_gpu(generator, classifier, who="house evaluation")
     with torch.no_grad():
         if noise is None:
             noise = _cf_draw(generator, rng, (1, N, generator.total_cat), dev)
-        out = _cf_launch(generator, classifier, x.to(dev, torch.float32).contiguous(), config, 1, CF_QUERY_GROUP, CF_ROW_OUTPUTS,
-                         noise.to(dev).contiguous(), mask.to(dev).contiguous(), mask_rows, target=target.to(dev, torch.int64).contiguous(),
-                         clamp_cls=True)
+        out = _cf_launch(generator, classifier, upload(x, dev), config, 1, CF_QUERY_GROUP, CF_ROW_OUTPUTS, upload(noise, dev),
+                         upload(mask, dev), mask_rows, target=upload(target, dev, torch.int64), clamp_cls=True)
     return {k: (v if k in ("logits_x", "pred_x") else v[0]) for k, v in out.items()}
 
 
@@ -1329,27 +1255,21 @@ def counterfactual_sweep(generator, classifier, X, y=None, config=CONFIG, mask=N
     and "class_counts" [4][n_tiles][4] (per source class; needs y), and the per-row `outputs` asked for ([4][N]...; logits_x,
     pred_x [N]...)} as device tensors."""
     _cf_nets(generator, classifier)
-    X = _cf_rows(X, "X")
+    X = _cfeval.rows_arg(X, 17, "X", floats_only=True, detach=True)[0]
     N, T = X.shape[0], generator.num_classes
     group = _cf_group(batch_size, config)
-    bad = [o for o in outputs if o not in CF_ROW_OUTPUTS]
-    if bad:
-        raise PcgError(f"outputs {bad} are not among {CF_ROW_OUTPUTS}")
-    if y is not None:
-        y = y.detach() if torch.is_tensor(y) else torch.as_tensor(np.asarray(y))
-        if tuple(y.shape) != (N,) or y.dtype.is_floating_point:
-            raise PcgError(f"y must be [N] integers (N = {N}), got {tuple(y.shape)} {y.dtype}")
-    elif class_sums:
+    _cfeval.check_outputs(outputs, CF_ROW_OUTPUTS)
+    y = _cfeval.labels_arg(y, N)
+    if y is None and class_sums:
         raise PcgError("class_sums splits the rows by their class: y is required")
     mask, mask_rows = _cf_mask(mask, config, N)
     noise = _cf_given_noise(generator, gumbel, T, N)
-    dev = _cf_device(generator, classifier)
+    dev = _cfeval.one_gpu(generator, classifier, who="house evaluation")
     with torch.no_grad():
         if noise is None:
             noise = _cf_draw(generator, rng, (T, N, generator.total_cat), dev)
-        return _cf_launch(generator, classifier, X.to(dev, torch.float32).contiguous(), config, T, group, tuple(outputs),
-                          noise.to(dev).contiguous(), mask.to(dev).contiguous(), mask_rows,
-                          y=None if y is None else y.to(dev, torch.int64).contiguous(), clamp_cls=clamp_cls, tile_sums=True,
+        return _cf_launch(generator, classifier, upload(X, dev), config, T, group, tuple(outputs), upload(noise, dev), upload(mask, dev),
+                          mask_rows, y=None if y is None else upload(y, dev, torch.int64), clamp_cls=clamp_cls, tile_sums=True,
                           class_sums=class_sums)
 
 
@@ -1379,17 +1299,7 @@ def metrics_from_sums(tile_sums, group):
     g = fold_tiles(tile_sums, group)
     if g.ndim != 3 or g.shape[2] != 4:
         raise PcgError(f"metrics_from_sums: tile_sums must be [T][n_tiles][4], got {np.shape(tile_sums)}")
-    out = np.full((g.shape[0], 3), np.nan)
-    for t in range(g.shape[0]):
-        r = g[t][g[t][:, 0] > 0]
-        if len(r):
-            out[t] = (np.mean(r[:, 1] / r[:, 0]), np.mean(r[:, 2] / r[:, 0]), np.mean(r[:, 3] / (17 * r[:, 0])))
-    return out
-
-
-def metric_rows(table):
-    """[T][3] -> the rows of the reference's DataFrame (eval_utils.py:274-279) as a list of dicts."""
-    return [dict({"target_class": t}, **{k: float(v) for k, v in zip(METRIC_FIELDS, row)}) for t, row in enumerate(table)]
+    return _cfeval.batch_mean_metrics(g, 17)
 
 
 def _metrics_one_launch(generator, classifier, X, y, config, gumbel_per_call, rng, max_vis):
@@ -1400,13 +1310,13 @@ def _metrics_one_launch(generator, classifier, X, y, config, gumbel_per_call, rn
     num_classes = int(np.unique(y_np).size)
     generator.eval(); classifier.eval()
     _cf_nets(generator, classifier)
-    X_t = _cf_rows(X_t, "X")
+    X_t = _cfeval.rows_arg(X_t, 17, "X", floats_only=True, detach=True)[0]
     N, Tc = X_t.shape[0], generator.total_cat
     if y_np.shape != (N,) or num_classes != generator.num_classes or y_np.min() < 0 or y_np.max() >= num_classes:
         raise PcgError(f"y must be [N] labels covering the generator's {generator.num_classes} classes, got shape {y_np.shape}, "
                        f"{num_classes} distinct values")
     bs = _cf_group(None, config)
-    dev = _cf_device(generator, classifier)
+    dev = _cfeval.one_gpu(generator, classifier, who="house evaluation")
     if gumbel_per_call is None and generator.rng is None:
         generator.rng = rng if rng is not None else ops.DeviceRNG(seed=0)
     noise_it = iter(gumbel_per_call) if gumbel_per_call is not None else None
@@ -1435,7 +1345,7 @@ def _metrics_one_launch(generator, classifier, X, y, config, gumbel_per_call, rn
                 done += n_sel
             if len(rows_t):
                 noise[t].index_copy_(0, torch.from_numpy(rows_t).to(dev), torch.cat(parts) if noise_it is not None else stage)
-        res = _cf_launch(generator, classifier, X_t.to(dev).contiguous(), config, num_classes, bs, ("x_cf_raw",), noise,
+        res = _cf_launch(generator, classifier, upload(X_t, dev), config, num_classes, bs, ("x_cf_raw",), noise,
                          torch.from_numpy(prompt_mask(config)).to(dev), False, y=torch.from_numpy(y_np.astype(np.int64)).to(dev),
                          tile_sums=True)
         table = metrics_from_sums(res["tile_sums"].cpu().numpy(), bs)          # the one read of the sums
@@ -1492,15 +1402,6 @@ def analyze_feature_shift_importance(X_orig, X_cf, feature_names, scaler=None):
     return rows
 
 
-def confusion_matrix(y_true, y_pred):
-    """sklearn.metrics.confusion_matrix(y_true, y_pred): labels = the sorted values that occur in either, rows true, columns predicted."""
-    y_true, y_pred = np.asarray(y_true), np.asarray(y_pred)
-    labels = np.unique(np.concatenate([y_true, y_pred]))
-    cm = np.zeros((len(labels), len(labels)), dtype=np.int64)
-    np.add.at(cm, (np.searchsorted(labels, y_true), np.searchsorted(labels, y_pred)), 1)
-    return cm
-
-
 def weighted_scores(cm):
     """Pure host.  accuracy and sklearn's precision / recall / f1 with average='weighted', zero_division=0, from a confusion matrix
     (rows true, columns predicted): per class tp / column sum, tp / row sum and their harmonic mean (0 where a denominator is 0),
@@ -1538,20 +1439,6 @@ def evaluate_classifier(classifier, X_test, y_test, class_names=None):
               for i in range(len(labels))]
     lines.append(f"{'weighted avg':>12} {sc['precision']:9.4f} {sc['recall']:9.4f} {sc['f1']:9.4f} {int(pc['support'].sum()):9d}")
     return dict(sc, confusion_matrix=cm, report="\n".join(lines) + "\n")
-
-
-def _csv_value(v):
-    return "" if isinstance(v, float) and np.isnan(v) else (repr(v) if isinstance(v, float) else str(v))
-
-
-def save_table(rows, save_path, columns):
-    """DataFrame.to_csv(index=False) of a list of dicts: shortest float repr, nan as an empty field (eval_utils.py:667-670)."""
-    import os
-    os.makedirs(os.path.dirname(save_path) or ".", exist_ok=True)
-    with open(save_path, "w") as f:
-        f.write(",".join(columns) + "\n")
-        for r in rows:
-            f.write(",".join(_csv_value(r[c]) for c in columns) + "\n")
 
 
 def evaluate_pipeline(generator, classifier, X_test, y_test, config):

@@ -23,7 +23,6 @@ not provided — training goes through train_countergan / TrainSteps.  The evalu
 its CSV files with plain Python (no pandas / scikit-learn on the product path); the plots are left out.
 """
 import ctypes
-import math
 import os
 
 import numpy as np
@@ -31,7 +30,8 @@ import torch
 import torch.nn as nn
 from torch.nn.utils import spectral_norm
 
-from . import _epoch, ops
+from . import _cfeval, _epoch, ops
+from ._cfeval import confusion_csv, confusion_matrix, metric_rows, upload  # noqa: F401  (public here: the host side is _cfeval's)
 from ._epoch import no_autograd, on_gpu
 from ._lib import (MoonsCfDesc, MoonsCfEvalArgs, MoonsCfFwdArgs, MoonsCfTrainArgs, MoonsClfFitArgs, MoonsClfFitDesc, PcgError,
                    load as _lib_load)
@@ -305,9 +305,7 @@ class ClassifierFit:
             raise PcgError("ClassifierFit: the fused step implements pcgan_amd.optim.Adam only")
         if len(opt.param_groups) != 1 or opt.param_groups[0]["weight_decay"] != 0.0 or opt.param_groups[0].get("amsgrad", False):
             raise PcgError("ClassifierFit: the optimizer must be one parameter group with weight decay 0 and no amsgrad")
-        if any(not p.is_cuda for p in clf.parameters()):
-            raise PcgError("ClassifierFit: the classifier is on the CPU; libpcgan_hip has no CPU path")
-        dev = _epoch.one_gpu(clf)
+        dev = _epoch.one_gpu(clf, who="ClassifierFit")
         self.clf, self.device, self.N = clf, dev, X.shape[0]
         self.X, self.Y = _epoch.resident(X, torch.float32, dev), _epoch.resident(y, torch.int64, dev)
         self.opt, self.seg = opt, opt.flat_segment(clf, "ClassifierFit")
@@ -549,7 +547,7 @@ MASKS = {                                                                     # 
     "x_only": np.array([1, 0], dtype=np.float32),
     "y_only": np.array([0, 1], dtype=np.float32),
 }
-METRIC_FIELDS = ("class_flip", "prediction_gain", "avg_actionability")
+METRIC_FIELDS = _cfeval.METRIC_FIELDS
 ROW_OUTPUTS = ("raw_residual", "masked_residual", "x_cf", "logits_cf", "logits_x", "pred_cf", "pred_x", "gain")
 EVAL_GROUP = 256        # rows per workgroup where the caller names no batch size (queries, the classifier alone)
 _OUT_FIELD = {"raw_residual": "raw", "masked_residual": "masked"}             # the argument struct's names where they differ
@@ -571,27 +569,10 @@ def _mask_vector(mask, what="mask"):
     return m
 
 
-def _rows_arg(x, what="x"):
-    """[N][2] rows, a tensor or an ndarray: the shape is checked on the host.  Returns (rows, given as a tensor)."""
-    given = torch.is_tensor(x)
-    if not given:
-        x = torch.as_tensor(np.asarray(x), dtype=torch.float32)
-    if x.dim() != 2 or x.shape[1] != INPUT_DIM or x.shape[0] < 1:
-        raise PcgError(f"{what} must be [N][{INPUT_DIM}] with N >= 1, got {tuple(x.shape)}")
-    return x, given
-
-
 def _eval_dims(generator, classifier):
     if generator is not None:
         _check_dims(generator.input_dim, generator.hidden_dim, generator.num_classes, clf_hidden=classifier.hidden_dim)
     _check_dims(classifier.input_dim, HIDDEN_DIMS[0], classifier.num_classes, clf_hidden=classifier.hidden_dim)
-
-
-def _eval_device(*nets):
-    devs = {n.flat_params.device for n in nets}                               # (flattening refuses parameters on the CPU)
-    if len(devs) != 1:
-        raise PcgError("the generator and the classifier must be on one GPU")
-    return devs.pop()
 
 
 def _eval_launch(generator, classifier, x, group, outputs, y=None, masks=None, target=None, row_mask=None, sums=False):
@@ -628,14 +609,10 @@ def _eval_launch(generator, classifier, x, group, outputs, y=None, masks=None, t
     return out
 
 
-def _upload(x, dev, dtype=torch.float32):
-    return x.to(dev, dtype).contiguous()
-
-
 def _guard(nets, x, given, *others):
     """The module forwards' guards: a tensor input must already be on the GPU (an ndarray is uploaded), the nets must be there, and
     nothing may ask for autograd."""
-    dev = _eval_device(*nets)
+    dev = _epoch.one_gpu(*nets, who="moons_countergan evaluation")
     for net in nets:
         if given:
             on_gpu(net, x)
@@ -649,7 +626,7 @@ def counterfactuals(generator, classifier, x, target, mask):
     sets it).  One launch.  Returns device tensors: x_cf, masked_residual, raw_residual [N][2], logits_cf, logits_x [N][3], pred_cf,
     pred_x [N] (int64), gain [N] = softmax(logits_cf)[target] - softmax(logits_x)[target]."""
     _eval_dims(generator, classifier)
-    x, given = _rows_arg(x)
+    x, given = _cfeval.rows_arg(x, INPUT_DIM)
     N = x.shape[0]
     if mask is not None and not isinstance(mask, str) and np.ndim(mask) == 2:
         row_mask = mask if torch.is_tensor(mask) else torch.as_tensor(np.asarray(mask), dtype=torch.float32)
@@ -657,18 +634,10 @@ def counterfactuals(generator, classifier, x, target, mask):
             raise PcgError(f"mask must be a name from MASKS, a ({INPUT_DIM},) vector or [N][{INPUT_DIM}] (N = {N}), got {tuple(row_mask.shape)}")
     else:
         row_mask = torch.from_numpy(np.ascontiguousarray(np.broadcast_to(_mask_vector(mask), (N, INPUT_DIM))))
-    if isinstance(target, (int, np.integer)):
-        target = torch.full((N,), int(target), dtype=torch.int64)
-    else:
-        target = target if torch.is_tensor(target) else torch.as_tensor(np.asarray(target))
-        if tuple(target.shape) != (N,) or target.dtype.is_floating_point or target.dtype == torch.bool:
-            raise PcgError(f"target must be an int or [N] integers (N = {N}), got {tuple(target.shape)} {target.dtype}")
-    lo, hi = int(target.min()), int(target.max())                             # it selects the one-hot input: refused on the host
-    if lo < 0 or hi >= NUM_CLASSES:
-        raise PcgError(f"targets must lie in [0, {NUM_CLASSES}), got [{lo}, {hi}]")
+    target = _cfeval.targets_arg(target, N, NUM_CLASSES)
     dev = _guard((generator, classifier), x, given, row_mask)
-    return _eval_launch(generator, classifier, _upload(x, dev), EVAL_GROUP, ROW_OUTPUTS, target=_upload(target, dev, torch.int64),
-                        row_mask=_upload(row_mask, dev))
+    return _eval_launch(generator, classifier, upload(x, dev), EVAL_GROUP, ROW_OUTPUTS, target=upload(target, dev, torch.int64),
+                        row_mask=upload(row_mask, dev))
 
 
 def counterfactual_sweep(generator, classifier, X, y=None, masks=MASKS, batch_size=64, outputs=()):
@@ -678,7 +647,7 @@ def counterfactual_sweep(generator, classifier, X, y=None, masks=MASKS, batch_si
     rows, rows with pred_cf == target, sum of gain, sum of |masked residual| over both features), and the per-row `outputs` asked for
     (names of ROW_OUTPUTS; [M][3][N]..., logits_x / pred_x [N]...)} as device tensors.  Eval mode is the caller's to set."""
     _eval_dims(generator, classifier)
-    X, given = _rows_arg(X, "X")
+    X, given = _cfeval.rows_arg(X, INPUT_DIM, "X")
     N = X.shape[0]
     vecs = [_mask_vector(m) for m in (masks.values() if isinstance(masks, dict) else masks)]
     if not vecs:
@@ -686,35 +655,18 @@ def counterfactual_sweep(generator, classifier, X, y=None, masks=MASKS, batch_si
     group = int(batch_size)
     if group < 1:
         raise PcgError(f"batch_size must be positive, got {batch_size}")
-    bad = [o for o in outputs if o not in ROW_OUTPUTS]
-    if bad:
-        raise PcgError(f"outputs {bad} are not among {ROW_OUTPUTS}")
-    if y is not None:
-        y = y if torch.is_tensor(y) else torch.as_tensor(np.asarray(y))
-        if tuple(y.shape) != (N,) or y.dtype.is_floating_point:
-            raise PcgError(f"y must be [N] integers (N = {N}), got {tuple(y.shape)} {y.dtype}")
+    _cfeval.check_outputs(outputs, ROW_OUTPUTS)
+    y = _cfeval.labels_arg(y, N)
     dev = _guard((generator, classifier), X, given)
-    return _eval_launch(generator, classifier, _upload(X, dev), group, tuple(outputs), y=None if y is None else _upload(y, dev, torch.int64),
-                        masks=_upload(torch.from_numpy(np.stack(vecs)), dev), sums=True)
+    return _eval_launch(generator, classifier, upload(X, dev), group, tuple(outputs), y=None if y is None else upload(y, dev, torch.int64),
+                        masks=upload(torch.from_numpy(np.stack(vecs)), dev), sums=True)
 
 
 def metrics_from_sums(sums):
     """Pure host.  sums [..., n_groups, 4] -> [..., 3] (METRIC_FIELDS) as eval_utils.py:83-103 forms them: per group with a row in
     it the mean over its rows (actionability over both features: / (2 count)), then np.mean over those groups — the mean of the
     per-batch means, so rows of a short batch weigh more.  No such group: nan."""
-    s = np.asarray(sums, dtype=np.float64)
-    out = np.full(s.shape[:-2] + (3,), np.nan)
-    for idx in np.ndindex(*s.shape[:-2]):
-        g = s[idx]
-        g = g[g[:, 0] > 0]
-        if len(g):
-            out[idx] = (np.mean(g[:, 1] / g[:, 0]), np.mean(g[:, 2] / g[:, 0]), np.mean(g[:, 3] / (INPUT_DIM * g[:, 0])))
-    return out
-
-
-def metric_rows(table):
-    """[3 targets][3] -> the rows of the reference's DataFrame as a list of dicts."""
-    return [dict({"target_class": t}, **{k: float(v) for k, v in zip(METRIC_FIELDS, row)}) for t, row in enumerate(table)]
+    return _cfeval.batch_mean_metrics(sums, INPUT_DIM)
 
 
 def compute_metrics_per_target(generator, classifier, X, y, config, mask=None):
@@ -736,26 +688,10 @@ def compute_metrics_per_target(generator, classifier, X, y, config, mask=None):
 
 
 def _classify(classifier, X):
-    X, given = _rows_arg(X, "X")
+    X, given = _cfeval.rows_arg(X, INPUT_DIM, "X")
     _eval_dims(None, classifier)
     dev = _guard((classifier,), X, given)
-    return _eval_launch(None, classifier, _upload(X, dev), EVAL_GROUP, ("pred_x",))["pred_x"]
-
-
-def confusion_matrix(y_true, y_pred):
-    """sklearn.metrics.confusion_matrix(y_true, y_pred): labels = the sorted values that occur in either, rows true, columns predicted."""
-    y_true, y_pred = np.asarray(y_true), np.asarray(y_pred)
-    labels = np.unique(np.concatenate([y_true, y_pred]))
-    cm = np.zeros((len(labels), len(labels)), dtype=np.int64)
-    np.add.at(cm, (np.searchsorted(labels, y_true), np.searchsorted(labels, y_pred)), 1)
-    return cm
-
-
-def confusion_csv(cm):
-    """The text of eval_utils.py:21-25's DataFrame.to_csv: a header of pred_j columns, one true_i row per class."""
-    lines = ["," + ",".join(f"pred_{j}" for j in range(cm.shape[1]))]
-    lines += [f"true_{i}," + ",".join(str(int(v)) for v in row) for i, row in enumerate(cm)]
-    return "\n".join(lines) + "\n"
+    return _eval_launch(None, classifier, upload(X, dev), EVAL_GROUP, ("pred_x",))["pred_x"]
 
 
 def evaluate_classifier(clf, X_test, y_test, config):
@@ -787,17 +723,9 @@ def decision_regions(classifier, X, n=200, pad=0.1):
     return xx, yy, Z.reshape(xx.shape)
 
 
-def _csv_value(v):
-    return "" if isinstance(v, float) and math.isnan(v) else (repr(v) if isinstance(v, float) else str(v))
-
-
 def save_metrics(rows, save_path, columns=("target_class",) + METRIC_FIELDS):
     """eval_utils.py:187-190: the rows as CSV (DataFrame.to_csv(index=False): shortest float repr, nan as an empty field)."""
-    os.makedirs(os.path.dirname(save_path), exist_ok=True)
-    with open(save_path, "w") as f:
-        f.write(",".join(columns) + "\n")
-        for r in rows:
-            f.write(",".join(_csv_value(r[c]) for c in columns) + "\n")
+    _cfeval.save_table(rows, save_path, columns)
     print(f"Saved metrics to {save_path}")
 
 

@@ -158,6 +158,70 @@ class FlatModule(nn.Module):
         return self._gflat
 
 
+# ---- frozen classifier ------------------------------------------------------------------------------------------------
+class _CFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, net, x):
+        logits, saved = net._run_forward(x)
+        ctx.net, ctx.saved = net, saved
+        return logits
+
+    @staticmethod
+    def backward(ctx, dlogits):
+        return None, ctx.net._run_backward(ctx.saved, dlogits)
+
+
+class _CTrainFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, net, x, masks, *params):
+        logits, saved = net._train_forward(x, masks)
+        ctx.net, ctx.saved = net, saved
+        return logits
+
+    @staticmethod
+    def backward(ctx, dlogits):
+        ctx.net._train_backward(ctx.saved, dlogits)
+        return (None,) * len(ctx.needs_input_grad)
+
+
+class FrozenClassifier(FlatModule):
+    """The host scaffold of the CounteRGAN classifiers (countergan.CNNClassifier, house.NNClassifier).  In the GAN step such a net is
+    frozen and in eval mode: `_run_forward(x, keep)` -> (logits, saved) on a packed image of the weights (`self._packed`), and
+    `_run_backward(saved, dlogits)` -> the gradient with respect to the input.  In training mode (its pre-training) it is a regular
+    trainable net: `_train_forward(x, masks)` -> (logits, saved), `_train_backward(saved, dlogits)` into the flat gradient buffer; the
+    Dropout masks are `self.dropout_masks` (runs that must reproduce given draws) or `_draw_dropout_masks(x)` from `self.rng`, a
+    device Philox stream (seed 0 unless one was set).  A subclass supplies those five methods and `_pack`."""
+
+    def __init__(self):
+        super().__init__()
+        self.rng = None
+        self.dropout_masks = None
+        self._packed = None
+
+    def train(self, mode=True):
+        # the optimizer kernel updates parameters in place without touching torch's version counters: drop the packed eval
+        # image whenever the mode changes so that eval after training sees the new weights
+        self._packed = None
+        return super().train(mode)
+
+    def forward(self, x):
+        if not x.is_cuda:
+            raise PcgError(f"{type(self).__name__}: input is on {x.device}; libpcgan_hip has no CPU path")
+        if self.training:
+            self._ensure_flat()
+            masks = self.dropout_masks
+            if masks is None:
+                if self.rng is None:
+                    self.rng = ops.DeviceRNG(seed=0)
+                masks = self._draw_dropout_masks(x)
+            if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+                return _CTrainFn.apply(self, x, masks, *self.parameters())
+            return self._train_forward(x, masks)[0]
+        if torch.is_grad_enabled() and x.requires_grad:
+            return _CFn.apply(self, x)
+        return self._run_forward(x, keep=False)[0]
+
+
 # ---------------------------------------------------------------------------------------------------
 class _LinearAsConv:
     """nn.Linear seen as a 1x1 convolution on a [B, 1, 1, F] activation: its [out, in] weight is already OHWI."""
