@@ -1079,6 +1079,26 @@ int pcg_tune_set(const char* name, int32_t value);
  * 72 k-tiles over 512 ranges", "GEMM + col2im: ...", "4 phases: stream-K over unequal phases: ..."): the host-side launch planning,
  * no device needed.  op: 0 forward, 1 grad-input, 2 grad-weight; assume_scratch != 0: plan as if the stream had stream-K scratch. */
 int pcg_conv_plan_describe(const pcg_conv_geom* g, int32_t op, int32_t assume_scratch, char* out, size_t out_bytes);
+/* Which route a non-convolution launch takes, as text — the host-side switches of csrc/tabular.hip, cf_ops.hip and pointwise.hip,
+ * evaluated by the predicates the launchers themselves call; no device needed.  args holds n_args integers:
+ *   PCG_PLAN_GEMM_ACT, PCG_PLAN_GEMM  (transA, transB, M, N, K)   "rowdot<4>: 129 blocks" | "skinny: 33 blocks, two columns per thread,
+ *                                      62784 bytes of LDS" | "64x64 tiles: 1 x 8" (grid x, y).  pcg_gemm has no skinny launch.
+ *   PCG_PLAN_LINEAR_WGRAD             (B, O, I)                   "64x64 tiles: 1, slabs: 2 of 64 rows"
+ *   PCG_PLAN_LINEAR_WGRAD_GROUPED     (B)                         "blocks per tile: 2, rows per wave: 64"
+ *   PCG_PLAN_MEAN, PCG_PLAN_ABS_MEAN  (n)                         "one block of 1024" | "64 partials + finish" (256 for abs_mean)
+ *   PCG_PLAN_CROSS_ENTROPY            (B, K, logits 16-byte aligned, dlogits absent or 16-byte aligned)
+ *                                                                 "256 threads, float4 rows" | "1024 threads, no float4 rows" | ...
+ *   PCG_PLAN_EMBED_CONCAT_BWD         (B, has_dtable, has_dx)     "batch-split table gradient + copy" | "batch-split table gradient" |
+ *                                                                 "one pass"
+ *   PCG_PLAN_ACT                      (n, every pointer 16-byte aligned)   pcg_act_fwd / pcg_act_bwd:
+ *                                                                 "float4 lanes: 8192 blocks of 256: 2 passes" | "scalar lanes: ..."
+ *   PCG_PLAN_ELEMENTWISE              (family, n work items)      the grid-stride launch of one thread per item, "4096 blocks of 256:
+ *                                      2 passes"; family: PCG_PLAN_EW_TABULAR (tabular.hip), PCG_PLAN_EW_CF_OPS (cf_ops.hip),
+ *                                      PCG_PLAN_EW_POINTWISE (pcg_add_bias_rows), PCG_PLAN_EW_GATHER_CHANNEL (pcg_gather_channel)  */
+enum { PCG_PLAN_GEMM_ACT = 0, PCG_PLAN_GEMM = 1, PCG_PLAN_LINEAR_WGRAD = 2, PCG_PLAN_LINEAR_WGRAD_GROUPED = 3, PCG_PLAN_MEAN = 4,
+       PCG_PLAN_ABS_MEAN = 5, PCG_PLAN_CROSS_ENTROPY = 6, PCG_PLAN_EMBED_CONCAT_BWD = 7, PCG_PLAN_ACT = 8, PCG_PLAN_ELEMENTWISE = 9 };
+enum { PCG_PLAN_EW_TABULAR = 0, PCG_PLAN_EW_CF_OPS = 1, PCG_PLAN_EW_POINTWISE = 2, PCG_PLAN_EW_GATHER_CHANNEL = 3 };
+int pcg_launch_plan_describe(int32_t op, const int64_t* args, int32_t n_args, char* out, size_t out_bytes);
 size_t pcg_conv_scratch_parts_bytes(void);
 size_t pcg_conv_scratch_arrivals_bytes(void);
 int pcg_conv_set_scratch(pcg_stream_t stream, void* parts, size_t parts_bytes, void* arrivals, size_t arrivals_bytes);

@@ -15,6 +15,10 @@ LIB_PATH = os.environ.get("PCG_LIB") or os.path.join(_HERE, "libpcgan_hip.so")  
 
 PCG_OK = 0
 ACT_NONE, ACT_RELU, ACT_LRELU, ACT_TANH, ACT_SIGMOID = 0, 1, 2, 3, 4
+# pcg_launch_plan_describe: ops and element-wise families (include/pcgan_hip.h)
+(PLAN_GEMM_ACT, PLAN_GEMM, PLAN_LINEAR_WGRAD, PLAN_LINEAR_WGRAD_GROUPED, PLAN_MEAN, PLAN_ABS_MEAN, PLAN_CROSS_ENTROPY,
+ PLAN_EMBED_CONCAT_BWD, PLAN_ACT, PLAN_ELEMENTWISE) = range(10)
+PLAN_EW_TABULAR, PLAN_EW_CF_OPS, PLAN_EW_POINTWISE, PLAN_EW_GATHER_CHANNEL = range(4)
 
 
 class PcgError(RuntimeError):
@@ -269,6 +273,7 @@ PROTOTYPES = {
     "pcg_tune_set": (_i, [_c.c_char_p, _i32]),
     "pcg_debug_stamp_buffer": (_i, [_vp, _i64]),
     "pcg_conv_plan_describe": (_i, [_c.POINTER(ConvGeom), _i32, _i32, _c.c_char_p, _sz]),
+    "pcg_launch_plan_describe": (_i, [_i32, _c.POINTER(_i64), _i32, _c.c_char_p, _sz]),
     "pcg_conv_scratch_parts_bytes": (_sz, []),
     "pcg_conv_scratch_arrivals_bytes": (_sz, []),
     "pcg_conv_set_scratch": (_i, [_vp, _vp, _sz, _vp, _sz]),

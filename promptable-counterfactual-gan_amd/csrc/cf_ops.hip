@@ -3,16 +3,13 @@
 // softmax cross-entropy.  All are small HBM-bound streaming kernels; reductions are fixed-order (reproducible).
 // Reference call sites are cited next to each prototype in include/pcgan_hip.h.
 #include "pcg_common.h"
+#include "launch_plan.h"
 
 namespace pcg {
 namespace {
 
-unsigned ew_blocks(size_t n) {
-  size_t b = (n + 255) / 256;
-  if (b > 8192) b = 8192;
-  if (b < 1) b = 1;
-  return (unsigned)b;
-}
+constexpr unsigned EW_MAX_BLOCKS = 8192;
+unsigned ew_blocks(size_t n) { return ew_grid(n, EW_MAX_BLOCKS); }
 
 // out[b][p][0] = x[b][p] ; out[b][p][1] = table[idx[b]][p] ; out[b][p][2] = mask[b][p] (C == 3)
 __global__ void __launch_bounds__(256) embed_concat_fwd_kernel(const float* __restrict__ x, const int64_t* __restrict__ idx,
@@ -212,6 +209,12 @@ __global__ void __launch_bounds__(256) avgpool_bwd_kernel(const float* __restric
   }
 }
 
+// the float4 row path of cross_entropy_kernel: four classes and 16-byte aligned rows.  The kernel decides it itself (the launch does not
+// depend on it), so the condition is a macro that the kernel and pcg_launch_plan_describe both expand.
+#define PCG_CE_FLOAT4_ROWS(K, z, dz) \
+  ((K) == 4 && (reinterpret_cast<uintptr_t>(z) & 15) == 0 && (!(dz) || (reinterpret_cast<uintptr_t>(dz) & 15) == 0))
+unsigned ce_threads(int B) { return B > 1024 ? 1024 : 256; }
+
 // softmax cross-entropy, reduction mean: one thread per row (K is the number of classes: 10), ONE block so that the loss is summed
 // in a fixed order; 1024 threads for large batches (batch 4096 on 256 threads was 16 rows of expf/logf per thread: 24 us)
 __global__ void __launch_bounds__(1024) cross_entropy_kernel(const float* __restrict__ z, const int64_t* __restrict__ target, int B,
@@ -222,7 +225,7 @@ __global__ void __launch_bounds__(1024) cross_entropy_kernel(const float* __rest
   float acc = 0.f;
   const float g = grad_scale * (gout ? gout[0] : 1.f) / (float)B;
   int bstart = threadIdx.x;
-  if (K == 4 && (reinterpret_cast<uintptr_t>(z) & 15) == 0 && (!dz || (reinterpret_cast<uintptr_t>(dz) & 15) == 0)) {
+  if (PCG_CE_FLOAT4_ROWS(K, z, dz)) {
     // four classes (the tabular classifier): a row is one float4.  A thread's rows are requested four at a time before any of them
     // is used (one dependent load chain per row made batch 4096 a 15 us launch); the rows are still ADDED in row order.
     for (; bstart + 3 * nt < B; bstart += 4 * nt) {
@@ -282,10 +285,11 @@ extern "C" int pcg_embed_concat_fwd(const float* x, const int64_t* idx, const fl
   return launch_status("embed_concat_fwd_kernel");
 }
 
+static bool embed_bwd_splits_batch(bool has_dtable, int B) { return has_dtable && B >= 64; }
 extern "C" int pcg_embed_concat_bwd(const float* dinp, const int64_t* idx, float* dtable, float* dx, int32_t B, int32_t HW,
                                     int32_t C, int32_t K, int accumulate, pcg_stream_t stream) {
   PCG_REQUIRE(dinp && idx && (dtable || dx) && B > 0 && HW > 0 && K > 0 && C >= 2, "pcg_embed_concat_bwd: bad arguments");
-  if (dtable && B >= 64) {     // table gradient with the batch split over 16 thread groups; the optional dx copy as its own launch
+  if (embed_bwd_splits_batch(dtable != nullptr, B)) {     // table gradient with the batch split over 16 thread groups; the optional dx copy as its own launch
     hipLaunchKernelGGL(embed_table_grad_kernel, dim3((unsigned)(((size_t)K * HW + 15) / 16)), dim3(256), 0, (hipStream_t)stream, dinp, idx,
                        dtable, B, HW, C, K, accumulate);
     if (int e = launch_status("embed_table_grad_kernel")) return e;
@@ -303,11 +307,12 @@ __global__ void __launch_bounds__(256) gather_channel_kernel(const float* __rest
   for (int i = blockIdx.x * 256 + threadIdx.x; i < rows; i += gridDim.x * 256) dst[i] = src[(size_t)i * C + ch];
 }
 } }
+static unsigned gather_channel_blocks(int rows) { return ew_grid((size_t)rows, 1024); }
 // dst[r] = src[r][ch] for a [rows][C] tensor: the OHWI weight of ONE input channel of a convolution (conv_in's label-map channel: the
 // only one of its three input channels whose gradient anybody reads, models/generator.py:73-74)
 extern "C" int pcg_gather_channel(const float* src, float* dst, int32_t rows, int32_t C, int32_t ch, pcg_stream_t stream) {
   PCG_REQUIRE(src && dst && rows > 0 && C > 0 && ch >= 0 && ch < C, "pcg_gather_channel: bad arguments");
-  hipLaunchKernelGGL(gather_channel_kernel, dim3((unsigned)((rows + 255) / 256 > 1024 ? 1024 : (rows + 255) / 256)), dim3(256), 0,
+  hipLaunchKernelGGL(gather_channel_kernel, dim3(gather_channel_blocks(rows)), dim3(256), 0,
                      (hipStream_t)stream, src, dst, rows, C, ch);
   return launch_status("gather_channel_kernel");
 }
@@ -358,6 +363,8 @@ extern "C" int pcg_clamp_add_bwd(const float* dy, const float* x, const float* r
 }
 
 extern "C" size_t pcg_abs_mean_workspace_bytes(void) { return AM_BLOCKS * sizeof(float); }
+// one block is enough up to ~16 elements per thread; beyond, 256 blocks + the parallel finish are faster
+static bool abs_mean_one_block(int64_t n) { return n <= 16 * 1024; }
 
 extern "C" int pcg_abs_mean_fwd(const float* a, const float* m, int one_minus_m, int64_t n, float* out, void* workspace,
                                 size_t workspace_bytes, pcg_stream_t stream) {
@@ -368,7 +375,7 @@ extern "C" int pcg_abs_mean_fwd(const float* a, const float* m, int one_minus_m,
   }
   hipStream_t s = (hipStream_t)stream;
   float* partial = (float*)workspace;
-  if (n <= 16 * 1024) {   // one block is enough up to ~16 elements per thread; beyond, 256 blocks + the parallel finish are faster
+  if (abs_mean_one_block(n)) {
     hipLaunchKernelGGL(abs_mean_small_kernel, dim3(1), dim3(1024), 0, s, a, m, one_minus_m, (size_t)n, 1.0 / (double)n, out);
     return launch_status("abs_mean_small_kernel");
   }
@@ -401,7 +408,7 @@ extern "C" int pcg_avgpool_bwd(const float* dy, float* dx, int32_t B, int32_t HW
 extern "C" int pcg_cross_entropy_fwd_bwd(const float* logits, const int64_t* target, int32_t B, int32_t K, float grad_scale,
                                          const float* grad_out_dev, float* loss, float* dlogits, pcg_stream_t stream) {
   PCG_REQUIRE(logits && target && B > 0 && K > 0 && (loss || dlogits), "pcg_cross_entropy_fwd_bwd: bad arguments");
-  hipLaunchKernelGGL(cross_entropy_kernel, dim3(1), dim3(B > 1024 ? 1024 : 256), 0, (hipStream_t)stream, logits, target, B, K, grad_scale,
+  hipLaunchKernelGGL(cross_entropy_kernel, dim3(1), dim3(ce_threads(B)), 0, (hipStream_t)stream, logits, target, B, K, grad_scale,
                      grad_out_dev, loss, dlogits);
   return launch_status("cross_entropy_kernel");
 }
@@ -563,4 +570,35 @@ extern "C" int pcg_weighted_sum_bwd(int32_t n, const float* weights, const float
   for (int i = 0; i < n; ++i) { t.w[i] = weights[i]; t.g[i] = grads[i]; }
   hipLaunchKernelGGL(weighted_sum_bwd_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, t, grad_out_dev);
   return launch_status("weighted_sum_bwd_kernel");
+}
+
+// this file's part of pcg_launch_plan_describe (tabular.hip): the routes of the launchers above, from the predicates they call
+int pcg::describe_cf_ops_plan(int32_t op, const int64_t* a, int32_t n_args, char* buf, size_t bytes) {
+  switch (op) {
+    case PCG_PLAN_ABS_MEAN:
+      PCG_REQUIRE(n_args == 1 && a[0] > 0, "pcg_launch_plan_describe: abs_mean takes (n)");
+      if (abs_mean_one_block(a[0])) snprintf(buf, bytes, "one block of 1024");
+      else snprintf(buf, bytes, "%d partials + finish", AM_BLOCKS);
+      return PCG_OK;
+    case PCG_PLAN_CROSS_ENTROPY: {
+      PCG_REQUIRE(n_args == 4 && a[0] > 0 && a[1] > 0, "pcg_launch_plan_describe: cross_entropy takes (B, K, logits 16-byte aligned, dlogits absent or 16-byte aligned)");
+      // stand-in addresses with the alignment asked about: the predicate looks at nothing else
+      const float* z = reinterpret_cast<const float*>((uintptr_t)(a[2] ? 16 : 4));
+      const float* dz = reinterpret_cast<const float*>((uintptr_t)(a[3] ? 0 : 4));
+      snprintf(buf, bytes, "%u threads, %s", ce_threads((int)a[0]), PCG_CE_FLOAT4_ROWS((int)a[1], z, dz) ? "float4 rows" : "no float4 rows");
+      return PCG_OK;
+    }
+    case PCG_PLAN_EMBED_CONCAT_BWD:
+      PCG_REQUIRE(n_args == 3 && a[0] > 0 && (a[1] || a[2]), "pcg_launch_plan_describe: embed_concat_bwd takes (B, has_dtable, has_dx)");
+      if (embed_bwd_splits_batch(a[1] != 0, (int)a[0])) snprintf(buf, bytes, "batch-split table gradient%s", a[2] ? " + copy" : "");
+      else snprintf(buf, bytes, "one pass");
+      return PCG_OK;
+    case PCG_PLAN_ELEMENTWISE:
+      PCG_REQUIRE(n_args == 2 && a[1] > 0, "pcg_launch_plan_describe: elementwise takes (family, n)");
+      if (a[0] == PCG_PLAN_EW_CF_OPS) { describe_ew_grid(buf, bytes, (size_t)a[1], ew_blocks((size_t)a[1])); return PCG_OK; }
+      if (a[0] == PCG_PLAN_EW_GATHER_CHANNEL) { describe_ew_grid(buf, bytes, (size_t)a[1], gather_channel_blocks((int)a[1])); return PCG_OK; }
+      return PCG_PLAN_NOT_MINE;
+    default:
+      return PCG_PLAN_NOT_MINE;
+  }
 }

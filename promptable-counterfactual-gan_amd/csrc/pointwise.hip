@@ -2,18 +2,17 @@
 // All HBM-bound streaming kernels (float4 lane accesses, grid-stride).  Reference call sites are listed
 // next to each prototype in include/pcgan_hip.h.
 #include <cstdlib>
+#include <cstdio>
 #include "epoch_wg.h"
+#include "launch_plan.h"
 
 namespace pcg {
 namespace {
 
-unsigned ew_blocks(size_t nv) {
-  size_t b = (nv + 255) / 256;
-  if (b > 8192) b = 8192;
-  if (b < 1) b = 1;
-  return (unsigned)b;
-}
+constexpr unsigned EW_MAX_BLOCKS = 8192;
+unsigned ew_blocks(size_t nv) { return ew_grid(nv, EW_MAX_BLOCKS); }
 bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+bool act_float4_lanes(int64_t n, bool all_aligned16) { return n % 4 == 0 && all_aligned16; }
 
 template <int VEC>
 __global__ void __launch_bounds__(256) act_fwd_kernel(const float* __restrict__ x, size_t n, int act, float slope,
@@ -280,7 +279,7 @@ using namespace pcg;
 extern "C" int pcg_act_fwd(const float* x, int64_t n, int act, float slope, float* y, pcg_stream_t stream) {
   PCG_REQUIRE(x && y && n > 0, "pcg_act_fwd: bad arguments");
   hipStream_t s = (hipStream_t)stream;
-  if (n % 4 == 0 && al16(x) && al16(y))
+  if (act_float4_lanes(n, al16(x) && al16(y)))
     hipLaunchKernelGGL(act_fwd_kernel<4>, dim3(ew_blocks((size_t)n / 4)), dim3(256), 0, s, x, (size_t)n, act, slope, y);
   else
     hipLaunchKernelGGL(act_fwd_kernel<1>, dim3(ew_blocks((size_t)n)), dim3(256), 0, s, x, (size_t)n, act, slope, y);
@@ -290,7 +289,7 @@ extern "C" int pcg_act_fwd(const float* x, int64_t n, int act, float slope, floa
 extern "C" int pcg_act_bwd(const float* dy, const float* y, int64_t n, int act, float slope, float* dx, pcg_stream_t stream) {
   PCG_REQUIRE(dy && y && dx && n > 0, "pcg_act_bwd: bad arguments");
   hipStream_t s = (hipStream_t)stream;
-  if (n % 4 == 0 && al16(dy) && al16(y) && al16(dx))
+  if (act_float4_lanes(n, al16(dy) && al16(y) && al16(dx)))
     hipLaunchKernelGGL(act_bwd_kernel<4>, dim3(ew_blocks((size_t)n / 4)), dim3(256), 0, s, dy, y, (size_t)n, act, slope, dx);
   else
     hipLaunchKernelGGL(act_bwd_kernel<1>, dim3(ew_blocks((size_t)n)), dim3(256), 0, s, dy, y, (size_t)n, act, slope, dx);
@@ -376,4 +375,21 @@ extern "C" int pcg_norm_sum(const float* flat, const int64_t* seg_dev, int32_t n
   PCG_REQUIRE(flat && seg_dev && out && nseg > 0, "pcg_norm_sum: bad arguments");
   hipLaunchKernelGGL(norm_sum_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, flat, seg_dev, nseg, out);
   return launch_status("norm_sum_kernel");
+}
+
+// this file's part of pcg_launch_plan_describe (tabular.hip)
+int pcg::describe_pointwise_plan(int32_t op, const int64_t* a, int32_t n_args, char* buf, size_t bytes) {
+  if (op == PCG_PLAN_ACT) {
+    PCG_REQUIRE(n_args == 2 && a[0] > 0, "pcg_launch_plan_describe: act takes (n, every pointer 16-byte aligned)");
+    const bool v4 = act_float4_lanes(a[0], a[1] != 0);
+    const size_t items = v4 ? (size_t)a[0] / 4 : (size_t)a[0];
+    const int k = snprintf(buf, bytes, "%s: ", v4 ? "float4 lanes" : "scalar lanes");
+    describe_ew_grid(buf + k, bytes - k, items, ew_blocks(items));
+    return PCG_OK;
+  }
+  if (op == PCG_PLAN_ELEMENTWISE && n_args == 2 && a[1] > 0 && a[0] == PCG_PLAN_EW_POINTWISE) {
+    describe_ew_grid(buf, bytes, (size_t)a[1], ew_blocks((size_t)a[1]));
+    return PCG_OK;
+  }
+  return PCG_PLAN_NOT_MINE;
 }

@@ -32,6 +32,7 @@ int launch_status(const char* what) {
 //   pcg_house_residual_{fwd,bwd}, pcg_house_diag); + pcg_abi_struct_bytes.  v6, additive: + pcg_house_cf_eval;
 //   + pcg_patch_mask_bits, pcg_mnist_cf_entry, pcg_mnist_cf_tail, pcg_mnist_cf_score (csrc/mnist_cf_eval.hip);
 //   + pcg_moons_clf_fit, pcg_moons_clf_fit_scratch_bytes (csrc/moons_clf.hip).
+//   + pcg_launch_plan_describe (csrc/tabular.hip: the routes of the non-convolution launches as text, host logic).
 // v5, additive: + pcg_conv_precision_set / _get (thread-local bf16-operand mode of the implicit-GEMM convolutions).
 // v5 (r04): + grouped batches (pcg_conv2d_fwd_bn_g, pcg_bn_apply_act_g, pcg_conv2d_dgrad_bn_phases, pcg_conv2d_dgrad_bnbwd_g,
 //   pcg_bn_bwd_partial_g(+_workspace_bytes), pcg_bn_act_bwd_premask_g(+pcg_bn_act_bwd_g_workspace_bytes), pcg_bce_pair),

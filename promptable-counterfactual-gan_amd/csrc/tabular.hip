@@ -6,18 +6,17 @@
 // op — the layer chain is launch-latency bound; the MI355X-shaped answer is one persistent fused kernel.
 // Reference call sites are cited next to each prototype in include/pcgan_hip.h.
 #include <algorithm>
+#include <cstdio>
+#include <cstring>
 #include "pcg_common.h"
+#include "launch_plan.h"
 #include "spectral_norm_body.h"
 
 namespace pcg {
 namespace {
 
-unsigned ew_blocks(size_t n) {
-  size_t b = (n + 255) / 256;
-  if (b > 4096) b = 4096;
-  if (b < 1) b = 1;
-  return (unsigned)b;
-}
+constexpr unsigned EW_MAX_BLOCKS = 4096;
+unsigned ew_blocks(size_t n) { return ew_grid(n, EW_MAX_BLOCKS); }
 
 // C[m][n] (+)= sum_k opA[m][k] * opB[k][n] (+ bias[n]);  opA = A (lda: row stride of [M][K]) or A^T (A stored [K][M]);
 // opB = B ([K][N]) or B^T (B stored [N][K]).  64x64 tile per block, 4x4 outputs per thread, K step 16.
@@ -80,7 +79,8 @@ __global__ void __launch_bounds__(256) gemm_kernel(int transA, int transB, int M
 // Skinny-N GEMM: C[M][N <= 32] (+)= A[M][K] opB (+ bias).  The 64x64 tile above gives such a problem one block per 64 rows (M = 4096,
 // N = 17, K = 256 — the frozen classifier's grad-input to the 17 features: 64 blocks on 256 CUs, 16 latency-bound k-steps, 48 us).
 // Here opB (K x N) sits in LDS whole, a block owns 16 rows (256 blocks at M = 4096) and a thread two columns of one row.
-constexpr int SK_R = 16, SK_LDB = 33;
+constexpr int SK_R = 16, SK_C = 16, SK_LDB = 33;      // rows per block; columns per pass of a row's 16 threads (a thread owns c and c + SK_C)
+static_assert(SK_R * SK_C == 256 && SK_C == 16, "gemm_skinny_kernel splits threadIdx.x as (row = x >> 4, column = x & 15)");
 __global__ void __launch_bounds__(256) gemm_skinny_kernel(int transB, int M, int N, int K, const float* __restrict__ A, int lda,
                                                           const float* __restrict__ B, int ldb, float* __restrict__ C, int ldc,
                                                           const float* __restrict__ bias, int accumulate, int act_on, float neg) {
@@ -100,17 +100,17 @@ __global__ void __launch_bounds__(256) gemm_skinny_kernel(int transB, int M, int
   const int r = threadIdx.x >> 4, c = threadIdx.x & 15;
   const float* a = As + r * (K + 1);
   float acc0 = 0.f, acc1 = 0.f;
-  const bool two = c + 16 < N;
+  const bool two = c + SK_C < N;
   for (int k = 0; k < K; ++k) {
     const float av = a[k];
     acc0 = fmaf(av, Bs[k * SK_LDB + c], acc0);
-    acc1 = fmaf(av, Bs[k * SK_LDB + c + 16], acc1);      // columns >= N of Bs are never written: the product is discarded below
+    acc1 = fmaf(av, Bs[k * SK_LDB + c + SK_C], acc1);      // columns >= N of Bs are never written: the product is discarded below
   }
   const int m = m0 + r;
   if (m >= M) return;
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
-    const int n = c + 16 * j;
+    const int n = c + SK_C * j;
     if (n >= N || (j == 1 && !two)) continue;
     float v = (j ? acc1 : acc0) + (bias ? bias[n] : 0.f);
     float* cp = C + (size_t)m * ldc + n;
@@ -119,11 +119,16 @@ __global__ void __launch_bounds__(256) gemm_skinny_kernel(int transB, int M, int
     *cp = v;
   }
 }
+bool skinny_takes(int transA, int M, int N, int K) { return !(transA || N > 32 || N < 2 || K > 320 || M < 512); }
+dim3 skinny_grid(int M) { return dim3((M + SK_R - 1) / SK_R); }
+bool skinny_two_columns(int N) { return N > SK_C; }       // some thread of a row owns a second column
+size_t skinny_lds_bytes(int K) { return ((size_t)K * SK_LDB + (size_t)SK_R * (K + 1)) * sizeof(float); }     // <= 63 KB at K = 320
+dim3 tile_grid(int M, int N) { return dim3((N + GT - 1) / GT, (M + GT - 1) / GT); }
 static bool launch_skinny(int transA, int transB, int M, int N, int K, const float* A, int lda, const float* B, int ldb, float* C, int ldc,
                           const float* bias, int accumulate, int act_on, float neg, hipStream_t s) {
-  if (transA || N > 32 || N < 2 || K > 320 || M < 512) return false;
-  const size_t lds = ((size_t)K * SK_LDB + (size_t)SK_R * (K + 1)) * sizeof(float);     // <= 63 KB at K = 320
-  hipLaunchKernelGGL(gemm_skinny_kernel, dim3((M + SK_R - 1) / SK_R), dim3(256), lds, s, transB, M, N, K, A, lda, B, ldb, C, ldc, bias,
+  if (!skinny_takes(transA, M, N, K)) return false;
+  const size_t lds = skinny_lds_bytes(K);
+  hipLaunchKernelGGL(gemm_skinny_kernel, skinny_grid(M), dim3(256), lds, s, transB, M, N, K, A, lda, B, ldb, C, ldc, bias,
                      accumulate, act_on, neg);
   return true;
 }
@@ -885,10 +890,12 @@ __global__ void __launch_bounds__(256) rowdot_kernel(int M, int K, const float* 
   }
 }
 
+bool rowdot_takes(int transA, int transB, int N, int K) { return !(transA || !transB || N > 4 || K < 256); }
+dim3 rowdot_grid(int M) { return dim3((M + 3) / 4); }       // one wave per row, four rows per block
 bool launch_rowdot(int transA, int transB, int M, int N, int K, const float* A, int lda, const float* B, int ldb, float* C, int ldc,
                    const float* bias, int accumulate, int act_on, float neg, hipStream_t s) {
-  if (transA || !transB || N > 4 || K < 256) return false;
-  const dim3 grid((M + 3) / 4), block(256);
+  if (!rowdot_takes(transA, transB, N, K)) return false;
+  const dim3 grid = rowdot_grid(M), block(256);
   switch (N) {
     case 1: hipLaunchKernelGGL(rowdot_kernel<1>, grid, block, 0, s, M, K, A, lda, B, ldb, C, ldc, bias, accumulate, act_on, neg); break;
     case 2: hipLaunchKernelGGL(rowdot_kernel<2>, grid, block, 0, s, M, K, A, lda, B, ldb, C, ldc, bias, accumulate, act_on, neg); break;
@@ -903,7 +910,7 @@ extern "C" int pcg_gemm(int transA, int transB, int32_t M, int32_t N, int32_t K,
                         int32_t ldb, float* C, int32_t ldc, const float* bias, int accumulate, pcg_stream_t stream) {
   PCG_REQUIRE(A && B && C && M > 0 && N > 0 && K > 0 && lda > 0 && ldb > 0 && ldc >= N, "pcg_gemm: bad arguments");
   if (launch_rowdot(transA, transB, M, N, K, A, lda, B, ldb, C, ldc, bias, accumulate, 0, 1.f, (hipStream_t)stream)) return launch_status("rowdot_kernel");
-  hipLaunchKernelGGL(gemm_kernel, dim3((N + GT - 1) / GT, (M + GT - 1) / GT), dim3(256), 0, (hipStream_t)stream, transA, transB, M, N, K,
+  hipLaunchKernelGGL(gemm_kernel, tile_grid(M, N), dim3(256), 0, (hipStream_t)stream, transA, transB, M, N, K,
                      A, lda, B, ldb, C, ldc, bias, accumulate, 0, 1.f);
   return launch_status("gemm_kernel");
 }
@@ -916,7 +923,7 @@ extern "C" int pcg_gemm_act(int transA, int transB, int32_t M, int32_t N, int32_
     return launch_status("rowdot_kernel");
   if (launch_skinny(transA, transB, M, N, K, A, lda, B, ldb, C, ldc, bias, accumulate, act != PCG_ACT_NONE, act_neg_of(act, slope), (hipStream_t)stream))
     return launch_status("gemm_skinny_kernel");
-  hipLaunchKernelGGL(gemm_kernel, dim3((N + GT - 1) / GT, (M + GT - 1) / GT), dim3(256), 0, (hipStream_t)stream, transA, transB, M, N, K,
+  hipLaunchKernelGGL(gemm_kernel, tile_grid(M, N), dim3(256), 0, (hipStream_t)stream, transA, transB, M, N, K,
                      A, lda, B, ldb, C, ldc, bias, accumulate, act != PCG_ACT_NONE, act_neg_of(act, slope));
   return launch_status("gemm_kernel");
 }
@@ -1098,12 +1105,13 @@ extern "C" int pcg_assemble_residual_bwd(const float* dres, int32_t ncont, const
 }
 
 extern "C" size_t pcg_mean_workspace_bytes(void) { return MEAN_BLOCKS * sizeof(float); }
+static bool mean_one_block(int64_t n) { return n <= 16 * 1024; }
 
 extern "C" int pcg_mean_fwd(const float* x, int64_t n, float* out, void* workspace, size_t workspace_bytes, pcg_stream_t stream) {
   PCG_REQUIRE(x && out && n > 0, "pcg_mean_fwd: bad arguments");
   if (!workspace || workspace_bytes < pcg_mean_workspace_bytes()) { set_error("pcg_mean_fwd: workspace too small"); return PCG_ERR_WORKSPACE; }
   hipStream_t s = (hipStream_t)stream;
-  if (n <= 16 * 1024) {
+  if (mean_one_block(n)) {
     hipLaunchKernelGGL(mean_small_kernel, dim3(1), dim3(1024), 0, s, x, (size_t)n, 1.0 / (double)n, out);
     return launch_status("mean_small_kernel");
   }
@@ -1336,4 +1344,56 @@ extern "C" int pcg_ce_weighted_tally(const float* logits, const int64_t* target,
   hipLaunchKernelGGL(ce_weighted_tally_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, logits, target, class_weight, B, K,
                      seg < B ? seg : B, tally, dlogits, dbias, seg_loss);
   return launch_status("ce_weighted_tally_kernel");
+}
+
+// Which route a non-convolution launch takes, as text: the predicates and planners the launchers above call (rowdot_takes,
+// skinny_takes, plan_linear_wgrad, plan_wgrad_mfma, mean_one_block, ew_blocks) and their counterparts in cf_ops.hip / pointwise.hip
+// (launch_plan.h) — host logic, no device.  The argument lists are in include/pcgan_hip.h.
+extern "C" int pcg_launch_plan_describe(int32_t op, const int64_t* args, int32_t n_args, char* out, size_t out_bytes) {
+  PCG_REQUIRE(out && out_bytes > 0 && args && n_args > 0, "pcg_launch_plan_describe: bad arguments");
+  char buf[256];
+  buf[0] = 0;
+  auto say = [&](const char* fmt, auto... a) { snprintf(buf + strlen(buf), sizeof(buf) - strlen(buf), fmt, a...); };
+  const int64_t* a = args;
+  switch (op) {
+    case PCG_PLAN_GEMM_ACT:
+    case PCG_PLAN_GEMM: {
+      PCG_REQUIRE(n_args == 5 && a[2] > 0 && a[3] > 0 && a[4] > 0, "pcg_launch_plan_describe: gemm takes (transA, transB, M, N, K)");
+      const int tA = (int)a[0], tB = (int)a[1], M = (int)a[2], N = (int)a[3], K = (int)a[4];
+      if (rowdot_takes(tA, tB, N, K)) say("rowdot<%d>: %u blocks", N, rowdot_grid(M).x);
+      else if (op == PCG_PLAN_GEMM_ACT && skinny_takes(tA, M, N, K))          // pcg_gemm has no skinny launch
+        say("skinny: %u blocks, %s, %zu bytes of LDS", skinny_grid(M).x, skinny_two_columns(N) ? "two columns per thread" : "one column per thread", skinny_lds_bytes(K));
+      else say("64x64 tiles: %u x %u", tile_grid(M, N).x, tile_grid(M, N).y);
+      break;
+    }
+    case PCG_PLAN_LINEAR_WGRAD: {
+      PCG_REQUIRE(n_args == 3 && a[0] > 0 && a[1] > 0 && a[2] > 0, "pcg_launch_plan_describe: linear_wgrad takes (B, O, I)");
+      const WgradPlan p = plan_linear_wgrad((int)a[0], (int)a[1], (int)a[2]);
+      say("64x64 tiles: %d, slabs: %d of %d rows", p.tiles, p.S, p.chunk);
+      break;
+    }
+    case PCG_PLAN_LINEAR_WGRAD_GROUPED: {
+      PCG_REQUIRE(n_args == 1 && a[0] > 0, "pcg_launch_plan_describe: linear_wgrad_grouped takes (B)");
+      const WgradMfmaPlan p = plan_wgrad_mfma((int)a[0]);
+      say("blocks per tile: %d, rows per wave: %d", p.Sb, p.chunk);
+      break;
+    }
+    case PCG_PLAN_MEAN:
+      PCG_REQUIRE(n_args == 1 && a[0] > 0, "pcg_launch_plan_describe: mean takes (n)");
+      if (mean_one_block(a[0])) say("%s", "one block of 1024");
+      else say("%d partials + finish", MEAN_BLOCKS);
+      break;
+    case PCG_PLAN_ELEMENTWISE:
+      PCG_REQUIRE(n_args == 2 && a[1] > 0, "pcg_launch_plan_describe: elementwise takes (family, n)");
+      if (a[0] == PCG_PLAN_EW_TABULAR) { describe_ew_grid(buf, sizeof(buf), (size_t)a[1], ew_blocks((size_t)a[1])); break; }
+      [[fallthrough]];
+    default: {
+      int e = describe_cf_ops_plan(op, a, n_args, buf, sizeof(buf));
+      if (e == PCG_PLAN_NOT_MINE) e = describe_pointwise_plan(op, a, n_args, buf, sizeof(buf));
+      PCG_REQUIRE(e != PCG_PLAN_NOT_MINE, "pcg_launch_plan_describe: unknown op %d (or element-wise family)", op);
+      if (e) return e;
+    }
+  }
+  snprintf(out, out_bytes, "%s", buf);
+  return PCG_OK;
 }

@@ -194,6 +194,15 @@ def conv_pad_clip_query(g, op, groups=1, assume_scratch=True):
     return bool(taken.value), order.value, rows.value, pred.value
 
 
+def launch_plan(op, *args):
+    """The route a non-convolution launch takes, as text (pcg_launch_plan_describe: host logic, no device).  op: one of _lib.PLAN_*;
+    args: that op's integers, e.g. launch_plan(_lib.PLAN_GEMM_ACT, transA, transB, M, N, K) -> 'skinny: 33 blocks, ...'."""
+    buf = ctypes.create_string_buffer(256)
+    arr = (ctypes.c_int64 * max(len(args), 1))(*[int(a) for a in args])
+    check(_lib.load().pcg_launch_plan_describe(int(op), arr, len(args), buf, 256), "pcg_launch_plan_describe")
+    return buf.value.decode()
+
+
 def _p(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
 

@@ -39,7 +39,8 @@ def _close(a, b, rtol, atol, msg=""):
 
 # ---------------------------------------------------------------------------------------------------------------------
 def test_gemm_all_layouts(pcg):
-    """pcg_gemm against float64 matmul: ragged sizes (the layer widths of this model are 38, 21, 17, 10, 9, 30, ...),
+    """ops.gemm -- pcg_gemm_act, the entry every GEMM of the package goes through (pcg_gemm, the export without an activation, is
+    called by tests/test_hip_small_ops.py alone) -- against float64 matmul: ragged sizes (the layer widths of this model are 38, 21, 17, 10, 9, 30, ...),
     transposes, strided column slices, bias, accumulate.  fp32 FMA accumulation over K <= 300: rtol 2e-5."""
     ops = pcg.ops
     g = torch.Generator().manual_seed(1)
