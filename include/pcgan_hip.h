@@ -1007,6 +1007,34 @@ int pcg_ce_weighted_tally(const float* logits, const int64_t* target, const floa
                           double* tally /*[3], accumulated*/, float* dlogits /*nullable*/, float* dbias /*nullable*/,
                           float* seg_loss /*nullable*/, pcg_stream_t stream);
 
+/* ---- classifier pre-training of the MNIST CounteRGAN as a replayed step (conditional_counteRGAN/mnist/trainer.py:8-39) ----------------
+ * All fp32, fixed summation order, no atomics on floats; every entry may be captured into a HIP graph.
+ * pcg_mnist_clf_batch(_counter): pcg_house_clf_batch(_counter) with TWO masks (models/classifier.py:14 Dropout2d [B][128], :20 Dropout
+ * [B][256]): rows perm[cursor .. cursor+B) of X [n_rows][D] / Y [n_rows] into x_out [B][D] / y_out [B]; m0 [B][w0], m1 [B][w1] hold what
+ * two pcg_rand_bernoulli calls write at offset and offset + (B*w0+3)/4.  Same counter layout, same clamping, same refusals. */
+int pcg_mnist_clf_batch(const float* X, const int64_t* Y, const int64_t* perm, int64_t n_perm, int64_t n_rows, float* x_out, int64_t* y_out,
+                        int32_t B, int32_t D, float* m0, int32_t w0, float keep0, float* m1, int32_t w1, float keep1, uint64_t seed,
+                        uint64_t offset, int64_t cursor, pcg_stream_t stream);
+int pcg_mnist_clf_batch_counter(const float* X, const int64_t* Y, const int64_t* perm, int64_t n_perm, int64_t n_rows, float* x_out,
+                                int64_t* y_out, int32_t B, int32_t D, float* m0, int32_t w0, float keep0, float* m1, int32_t w1, float keep1,
+                                uint64_t seed, uint64_t* counter, pcg_stream_t stream);
+/* nn.Dropout2d + nn.Flatten of the NCHW tensor (models/classifier.py:14,17) from the NHWC activation a [R][HW][C] in one launch:
+ * out[b][c*HW + p] = a[b][p][c] * mask[b][c] * scale -- bit for bit pcg_dropout_apply(inner = HW) followed by pcg_nhwc_to_nchw_flat. */
+int pcg_drop2d_flatten_fwd(const float* a, const float* mask /*[R][C]*/, float scale, int32_t R, int32_t HW, int32_t C, float* out,
+                           pcg_stream_t stream);
+/* Its backward with the derivative of the activation whose output y [R][HW][C] was saved (classifier.py:13):
+ * out[b][p][c] = dflat[b][c*HW + p] * mask[b][c] * scale * act'(y[b][p][c]) -- bit for bit pcg_nhwc_to_nchw_flat(inverse),
+ * pcg_dropout_apply, pcg_act_bwd. */
+int pcg_drop2d_flatten_bwd(const float* dflat, const float* mask, float scale, const float* y, int act, float slope, int32_t R, int32_t HW,
+                           int32_t C, float* out, pcg_stream_t stream);
+/* Everything above fc1's output (classifier.py:19-21, trainer.py:10,19-20) in one launch of one workgroup; R <= 128, I == 256, K <= 16.
+ * h [R][I] is fc1's post-ReLU output, m1 [R][I] the Dropout mask.  logits [R][K] = (h * m1 * scale) W2^T + b2; loss [1] the mean
+ * cross-entropy; tally double[3] += (loss * R, rows whose argmax is the label -- first maximum, as pcg_ce_weighted_tally --, R);
+ * dW2 [K][I], db2 [K]; dh [R][I] = (dlogits W2) * m1 * scale * [h > 0] with dlogits = (softmax - onehot) / R; db1 [I] its column sums. */
+int pcg_mnist_clf_head(const float* h, const float* m1, float scale, const float* W2, const float* b2, const int64_t* y, int32_t R, int32_t I,
+                       int32_t K, float* logits, float* loss, double* tally /*[3], accumulated*/, float* dW2, float* db2, float* dh, float* db1,
+                       pcg_stream_t stream);
+
 /* A barrier of the ranks on the library's own communicator (a 4-byte all-reduce in stream order; synchronise `stream` afterwards):
  * bench.py brackets its timed region with it, so that region uses ONE communicator — the one that carries the gradient exchange.
  * pcg_dp_rccl_version: ncclGetVersion of the RCCL the library bound (22105 = 2.21.5; 0 = unknown).                              */

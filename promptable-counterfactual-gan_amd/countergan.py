@@ -6,6 +6,7 @@
     models/generator.py  ResidualGenerator :25-86           ResidualGenerator (same ctor args, same state_dict keys)
     models/discriminator.py Discriminator  :5-38            Discriminator
     models/classifier.py CNNClassifier     :4-28            CNNClassifier (frozen / eval use: forward + grad-input)
+    trainer.py           train_classifier  :8-39            train_classifier (fused=True: ClassifierFit, one graph replay per step)
     trainer.py           build_mask        :45-72           build_mask (same draws from torch's RNG)
     trainer.py           train_countergan  :76-123          make_optimizers + train_step (+ train_countergan loop)
 
@@ -788,24 +789,289 @@ def generate_counterfactuals(generator, classifier, x, y, y_target, mask, device
     return raw_residual, masked_residual, x_cf
 
 
-def train_classifier(classifier, train_loader, valid_loader, cfg, device, save=True):
+_fused_fallback_warned = False
+
+
+def _warn_fused_fallback(why):
+    global _fused_fallback_warned
+    if not _fused_fallback_warned:
+        import warnings
+        warnings.warn(f"train_classifier(fused=True): {why}; running the op chain instead", RuntimeWarning, stacklevel=3)
+        _fused_fallback_warned = True
+
+
+class ClassifierFit:
+    """The classifier pre-training step (trainer.py:16-21) with fused launches around the three convolutions (csrc/mnist_clf.hip;
+    DESIGN.md §3.17): the batch gather with the two Dropout masks, conv1..3 with their ReLU, Dropout2d + Flatten, fc1 with its ReLU,
+    the head (Dropout, fc2, loss, tally and their backward down to fc1's pre-activation), fc1's weight gradient and grad-input, the
+    backward of Dropout2d + Flatten + ReLU, the conv backwards and Adam -- captured once as a single-stream, strictly linear HIP
+    graph, so a step is one replay.  The training set, the epoch's permutation, the activations and the tally (sum of loss * rows,
+    correct rows, rows) live on the device; nothing is read back inside an epoch.  One graph for the full batch, one for the tail
+    N % batch_size (a tail of one row is valid: there is no BatchNorm).  Gradients are overwritten every step: no zero_grad.
+    graph=False: the same entries called eagerly with by-value draws (what the replays must equal)."""
+
+    CHANNELS = [1, 32, 64, 128]
+    HW_IN, FEAT, HIDDEN, MAX_K, MAX_ROWS = 28, 128 * 7 * 7, 256, 16, 128
+
+    @staticmethod
+    def unsupported(classifier, batch_size):
+        """None, or why this net / batch cannot take the fused path."""
+        convs = [m for m in getattr(classifier, "conv", []) if isinstance(m, nn.Conv2d)]
+        fcs = [m for m in getattr(classifier, "fc", []) if isinstance(m, nn.Linear)]
+        want = [(1, 32, 1), (32, 64, 2), (64, 128, 2)]
+        got = [(c.in_channels, c.out_channels, c.stride[0]) for c in convs]
+        if got != want or any(c.kernel_size != (3, 3) or c.padding != (1, 1) or c.bias is None for c in convs):
+            return f"convolutions {got} are not the reference's 3x3 {want} on 28x28"
+        if len(fcs) != 2 or (fcs[0].in_features, fcs[0].out_features, fcs[1].in_features) != (ClassifierFit.FEAT, ClassifierFit.HIDDEN,
+                                                                                             ClassifierFit.HIDDEN):
+            return f"linear layers {[(f.in_features, f.out_features) for f in fcs]} are not 6272 -> 256 -> K"
+        if fcs[1].out_features > ClassifierFit.MAX_K:
+            return f"{fcs[1].out_features} classes are above the {ClassifierFit.MAX_K} one MFMA tile holds"
+        if batch_size > ClassifierFit.MAX_ROWS:
+            return f"batch size {batch_size} is above the {ClassifierFit.MAX_ROWS} rows one workgroup holds"
+        prec = getattr(classifier, "conv_precision", "fp32")
+        if prec != "fp32":
+            return f"conv_precision {prec!r}: the fused fit is fp32 only"
+        return None
+
+    def __init__(self, classifier, x_train, y_train, batch_size, lr=Config.cls_lr, rng=None, graph=True):
+        why = self.unsupported(classifier, batch_size)
+        if why is not None:
+            raise PcgError(f"ClassifierFit: {why}")
+        dev = next(classifier.parameters()).device
+        if dev.type != "cuda":
+            raise PcgError(f"ClassifierFit: the classifier is on {dev}; libpcgan_hip has no CPU path")
+        self.classifier, self.B = classifier, int(batch_size)
+        X = torch.as_tensor(x_train).to(dev, torch.float32)
+        self.N = int(X.shape[0])
+        D = self.HW_IN * self.HW_IN
+        if self.N < 1 or self.B < 1 or X.numel() != self.N * D:
+            raise PcgError(f"ClassifierFit: need x [N, 1, {self.HW_IN}, {self.HW_IN}] and y [N]")
+        self.X = X.reshape(self.N, D).contiguous()
+        self.Y = torch.as_tensor(y_train).to(dev, torch.int64).contiguous()
+        if self.Y.shape != (self.N,):
+            raise PcgError(f"ClassifierFit: need x [N, 1, {self.HW_IN}, {self.HW_IN}] and y [N]")
+        self.tail = self.N % self.B
+        self.rng = rng if rng is not None else ops.DeviceRNG(seed=0)
+        classifier.train()
+        classifier._ensure_flat()
+        classifier.zero_grad()                                # attaches the .grad views; every step OVERWRITES them (no zero_grad)
+        self.optimizer = Adam(classifier.parameters(), lr=lr)
+        self._convs = [m for m in classifier.conv if isinstance(m, nn.Conv2d)]
+        self._fc1, self._fc2 = classifier.fc[1], classifier.fc[4]
+        self._p2d, self._p1 = classifier.conv[6].p, classifier.fc[3].p
+        self.K = self._fc2.out_features
+        self._tallies = torch.zeros(6, dtype=torch.float64, device=dev)
+        self.tally, self.val_tally = self._tallies[:3], self._tallies[3:]
+        self.perm = torch.arange(self.N, dtype=torch.int64, device=dev)               # identity until new_epoch()
+        self._cur = 0
+        self._ctr = self.rng.device_counter(dev, cursor=True)
+        f32 = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev)      # noqa: E731
+        C = self.CHANNELS
+        self._bufs = {}
+        for R in sorted({self.B if self.N >= self.B else 0, self.tail} - {0}):
+            geoms, hw = [], self.HW_IN
+            for conv in self._convs:
+                geoms.append(_geom(conv, R, hw, hw))
+                hw = geoms[-1].OH
+            self._bufs[R] = {"x": f32(R, D), "y": torch.zeros((R,), dtype=torch.int64, device=dev), "m": [f32(R, C[3]), f32(R, self.HIDDEN)],
+                             "g": geoms, "a": [f32(R, g.OH, g.OW, g.Cout) for g in geoms], "flat": f32(R, self.FEAT), "h": f32(R, self.HIDDEN),
+                             "logits": f32(R, self.K), "loss": f32(1), "dh": f32(R, self.HIDDEN), "dflat": f32(R, self.FEAT),
+                             "d3": f32(R, geoms[2].OH, geoms[2].OW, C[3])}
+        self._graphs = self._capture() if graph else None
+
+    def _span(self, R):
+        return ops.DeviceRNG.mnist_clf_batch_span(R, [self.CHANNELS[3], self.HIDDEN])
+
+    def _launches(self, b, cursor=None):
+        """One step, Adam included, over the buffer set b; cursor None: offsets and rows from the device counter (the captured form)."""
+        self.rng.mnist_clf_batch(self.X, self.Y, self.perm, (b["x"], b["y"]), b["m"], [1.0 - self._p2d, 1.0 - self._p1],
+                                 counter=self._ctr if cursor is None else None, cursor=cursor or 0)
+        self._forward_backward(b)
+        self.optimizer.step()
+
+    def _forward_backward(self, b):
+        from .nn import _lin_mfma
+        fc1, fc2, convs, geoms = self._fc1, self._fc2, self._convs, b["g"]
+        R = b["x"].shape[0]
+        a = b["x"].view(R, self.HW_IN, self.HW_IN, 1)
+        for conv, g, out in zip(convs, geoms, b["a"]):
+            a = ops.conv2d_fwd(g, a, ops.ohwi(conv.weight.data), conv.bias.data, act=ACT_RELU, out=out)
+        HW, C = geoms[2].OH * geoms[2].OW, geoms[2].Cout
+        ops.drop2d_flatten_fwd(b["a"][2], b["m"][0], self._p2d, R, HW, C, out=b["flat"])
+        # fc1 with its ReLU in the launch, on the route nn.linear_fwd takes for these sizes (a 1x1 convolution on the matrix cores from
+        # 11 rows up); pcg_dense_rows_fwd would give each of its 16 workgroups all of W1's 6.4 MB panel rows to stream alone
+        mfma = _lin_mfma(R, self.FEAT, self.HIDDEN)
+        g1 = ops.conv_geom(R, 1, 1, self.FEAT, self.HIDDEN, 1, 1, 1, 0)
+        if mfma:
+            ops.conv2d_fwd(g1, b["flat"], fc1.weight.data, fc1.bias.data, act=ACT_RELU, out=b["h"])
+        else:
+            ops.gemm(b["flat"], fc1.weight.data, R, self.HIDDEN, self.FEAT, transB=True, bias=fc1.bias.data, out=b["h"], act=ACT_RELU)
+        ops.mnist_clf_head(b["h"], b["m"][1], self._p1, fc2.weight.data, fc2.bias.data, b["y"], self.tally, logits=b["logits"], loss=b["loss"],
+                           dW2=fc2.weight.grad, db2=fc2.bias.grad, dh=b["dh"], db1=fc1.bias.grad)
+        if mfma:
+            ops.conv2d_wgrad(g1, b["flat"], b["dh"], fc1.weight.grad, False)
+            ops.conv2d_dgrad(g1, b["dh"], fc1.weight.data, out=b["dflat"])
+        else:
+            ops.linear_wgrad(b["dh"], b["flat"], R, self.HIDDEN, self.FEAT, fc1.weight.grad)
+            ops.gemm(b["dh"], fc1.weight.data, R, self.FEAT, self.HIDDEN, out=b["dflat"])
+        d = ops.drop2d_flatten_bwd(b["dflat"], b["m"][0], self._p2d, b["a"][2], R, HW, C, act=ACT_RELU, out=b["d3"])
+        for i in (2, 1, 0):
+            conv, g = convs[i], geoms[i]
+            below = b["a"][i - 1] if i > 0 else b["x"]
+            ops.conv2d_wgrad(g, below, d, ops.ohwi(conv.weight.grad), False)
+            ops.colsum(d.numel() // conv.out_channels, conv.out_channels, d, conv.bias.grad, False)
+            if i > 0:
+                d = _dgrad_act(g, d, ops.ohwi(conv.weight.data), below, ACT_RELU, 0.0)
+
+    def _capture(self):
+        """Capture needs one real execution of every launch first; the parameters, the Adam state, the tally and the counter are put
+        back afterwards."""
+        net = self.classifier
+        params0 = net.flat_params.clone()
+        ctr0, tal0 = self._ctr.clone(), self._tallies.clone()
+        snap = self.optimizer.snapshot()
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            for R, b in self._bufs.items():
+                self._launches(b)
+                self._ctr.copy_(ctr0)
+        torch.cuda.current_stream().wait_stream(side)
+        # no finalizer may run while the stream captures (see nn._HipGraphCapture.begin): the cyclic collector is held off.  It is not
+        # run first: what is garbage now stays so until the collector is back on.
+        import gc
+        gc_on = gc.isenabled()
+        gc.disable()
+        graphs = {}
+        try:
+            for R, b in self._bufs.items():
+                graphs[R] = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(graphs[R]):
+                    self._launches(b)
+        finally:
+            if gc_on:
+                gc.enable()
+        net.flat_params.copy_(params0)
+        self.optimizer.restore(snap)
+        self._ctr.copy_(ctr0); self._tallies.copy_(tal0)
+        return graphs
+
+    def new_epoch(self, perm):
+        """Upload this epoch's row order (N entries) and rewind the cursor: one small copy per EPOCH."""
+        if perm.numel() != self.N:
+            raise PcgError(f"ClassifierFit.new_epoch: permutation of {perm.numel()} entries, {self.N} needed")
+        self.perm.copy_(perm.to(torch.int64))
+        self._ctr[2:3].zero_()
+        self._cur = 0
+
+    @property
+    def steps_per_epoch(self):
+        return self.N // self.B + (1 if self.tail else 0)
+
+    def step(self, record=None):
+        """The next batch of the epoch: one replay (Adam is inside it).  record (a dict): receives clones of the batch's rows ("x",
+        "y"), its masks ("masks") and its loss ("loss", a [1] device tensor)."""
+        left = self.N - self._cur
+        if left <= 0:
+            raise PcgError("ClassifierFit.step: the epoch is used up; call new_epoch(perm)")
+        R = self.B if left >= self.B else left
+        b = self._bufs[R]
+        if self._graphs is not None:
+            self._graphs[R].replay()
+            self.rng.offset += self._span(R)                  # the host-side mirror of the device counter
+        else:
+            self._launches(b, cursor=self._cur)
+        self._cur += R
+        if record is not None:
+            record.update(x=b["x"].clone(), y=b["y"].clone(), masks=[m.clone() for m in b["m"]], loss=b["loss"].clone())
+        return R
+
+    def run_batch(self, x, y, masks):
+        """Forward, loss and backward of one GIVEN batch with GIVEN Dropout masks (runs that must reproduce recorded draws), called
+        eagerly: the gradients land in the flat gradient buffer, the tally counts the batch; no Adam.  Returns the loss ([1], device)."""
+        R = int(x.shape[0])
+        if R not in self._bufs:
+            raise PcgError(f"ClassifierFit.run_batch: {R} rows; this fit holds buffers for {sorted(self._bufs)}")
+        b = self._bufs[R]
+        b["x"].copy_(x.reshape(R, -1)); b["y"].copy_(y)
+        for dst, src in zip(b["m"], masks):
+            dst.copy_(src.reshape(dst.shape))
+        self._forward_backward(b)
+        return b["loss"]
+
+    def epoch(self, perm):
+        """All steps of one epoch in the order perm, with no host read."""
+        self.new_epoch(perm)
+        for _ in range(self.steps_per_epoch):
+            self.step()
+
+    def read_tally(self):
+        """(sum of loss * rows, correct rows, rows) of the training steps since the last read; clears it.  One host read."""
+        t = self.tally.cpu().tolist()
+        self.tally.zero_()
+        return tuple(t)
+
+    def read_tallies(self):
+        """The training tally and val_tally (same layout; train_classifier's validation launches add to it) in ONE host read; clears
+        both."""
+        t = self._tallies.cpu().tolist()
+        self._tallies.zero_()
+        return tuple(t)
+
+
+VAL_CHUNK = 4096   # rows per eval-mode forward of train_classifier(fused=True)'s validation
+
+
+def train_classifier(classifier, train_loader, valid_loader, cfg, device, save=True, fused=False):
     """trainer.py:8-39 — Adam(cls_lr), CrossEntropyLoss, per-epoch validation accuracy, best state saved to
-    cfg.classifier_path."""
-    optimizer = Adam(classifier.parameters(), lr=cfg.cls_lr)
+    cfg.classifier_path.  fused=True (train_loader a data.DeviceLoader, the reference's net, batch <= 128): the batches run through
+    ClassifierFit -- one graph replay per step, in the order and with the Dropout masks the chain sees for the same loader seed and
+    classifier.rng -- the validation is eval-mode forwards of at most VAL_CHUNK rows, each tallied on the device, and the epoch makes
+    ONE host read.  Anything else warns once and runs the op chain."""
+    from .data import DeviceLoader
+    fit = None
+    if fused:
+        why = None
+        if not isinstance(train_loader, DeviceLoader):
+            why = "train_loader is not a data.DeviceLoader (the fit needs the training set resident on the device)"
+        elif not train_loader.shuffle:
+            why = "the training loader does not shuffle"
+        else:
+            why = ClassifierFit.unsupported(classifier, train_loader.batch_size)
+        if why is None:
+            if classifier.rng is None:
+                classifier.rng = ops.DeviceRNG(seed=0)                                        # the stream CNNClassifier.forward draws from
+            fit = ClassifierFit(classifier, train_loader.x, train_loader.y, train_loader.batch_size, lr=cfg.cls_lr, rng=classifier.rng)
+            ones = torch.ones(fit.K, dtype=torch.float32, device=fit.X.device)
+            xv, yv = (valid_loader.x, valid_loader.y) if isinstance(valid_loader, DeviceLoader) else \
+                (torch.cat(t) for t in zip(*((x, y) for x, y in valid_loader)))               # setup: the validation set, resident
+            xv, yv = xv.to(device, torch.float32).contiguous(), yv.to(device, torch.int64).contiguous()
+        else:
+            _warn_fused_fallback(why)
+    optimizer = fit.optimizer if fit is not None else Adam(classifier.parameters(), lr=cfg.cls_lr)
     criterion = CrossEntropyLoss()
     best_acc, history = 0.0, []
     for epoch in range(cfg.num_epochs_clf):
         classifier.train()
-        for x, y in train_loader:
+        for x, y in (train_loader if fit is None else ()):
             x, y = x.to(device), y.to(device)
             optimizer.zero_grad()
             loss = criterion(classifier(x), y)
             loss.backward()
             optimizer.step()
+        if fit is not None:
+            fit.epoch(train_loader.epoch_order())                                             # the order train_loader would walk
         classifier.eval()
         correct, total = 0.0, 0
         with torch.no_grad():
-            for x, y in valid_loader:
+            if fit is not None:
+                classifier._packed = None        # the in-place optimizer kernel bumps no tensor version: _pack would serve the old image
+                for i in range(0, xv.shape[0], VAL_CHUNK):
+                    ops.ce_weighted_tally(classifier(xv[i:i + VAL_CHUNK]).contiguous(), yv[i:i + VAL_CHUNK], ones, fit.val_tally,
+                                          seg=VAL_CHUNK)
+                correct, total = fit.read_tallies()[4:6]                                      # the epoch's one host read
+            for x, y in (valid_loader if fit is None else ()):
                 x, y = x.to(device), y.to(device)
                 acc_b = ops.cf_metrics(classifier(x).contiguous(), y, other=y)[0].item()     # mean(argmax == y)
                 correct += acc_b * y.size(0)

@@ -470,6 +470,48 @@ extern "C" int pcg_house_clf_batch(const float* X, const int64_t* Y, const int64
                                 seed, offset, cursor, nullptr, stream);
 }
 
+// The MNIST classifier fit's batch (conditional_counteRGAN/mnist/trainer.py:16-17: the shuffled DataLoader's next batch) and the two
+// Dropout masks of its forward (models/classifier.py:14 Dropout2d(0.25) [B, 128], :20 Dropout(0.5) [B, 256]) in one launch: the house
+// entry's twin.  It launches house_clf_batch_kernel itself with an EMPTY third mask (n = 0: no lane enters its loop and the offset does
+// not move), so the rows, the clamping, the ticket and the values -- those of two pcg_rand_bernoulli calls at offset and
+// offset + (B*w0+3)/4 -- are that kernel's, and no device code is added.
+namespace {
+int mnist_clf_batch_launch(const char* who, const float* X, const int64_t* Y, const int64_t* perm, int64_t n_perm, int64_t n_rows, float* x_out,
+                           int64_t* y_out, int32_t B, int32_t D, float* m0, int32_t w0, float keep0, float* m1, int32_t w1, float keep1,
+                           uint64_t seed, uint64_t offset, int64_t cursor, unsigned long long* counter, pcg_stream_t stream) {
+  PCG_REQUIRE(X && Y && perm && x_out && y_out && m0 && m1 && B > 0 && D > 0 && w0 > 0 && w1 > 0 && n_rows > 0, "%s: bad arguments", who);
+  PCG_REQUIRE(n_perm >= B && cursor >= 0 && cursor + B <= n_perm, "%s: rows %lld .. +%d of a permutation of %lld entries", who,
+              (long long)cursor, B, (long long)n_perm);
+  PCG_REQUIRE(keep0 >= 0.f && keep0 <= 1.f && keep1 >= 0.f && keep1 <= 1.f, "%s: keep probabilities must lie in [0, 1]", who);
+  ClfMasks mk{};
+  mk.m[0] = m0; mk.m[1] = m1; mk.m[2] = nullptr;
+  mk.n[0] = (int64_t)B * w0; mk.n[1] = (int64_t)B * w1; mk.n[2] = 0;
+  mk.keep[0] = keep0; mk.keep[1] = keep1; mk.keep[2] = 0.f;
+  const int64_t quads = std::max(std::max((mk.n[0] + 3) / 4, (mk.n[1] + 3) / 4), ((int64_t)B * D + 3) / 4);
+  unsigned blocks = grid_for(quads);
+  if (blocks > 256u) blocks = 256u;                           // one same-address ticket per block
+  hipLaunchKernelGGL(house_clf_batch_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, X, Y, perm, n_perm, n_rows, x_out, y_out, B, D, mk,
+                     seed, offset, cursor, counter);
+  return launch_status("house_clf_batch_kernel");
+}
+}  // namespace
+
+extern "C" int pcg_mnist_clf_batch(const float* X, const int64_t* Y, const int64_t* perm, int64_t n_perm, int64_t n_rows, float* x_out,
+                                   int64_t* y_out, int32_t B, int32_t D, float* m0, int32_t w0, float keep0, float* m1, int32_t w1, float keep1,
+                                   uint64_t seed, uint64_t offset, int64_t cursor, pcg_stream_t stream) {
+  return mnist_clf_batch_launch("pcg_mnist_clf_batch", X, Y, perm, n_perm, n_rows, x_out, y_out, B, D, m0, w0, keep0, m1, w1, keep1, seed, offset,
+                                cursor, nullptr, stream);
+}
+
+// counter: as pcg_house_clf_batch_counter's
+extern "C" int pcg_mnist_clf_batch_counter(const float* X, const int64_t* Y, const int64_t* perm, int64_t n_perm, int64_t n_rows, float* x_out,
+                                           int64_t* y_out, int32_t B, int32_t D, float* m0, int32_t w0, float keep0, float* m1, int32_t w1,
+                                           float keep1, uint64_t seed, uint64_t* counter, pcg_stream_t stream) {
+  PCG_REQUIRE(counter, "pcg_mnist_clf_batch_counter: null counter");
+  return mnist_clf_batch_launch("pcg_mnist_clf_batch_counter", X, Y, perm, n_perm, n_rows, x_out, y_out, B, D, m0, w0, keep0, m1, w1, keep1, seed,
+                                0, 0, reinterpret_cast<unsigned long long*>(counter), stream);
+}
+
 // counter: uint64[4] on the device = [Philox offset, ticket, row cursor into perm, unused]; the launch advances offset and cursor itself
 // (the host keeps cursor + B <= n_perm: the kernel clamps, it cannot report).
 extern "C" int pcg_house_clf_batch_counter(const float* X, const int64_t* Y, const int64_t* perm, int64_t n_perm, int64_t n_rows, float* x_out,

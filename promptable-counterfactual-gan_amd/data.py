@@ -215,9 +215,15 @@ class DeviceLoader:
     def __len__(self):
         return (self.x.shape[0] + self.batch_size - 1) // self.batch_size
 
+    def epoch_order(self):
+        """The next epoch's row order (host tensor; None without shuffling): the one draw an iteration makes from the loader's
+        generator, so a consumer that walks the rows itself (countergan.ClassifierFit) sees the batches __iter__ would yield."""
+        return torch.randperm(self.x.shape[0], generator=self._gen) if self.shuffle else None
+
     def __iter__(self):
         n = self.x.shape[0]
-        order = torch.randperm(n, generator=self._gen).to(self.x.device) if self.shuffle else None
+        order = self.epoch_order()
+        order = order.to(self.x.device) if order is not None else None
         for i in range(0, n, self.batch_size):
             if order is None:
                 yield self.x[i:i + self.batch_size], self.y[i:i + self.batch_size]

@@ -1654,6 +1654,59 @@ def nhwc_to_nchw_flat(src, B, HW, C, inverse=False):
     return dst
 
 
+def drop2d_flatten_fwd(a, mask, p, R, HW, C, out=None):
+    """nn.Dropout2d(p) + nn.Flatten of the NCHW tensor from the NHWC activation a [R, HW, C] in one launch
+    (pcg_drop2d_flatten_fwd): out [R, C * HW], out[b, c * HW + q] = a[b, q, c] * mask[b, c] / (1 - p) -- the bits of
+    dropout_apply(inner=HW) followed by nhwc_to_nchw_flat."""
+    _chk(a, "a"); _chk(mask, "mask")
+    if a.numel() != R * HW * C or mask.numel() != R * C:
+        raise _lib.PcgError(f"drop2d_flatten_fwd: a must hold {R}x{HW}x{C} values and mask {R}x{C}")
+    out = out if out is not None else torch.empty((R, C * HW), dtype=torch.float32, device=a.device)
+    if _chk(out, "out").numel() != a.numel():
+        raise _lib.PcgError(f"drop2d_flatten_fwd: out must be [{R}, {C * HW}]")
+    check(_lib.load().pcg_drop2d_flatten_fwd(_p(a), _p(mask), 1.0 / (1.0 - p), R, HW, C, _p(out), _stream()), "pcg_drop2d_flatten_fwd")
+    return out
+
+
+def drop2d_flatten_bwd(dflat, mask, p, y, R, HW, C, act=_lib.ACT_RELU, slope=0.0, out=None):
+    """The backward of drop2d_flatten_fwd and of the activation whose output y [R, HW, C] feeds it, in one launch
+    (pcg_drop2d_flatten_bwd): out[b, q, c] = dflat[b, c * HW + q] * mask[b, c] / (1 - p) * act'(y[b, q, c]) -- the bits of
+    nhwc_to_nchw_flat(inverse=True), dropout_apply(inner=HW), act_bwd."""
+    _chk(dflat, "dflat"); _chk(mask, "mask"); _chk(y, "y")
+    if dflat.numel() != R * HW * C or y.numel() != R * HW * C or mask.numel() != R * C:
+        raise _lib.PcgError(f"drop2d_flatten_bwd: dflat and y must hold {R}x{HW}x{C} values and mask {R}x{C}")
+    out = out if out is not None else torch.empty_like(y)
+    if _chk(out, "out").numel() != y.numel():
+        raise _lib.PcgError(f"drop2d_flatten_bwd: out must hold {R}x{HW}x{C} values")
+    check(_lib.load().pcg_drop2d_flatten_bwd(_p(dflat), _p(mask), 1.0 / (1.0 - p), _p(y), int(act), float(slope), R, HW, C, _p(out), _stream()),
+          "pcg_drop2d_flatten_bwd")
+    return out
+
+
+def mnist_clf_head(h, m1, p, W2, b2, y, tally, logits=None, loss=None, dW2=None, db2=None, dh=None, db1=None):
+    """Everything above fc1's output of the MNIST classifier's training step in one launch of one workgroup (pcg_mnist_clf_head):
+    Dropout(p) with the mask m1, Linear(W2, b2), mean cross-entropy against y, and the backward down to fc1's pre-activation.
+    h [R, 256] is fc1's post-ReLU output, R <= 128, K = W2.shape[0] <= 16.  tally (float64[3]) += (loss * R, rows whose argmax is
+    the label, R).  Returns (logits [R, K], loss [1], dW2 [K, 256], db2 [K], dh [R, 256], db1 [256]); buffers given are filled."""
+    _chk(h, "h"); _chk(m1, "m1"); _chk(W2, "W2"); _chk(b2, "b2"); _chk_idx(y, W2.shape[0], "y"); _chk(tally, "tally", torch.float64)
+    R, I = h.shape
+    K = W2.shape[0]
+    if tuple(m1.shape) != (R, I) or W2.shape[1] != I or b2.numel() != K or y.numel() != R or tally.numel() < 3:
+        raise _lib.PcgError(f"mnist_clf_head: h [R, I] {tuple(h.shape)}, m1 {tuple(m1.shape)}, W2 [K, I] {tuple(W2.shape)}, b2 [K], y [R], "
+                            "tally float64[3] do not agree")
+    f32 = lambda *s: torch.empty(s, dtype=torch.float32, device=h.device)      # noqa: E731
+    outs = []
+    for t, name, shape in ((logits, "logits", (R, K)), (loss, "loss", (1,)), (dW2, "dW2", (K, I)), (db2, "db2", (K,)), (dh, "dh", (R, I)),
+                           (db1, "db1", (I,))):
+        t = t if t is not None else f32(*shape)
+        if tuple(_chk(t, name).shape) != shape:
+            raise _lib.PcgError(f"mnist_clf_head: {name} must be {list(shape)}, got {list(t.shape)}")
+        outs.append(t)
+    check(_lib.load().pcg_mnist_clf_head(_p(h), _p(m1), 1.0 / (1.0 - p), _p(W2), _p(b2), _p(y), R, I, K, *[_p(t) for t in outs[:2]], _p(tally),
+                                         *[_p(t) for t in outs[2:]], _stream()), "pcg_mnist_clf_head")
+    return tuple(outs)
+
+
 def interpolate(alpha, real, fake):
     _chk(alpha, "alpha"); _chk(real, "real"); _chk(fake, "fake")
     B = alpha.numel()
@@ -1800,6 +1853,37 @@ class DeviceRNG:
     @staticmethod
     def house_clf_batch_span(B, widths):
         """Counter values one house_clf_batch call consumes."""
+        return sum((B * w + 3) // 4 for w in widths)
+
+    def mnist_clf_batch(self, X, Y, perm, out, masks, keeps, counter=None, cursor=0):
+        """house_clf_batch with the MNIST classifier's TWO Dropout masks: rows perm[cursor .. cursor+B) of the resident set (X [N, D]
+        float32, Y [N] int64) into out = (x [B, D], y [B]), and masks = (m0 [B, w0], m1 [B, w1]) with P(1) = keeps[i] -- the values
+        two bernoulli() calls give in this order.  counter None: by value, the host offset advances; counter
+        (device_counter(device, cursor=True)): offset and cursor live on the device and the launch advances them (capturable)."""
+        o_x, o_y = out
+        B, D = o_x.shape
+        _chk(X, "X"); _chk(Y, "Y", torch.int64); _chk(perm, "perm", torch.int64); _chk(o_x, "x"); _chk(o_y, "y", torch.int64)
+        if len(masks) != 2 or len(keeps) != 2 or any(_chk(m, "mask").dim() != 2 or m.shape[0] != B for m in masks):
+            raise _lib.PcgError(f"mnist_clf_batch: two masks of {B} rows and two keep probabilities")
+        if X.dim() != 2 or X.shape[1] != D or Y.numel() != X.shape[0] or o_y.numel() != B or perm.numel() < B:
+            raise _lib.PcgError("mnist_clf_batch: X [N, D], Y [N], x [B, D], y [B], perm >= B entries")
+        args = [a for m, k in zip(masks, keeps) for a in (_p(m), m.shape[1], float(k))]
+        if counter is not None:
+            if counter.numel() < 4 or counter.dtype != torch.int64 or not counter.is_cuda:
+                raise _lib.PcgError("mnist_clf_batch: counter must be int64[4] on the device (device_counter(cursor=True))")
+            check(_lib.load().pcg_mnist_clf_batch_counter(_p(X), _p(Y), _p(perm), perm.numel(), X.shape[0], _p(o_x), _p(o_y), B, D, *args, self.seed,
+                                                          _p(counter), _stream()), "pcg_mnist_clf_batch_counter")
+            return out, masks
+        if cursor < 0 or cursor + B > perm.numel():
+            raise _lib.PcgError(f"mnist_clf_batch: rows {cursor} .. +{B} of a permutation of {perm.numel()} entries")
+        off = self._advance(self.mnist_clf_batch_span(B, [m.shape[1] for m in masks]))
+        check(_lib.load().pcg_mnist_clf_batch(_p(X), _p(Y), _p(perm), perm.numel(), X.shape[0], _p(o_x), _p(o_y), B, D, *args, self.seed, off,
+                                              int(cursor), _stream()), "pcg_mnist_clf_batch")
+        return out, masks
+
+    @staticmethod
+    def mnist_clf_batch_span(B, widths):
+        """Counter values one mnist_clf_batch call consumes."""
         return sum((B * w + 3) // 4 for w in widths)
 
     @staticmethod
