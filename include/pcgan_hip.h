@@ -1433,6 +1433,22 @@ int pcg_calib_mfma(int32_t iters, int32_t rounds, void* workspace, size_t worksp
                    uint64_t** stamps_out /*nullable*/, pcg_stream_t stream);
 int pcg_calib_copy(const void* src, void* dst, int64_t nbytes, pcg_stream_t stream);
 
+/* ---- ReLU + MaxPool2d(2) of the max-pool MNIST classifier (conditional_counteRGAN/mnist/modules/classifier.py:9-13) --------------------
+ * fp32, NHWC [B][H][W][C] with C % 4 == 0 (any other C is refused), 2x2 windows, stride 2, floor mode: Hp = H / 2, Wp = W / 2.
+ * Streaming kernels (maxpool.hip): one thread owns four channels of one pooled pixel; no LDS, no atomics, grid-stride; every entry may
+ * be captured into a HIP graph.
+ * pcg_relu_maxpool2_fwd replaces nn.ReLU + nn.MaxPool2d(2) (modules/classifier.py:9-10 and :12-13): z is the convolution's output, raw
+ * or already through ReLU (the kernel applies ReLU itself; a NaN survives it).  p [B][Hp][Wp][C] = max over the window of relu(z);
+ * idx [B][Hp][Wp][C] (uint8, dh * 2 + dw) = the position torch.nn.functional.max_pool2d(..., return_indices=True) picks: row-major scan,
+ * a later cell wins only if strictly greater or NaN, so ties (the all-zero window of a dead ReLU patch too) keep the first cell. */
+int pcg_relu_maxpool2_fwd(const float* z, float* p, uint8_t* idx, int32_t B, int32_t H, int32_t W, int32_t C, pcg_stream_t stream);
+/* The backward of the same two layers (modules/classifier.py:9-10, :12-13) in one pass: dz [B][H][W][C], the gradient with respect to the
+ * convolution's RAW output.  The chosen cell of each window gets dp where p > 0 (p > 0 is that cell's ReLU mask, so z is not read; a NaN
+ * p counts as live, as in torch) and 0 elsewhere; the other three cells, and the row / column an odd H / W leaves outside every
+ * window, get 0.  Every element of dz is stored exactly once: no pre-zeroing, no atomics, deterministic. */
+int pcg_relu_maxpool2_bwd(const float* dp, const float* p, const uint8_t* idx, float* dz, int32_t B, int32_t H, int32_t W, int32_t C,
+                          pcg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

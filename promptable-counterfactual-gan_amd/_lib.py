@@ -487,6 +487,8 @@ PROTOTYPES = {
     "pcg_mnist_clf_batch_counter": (_i, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _i32, _i32, _vp, _i32, _f, _vp, _i32, _f, _c.c_uint64, _vp, _vp]),
     "pcg_drop2d_flatten_fwd": (_i, [_vp, _vp, _f, _i32, _i32, _i32, _vp, _vp]),
     "pcg_drop2d_flatten_bwd": (_i, [_vp, _vp, _f, _vp, _i, _f, _i32, _i32, _i32, _vp, _vp]),
+    "pcg_relu_maxpool2_fwd": (_i, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
+    "pcg_relu_maxpool2_bwd": (_i, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
     "pcg_mnist_clf_head": (_i, [_vp, _vp, _f, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pcg_spectral_norm_fwd": (_i, [_vp, _i32, _i32, _vp, _vp, _f, _i, _vp, _vp, _vp, _vp, _vp]),
     "pcg_spectral_norm_bwd": (_i, [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _i, _vp]),

@@ -6,6 +6,9 @@
     models/generator.py  ResidualGenerator :25-86           ResidualGenerator (same ctor args, same state_dict keys)
     models/discriminator.py Discriminator  :5-38            Discriminator
     models/classifier.py CNNClassifier     :4-28            CNNClassifier (frozen / eval use: forward + grad-input)
+    modules/classifier.py Classifier       :4-30            Classifier, save_classifier, load_classifier (the max-pool net of countergan2.py /
+                                                            gan_train.py; fit_pool_classifier: countergan2.py:120-151; get_pool_classifier:
+                                                            gan_train.py:49-88)
     trainer.py           train_classifier  :8-39            train_classifier (fused=True: ClassifierFit, one graph replay per step)
     trainer.py           build_mask        :45-72           build_mask (same draws from torch's RNG)
     trainer.py           train_countergan  :76-123          make_optimizers + train_step (+ train_countergan loop)
@@ -730,6 +733,202 @@ class CNNClassifier(FrozenClassifier):
         return d.view(B, 1, 28, 28)
 
 
+# ---- the max-pool classifier of countergan2.py / gan_train.py (modules/classifier.py) ---------------------------------------------
+class Classifier(FrozenClassifier):
+    """modules/classifier.py:4-21 — Conv(1->32, k3 p1), ReLU, MaxPool2d(2), Conv(32->64, k3 p1), ReLU, MaxPool2d(2), Flatten,
+    Linear(3136->128), ReLU, Linear(128->10) under `self.net`, the reference's nn.Sequential: state_dict() keys `net.{0,3,7,9}.*` and
+    shapes are the reference's, so the shipped models/classifier.pt loads with strict=True and ours loads into the reference's module.
+    ReLU + MaxPool2d are one launch each way (ops.relu_maxpool2_fwd / _bwd): the forward keeps the pooled tensor and
+    the window positions, never the un-pooled convolution output.  Frozen / eval: forward and input gradient in six launches each, on
+    packed weights.  Training mode: a regular trainable net (fit_pool_classifier); it has no Dropout."""
+
+    honours_conv_precision = True   # conv2 and fc1 are implicit-GEMM layers; the pooling kernels are fp32 either way
+
+    def __init__(self):
+        super().__init__()
+        self.net = nn.Sequential(
+            nn.Conv2d(1, 32, 3, padding=1), nn.ReLU(), nn.MaxPool2d(2),
+            nn.Conv2d(32, 64, 3, padding=1), nn.ReLU(), nn.MaxPool2d(2),
+            nn.Flatten(), nn.Linear(64 * 7 * 7, 128), nn.ReLU(), nn.Linear(128, 10),
+        )
+        self.num_classes = 10
+
+    def _pack(self):
+        """Images of the frozen weights (rebuilt if the parameters change): conv weights OHWI; net.7's columns re-ordered from
+        (c,h,w) to (h,w,c) so it consumes the NHWC pooled tensor with no flatten launch; net.9 padded from 10 to 12 outputs
+        (16-byte rows), as CNNClassifier pads its head.  One-time setup copies, not part of the step."""
+        key = tuple((p.data_ptr(), p._version) for p in self.parameters())
+        if self._packed is not None and self._packed[0] == key:
+            return self._packed[1]
+        if self.training:
+            raise PcgError("Classifier: the packed path is the eval path (training mode runs on the trainable parameters)")
+        c1, c2, fc1, fc2 = self.net[0], self.net[3], self.net[7], self.net[9]
+        with torch.no_grad():
+            cw = [(c, c.weight.permute(0, 2, 3, 1).contiguous(), c.bias.contiguous()) for c in (c1, c2)]
+            w1 = fc1.weight.view(fc1.out_features, 64, 7, 7).permute(0, 2, 3, 1).contiguous().view(fc1.out_features, -1)
+            kp = (self.num_classes + 3) // 4 * 4
+            w2 = torch.zeros(kp, fc2.in_features, device=fc2.weight.device)
+            w2[: self.num_classes] = fc2.weight
+            b2 = torch.zeros(kp, device=fc2.weight.device)
+            b2[: self.num_classes] = fc2.bias
+        packed = (cw, w1, fc1.bias.contiguous(), w2, b2, kp)
+        self._packed = (key, packed)
+        return packed
+
+    def _draw_dropout_masks(self, x):
+        return []                                     # the net has no Dropout
+
+    # -- frozen / eval -----------------------------------------------------------------------------------------------------------
+    def _logits_padded(self, a, keep, out=None):
+        """Six launches from the NHWC image a [B, 28, 28, 1] to the padded logits [B, kp]: conv1 (thin), pool, conv2, pool, fc1 as a
+        1x1 convolution with ReLU, fc2.  The convolutions write their raw output; the pooling kernel applies the ReLU."""
+        cw, w1, b1, w2, b2, kp = self._pack()
+        B = a.shape[0]
+        pooled = []
+        for conv, w, b in cw:
+            g = _geom(conv, B, a.shape[1], a.shape[2])
+            p, idx = ops.relu_maxpool2_fwd(ops.conv2d_fwd(g, a, w, b))
+            pooled.append((g, w, p, idx))
+            a = p
+        feat = a.numel() // B
+        g1 = ops.conv_geom(B, 1, 1, feat, w1.shape[0], 1, 1, 1, 0)
+        h = ops.conv2d_fwd(g1, a.view(B, 1, 1, feat), w1, b1, act=ACT_RELU)
+        g2 = ops.conv_geom(B, 1, 1, w1.shape[0], kp, 1, 1, 1, 0)
+        logits = ops.conv2d_fwd(g2, h, w2, b2, out=out).view(B, kp)
+        if not keep:
+            return logits, None
+        (gc1, wc1, p1, idx1), (gc2, wc2, p2, idx2) = pooled
+        return logits, dict(p1=p1, idx1=idx1, p2=p2, idx2=idx2, h=h, geoms=(gc1, gc2, g1, g2), weights=(wc1, wc2, w1, w2), kp=kp)
+
+    @in_conv_precision
+    def _run_forward(self, x, keep=True):
+        B = x.shape[0]
+        logits, saved = self._logits_padded(_as_rows(x, B).view(B, 28, 28, 1), keep)
+        return logits[:, : self.num_classes], saved
+
+    @in_conv_precision
+    def padded_logits(self, rows, out=None):
+        """The eval forward on image rows [n, 784] with the padded columns kept ([n, kp], kp = 12) and an optional destination:
+        what the counterfactual front ends' score kernel reads."""
+        n = rows.shape[0]
+        return self._logits_padded(rows.view(n, 28, 28, 1), False, out=out)[0]
+
+    @in_conv_precision
+    def _run_backward(self, saved, dlogits):
+        """The input gradient in six launches: fc2 grad-input with h's ReLU, fc1 grad-input, pool backward, conv2 grad-input, pool
+        backward, conv1 grad-input.  The pool backward applies the ReLU mask of the layer below it (p > 0), so the grad-inputs that
+        feed it carry no activation."""
+        gc1, gc2, g1, g2 = saved["geoms"]
+        wc1, wc2, w1, w2 = saved["weights"]
+        kp = saved["kp"]
+        B = dlogits.shape[0]
+        dl = torch.empty((B, kp), dtype=torch.float32, device=dlogits.device)
+        ops.fill(dl, 0.0)
+        dl[:, : self.num_classes].copy_(dlogits)      # pad 10 -> 12 columns (tiny strided copy)
+        d = _dgrad_act(g2, dl, w2, saved["h"], ACT_RELU, 0.0)
+        d = ops.conv2d_dgrad(g1, d, w1).view(saved["p2"].shape)
+        d = ops.relu_maxpool2_bwd(d, saved["p2"], saved["idx2"], (gc2.OH, gc2.OW))
+        d = ops.conv2d_dgrad(gc2, d, wc2).view(saved["p1"].shape)
+        d = ops.relu_maxpool2_bwd(d, saved["p1"], saved["idx1"], (gc1.OH, gc1.OW))
+        return ops.conv2d_dgrad(gc1, d, wc1).view(B, 1, 28, 28)
+
+    # -- training mode (countergan2.py:127-136) -------------------------------------------------------------------------------------
+    @in_conv_precision
+    def _train_forward(self, x, masks):
+        from .nn import linear_fwd
+        B = x.shape[0]
+        c1, c2, fc1, fc2 = self.net[0], self.net[3], self.net[7], self.net[9]
+        a0 = _as_rows(x, B).view(B, 28, 28, 1)
+        g1, z1 = _conv_fwd(c1, a0)
+        p1, idx1 = ops.relu_maxpool2_fwd(z1)
+        g2, z2 = _conv_fwd(c2, p1)
+        p2, idx2 = ops.relu_maxpool2_fwd(z2)
+        HW, C = p2.shape[1] * p2.shape[2], p2.shape[3]
+        flat = ops.nhwc_to_nchw_flat(p2, B, HW, C).view(B, HW * C)        # nn.Flatten of the NCHW tensor: net.7's own column order
+        h = linear_fwd(fc1, flat, act=ACT_RELU)
+        logits = linear_fwd(fc2, h)
+        return logits, (a0, g1, p1, idx1, g2, p2, idx2, flat, h)
+
+    @in_conv_precision
+    def _train_backward(self, saved, dlogits):
+        from .nn import linear_dgrad, linear_wgrad
+        a0, g1, p1, idx1, g2, p2, idx2, flat, h = saved
+        B = flat.shape[0]
+        c1, c2, fc1, fc2 = self.net[0], self.net[3], self.net[7], self.net[9]
+        dl = dlogits.contiguous()
+        linear_wgrad(self, fc2, h, dl)
+        d = linear_dgrad(fc2.weight.data, dl, B)
+        ops.act_bwd(d, h, ACT_RELU, 0.0, out=d)
+        linear_wgrad(self, fc1, flat, d)
+        d = linear_dgrad(fc1.weight.data, d, B)
+        d = ops.nhwc_to_nchw_flat(d, B, p2.shape[1] * p2.shape[2], p2.shape[3], inverse=True).view(p2.shape)
+        d = ops.relu_maxpool2_bwd(d, p2, idx2, (g2.OH, g2.OW))
+        d = _conv_bwd(self, c2, g2, p1, d, True, True).view(p1.shape)
+        d = ops.relu_maxpool2_bwd(d, p1, idx1, (g1.OH, g1.OW))
+        _conv_bwd(self, c1, g1, a0, d, True, False)
+
+
+def save_classifier(model, path):
+    """modules/classifier.py:23-24."""
+    torch.save({k: v.detach().cpu().contiguous() for k, v in model.state_dict().items()}, path)
+
+
+def load_classifier(path, device):
+    """modules/classifier.py:26-30: a Classifier with the checkpoint's weights, on `device`, in eval mode."""
+    model = Classifier()
+    model.load_state_dict(torch.load(path, map_location="cpu", weights_only=True), strict=True)
+    return model.to(device).eval()
+
+
+def pool_fit_step(classifier, optimizer, x, y, ones, tally, loss_out=None):
+    """One iteration of countergan2.py:129-136: forward, mean cross-entropy, backward, Adam.  The loss, its gradient and the epoch's
+    running sum (tally += loss * rows, hits, rows) come out of one launch; nothing is read back."""
+    optimizer.zero_grad()
+    logits = classifier(x)
+    lc = logits.detach().contiguous()
+    dl = torch.empty_like(lc)
+    ops.ce_weighted_tally(lc, y, ones, tally, dlogits=dl, seg_loss=loss_out)
+    logits.backward(dl)
+    optimizer.step()
+
+
+def fit_pool_classifier(classifier, train_loader, valid_loader, epochs=10, lr=1e-3, device=Config.device):
+    """countergan2.py:120-151 — Adam(lr), CrossEntropyLoss, per-epoch train and validation loss (sum of loss * rows / rows).  The
+    sums stay on the device (ops.ce_weighted_tally) and each epoch makes ONE host read.  Returns (train_losses, valid_losses)."""
+    classifier.to(device)
+    optimizer = Adam(classifier.parameters(), lr=lr)
+    ones = torch.ones(classifier.num_classes, dtype=torch.float32, device=device)
+    tallies = torch.zeros(2, 3, dtype=torch.float64, device=device)
+    train_losses, valid_losses = [], []
+    for epoch in range(epochs):
+        ops.fill(tallies.view(torch.float32), 0.0)
+        classifier.train()
+        for x, y in train_loader:
+            pool_fit_step(classifier, optimizer, x.to(device), y.to(device), ones, tallies[0])
+        classifier.eval()
+        with torch.no_grad():
+            for x, y in valid_loader:
+                ops.ce_weighted_tally(classifier(x.to(device)).contiguous(), y.to(device), ones, tallies[1])
+        t = tallies.cpu()                                                          # the epoch's one host read
+        train_losses.append(float(t[0, 0] / max(float(t[0, 2]), 1.0)))
+        valid_losses.append(float(t[1, 0] / max(float(t[1, 2]), 1.0)))
+        print(f"Epoch {epoch + 1} - Train loss: {train_losses[-1]:.4f} | Valid loss: {valid_losses[-1]:.4f}")
+    return train_losses, valid_losses
+
+
+def get_pool_classifier(path, train_loader=None, valid_loader=None, epochs=10, lr=1e-3, device=Config.device):
+    """gan_train.py:49-88 — load the classifier if `path` exists, else fit one (fit_pool_classifier) and save it there.  Returns the
+    net in eval mode."""
+    if os.path.exists(path):
+        return load_classifier(path, device)
+    if train_loader is None or valid_loader is None:
+        raise PcgError(f"get_pool_classifier: {path} does not exist and no loaders were given to fit a classifier")
+    classifier = Classifier().to(device)
+    fit_pool_classifier(classifier, train_loader, valid_loader, epochs=epochs, lr=lr, device=device)
+    save_classifier(classifier, path)
+    return classifier.eval()
+
+
 # ---- trainer ------------------------------------------------------------------------------------------------------------
 def build_mask(x, patch_size, device, num_modifiable_patches=None):
     """trainer.py:45-72 — same draws from torch's RNG as the reference (host loop over the batch; moving this to the
@@ -1316,7 +1515,10 @@ def make_mask_from_patch_list(x_batch, patch_size, allowed_patches, device=None)
 
 def _padded_logits(classifier, rows, out=None):
     """The frozen classifier's logits [n, kp] (kp = num_classes padded to a multiple of 4) of image rows [n, 784]: CNNClassifier's
-    eval forward with the padded columns kept (the score kernel reads rows of kp floats) and an optional destination."""
+    eval forward with the padded columns kept (the score kernel reads rows of kp floats) and an optional destination.  A classifier
+    with a `padded_logits(rows, out)` method of its own (Classifier) supplies them itself."""
+    if hasattr(classifier, "padded_logits"):
+        return classifier.padded_logits(rows, out=out)
     with ops.conv_precision(classifier.conv_precision):
         cw, w1, b1, w2, b2, kp = classifier._pack()
         n = rows.shape[0]

@@ -1654,6 +1654,57 @@ def nhwc_to_nchw_flat(src, B, HW, C, inverse=False):
     return dst
 
 
+def _chk_pool(args):
+    """args: (tensor, name, dtype, expected shape or None) per NHWC argument of a pooling call.  Shape, dtype and contiguity of EVERY
+    argument first, the device last: the host-only checks can be exercised without a GPU."""
+    for t, name, dtype, shape in args:
+        if t.dim() != 4:
+            raise _lib.PcgError(f"{name}: expected an NHWC tensor [B, H, W, C], got shape {tuple(t.shape)}")
+        if shape is not None and tuple(t.shape) != tuple(shape):
+            raise _lib.PcgError(f"{name}: expected shape {tuple(shape)}, got {tuple(t.shape)}")
+        if t.shape[3] % 4 != 0:
+            raise _lib.PcgError(f"{name}: C must be a multiple of 4 (one thread owns four channels), got {t.shape[3]}")
+        if t.dtype != dtype:
+            raise _lib.PcgError(f"{name}: expected {dtype}, got {t.dtype}")
+        if not t.is_contiguous():
+            raise _lib.PcgError(f"{name}: expected a contiguous tensor, got strides {t.stride()} for shape {tuple(t.shape)}")
+    for t, name, _, _ in args:
+        if not t.is_cuda:
+            raise _lib.PcgError(f"{name}: expected a tensor on the GPU (libpcgan_hip has no CPU path), got {t.device}")
+
+
+def relu_maxpool2_fwd(z, out=None, idx=None):
+    """nn.ReLU + nn.MaxPool2d(2) of the NHWC activation z [B, H, W, C] (C % 4 == 0) in one launch (pcg_relu_maxpool2_fwd):
+    (p [B, H//2, W//2, C] fp32, idx uint8 of the same shape: the winning cell dh * 2 + dw, chosen as torch's max_pool2d chooses it).
+    z may be raw or already through ReLU."""
+    if z.dim() == 4 and min(z.shape[1], z.shape[2]) < 2:
+        raise _lib.PcgError(f"relu_maxpool2_fwd: H and W must be at least 2, got {z.shape[1]}x{z.shape[2]}")
+    ps = (z.shape[0], z.shape[1] // 2, z.shape[2] // 2, z.shape[3]) if z.dim() == 4 else None
+    _chk_pool([(z, "z", torch.float32, None)] + ([(out, "out", torch.float32, ps)] if out is not None else [])
+              + ([(idx, "idx", torch.uint8, ps)] if idx is not None else []))
+    B, H, W, C = z.shape
+    p = out if out is not None else torch.empty(ps, dtype=torch.float32, device=z.device)
+    idx = idx if idx is not None else torch.empty(ps, dtype=torch.uint8, device=z.device)
+    check(_lib.load().pcg_relu_maxpool2_fwd(_p(z), _p(p), _p(idx), B, H, W, C, _stream()), "pcg_relu_maxpool2_fwd")
+    return p, idx
+
+
+def relu_maxpool2_bwd(dp, p, idx, hw, out=None):
+    """The backward of relu_maxpool2_fwd in one launch (pcg_relu_maxpool2_bwd): dz [B, H, W, C] for hw = (H, W), the gradient with
+    respect to the convolution's raw output -- dp where p > 0 at each window's chosen cell, 0 everywhere else, every element
+    written once.  Reads p (the forward's output), never z."""
+    H, W = int(hw[0]), int(hw[1])
+    if dp.dim() == 4 and (H // 2 != dp.shape[1] or W // 2 != dp.shape[2] or min(dp.shape[1], dp.shape[2]) < 1):
+        raise _lib.PcgError(f"relu_maxpool2_bwd: hw = {H}x{W} does not pool to dp's {dp.shape[1]}x{dp.shape[2]}")
+    zs = (dp.shape[0], H, W, dp.shape[3]) if dp.dim() == 4 else None
+    _chk_pool([(dp, "dp", torch.float32, None), (p, "p", torch.float32, dp.shape), (idx, "idx", torch.uint8, dp.shape)]
+              + ([(out, "out", torch.float32, zs)] if out is not None else []))
+    B, C = dp.shape[0], dp.shape[3]
+    dz = out if out is not None else torch.empty(zs, dtype=torch.float32, device=dp.device)
+    check(_lib.load().pcg_relu_maxpool2_bwd(_p(dp), _p(p), _p(idx), _p(dz), B, H, W, C, _stream()), "pcg_relu_maxpool2_bwd")
+    return dz
+
+
 def drop2d_flatten_fwd(a, mask, p, R, HW, C, out=None):
     """nn.Dropout2d(p) + nn.Flatten of the NCHW tensor from the NHWC activation a [R, HW, C] in one launch
     (pcg_drop2d_flatten_fwd): out [R, C * HW], out[b, c * HW + q] = a[b, q, c] * mask[b, c] / (1 - p) -- the bits of
