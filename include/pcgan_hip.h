@@ -1449,6 +1449,123 @@ int pcg_relu_maxpool2_fwd(const float* z, float* p, uint8_t* idx, int32_t B, int
 int pcg_relu_maxpool2_bwd(const float* dp, const float* p, const uint8_t* idx, float* dz, int32_t B, int32_t H, int32_t W, int32_t C,
                           pcg_stream_t stream);
 
+/* ---- the launches around the convolutions of the additive-delta MNIST CounteRGAN (conditional_counteRGAN/mnist/gan_train.py:117-144
+ * on modules/generator.py and modules/discriminator.py; csrc/delta_gan.hip) ---------------------------------
+ * All fp32, gfx950 only, every sum in a fixed order, no floating-point atomics; every entry takes a stream and may be captured into a
+ * HIP graph.  Every entry validates its arguments before it touches HIP: PCG_ERR_INVALID and a pcg_last_error text otherwise.
+ * Rows are images of HW pixels; an NHWC tensor of C channels holds pixel p of row b at [b][p][c].                                      */
+#define PCG_DELTA_GAN_BUILD 0     /* pcg_delta_gan_entry: build g_in and d_in                                                          */
+#define PCG_DELTA_GAN_REGATHER 1  /* pcg_delta_gan_entry: rewrite channel 1 of d_in rows B..2B only                                    */
+#define PCG_LOGIT_HEAD_D 0        /* pcg_logit_head_fwd: rows 0..R/2 labelled 1, the rest 0; loss = mean(real) + mean(fake)            */
+#define PCG_LOGIT_HEAD_G 1        /* pcg_logit_head_fwd: every row labelled 1; loss = mean                                             */
+#define PCG_DELTA_GAN_CHUNK 1024  /* elements per partial sum of pcg_delta_gan_tail_fwd                                                */
+
+/* The 2-channel inputs of both nets in one launch (generator.py:19-20 at gan_train.py:122,133; discriminator.py:21-22 at :123-124):
+ *   g_in [B][HW][2]  = (x, table_g[target])
+ *   d_in [2B][HW][2]: rows 0..B = (x, table_d[y]); rows B..2B get channel 1 = table_d[target] (their channel 0 is x_cf, written by
+ *                     pcg_delta_gan_tail_fwd).
+ * Pure copies: the bits pcg_embed_concat_fwd writes.  mode PCG_DELTA_GAN_REGATHER writes nothing but channel 1 of d_in rows B..2B
+ * (the label map of D's pass in the G step, :134, from the table Adam(D) has just updated, :130); x, y, table_g, g_in may be null then.
+ * labels_2b (nullable, [2B]) receives (y, target): the index of D's embedding-table gradient.  head_w / head_w_packed (nullable, both
+ * or neither; [head_P * head_C]) : head_w_packed[p * head_C + c] = head_w[c * head_P + p], the (h,w,c) image of a Linear weight row
+ * whose columns nn.Flatten orders (c,h,w) (discriminator.py:15-16), refreshed by the same launch in either mode.
+ * y and target are device pointers.  y_host / target_host (nullable) are host copies of the same labels: where given, a label outside
+ * 0..K-1 is refused before any launch.  Without them a label is clamped into the table, as pcg_embed_concat_fwd clamps it.           */
+typedef struct pcg_delta_gan_entry_args {
+  const float* x;              /* [B][HW]                                                      */
+  const int64_t* y;            /* [B], device                                                  */
+  const int64_t* target;       /* [B], device                                                  */
+  const int64_t* y_host;       /* nullable: host copy of y, range-checked                      */
+  const int64_t* target_host;  /* nullable: host copy of target, range-checked                 */
+  const float* table_g;        /* [K][HW]                                                      */
+  const float* table_d;        /* [K][HW]                                                      */
+  float* g_in;                 /* [B][HW][2]                                                   */
+  float* d_in;                 /* [2B][HW][2]                                                  */
+  int64_t* labels_2b;          /* nullable: [2B] = (y, target)                                 */
+  const float* head_w;         /* nullable: [head_C * head_P], columns (c, p)                  */
+  float* head_w_packed;        /* nullable: [head_P * head_C], columns (p, c)                  */
+  int32_t B, HW, K, mode, head_C, head_P;
+} pcg_delta_gan_entry_args;
+int pcg_delta_gan_entry(const pcg_delta_gan_entry_args* args, pcg_stream_t stream);
+
+/* What follows G's last, one-channel convolution (generator.py:22 at gan_train.py:133, the input of :134-135, and :139):
+ *   x_cf[b][p] = x[b][p] + delta[b][p]                   (the classifier's input)
+ *   d_in[B + b][p][0] = the same value                   (channel 0 of D's rows B..2B; d_in is the [2B][HW][2] tensor of the entry)
+ *   loss_reg[0] = mean |delta|
+ * The mean's order is fixed by the data alone: the n = B * HW elements are cut into chunks of PCG_DELTA_GAN_CHUNK, a chunk's sum is
+ * one 256-thread tree over four-element thread sums, and the last workgroup to arrive adds the chunk sums in index order (thread t
+ * takes chunks t, t + 256, ... in float64, then a tree).  grid (0: one workgroup per chunk, at most 1024) changes no bit.
+ * workspace: pcg_delta_gan_tail_workspace_bytes(B, HW) bytes, 16-byte aligned, whose first 16 bytes are zero at the first call; the
+ * entry leaves them zero.  HW % 4 == 0; x, delta, x_cf 16-byte aligned, d_in 8-byte aligned.                                          */
+typedef struct pcg_delta_gan_tail_fwd_args {
+  const float* x;       /* [B][HW] */
+  const float* delta;   /* [B][HW] */
+  float* x_cf;          /* [B][HW] */
+  float* d_in;          /* [2B][HW][2] */
+  float* loss_reg;      /* [1] */
+  void* workspace;
+  size_t workspace_bytes;
+  int32_t B, HW, grid;
+} pcg_delta_gan_tail_fwd_args;
+size_t pcg_delta_gan_tail_workspace_bytes(int32_t B, int32_t HW);
+int pcg_delta_gan_tail_fwd(const pcg_delta_gan_tail_fwd_args* args, pcg_stream_t stream);
+
+/* nn.Flatten + nn.Linear(F -> 1) (discriminator.py:15-16) + nn.BCEWithLogitsLoss (gan_train.py:127 in mode PCG_LOGIT_HEAD_D, :137 in
+ * mode PCG_LOGIT_HEAD_G) and the loss's gradient, in one launch.  a [R][F]: D's last activation, NHWC, through its LeakyReLU; w [F]:
+ * the weight row with its columns packed (h,w,c) (pcg_delta_gan_entry's head_w_packed); bias [1].
+ *   logits[r] = a[r] . w + bias      one workgroup per row: thread t folds the 16-byte groups t, t + 256, ... with fmaf, then a tree
+ *   loss[0]   = mode D: mean over rows 0..R/2 of l(z, 1) + mean over rows R/2..R of l(z, 0); mode G: mean over all rows of l(z, 1),
+ *               l(z, t) = (1 - t) z + max(-z, 0) + log(exp(-max(-z, 0)) + exp(-z - max(-z, 0)))  -- pcg_bce_logits_fwd_bwd's element
+ *   dlogit[r] = (1 / rows of the mean) * (sigmoid(z) - t)                                        -- pcg_bce_logits_fwd_bwd's element
+ *   db[0]     = sum over r of dlogit[r]   (thread t takes rows t, t + 256, ... in order, then a tree)
+ * The last workgroup to arrive forms loss, dlogit and db.  workspace: 16 bytes, 4-byte aligned, zero at the first call, left zero.
+ * R >= 1, even in mode D; F % 4 == 0; a and w 16-byte aligned.                                                                         */
+typedef struct pcg_logit_head_fwd_args {
+  const float* a;       /* [R][F] */
+  const float* w;       /* [F], packed (h,w,c) */
+  const float* bias;    /* [1] */
+  float* logits;        /* [R] */
+  float* loss;          /* [1] */
+  float* dlogit;        /* [R] */
+  float* db;            /* [1] */
+  void* workspace;      /* 16 bytes */
+  int32_t R, F, mode;
+} pcg_logit_head_fwd_args;
+int pcg_logit_head_fwd(const pcg_logit_head_fwd_args* args, pcg_stream_t stream);
+
+/* The backward of the same head down to conv3's pre-activation (gan_train.py:129 / :143 through discriminator.py:14-16), one pass over a:
+ *   da[r][f] = (dlogit[r] * w[f]) * (a[r][f] > 0 ? 1 : slope)     the grad-input with the LeakyReLU derivative already applied
+ *   dw[f]    = sum over r of dlogit[r] * a[r][f]                   (nullable: mode G passes NULL and dw is not touched)
+ * dw's rows are taken in index order: the R rows are cut into 16 contiguous groups of ceil(R / 16), a group is folded row by row with
+ * fmaf, and the group sums are added in group order.  dw_C, dw_P (both 0: dw[f] is stored at f): column f = p * dw_C + c is stored at
+ * dw[c * dw_P + p], the (c,h,w) order of the Linear weight's own gradient; dw_C * dw_P == F then.
+ * F % 4 == 0; a, w, da 16-byte aligned.                                                                                                */
+typedef struct pcg_logit_head_bwd_args {
+  const float* a;        /* [R][F] */
+  const float* w;        /* [F], packed (h,w,c) */
+  const float* dlogit;   /* [R] */
+  float* da;             /* [R][F] */
+  float* dw;             /* nullable: [F] */
+  float slope;
+  int32_t R, F, dw_C, dw_P;
+} pcg_logit_head_bwd_args;
+int pcg_logit_head_bwd(const pcg_logit_head_bwd_args* args, pcg_stream_t stream);
+
+/* The gradient of loss_G (gan_train.py:141-143) with respect to delta in one launch:
+ *   d_delta[b][p] = dD[(b * HW + p) * dD_stride] + lambda_cls * dC[b][p] + reg_scale * sign(delta[b][p])
+ * added in exactly that order, every product and sum rounded on its own (no contraction).  dD: channel 0 of D's grad-input (dD_stride
+ * 2), or the one-channel grad-input (dD_stride 1); dC: the classifier's input gradient; reg_scale = lambda_reg / (B * HW), the
+ * caller's rounding; sign(0) = 0, as the backward of torch.abs has it.                                                                 */
+typedef struct pcg_delta_gan_tail_bwd_args {
+  const float* dD;
+  const float* dC;       /* [B][HW] */
+  const float* delta;    /* [B][HW] */
+  float* d_delta;        /* [B][HW] */
+  float lambda_cls, reg_scale;
+  int32_t B, HW, dD_stride;
+} pcg_delta_gan_tail_bwd_args;
+int pcg_delta_gan_tail_bwd(const pcg_delta_gan_tail_bwd_args* args, pcg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -242,6 +242,38 @@ class HouseDiagArgs(ctypes.Structure):
                 ("out4", _P), ("acc", _P)])
 
 
+class DeltaGanEntryArgs(ctypes.Structure):
+    """pcg_delta_gan_entry_args."""
+    _fields_ = ([(n, _P) for n in ("x", "y", "target", "y_host", "target_host", "table_g", "table_d", "g_in", "d_in", "labels_2b", "head_w",
+                                   "head_w_packed")] + [(n, _I) for n in ("B", "HW", "K", "mode", "head_C", "head_P")])
+
+
+class DeltaGanTailFwdArgs(ctypes.Structure):
+    """pcg_delta_gan_tail_fwd_args."""
+    _fields_ = ([(n, _P) for n in ("x", "delta", "x_cf", "d_in", "loss_reg", "workspace")] + [("workspace_bytes", ctypes.c_size_t)] +
+                [(n, _I) for n in ("B", "HW", "grid")])
+
+
+class LogitHeadFwdArgs(ctypes.Structure):
+    """pcg_logit_head_fwd_args."""
+    _fields_ = [(n, _P) for n in ("a", "w", "bias", "logits", "loss", "dlogit", "db", "workspace")] + [(n, _I) for n in ("R", "F", "mode")]
+
+
+class LogitHeadBwdArgs(ctypes.Structure):
+    """pcg_logit_head_bwd_args."""
+    _fields_ = [(n, _P) for n in ("a", "w", "dlogit", "da", "dw")] + [("slope", _F)] + [(n, _I) for n in ("R", "F", "dw_C", "dw_P")]
+
+
+class DeltaGanTailBwdArgs(ctypes.Structure):
+    """pcg_delta_gan_tail_bwd_args."""
+    _fields_ = ([(n, _P) for n in ("dD", "dC", "delta", "d_delta")] + [("lambda_cls", _F), ("reg_scale", _F)] +
+                [(n, _I) for n in ("B", "HW", "dD_stride")])
+
+
+DELTA_GAN_BUILD, DELTA_GAN_REGATHER = 0, 1               # PCG_DELTA_GAN_* (include/pcgan_hip.h)
+LOGIT_HEAD_D, LOGIT_HEAD_G = 0, 1                        # PCG_LOGIT_HEAD_*
+DELTA_GAN_CHUNK = 1024                                   # PCG_DELTA_GAN_CHUNK
+
 # typedef name in include/pcgan_hip.h -> its class here (pcg_abi_struct_bytes checks the sizes: tests/test_house_abi_host.py)
 STRUCTS = {"pcg_conv_geom": ConvGeom, "pcg_in_xform": InXform, "pcg_wgrad_item": WgradItem, "pcg_sn_fwd_batch": SnFwdBatch,
            "pcg_sn_bwd_batch": SnBwdBatch, "pcg_house_g_desc": HouseGDesc, "pcg_house_g_fwd_args": HouseGFwdArgs,
@@ -255,7 +287,9 @@ STRUCTS = {"pcg_conv_geom": ConvGeom, "pcg_in_xform": InXform, "pcg_wgrad_item":
            "pcg_mnist_cf_score_args": MnistCfScoreArgs, "pcg_dense_bn": DenseBn,
            "pcg_dense_bn_bwd": DenseBnBwd, "pcg_moons_gan_desc": MoonsGanDesc, "pcg_moons_gan_train_args": MoonsGanTrainArgs,
            "pcg_moons_gan_fwd_args": MoonsGanFwdArgs, "pcg_moons_clf_fit_desc": MoonsClfFitDesc,
-           "pcg_moons_clf_fit_args": MoonsClfFitArgs}
+           "pcg_moons_clf_fit_args": MoonsClfFitArgs, "pcg_delta_gan_entry_args": DeltaGanEntryArgs,
+           "pcg_delta_gan_tail_fwd_args": DeltaGanTailFwdArgs, "pcg_logit_head_fwd_args": LogitHeadFwdArgs,
+           "pcg_logit_head_bwd_args": LogitHeadBwdArgs, "pcg_delta_gan_tail_bwd_args": DeltaGanTailBwdArgs}
 
 _c = ctypes
 _vp, _f, _i, _i64, _sz = _c.c_void_p, _c.c_float, _c.c_int, _c.c_int64, _c.c_size_t
@@ -490,6 +524,12 @@ PROTOTYPES = {
     "pcg_relu_maxpool2_fwd": (_i, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
     "pcg_relu_maxpool2_bwd": (_i, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
     "pcg_mnist_clf_head": (_i, [_vp, _vp, _f, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "pcg_delta_gan_entry": (_i, [_c.POINTER(DeltaGanEntryArgs), _vp]),
+    "pcg_delta_gan_tail_workspace_bytes": (_sz, [_i32, _i32]),
+    "pcg_delta_gan_tail_fwd": (_i, [_c.POINTER(DeltaGanTailFwdArgs), _vp]),
+    "pcg_logit_head_fwd": (_i, [_c.POINTER(LogitHeadFwdArgs), _vp]),
+    "pcg_logit_head_bwd": (_i, [_c.POINTER(LogitHeadBwdArgs), _vp]),
+    "pcg_delta_gan_tail_bwd": (_i, [_c.POINTER(DeltaGanTailBwdArgs), _vp]),
     "pcg_spectral_norm_fwd": (_i, [_vp, _i32, _i32, _vp, _vp, _f, _i, _vp, _vp, _vp, _vp, _vp]),
     "pcg_spectral_norm_bwd": (_i, [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _i, _vp]),
 }

@@ -1025,10 +1025,10 @@ def avgpool_bwd(dy, B, HW, C):
     return dx
 
 
-def cross_entropy_fwd_bwd(logits, target, need_loss=True, need_grad=True, grad_out=None, grad_scale=1.0):
+def cross_entropy_fwd_bwd(logits, target, need_loss=True, need_grad=True, grad_out=None, grad_scale=1.0, loss_out=None):
     _chk(logits, "logits"); _chk_idx(target, logits.shape[-1], "target")
     B, K = logits.shape
-    loss = torch.empty(1, dtype=torch.float32, device=logits.device) if need_loss else None
+    loss = (loss_out if loss_out is not None else torch.empty(1, dtype=torch.float32, device=logits.device)) if need_loss else None
     dz = torch.empty_like(logits) if need_grad else None
     check(_lib.load().pcg_cross_entropy_fwd_bwd(_p(logits), _p(target), B, K, float(grad_scale), _p(grad_out), _p(loss), _p(dz),
                                                 _stream()), "pcg_cross_entropy_fwd_bwd")
@@ -1562,9 +1562,9 @@ def dropout_apply(x, mask, p, inner=1, C=None, out=None):
     return y
 
 
-def weighted_sum_fwd(terms, weights):
+def weighted_sum_fwd(terms, weights, out=None):
     n = len(terms)
-    out = torch.empty(1, dtype=torch.float32, device=terms[0].device)
+    out = out if out is not None else torch.empty(1, dtype=torch.float32, device=terms[0].device)
     check(_lib.load().pcg_weighted_sum_fwd(n, _ptr_array(terms), (ctypes.c_float * n)(*[float(w) for w in weights]), _p(out), _stream()),
           "pcg_weighted_sum_fwd")
     return out
@@ -1756,6 +1756,153 @@ def mnist_clf_head(h, m1, p, W2, b2, y, tally, logits=None, loss=None, dW2=None,
     check(_lib.load().pcg_mnist_clf_head(_p(h), _p(m1), 1.0 / (1.0 - p), _p(W2), _p(b2), _p(y), R, I, K, *[_p(t) for t in outs[:2]], _p(tally),
                                          *[_p(t) for t in outs[2:]], _stream()), "pcg_mnist_clf_head")
     return tuple(outs)
+
+
+# ---- the additive-delta MNIST CounteRGAN step (csrc/delta_gan.hip) -----------------------------------------------------
+def delta_gan_workspace(B, HW, device):
+    """A zeroed workspace for delta_gan_tail_fwd (arrival counter + one partial per 1024 elements) and, in its own tensor, the 16
+    bytes of logit_head_fwd: (tail_ws, head_ws).  Allocate it outside any graph capture; the kernels leave the counters zero."""
+    need = _lib.load().pcg_delta_gan_tail_workspace_bytes(int(B), int(HW))
+    if need == 0:
+        raise _lib.PcgError(f"delta_gan_workspace: {B} rows of {HW} pixels are outside the index range")
+    return torch.zeros(need, dtype=torch.uint8, device=device), torch.zeros(16, dtype=torch.uint8, device=device)
+
+
+def _delta_ws(B, HW, device):
+    """The current stream's cached workspace pair, grown on demand (never while the stream captures: the zero fill would replay)."""
+    stream = torch.cuda.current_stream(device).cuda_stream
+    key = (device.type, device.index, stream, "delta_gan")
+    ws = _ws_cache.get(key)
+    need = _lib.load().pcg_delta_gan_tail_workspace_bytes(int(B), int(HW))
+    if ws is None or ws[0].numel() < need:
+        if torch.cuda.is_current_stream_capturing():
+            raise _lib.PcgError("delta_gan: pass a workspace from ops.delta_gan_workspace() made before the capture")
+        if ws is not None:
+            _ws_retired.append(ws)
+        ws = delta_gan_workspace(B, HW, device)
+        _ws_cache[key] = ws
+    return ws
+
+
+def _host_labels(t, name):
+    if t is None:
+        return None, ctypes.c_void_p(0)
+    h = torch.as_tensor(t, dtype=torch.int64, device="cpu").contiguous()
+    return h, ctypes.c_void_p(h.data_ptr())
+
+
+def delta_gan_entry(x, y, target, table_g, table_d, g_in=None, d_in=None, labels_2b=None, head_w=None, head_w_packed=None, head_shape=None,
+                    regather=False, y_host=None, target_host=None):
+    """pcg_delta_gan_entry: g_in [B, HW, 2] = (x, table_g[target]); d_in [2B, HW, 2] rows 0..B = (x, table_d[y]), rows B..2B channel 1 =
+    table_d[target]; labels_2b [2B] = (y, target); head_w_packed = the (h,w,c) image of head_w, head_shape = (C, P).  regather=True
+    writes only channel 1 of d_in rows B..2B (and the packed head weight).  y_host / target_host: host copies, range-checked by the
+    library before the launch.  Returns (g_in, d_in)."""
+    _chk(table_d, "table_d"); _chk_idx(target, table_d.shape[0], "target")
+    B, (K, HW) = target.numel(), table_d.shape
+    dev = table_d.device
+    if regather:
+        if d_in is None:
+            raise _lib.PcgError("delta_gan_entry: the regather needs the d_in it rewrites")
+    else:
+        _chk(x, "x"); _chk(table_g, "table_g"); _chk_idx(y, K, "y")
+        if x.numel() != B * HW or y.numel() != B or tuple(table_g.shape) != (K, HW):
+            raise _lib.PcgError(f"delta_gan_entry: x {tuple(x.shape)}, y {tuple(y.shape)}, tables {tuple(table_g.shape)} / {tuple(table_d.shape)} do not agree")
+        g_in = g_in if g_in is not None else torch.empty((B, HW, 2), dtype=torch.float32, device=dev)
+        d_in = d_in if d_in is not None else torch.empty((2 * B, HW, 2), dtype=torch.float32, device=dev)
+        _chk(g_in, "g_in")
+        if g_in.numel() != 2 * B * HW:
+            raise _lib.PcgError(f"delta_gan_entry: g_in holds {g_in.numel()} floats, {2 * B * HW} needed")
+    _chk(d_in, "d_in")
+    if d_in.numel() != 4 * B * HW:
+        raise _lib.PcgError(f"delta_gan_entry: d_in holds {d_in.numel()} floats, {4 * B * HW} needed")
+    if labels_2b is not None and (_chk(labels_2b, "labels_2b", torch.int64).numel() != 2 * B):
+        raise _lib.PcgError(f"delta_gan_entry: labels_2b holds {labels_2b.numel()} entries, {2 * B} needed")
+    hc = hp = 0
+    if head_w is not None:
+        hc, hp = (int(v) for v in head_shape)
+        _chk(head_w, "head_w"); _chk(head_w_packed, "head_w_packed")
+        if head_w.numel() != hc * hp or head_w_packed.numel() != hc * hp:
+            raise _lib.PcgError(f"delta_gan_entry: head weight of {head_w.numel()} columns is not {hc} x {hp}")
+    yh, yhp = _host_labels(y_host, "y_host")
+    th, thp = _host_labels(target_host, "target_host")
+    a = _lib.DeltaGanEntryArgs(_p(None if regather else x), _p(None if regather else y), _p(target), yhp, thp, _p(None if regather else table_g),
+                               _p(table_d), _p(None if regather else g_in), _p(d_in), _p(labels_2b), _p(head_w), _p(head_w_packed), B, HW, K,
+                               _lib.DELTA_GAN_REGATHER if regather else _lib.DELTA_GAN_BUILD, hc, hp)
+    check(_lib.load().pcg_delta_gan_entry(ctypes.byref(a), _stream()), "pcg_delta_gan_entry")
+    return g_in, d_in
+
+
+def delta_gan_tail_fwd(x, delta, d_in, x_cf=None, loss_reg=None, ws=None, grid=0):
+    """pcg_delta_gan_tail_fwd: x_cf = x + delta to x_cf [B, HW] and to channel 0 of d_in rows B..2B; loss_reg [1] = mean|delta|.
+    ws: the tail workspace of delta_gan_workspace (default: the stream's cached one).  Returns (x_cf, loss_reg)."""
+    _chk(x, "x"); _chk(delta, "delta"); _chk(d_in, "d_in")
+    B = x.shape[0]
+    HW = x.numel() // B
+    if delta.numel() != B * HW or d_in.numel() != 4 * B * HW:
+        raise _lib.PcgError(f"delta_gan_tail_fwd: x {tuple(x.shape)}, delta {tuple(delta.shape)}, d_in {tuple(d_in.shape)} do not agree")
+    x_cf = x_cf if x_cf is not None else torch.empty((B, HW), dtype=torch.float32, device=x.device)
+    loss_reg = loss_reg if loss_reg is not None else torch.empty(1, dtype=torch.float32, device=x.device)
+    _chk(x_cf, "x_cf"); _chk(loss_reg, "loss_reg")
+    if x_cf.numel() != B * HW:
+        raise _lib.PcgError(f"delta_gan_tail_fwd: x_cf holds {x_cf.numel()} floats, {B * HW} needed")
+    ws = ws if ws is not None else _delta_ws(B, HW, x.device)[0]
+    a = _lib.DeltaGanTailFwdArgs(_p(x), _p(delta), _p(x_cf), _p(d_in), _p(loss_reg), _p(ws), ws.numel(), B, HW, int(grid))
+    check(_lib.load().pcg_delta_gan_tail_fwd(ctypes.byref(a), _stream()), "pcg_delta_gan_tail_fwd")
+    return x_cf, loss_reg
+
+
+def logit_head_fwd(a, w, bias, mode_g=False, logits=None, loss=None, dlogit=None, db=None, ws=None):
+    """pcg_logit_head_fwd: logits [R] = a [R, F] . w [F] + bias; the BCE-with-logits loss of gan_train.py:127 (mode D: rows 0..R/2
+    labelled 1, the rest 0, mean + mean) or :137 (mode_g: all rows labelled 1), its gradient dlogit [R] and db [1] = sum dlogit.
+    Returns (logits, loss, dlogit, db)."""
+    _chk(a, "a"); _chk(w, "w"); _chk(bias, "bias")
+    R = a.shape[0]
+    F = a.numel() // R
+    if w.numel() != F or bias.numel() != 1:
+        raise _lib.PcgError(f"logit_head_fwd: a [R, F] {tuple(a.shape)}, w {tuple(w.shape)}, bias {tuple(bias.shape)} do not agree")
+    f32 = lambda n: torch.empty(n, dtype=torch.float32, device=a.device)      # noqa: E731
+    outs = []
+    for t, name, n in ((logits, "logits", R), (loss, "loss", 1), (dlogit, "dlogit", R), (db, "db", 1)):
+        t = t if t is not None else f32(n)
+        if _chk(t, name).numel() != n:
+            raise _lib.PcgError(f"logit_head_fwd: {name} holds {t.numel()} floats, {n} needed")
+        outs.append(t)
+    ws = ws if ws is not None else _delta_ws(1, 4, a.device)[1]
+    args = _lib.LogitHeadFwdArgs(_p(a), _p(w), _p(bias), *[_p(t) for t in outs], _p(ws), R, F, _lib.LOGIT_HEAD_G if mode_g else _lib.LOGIT_HEAD_D)
+    check(_lib.load().pcg_logit_head_fwd(ctypes.byref(args), _stream()), "pcg_logit_head_fwd")
+    return tuple(outs)
+
+
+def logit_head_bwd(a, w, dlogit, slope, da=None, dw=None, dw_shape=None):
+    """pcg_logit_head_bwd: da [R, F] = dlogit[r] * w[f] * (a > 0 ? 1 : slope); dw [F] (None: not formed) = sum_r dlogit[r] * a[r][f],
+    stored in w's packed order, or with dw_shape = (C, P) at [c * P + p] for the packed column p * C + c.  Returns (da, dw)."""
+    _chk(a, "a"); _chk(w, "w"); _chk(dlogit, "dlogit")
+    R = a.shape[0]
+    F = a.numel() // R
+    if w.numel() != F or dlogit.numel() != R:
+        raise _lib.PcgError(f"logit_head_bwd: a [R, F] {tuple(a.shape)}, w {tuple(w.shape)}, dlogit {tuple(dlogit.shape)} do not agree")
+    da = da if da is not None else torch.empty_like(a)
+    _chk(da, "da")
+    if da.numel() != a.numel() or (dw is not None and _chk(dw, "dw").numel() != F):
+        raise _lib.PcgError("logit_head_bwd: da must match a and dw must hold F floats")
+    c, p = (int(v) for v in dw_shape) if dw_shape is not None else (0, 0)
+    args = _lib.LogitHeadBwdArgs(_p(a), _p(w), _p(dlogit), _p(da), _p(dw), float(slope), R, F, c, p)
+    check(_lib.load().pcg_logit_head_bwd(ctypes.byref(args), _stream()), "pcg_logit_head_bwd")
+    return da, dw
+
+
+def delta_gan_tail_bwd(dD, dC, delta, lambda_cls, lambda_reg, dD_stride=1, out=None):
+    """pcg_delta_gan_tail_bwd: d_delta = dD[.. * dD_stride] + lambda_cls * dC + (lambda_reg / (B * HW)) * sign(delta), in that order."""
+    _chk(dD, "dD"); _chk(dC, "dC"); _chk(delta, "delta")
+    B = delta.shape[0]
+    HW = delta.numel() // B
+    if dC.numel() != B * HW or dD.numel() != B * HW * int(dD_stride):
+        raise _lib.PcgError(f"delta_gan_tail_bwd: dD {tuple(dD.shape)}, dC {tuple(dC.shape)}, delta {tuple(delta.shape)} do not agree")
+    out = out if out is not None else torch.empty((B, HW), dtype=torch.float32, device=delta.device)
+    _chk(out, "d_delta")
+    args = _lib.DeltaGanTailBwdArgs(_p(dD), _p(dC), _p(delta), _p(out), float(lambda_cls), float(lambda_reg) / (B * HW), B, HW, int(dD_stride))
+    check(_lib.load().pcg_delta_gan_tail_bwd(ctypes.byref(args), _stream()), "pcg_delta_gan_tail_bwd")
+    return out
 
 
 def interpolate(alpha, real, fake):
