@@ -1566,6 +1566,58 @@ typedef struct pcg_delta_gan_tail_bwd_args {
 } pcg_delta_gan_tail_bwd_args;
 int pcg_delta_gan_tail_bwd(const pcg_delta_gan_tail_bwd_args* args, pcg_stream_t stream);
 
+/* ---- the prompted half of the additive-delta MNIST CounteRGAN (conditional_counteRGAN/mnist/gan_train_copy.py on
+ * modules/generator.py; csrc/delta_cf_eval.hip) ------------------------------------------------------------------
+ * All fp32, gfx950 only, no floating-point atomics, every sum in an order fixed by the shapes alone; every entry takes a stream and may
+ * be captured into a HIP graph.  Every entry validates its arguments before it touches HIP: PCG_ERR_INVALID and a pcg_last_error text
+ * otherwise.  A query is q = t * B + b (target slot t of T, row b of B), as in pcg_mnist_cf_entry; entry and tail work on the window
+ * [q0, q0 + nq) of the T * B queries and index their per-query tensors relative to q0.  The classifier's logits of x_cf are scored by
+ * pcg_mnist_cf_score as it is: pcg_delta_cf_tail's sums are its tail_sums.                                                              */
+
+/* The generator's 2-channel input for a window of queries (modules/generator.py:19-20 at gan_train_copy.py:165):
+ *   out[q - q0][p] = (x[b][p], table[target(q)][p])
+ * target NULL: the sweep, target(q) = t, T <= K.  target [B] (device): target(q) = target[b], and T must be 1.  The broadcast of x over
+ * the T targets is done by indexing.  Pure copies: at T = 1, q0 = 0 the bits are pcg_delta_gan_entry's g_in.  A device label outside
+ * 0..K-1 is clamped into the table, as pcg_embed_concat_fwd clamps it; target_host (nullable) is a host copy of target: where given, a
+ * label outside 0..K-1 is refused before any launch.  HW % 4 == 0; out is written 8 bytes at a time.                                   */
+typedef struct pcg_delta_cf_entry_args {
+  const float* x;              /* [B][HW]                                          */
+  const float* table;          /* [K][HW]                                          */
+  const int64_t* target;       /* nullable: [B], device                            */
+  const int64_t* target_host;  /* nullable: host copy of target, range-checked     */
+  float* out;                  /* [nq][HW][2]                                      */
+  int32_t B, T, HW, K, q0, nq;
+} pcg_delta_cf_entry_args;
+int pcg_delta_cf_entry(const pcg_delta_cf_entry_args* args, pcg_stream_t stream);
+
+/* What follows G's last convolution for a window of queries (gan_train_copy.py:165-166):
+ *   x_cf[q - q0][p] = clamp(x[b][p] + delta[q - q0][p], -1, 1)     the sum is rounded first, then clamped; a NaN stays a NaN
+ *   sums[q - q0]    = { sum |x_cf - x|, sum |delta|, sum (x_cf - x)^2 } over the HW pixels
+ * One wave per query: lane l folds the 16-byte groups l, l + 64, ... element by element, every term rounded on its own, then a fixed
+ * xor butterfly adds the 64 lane sums.  All three sums are continuous in the inputs.  HW % 4 == 0; delta, x, x_cf 16-byte aligned.     */
+typedef struct pcg_delta_cf_tail_args {
+  const float* delta;   /* [nq][HW] */
+  const float* x;       /* [B][HW]  */
+  float* x_cf;          /* [nq][HW] */
+  float* sums;          /* [nq][3]  */
+  int32_t B, T, HW, q0, nq;
+} pcg_delta_cf_tail_args;
+int pcg_delta_cf_tail(const pcg_delta_cf_tail_args* args, pcg_stream_t stream);
+
+/* The iteration's one random class (gan_train_copy.py:119-120: torch.randint(0, 10, (1,)), torch.full_like(y_true, .)): ONE class, the
+ * value pcg_randint(out, 1, 0, K, NULL, seed, offset) writes to out[0], written to all B rows of target.  counter NULL: the Philox
+ * offset is the by-value argument.  counter (device, uint64[2], 8-byte aligned): the offset is counter[0] and the launch advances
+ * counter[0] by 1, the (1 + 3) / 4 counter values a one-element pcg_randint spans; counter[1] is not touched.  One workgroup: every
+ * thread reads the counter, a barrier, one thread writes the increment -- a captured launch draws the next class of the stream on every
+ * replay.                                                                                                                              */
+typedef struct pcg_delta_gan_target_draw_args {
+  int64_t* target;      /* [B], device             */
+  uint64_t* counter;    /* nullable: device [2]    */
+  uint64_t seed, offset;
+  int32_t B, K;
+} pcg_delta_gan_target_draw_args;
+int pcg_delta_gan_target_draw(const pcg_delta_gan_target_draw_args* args, pcg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

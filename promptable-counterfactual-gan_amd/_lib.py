@@ -270,6 +270,21 @@ class DeltaGanTailBwdArgs(ctypes.Structure):
                 [(n, _I) for n in ("B", "HW", "dD_stride")])
 
 
+class DeltaCfEntryArgs(ctypes.Structure):
+    """pcg_delta_cf_entry_args."""
+    _fields_ = [(n, _P) for n in ("x", "table", "target", "target_host", "out")] + [(n, _I) for n in ("B", "T", "HW", "K", "q0", "nq")]
+
+
+class DeltaCfTailArgs(ctypes.Structure):
+    """pcg_delta_cf_tail_args."""
+    _fields_ = [(n, _P) for n in ("delta", "x", "x_cf", "sums")] + [(n, _I) for n in ("B", "T", "HW", "q0", "nq")]
+
+
+class DeltaGanTargetDrawArgs(ctypes.Structure):
+    """pcg_delta_gan_target_draw_args."""
+    _fields_ = [("target", _P), ("counter", _P), ("seed", ctypes.c_uint64), ("offset", ctypes.c_uint64), ("B", _I), ("K", _I)]
+
+
 DELTA_GAN_BUILD, DELTA_GAN_REGATHER = 0, 1               # PCG_DELTA_GAN_* (include/pcgan_hip.h)
 LOGIT_HEAD_D, LOGIT_HEAD_G = 0, 1                        # PCG_LOGIT_HEAD_*
 DELTA_GAN_CHUNK = 1024                                   # PCG_DELTA_GAN_CHUNK
@@ -289,7 +304,9 @@ STRUCTS = {"pcg_conv_geom": ConvGeom, "pcg_in_xform": InXform, "pcg_wgrad_item":
            "pcg_moons_gan_fwd_args": MoonsGanFwdArgs, "pcg_moons_clf_fit_desc": MoonsClfFitDesc,
            "pcg_moons_clf_fit_args": MoonsClfFitArgs, "pcg_delta_gan_entry_args": DeltaGanEntryArgs,
            "pcg_delta_gan_tail_fwd_args": DeltaGanTailFwdArgs, "pcg_logit_head_fwd_args": LogitHeadFwdArgs,
-           "pcg_logit_head_bwd_args": LogitHeadBwdArgs, "pcg_delta_gan_tail_bwd_args": DeltaGanTailBwdArgs}
+           "pcg_logit_head_bwd_args": LogitHeadBwdArgs, "pcg_delta_gan_tail_bwd_args": DeltaGanTailBwdArgs,
+           "pcg_delta_cf_entry_args": DeltaCfEntryArgs, "pcg_delta_cf_tail_args": DeltaCfTailArgs,
+           "pcg_delta_gan_target_draw_args": DeltaGanTargetDrawArgs}
 
 _c = ctypes
 _vp, _f, _i, _i64, _sz = _c.c_void_p, _c.c_float, _c.c_int, _c.c_int64, _c.c_size_t
@@ -530,6 +547,9 @@ PROTOTYPES = {
     "pcg_logit_head_fwd": (_i, [_c.POINTER(LogitHeadFwdArgs), _vp]),
     "pcg_logit_head_bwd": (_i, [_c.POINTER(LogitHeadBwdArgs), _vp]),
     "pcg_delta_gan_tail_bwd": (_i, [_c.POINTER(DeltaGanTailBwdArgs), _vp]),
+    "pcg_delta_cf_entry": (_i, [_c.POINTER(DeltaCfEntryArgs), _vp]),
+    "pcg_delta_cf_tail": (_i, [_c.POINTER(DeltaCfTailArgs), _vp]),
+    "pcg_delta_gan_target_draw": (_i, [_c.POINTER(DeltaGanTargetDrawArgs), _vp]),
     "pcg_spectral_norm_fwd": (_i, [_vp, _i32, _i32, _vp, _vp, _f, _i, _vp, _vp, _vp, _vp, _vp]),
     "pcg_spectral_norm_bwd": (_i, [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _i, _vp]),
 }

@@ -11,27 +11,11 @@
 // distribution: exact patch counts, uniform marginals, N(0,1) moments, determinism in (seed, offset).
 #include <algorithm>
 #include "pcg_common.h"
+#include "philox.h"
 
 namespace pcg {
 namespace {
 
-struct U4 { uint32_t x, y, z, w; };
-
-__device__ __forceinline__ U4 philox4x32_10(U4 ctr, uint32_t k0, uint32_t k1) {
-  constexpr uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u, W0 = 0x9E3779B9u, W1 = 0xBB67AE85u;
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint32_t hi0 = __umulhi(M0, ctr.x), lo0 = M0 * ctr.x;
-    const uint32_t hi1 = __umulhi(M1, ctr.z), lo1 = M1 * ctr.z;
-    ctr = U4{hi1 ^ ctr.y ^ k0, lo1, hi0 ^ ctr.w ^ k1, lo0};
-    k0 += W0; k1 += W1;
-  }
-  return ctr;
-}
-__device__ __forceinline__ U4 draw(uint64_t seed, uint64_t offset, uint64_t idx) {
-  const uint64_t c = offset + idx;
-  return philox4x32_10(U4{(uint32_t)c, (uint32_t)(c >> 32), 0x5eed5eedu, 0u}, (uint32_t)seed, (uint32_t)(seed >> 32));
-}
 __device__ __forceinline__ float u01(uint32_t v) { return ((float)(v >> 8) + 0.5f) * (1.0f / 16777216.0f); }  // (0,1)
 
 // one thread per sample: partial Fisher-Yates over <= 64 patches held as a 64-bit "taken" set, then the sample's

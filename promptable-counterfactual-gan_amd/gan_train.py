@@ -11,17 +11,22 @@ and the outputs3/ pictures -- on the HIP kernels.
     gan_train.py           loop body         :117-144       train_step (op chain) / GraphedTrainStep (fused, one graph replay)
     gan_train.py           loop              :115-148       train_gan
     gan_train.py           test pictures     :150-159       counterfactual_batch
+    gan_train_copy.py      params            :17-29         params_random_target (no target_class: a random class per iteration)
+    gan_train_copy.py      the class draw    :119-120       ops.DeviceRNG.delta_gan_target (train_gan / GraphedTrainStep(rng=...))
+    gan_train_copy.py      prompted queries  :161-172       counterfactuals, counterfactual_sweep, evaluate_examples
+    eval_utils.py          per-target means  :58-66,:97-102 evaluate_per_target
 
 The torch layer objects are kept as parameter containers (`label_embed`, and `net`, the reference's nn.Sequential layer for layer), so
 `state_dict()` keys and shapes are the reference's in both directions with strict=True.  Forward and backward are one autograd node per
 network sequencing C-ABI calls on NHWC activations (csrc/delta_gan.hip holds the fused launches around the convolutions; DESIGN.md
-§3.19)."""
+§3.19; csrc/delta_cf_eval.hip the query windows and the class draw, §3.20)."""
 import torch
 import torch.nn as nn
 
 from . import ops
 from ._lib import ACT_LRELU, ACT_NONE, ACT_RELU, PcgError
-from .countergan import BCEWithLogitsLoss, Classifier, CrossEntropyLoss, _as_rows, _conv_fwd, _conv_wgrad, _dgrad_act, _geom, abs_mean
+from .countergan import (PER_CLASS_FIELDS, BCEWithLogitsLoss, Classifier, CrossEntropyLoss, _as_rows, _conv_fwd, _conv_wgrad, _dgrad_act, _geom,
+                         _labels, _padded_logits, abs_mean, metrics_from_sums)
 from .nn import FlatModule, in_conv_precision, linear_dgrad, linear_fwd, linear_wgrad, weighted_sum
 from .optim import Adam
 
@@ -35,6 +40,18 @@ params = {                                             # gan_train.py:17-30
     "lambda_cls": 3.0,
     "lambda_reg": 0.05,
     "target_class": 5,
+    "device": "cuda",
+}
+
+params_random_target = {                               # gan_train_copy.py:17-29; no target_class: train_gan draws one per iteration (:119)
+    "batch_size": 128,
+    "epochs_clf": 10,
+    "epochs_gan": 50,
+    "lr_G": 5e-5,
+    "lr_D": 1e-5,
+    "lr_C": 1e-3,
+    "lambda_cls": 2.0,
+    "lambda_reg": 0.01,
     "device": "cuda",
 }
 
@@ -108,6 +125,34 @@ class Generator(FlatModule):
         delta = a.view(B, HW)
         x_cf = ops.axpby(1.0, xr, 1.0, delta)                                                       # :22
         return x_cf.view(B, 1, H, W), delta.view(B, 1, H, W), ((layers, c) if keep else None)
+
+    @in_conv_precision
+    def forward_queries(self, x_rows, target, T=None, q0=0, nq=None, out=None):
+        """The forward over the window [q0, q0 + nq) of the queries q = t * B + b, clamped as gan_train_copy.py:165-166 clamps it.
+        x_rows [B, 784] (or [B,1,28,28]); target None: the sweep, query (t, b) asks for class t of T (default num_classes), or [B]
+        int64 on the GPU with T = 1 -- x is never replicated.  One entry launch, the four convolutions on nq rows, one tail launch.
+        Returns {"x_cf" [nq, 784], "delta" [nq, 784], "sums" [nq, 3]: sum |x_cf - x|, sum |delta|, sum (x_cf - x)^2}; `out`:
+        preallocated tensors under those names."""
+        _need_gpu(x_rows, "Generator.forward_queries")
+        self._ensure_flat()
+        B = x_rows.shape[0]
+        xr = _as_rows(x_rows, B)
+        if xr.shape[1] != HW:
+            raise PcgError(f"Generator.forward_queries: expected {HW} pixels per row, got shape {tuple(x_rows.shape)}")
+        T = (self.label_embed.num_embeddings if target is None else 1) if T is None else int(T)
+        out = out or {}
+        a = ops.delta_cf_entry(xr, target, self.label_embed.weight.data, T, q0, nq)                # generator.py:19-20
+        n = a.shape[0]
+        a = a.view(n, H, W, 2)
+        convs = self._convs()
+        for i, conv in enumerate(convs):
+            last = i + 1 == len(convs)
+            dst = out.get("delta") if last else None
+            a = ops.conv2d_fwd(_geom(conv, n, H, W), a, ops.ohwi(conv.weight.data), conv.bias.data, act=ACT_NONE if last else ACT_RELU,
+                               out=dst.view(n, H, W, 1) if dst is not None else None)
+        delta = a.view(n, HW)
+        x_cf, sums = ops.delta_cf_tail(delta, xr, T, q0, n, out=out)                                # gan_train_copy.py:165-166
+        return {"x_cf": x_cf, "delta": delta, "sums": sums}
 
     @in_conv_precision
     def _run_backward(self, saved, d_xcf, d_delta):
@@ -262,6 +307,19 @@ def train_step(G, D, C, opt_g, opt_d, x, y, target, params=params):
             "loss_reg": loss_reg.detach()}
 
 
+_warmup_streams = {}
+
+
+def _warmup_stream(dev):
+    """ONE side stream per device for the warm-up execution of every capture.  A stream's first convolution hands it 64 MiB of stream-K
+    scratch for the life of the process (ops._conv_scratch), so a fresh stream per capture -- one per batch size per stepper -- pinned
+    that much per graph."""
+    key = dev.index if dev.index is not None else torch.cuda.current_device()
+    if key not in _warmup_streams:
+        _warmup_streams[key] = torch.cuda.Stream(dev)
+    return _warmup_streams[key]
+
+
 class GraphedTrainStep:
     """The iteration of gan_train.py:117-144 on the fused launches of csrc/delta_gan.hip around the library's convolutions, captured
     once per batch size as a single-stream, strictly linear HIP graph: a step is two small copies (the batch into the graph's input
@@ -298,7 +356,10 @@ class GraphedTrainStep:
                 return f"conv_precision {prec!r} on {type(net).__name__}: the fused step is fp32 only"
         return None
 
-    def __init__(self, G, D, C, batch_size, params=params, graph=True):
+    def __init__(self, G, D, C, batch_size, params=params, graph=True, rng=None):
+        """rng (ops.DeviceRNG): step(x, y) with no target then draws the iteration's one class (gan_train_copy.py:119-120) as the FIRST
+        launch of the step -- 65 launches -- into the step's own target buffer, its Philox offset read from a device counter that the
+        launch advances itself, so every replay draws the next class of the stream; rng.offset is kept in step on the host."""
         why = self.unsupported(G, D, C)
         if why is not None:
             raise PcgError(f"GraphedTrainStep: {why}")
@@ -314,7 +375,9 @@ class GraphedTrainStep:
             net.zero_grad()                                   # attaches the .grad views; every step OVERWRITES them (no zero_grad)
         self.opt_g, self.opt_d = make_optimizers(G, D, self.params)
         self._graph = bool(graph)
-        self._bufs, self._graphs = {}, {}
+        self._bufs, self._graphs, self._draw_graphs = {}, {}, {}
+        self._rng = rng
+        self._ctr = rng.device_counter(dev) if rng is not None else None
 
     # -- buffers of one batch size --------------------------------------------------------------------------------------------------------
     def _buffers(self, R):
@@ -339,7 +402,9 @@ class GraphedTrainStep:
                 "cls_logits": f32(R, self.C.num_classes)}
 
     # -- one step, Adam included, over the buffer set b -----------------------------------------------------------------------------------
-    def _launches(self, b):
+    def _launches(self, b, draw=False):
+        if draw:
+            self._rng.delta_gan_target(b["t"], self.K, counter=self._ctr)                                                    # :119-120
         with ops.conv_precision("fp32"):
             self._step(b)
 
@@ -420,15 +485,17 @@ class GraphedTrainStep:
         ops.weighted_sum_fwd([out["loss_adv"], out["loss_cls"], out["loss_reg"]], [1.0, self.params["lambda_cls"], self.params["lambda_reg"]],
                              out=out["loss_G"])                                                                              # :141
 
-    def _capture(self, b):
-        """Capture needs one real execution of every launch first; the parameters and the Adam state are put back afterwards."""
+    def _capture(self, b, draw=False):
+        """Capture needs one real execution of every launch first; the parameters, the Adam state and the draw's device counter are put
+        back afterwards."""
         G, D = self.G, self.D
         p0 = G.flat_params.clone(), D.flat_params.clone()
+        ctr0 = self._ctr.clone() if draw else None
         snaps = self.opt_g.snapshot(), self.opt_d.snapshot()
-        side = torch.cuda.Stream()
+        side = _warmup_stream(self.dev)
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
-            self._launches(b)
+            self._launches(b, draw)
         torch.cuda.current_stream().wait_stream(side)
         if snaps[0] is None:                                  # the first execution built the Adam state: capture sees it at step 0 again
             self.opt_g.restore(None); self.opt_d.restore(None)
@@ -439,21 +506,28 @@ class GraphedTrainStep:
         try:
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph):
-                self._launches(b)
+                self._launches(b, draw)
         finally:
             if gc_on:
                 gc.enable()
         G.flat_params.copy_(p0[0]); D.flat_params.copy_(p0[1])
         self.opt_g.restore(snaps[0]); self.opt_d.restore(snaps[1])
+        if draw:
+            self._ctr.copy_(ctr0)                             # the warm-up execution drew from the counter: back to the stream's position
         return graph
 
-    def step(self, x, y, target):
-        """One iteration on the batch (x [R,1,28,28] or [R,784], y [R], target [R]).  Returns the device scalars {loss_D, loss_G,
-        loss_adv, loss_cls, loss_reg}: views of this batch size's loss buffer, overwritten by its next step."""
+    def step(self, x, y, target=None):
+        """One iteration on the batch (x [R,1,28,28] or [R,784], y [R], target [R]).  target None (a stepper built with rng): the
+        step draws its one random class itself.  Returns the device scalars {loss_D, loss_G, loss_adv, loss_cls, loss_reg}: views of
+        this batch size's loss buffer, overwritten by its next step."""
         R = int(x.shape[0])
-        if R < 1 or y.numel() != R or target.numel() != R or x.numel() != R * HW:
-            raise PcgError(f"GraphedTrainStep.step: x {tuple(x.shape)}, y {tuple(y.shape)}, target {tuple(target.shape)} are not one batch of 28 x 28 images")
-        for name, t in (("y", y), ("target", target)):
+        draw = target is None
+        if draw and self._rng is None:
+            raise PcgError("GraphedTrainStep.step: no target given and the stepper was built without rng: there is nothing to draw the class from")
+        if R < 1 or y.numel() != R or (not draw and target.numel() != R) or x.numel() != R * HW:
+            raise PcgError(f"GraphedTrainStep.step: x {tuple(x.shape)}, y {tuple(y.shape)}, target "
+                           f"{'(drawn)' if draw else tuple(target.shape)} are not one batch of 28 x 28 images")
+        for name, t in (("y", y),) if draw else (("y", y), ("target", target)):
             if not t.is_cuda and t.numel():                   # host-visible labels: refused here; device labels are clamped by the kernel
                 v = t.numpy()
                 if v.min() < 0 or v.max() >= self.K:
@@ -461,13 +535,18 @@ class GraphedTrainStep:
         b = self._bufs.get(R)
         if b is None:
             b = self._bufs[R] = self._buffers(R)
-        b["x"].copy_(x.reshape(R, HW)); b["y"].copy_(y); b["t"].copy_(target)
+        b["x"].copy_(x.reshape(R, HW)); b["y"].copy_(y)
+        if not draw:
+            b["t"].copy_(target)
         if self._graph:
-            if R not in self._graphs:
-                self._graphs[R] = self._capture(b)
-            self._graphs[R].replay()
+            graphs = self._draw_graphs if draw else self._graphs
+            if R not in graphs:
+                graphs[R] = self._capture(b, draw)
+            graphs[R].replay()
         else:
-            self._launches(b)
+            self._launches(b, draw)
+        if draw:
+            self._rng.offset += 1                             # the host-side mirror of the device counter (DeviceRNG.randint(.., 1)'s span)
         return b["out"]
 
 
@@ -482,37 +561,82 @@ def _warn_fused_fallback(why):
         _fused_fallback_warned = True
 
 
-def train_gan(G, D, C, train_loader, params=params, fused=False, verbose=True):
+class _TargetSource:
+    """Where an iteration's target class comes from (host logic; gan_train.py:119 / gan_train_copy.py:119-120).  params["target_class"]
+    set: one fill per batch size, as before, and nothing is ever drawn.  Otherwise `targets` (an iterable of ints, one per iteration)
+    or a draw: by the fused step itself (in_step: next() returns None) or by ops.DeviceRNG.delta_gan_target with the offset passed by
+    value."""
+
+    def __init__(self, params, K, dev, rng=None, targets=None, in_step=False):
+        self.fixed, self.K, self.dev, self.rng, self.in_step = params.get("target_class"), int(K), dev, rng, bool(in_step)
+        if self.fixed is not None and targets is not None:
+            raise PcgError("train_gan: `targets` replaces the draws of random-target training, but params['target_class'] is set")
+        self.given = iter(targets) if targets is not None else None
+        if self.fixed is None and self.given is None and rng is None:
+            raise PcgError("train_gan: params has no target_class, so every iteration draws its class: pass rng=ops.DeviceRNG(seed) "
+                           "(or targets=, one class per iteration)")
+        self._bufs, self.count = {}, 0
+
+    def _buf(self, R):
+        if R not in self._bufs:
+            self._bufs[R] = torch.zeros(R, dtype=torch.int64, device=self.dev)
+        return self._bufs[R]
+
+    def next(self, R):
+        """The [R] int64 target tensor of the next iteration, or None: the fused step draws the class itself."""
+        self.count += 1
+        if self.fixed is not None:
+            if R not in self._bufs:                                                    # :119, one fill per batch size
+                self._bufs[R] = torch.full((R,), int(self.fixed), dtype=torch.int64, device=self.dev)
+            return self._bufs[R]
+        if self.given is not None:
+            try:
+                cls = int(next(self.given))
+            except StopIteration:
+                raise PcgError(f"train_gan: `targets` ran out at iteration {self.count}") from None
+            if not 0 <= cls < self.K:
+                raise PcgError(f"train_gan: target class {cls} of iteration {self.count} is outside 0..{self.K - 1}")
+            return self._buf(R).fill_(cls)
+        if self.in_step:
+            return None
+        return self.rng.delta_gan_target(self._buf(R), self.K)                         # gan_train_copy.py:119-120
+
+
+def train_gan(G, D, C, train_loader, params=params, fused=False, rng=None, targets=None, verbose=True):
     """gan_train.py:115-148 over any iterable of (x, y).  The reference prints and records the last iteration's loss_D / loss_G of each
     epoch, so an epoch makes ONE host read and none inside it.  fused=True: the iterations run through GraphedTrainStep (one replay
-    each); nets or a conv_precision the fused step does not take warn once and run the op chain.  Returns {"g_losses", "d_losses"}."""
+    each); nets or a conv_precision the fused step does not take warn once and run the op chain.  params without "target_class"
+    (params_random_target) is gan_train_copy.py's loop: every iteration's class is drawn on the device from rng (ops.DeviceRNG; inside
+    the replayed step when fused), or taken from `targets`, an iterable of ints, one per iteration.  Returns {"g_losses", "d_losses"}."""
     _check_classifier(C)
     dev = next(G.parameters()).device
     if dev.type != "cuda":
         raise PcgError(f"train_gan: the nets are on {dev}; libpcgan_hip has no CPU path")
     for p in C.parameters():
         p.requires_grad_(False)                                                        # :99-100
+    drawn = params.get("target_class") is None and targets is None
     stepper = None
     if fused:
         why = GraphedTrainStep.unsupported(G, D, C)
         if why is None:
-            stepper = GraphedTrainStep(G, D, C, params["batch_size"], params)
+            if drawn and rng is None:
+                raise PcgError("train_gan(fused=True): params has no target_class and no rng was given: the fused step draws the class "
+                               "on the device and needs rng=ops.DeviceRNG(seed)")
+            stepper = GraphedTrainStep(G, D, C, params["batch_size"], params, rng=rng if drawn else None)
         else:
             _warn_fused_fallback(why)
     opt_g, opt_d = (stepper.opt_g, stepper.opt_d) if stepper is not None else make_optimizers(G, D, params)
-    targets = {}
+    source = _TargetSource(params, G.label_embed.num_embeddings, dev, rng=rng, targets=targets, in_step=stepper is not None)
     g_losses, d_losses = [], []
     for epoch in range(params["epochs_gan"]):
         out = None
         for x, y in train_loader:
             x, y = x.to(dev), y.to(dev)                                                # :117-118
-            R = int(y.shape[0])
-            if R not in targets:                                                       # :119, one fill per batch size
-                targets[R] = torch.full((R,), int(params["target_class"]), dtype=torch.int64, device=dev)
+            target = source.next(int(y.shape[0]))
             if stepper is not None:
-                out = stepper.step(x, y, targets[R])
+                out = stepper.step(x, y, target)
             else:
-                out = train_step(G, D, C, opt_g, opt_d, x, y, targets[R], params)
+                out = train_step(G, D, C, opt_g, opt_d, x, y, target, params)
         if out is None:
             raise PcgError("train_gan: the loader gave no batch")
         ld, lg = torch.cat([out["loss_D"].reshape(1), out["loss_G"].reshape(1)]).cpu().tolist()     # the epoch's one host read (:146-148)
@@ -531,3 +655,170 @@ def counterfactual_batch(G, imgs, target):
         B = imgs.shape[0]
         cf = ops.clamp_add_fwd(_as_rows(imgs, B), delta.reshape(B, HW), -1.0, 1.0)
     return cf.view(B, 1, H, W), delta
+
+
+# ---- the promptable half: queries, the all-targets sweep, per-target evaluation (gan_train_copy.py:161-172) -------------
+EVAL_FIELDS = PER_CLASS_FIELDS + ("mean_abs_delta", "l2")
+
+
+def _check_query_nets(G, C, imgs, who, query_chunk=1):
+    """The refusals of the query front ends, all on the host before any launch."""
+    if int(query_chunk) < 1:
+        raise PcgError(f"{who}: query_chunk {query_chunk}: a window holds at least one query")
+    if not (torch.is_tensor(imgs) and imgs.is_cuda):
+        raise PcgError(f"{who}: the images are on {getattr(imgs, 'device', type(imgs))}; libpcgan_hip has no CPU path")
+    if imgs.dim() < 2 or imgs.shape[0] < 1 or imgs.numel() != imgs.shape[0] * HW:
+        raise PcgError(f"{who}: expected [B,1,{H},{W}] images, got shape {tuple(imgs.shape)}")
+    for name, net in (("generator", G), ("classifier", C)):
+        dev = next(net.parameters()).device
+        if dev.type != "cuda":
+            raise PcgError(f"{who}: the {name} is on {dev}; libpcgan_hip has no CPU path")
+    if not isinstance(G, Generator):
+        raise PcgError(f"{who}: the generator is a {type(G).__name__}, not gan_train.Generator")
+    if C.training:
+        raise PcgError(f"{who}: the classifier is in training mode: call .eval() first (gan_train_copy.py:164 runs it frozen)")
+    if getattr(C, "num_classes", None) != G.label_embed.num_embeddings:
+        raise PcgError(f"{who}: the generator embeds {G.label_embed.num_embeddings} classes, the classifier has {getattr(C, 'num_classes', None)}")
+
+
+def _query_labels(v, B, K, dev, name):
+    """An int, a list or a tensor of one class per row -> [B] int64 on the GPU.  Where the values are visible to the host a class
+    outside 0..K-1 is refused; labels already on the device are clamped into the table by the kernels."""
+    if v is None:
+        return None
+    host = None
+    if not torch.is_tensor(v):
+        host = torch.as_tensor(v, dtype=torch.int64).reshape(-1)
+        if host.numel() == 1 and not isinstance(v, (list, tuple)):
+            host = host.expand(B)
+    elif not v.is_cuda:
+        host = v.reshape(-1).to(torch.int64)
+    if host is not None:
+        if host.numel() != B:
+            raise PcgError(f"{name}: expected {B} labels, got {host.numel()}")
+        if int(host.min()) < 0 or int(host.max()) >= K:
+            raise PcgError(f"{name}: a label is outside 0..{K - 1}")
+        return host.contiguous().to(dev)
+    return _labels(v, B, dev, name)
+
+
+def _run_queries(G, C, x, target, T, y_true=None, group_rows=None, query_chunk=2048, keep=True, with_orig=True, outputs=ops.SCORE_FIELDS):
+    """All T * B queries of a batch: generator + classifier over windows of `query_chunk` queries, then ONE score launch."""
+    B = x.shape[0]
+    xr = _as_rows(x, B)
+    K, TB, dev = C.num_classes, T * B, x.device
+    kp = (K + 3) // 4 * 4
+    f32 = dict(dtype=torch.float32, device=dev)
+    with torch.no_grad():
+        logits, sums = torch.empty((TB, kp), **f32), torch.empty((TB, 3), **f32)
+        full = {k: torch.empty((TB, HW), **f32) for k in ("x_cf", "delta")} if keep else None
+        for q0 in range(0, TB, int(query_chunk)):
+            nq = min(int(query_chunk), TB - q0)
+            out = {"sums": sums[q0:q0 + nq]}
+            if keep:
+                out.update({k: v[q0:q0 + nq] for k, v in full.items()})
+            r = G.forward_queries(xr, target, T=T, q0=q0, nq=nq, out=out)
+            _padded_logits(C, r["x_cf"], out=logits[q0:q0 + nq])
+        logits_orig = _padded_logits(C, xr) if (with_orig and y_true is not None) else None
+        res = ops.mnist_cf_score(logits, K, B, T, target=target, y_true=y_true, logits_orig=logits_orig, tail_sums=sums, group_rows=group_rows,
+                                 outputs=outputs)
+    res.update(sums=sums, logits=logits)
+    if keep:
+        res.update(full)
+    return res
+
+
+def counterfactuals(G, C, imgs, target, y_true=None, query_chunk=2048):
+    """The prompted query of gan_train_copy.py:161-172: "turn these images into `target`" (an int, or one class per row).  C: any
+    classifier countergan._padded_logits accepts, in eval mode.  Returns device tensors: x_cf (clamped, :166), delta [B,1,28,28]; pred
+    (int64, the first maximum, :171), conf (:172), p_target, p_true / p_orig_true (with y_true), flip [B]; sums [B,3] = sum |x_cf - x|,
+    sum |delta|, sum (x_cf - x)^2 over the pixels; group_sums [1,1,8] (countergan.SUM_FIELDS)."""
+    _check_query_nets(G, C, imgs, "counterfactuals", query_chunk)
+    B, K = imgs.shape[0], C.num_classes
+    res = _run_queries(G, C, imgs, _query_labels(target, B, K, imgs.device, "target"), 1,
+                       y_true=_query_labels(y_true, B, K, imgs.device, "y_true"), query_chunk=query_chunk)
+    shp = (B, 1, H, W)
+    out = {"x_cf": res["x_cf"].view(shp), "delta": res["delta"].view(shp), "sums": res["sums"], "group_sums": res["group_sums"]}
+    out.update({k: res[k] for k in ops.SCORE_FIELDS})
+    return out
+
+
+def counterfactual_sweep(G, C, imgs, y_true=None, query_chunk=2048, group_rows=None):
+    """counterfactuals() for ALL num_classes targets of every row: windows of `query_chunk` queries through G and C, then ONE score
+    launch.  Results shaped [T,B,...] (x_cf, delta [T,B,1,28,28]; pred ... flip [T,B]; sums [T,B,3]) and group_sums
+    [T, ceil(B / group_rows), 8] (countergan.SUM_FIELDS)."""
+    _check_query_nets(G, C, imgs, "counterfactual_sweep", query_chunk)
+    B, T = imgs.shape[0], G.label_embed.num_embeddings
+    res = _run_queries(G, C, imgs, None, T, y_true=_query_labels(y_true, B, C.num_classes, imgs.device, "y_true"), group_rows=group_rows,
+                       query_chunk=query_chunk)
+    shp = (T, B, 1, H, W)
+    out = {"x_cf": res["x_cf"].view(shp), "delta": res["delta"].view(shp), "sums": res["sums"].view(T, B, 3), "group_sums": res["group_sums"]}
+    out.update({k: res[k].view(T, B) for k in ops.SCORE_FIELDS})
+    return out
+
+
+def evaluate_examples(G, C, imgs, targets=None, rng=None):
+    """gan_train_copy.py:158-172 without the figure: one random target per image (:162), drawn on the device with rng.randint, or the
+    `targets` supplied; the clamped counterfactuals and the classifier's prediction and confidence for each.  Returns
+    (targets, x_cf, delta, pred, conf), all on the device."""
+    _check_query_nets(G, C, imgs, "evaluate_examples")
+    B, K = imgs.shape[0], C.num_classes
+    if targets is None:
+        if rng is None:
+            raise PcgError("evaluate_examples: no targets given and no rng to draw them from: pass rng=ops.DeviceRNG(seed)")
+        targets = rng.randint(0, K, B, imgs.device)                                                                       # :162
+    else:
+        targets = _query_labels(targets, B, K, imgs.device, "targets")
+    res = _run_queries(G, C, imgs, targets, 1, outputs=("pred", "conf"), keep=True)
+    shp = (B, 1, H, W)
+    return targets, res["x_cf"].view(shp), res["delta"].view(shp), res["pred"], res["conf"]
+
+
+def _fold_eval(group_sums):
+    """Pure host.  [T][J][8] group sums (J loader batches) -> {target: {EVAL_FIELDS}} in float64: per target the mean over the batches
+    of the per-batch means, the order of eval_utils.py:97-102 (a ragged last batch weighs as much as a full one).  class_flip_rate,
+    prediction_gain and actionability as eval_utils.py:58-66 defines them; mean_abs_delta = mean |delta| (the un-clamped change); l2 =
+    sqrt(mean over the batch's rows of sum_pixels (x_cf - x)^2), the root-mean-square L2 distance of a batch."""
+    import numpy as np
+    per = metrics_from_sums(group_sums, HW)
+    if per["count"].ndim != 2:
+        raise PcgError(f"_fold_eval: expected [T][J][8] sums, got {np.asarray(group_sums).shape}")
+    live = per["count"] > 0
+    if not live.any(axis=1).all():
+        raise PcgError("_fold_eval: a target class has no batch")
+    with np.errstate(invalid="ignore"):
+        cols = {"class_flip_rate": per["class_flip_rate"], "prediction_gain": per["prediction_gain"], "actionability": per["actionability"],
+                "mean_abs_delta": per["allowed_l1"], "l2": np.sqrt(per["mask_penalty_pre"] * float(HW))}
+    folded = {k: np.where(live, v, 0.0).sum(axis=1) / live.sum(axis=1) for k, v in cols.items()}
+    return {cls: {k: float(folded[k][cls]) for k in EVAL_FIELDS} for cls in range(live.shape[0])}
+
+
+def evaluate_per_target(G, C, loader, one_pass=True, query_chunk=2048, verbose=True):
+    """Per target class, over any iterable of (x, y): class_flip_rate, prediction_gain and actionability exactly as
+    mnist/eval_utils.py:58-66 defines them for any generator, plus mean_abs_delta and l2 (_fold_eval), each the mean over the loader's
+    batches of the per-batch means (:97-102).  one_pass: all num_classes targets of a loader batch in ONE sweep (windows of
+    query_chunk queries), the group sums kept on the device and read ONCE for the whole loader; one_pass=False: one counterfactuals()
+    call and one host read per (batch, target), the reference's own loop.  Host arithmetic in float64.  Returns
+    {target class: {metric: value}}, which countergan.per_class_csv(result, fields=EVAL_FIELDS) prints."""
+    import numpy as np
+    from .countergan import per_class_csv
+    T, dev = G.label_embed.num_embeddings, next(G.parameters()).device
+    groups = []
+    for x, y in loader:
+        x = x.to(dev)
+        _check_query_nets(G, C, x, "evaluate_per_target", query_chunk)
+        B = x.shape[0]
+        y = _query_labels(y, B, C.num_classes, dev, "y")
+        if one_pass:
+            groups.append(_run_queries(G, C, x, None, T, y_true=y, group_rows=B, query_chunk=query_chunk, keep=False, with_orig=False,
+                                       outputs=())["group_sums"])
+        else:
+            groups.append(np.concatenate([counterfactuals(G, C, x, cls, y_true=y, query_chunk=query_chunk)["group_sums"].cpu().numpy()
+                                          for cls in range(T)], axis=0))
+    if not groups:
+        raise PcgError("evaluate_per_target: the loader yielded no batch")
+    sums = torch.cat(groups, dim=1).cpu().numpy() if one_pass else np.concatenate(groups, axis=1)      # [T][J][8]; one_pass: the one host read
+    avg = _fold_eval(sums)
+    if verbose:
+        print(per_class_csv(avg, fields=EVAL_FIELDS), end="")
+    return avg

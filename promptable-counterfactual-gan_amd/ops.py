@@ -1905,6 +1905,68 @@ def delta_gan_tail_bwd(dD, dC, delta, lambda_cls, lambda_reg, dD_stride=1, out=N
     return out
 
 
+# ---- the additive-delta CounteRGAN's prompted queries and random-target draw (csrc/delta_cf_eval.hip) ------------------
+def delta_cf_entry(x, target, table, T=1, q0=0, nq=None, out=None, target_host=None):
+    """pcg_delta_cf_entry: [nq, HW, 2] with channels (x[b], table[target(q)]) for the queries q = t * B + b of the window; x [B, HW];
+    target None (the sweep over T classes) or [B] int64 on the GPU with T = 1.  target_host: a host copy of target, range-checked by
+    the library before the launch (device labels are clamped into the table)."""
+    _chk(x, "x"); _chk(table, "table")
+    K, HW = table.shape
+    B = x.numel() // HW
+    if B < 1 or x.numel() != B * HW:
+        raise _lib.PcgError(f"delta_cf_entry: x {tuple(x.shape)} is not rows of {HW} pixels")
+    target = _targets(target, B, T, K)
+    q0, nq = _window(B, T, q0, nq)
+    out = out if out is not None else torch.empty((nq, HW, 2), dtype=torch.float32, device=x.device)
+    if _chk(out, "out").numel() != nq * HW * 2:
+        raise _lib.PcgError(f"delta_cf_entry: out holds {out.numel()} floats, {nq * HW * 2} needed")
+    th, thp = _host_labels(target_host, "target_host")
+    if th is not None and (target is None or th.numel() != B):
+        raise _lib.PcgError(f"delta_cf_entry: target_host is the host copy of a target of {B} rows")
+    a = _lib.DeltaCfEntryArgs(_p(x), _p(table), _p(target), thp, _p(out), B, int(T), HW, K, q0, nq)
+    check(_lib.load().pcg_delta_cf_entry(ctypes.byref(a), _stream()), "pcg_delta_cf_entry")
+    return out
+
+
+def delta_cf_tail(delta, x, T=1, q0=0, nq=None, out=None):
+    """pcg_delta_cf_tail: delta [nq, HW] of the window, x [B, HW] -> (x_cf [nq, HW] = clamp(x[b] + delta, -1, 1), sums [nq, 3] =
+    sum |x_cf - x|, sum |delta|, sum (x_cf - x)^2); `out`: a dict of preallocated tensors under "x_cf" / "sums"."""
+    _chk(delta, "delta"); _chk(x, "x")
+    nq_d = delta.shape[0]
+    HW = delta.numel() // nq_d
+    B = x.numel() // HW
+    if B < 1 or x.numel() != B * HW:
+        raise _lib.PcgError(f"delta_cf_tail: x {tuple(x.shape)} is not rows of {HW} pixels")
+    q0, nq = _window(B, T, q0, nq_d if nq is None else nq)
+    if nq != nq_d:
+        raise _lib.PcgError(f"delta holds {nq_d} queries, the window {nq}")
+    out = out or {}
+    res = []
+    for name, shape in (("x_cf", (nq, HW)), ("sums", (nq, 3))):
+        t = out.get(name)
+        t = t if t is not None else torch.empty(shape, dtype=torch.float32, device=delta.device)
+        if _chk(t, name).numel() != shape[0] * shape[1]:
+            raise _lib.PcgError(f"out[{name!r}]: expected {shape[0] * shape[1]} values, got shape {tuple(t.shape)}")
+        res.append(t)
+    a = _lib.DeltaCfTailArgs(_p(delta), _p(x), _p(res[0]), _p(res[1]), B, int(T), HW, q0, nq)
+    check(_lib.load().pcg_delta_cf_tail(ctypes.byref(a), _stream()), "pcg_delta_cf_tail")
+    return res[0], res[1]
+
+
+def delta_gan_target_draw(target, K, seed, offset=0, counter=None):
+    """pcg_delta_gan_target_draw: ONE class in [0, K) -- out[0] of pcg_randint(out, 1, 0, K, NULL, seed, offset) -- written to every row
+    of target [B] int64.  counter (int64[2] on the GPU, DeviceRNG.device_counter): the offset is counter[0] and the launch advances it
+    by 1; `offset` is ignored then.  DeviceRNG.delta_gan_target keeps the host bookkeeping."""
+    _chk_idx(target, K, "target")
+    if counter is not None and (counter.dtype != torch.int64 or not counter.is_cuda or counter.numel() < 2 or not counter.is_contiguous()):
+        raise _lib.PcgError("delta_gan_target_draw: counter must be int64[2] on the GPU (DeviceRNG.device_counter)")
+    if target.numel() < 1 or int(K) < 1:
+        raise _lib.PcgError(f"delta_gan_target_draw: {target.numel()} rows, {K} classes")
+    a = _lib.DeltaGanTargetDrawArgs(_p(target), _p(counter), int(seed) & 0xFFFFFFFFFFFFFFFF, int(offset) & 0xFFFFFFFFFFFFFFFF, target.numel(), int(K))
+    check(_lib.load().pcg_delta_gan_target_draw(ctypes.byref(a), _stream()), "pcg_delta_gan_target_draw")
+    return target
+
+
 def interpolate(alpha, real, fake):
     _chk(alpha, "alpha"); _chk(real, "real"); _chk(fake, "fake")
     B = alpha.numel()
@@ -1970,6 +2032,15 @@ class DeviceRNG:
         check(_lib.load().pcg_randint(_p(out), n, low, high, _p(exclude), self.seed, self._advance((n + 3) // 4), _stream()),
               "pcg_randint")
         return out
+
+    def delta_gan_target(self, target, K, counter=None):
+        """The random-target iteration's ONE class (gan_train_copy.py:119-120) into every row of target [B]: the value
+        randint(0, K, 1) gives at this offset.  counter None: the offset goes by value and the host offset advances by randint's span
+        of one counter value.  counter (device_counter()): the launch reads and advances the device offset itself -- the form a HIP
+        graph can capture; the host-side offset is not touched (see gan_train.GraphedTrainStep(rng=...))."""
+        if counter is not None:
+            return delta_gan_target_draw(target, K, self.seed, counter=counter)
+        return delta_gan_target_draw(target, K, self.seed, offset=self._advance(1))
 
     def randn(self, shape, device, mean=0.0, std=1.0):
         out = torch.empty(shape, dtype=torch.float32, device=device)

@@ -9,7 +9,13 @@ One process, one GPU.  Synthetic rows (ten 28x28 templates plus noise) at the re
 device and walked round-robin.  Every leg is run once untimed (which also captures the graph), then `--rounds` alternating rounds
 (fused, chain, eager, fused, ...) of device-synchronised wall time around `--steps` iterations: median and min..max per leg, per step.
 The library calls of one step of both paths are counted through ops.check.  One JSON line (scripts/_benchlib.py: emit), also written
-to `--out`."""
+to `--out`.
+
+  python scripts/bench_delta_gan.py --random-target [--out profiles/delta_gan_random_target_bench_line.json]
+
+measures instead the random-target fused step (gan_train_copy.py:119-146: GraphedTrainStep(rng=...), the class draw as the first of 65
+captured launches) against the fixed-target fused step (64 launches) under the same parameters, in the same
+alternating rounds, and the draw launch on its own (a captured graph of 100 draws, per launch)."""
 import argparse
 import json
 import os
@@ -90,15 +96,99 @@ def eager_stepper(dev, p):
     return step
 
 
+def random_target(args):
+    """The random-target fused step against the fixed-target one: same nets, same parameters, alternating rounds."""
+    import pcgan_amd
+    from pcgan_amd import countergan as K, gan_train as T
+    pcgan_amd.load()
+    ops = pcgan_amd.ops
+    dev = torch.device("cuda:0")
+    B, p = args.batch, dict(T.params, batch_size=args.batch)
+    xs, ys = synthetic(8 * B, 1)
+    batches = [(xs[i:i + B].to(dev).contiguous(), ys[i:i + B].to(dev).contiguous()) for i in range(0, 8 * B, B)]
+    target = torch.full((B,), p["target_class"], dtype=torch.int64, device=dev)
+
+    def stepper(rng):
+        torch.manual_seed(7)
+        G, D = T.Generator().to(dev), T.Discriminator().to(dev)
+        torch.manual_seed(5)
+        return T.GraphedTrainStep(G, D, K.Classifier().to(dev).eval(), B, p, rng=rng)
+    fixed, drawn = stepper(None), stepper(ops.DeviceRNG(11))
+    legs = {"fixed_target": lambda x, y: fixed.step(x, y, target), "random_target": lambda x, y: drawn.step(x, y)}
+
+    def run(fn, n):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for i in range(n):
+            out = fn(*batches[i % len(batches)])
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e6 / n, out
+    for fn in legs.values():
+        run(fn, 10)
+    # the draw launch on its own: 100 of them captured into one graph, per launch
+    rng, n_draw = ops.DeviceRNG(13), 100
+    ctr = rng.device_counter(dev)
+    tbuf = torch.zeros(B, dtype=torch.int64, device=dev)
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        rng.delta_gan_target(tbuf, 10, counter=ctr)
+    torch.cuda.current_stream().wait_stream(side)
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        for _ in range(n_draw):
+            rng.delta_gan_target(tbuf, 10, counter=ctr)
+    draw_us = []
+    for _ in range(args.rounds + 1):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        graph.replay()
+        torch.cuda.synchronize()
+        draw_us.append((time.perf_counter() - t0) * 1e6 / n_draw)
+    draw_us = draw_us[1:]
+    us, last = {k: [] for k in legs}, {}
+    for _ in range(args.rounds):
+        for k, fn in legs.items():
+            t, last[k] = run(fn, args.steps)
+            us[k].append(t)
+    for k, out in last.items():
+        v = [float(out["loss_D"].cpu()), float(out["loss_G"].cpu())]
+        if not np.isfinite(v).all():
+            sys.exit(f"{k}: losses {v}")
+    f, r, d = spread(us["fixed_target"]), spread(us["random_target"]), spread(draw_us, 2)
+    allowance = f["median"] + d["median"] + (f["max"] - f["min"])
+    line = {
+        "metric": f"additive-delta MNIST CounteRGAN step at batch {B}, random-target fused step (gan_train_copy.py:119-146)",
+        "value": r["median"], "unit": "us", "n_gpus": 1, "higher_is_better": False, "dtype": "f32",
+        "us_per_step": {"fixed_target": f, "random_target": r}, "draw_launch_us": d,
+        "steps_per_round": args.steps, "rounds": args.rounds, "batch": B,
+        "random_minus_fixed_us": round(r["median"] - f["median"], 1), "fixed_round_spread_us": round(f["max"] - f["min"], 1),
+        "allowance_us": round(allowance, 1), "random_within_fixed_plus_draw_plus_spread": bool(r["median"] <= allowance),
+        "classes_drawn": int(drawn._rng.offset),
+        "config": {"workload": "the fused step of scripts/bench_delta_gan.py with the iteration's class drawn by the step's first launch "
+                               "(65 captured launches) against a fixed target tensor (64)", "parallelism": "dp1"},
+        "roofline": {"bound": "the convolution launches of the replayed step (DESIGN.md §3.19)", "kernel": "delta_gan_target_draw_kernel: one workgroup"},
+    }
+    if args.out:
+        with open(args.out, "w") as fh:
+            fh.write(json.dumps(line, indent=1) + "\n")
+    _benchlib.emit(line)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--batch", type=int, default=128)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "delta_gan_bench_line.json"))
+    ap.add_argument("--random-target", action="store_true", help="the random-target fused step against the fixed-target one")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "delta_gan_random_target_bench_line.json" if args.random_target else "delta_gan_bench_line.json")
     if not torch.cuda.is_available():
         sys.exit("needs an MI355X: torch.cuda.is_available() is False (there is no CPU path)")
+    if args.random_target:
+        return random_target(args)
     import pcgan_amd
     from pcgan_amd import countergan as K, gan_train as T
     pcgan_amd.load()
