@@ -1618,6 +1618,66 @@ typedef struct pcg_delta_gan_target_draw_args {
 } pcg_delta_gan_target_draw_args;
 int pcg_delta_gan_target_draw(const pcg_delta_gan_target_draw_args* args, pcg_stream_t stream);
 
+/* ---- the head and the losses of the full-resolution MNIST CounteRGAN (conditional_counteRGAN/mnist/countergan2.py:76-93, :188, :198;
+ * csrc/prob_head.hip) ----------------------------------------------------------------------------------------
+ * All fp32, gfx950 only, every sum in an order fixed by the data and the arguments, no floating-point atomics, no grid barrier; every
+ * entry takes a stream and may be captured into a HIP graph.  Every entry validates its arguments before it touches HIP:
+ * PCG_ERR_INVALID (PCG_ERR_WORKSPACE for a workspace too small) and a pcg_last_error text otherwise.                                   */
+#define PCG_PROB_HEAD_D 0          /* rows 0..R/2 are D(real), rows R/2..R are D(fake): countergan2.py:188                             */
+#define PCG_PROB_HEAD_G 1          /* every row is D(fake) of the generator's step: countergan2.py:198                                 */
+#define PCG_PROB_HEAD_MAX_SLABS 16
+
+/* nn.Flatten + nn.Linear(F -> 1) + nn.Sigmoid (countergan2.py:85-87 at :186-187 and :195), the log-eps loss of :188 (mode D) or :198
+ * (mode G), the loss's gradient with respect to the logit and the bias gradient, in one launch.  a [R][F]: D's last activation, NHWC,
+ * through its LeakyReLU; w [F]: the weight row packed (h,w,c) by pcg_delta_gan_entry; bias [1].  With half = R/2 (mode D) or R (mode G):
+ *   logits[r] = a[r] . w + bias
+ *   prob[r]   = d = 1 / (1 + exp(-logit))                    pcg_act_fwd's PCG_ACT_SIGMOID expression: the same bits for the same logit
+ *   loss[0]   = mode D: -(1/half) * sum_b [ log(d_b + eps) + log((1 - d_{half+b}) + eps) ]       the fake term left to right, as :188
+ *               mode G: -(1/R) * sum_b log(d_b + eps)
+ *   dlogit[r] = real rows (all rows in mode G): -(1/half) * d (1 - d) / (d + eps);  fake rows: +(1/half) * d (1 - d) / ((1 - d) + eps)
+ *   db[0]     = sum over r of dlogit[r]
+ * One workgroup of 256 threads per (row, slab): the F/4 16-byte groups of a row are cut into `slabs` contiguous slabs of
+ * ceil((F/4) / slabs) groups (a slab past the end is empty and contributes +0); thread t folds groups t, t + 256, ... of its slab with
+ * fmaf, then a 256-wide tree.  The last workgroup to arrive finishes: thread t takes rows t, t + 256, ...: logit = ((p_0 + p_1) + ...)
+ * + bias over the slab partials in slab order, then d, dlogit; the loss terms are summed in the order of pcg_log_eps_loss_fwd_bwd, db
+ * over rows t, t + 256, ... in order, each then a tree.  With slabs = 1 the logits are pcg_logit_head_fwd's bit for bit.
+ * slabs: 1..16, or 0 for the library's choice: 2 for R <= 128, 1 above.  That is what scripts/bench_countergan2.py showed at
+ * F = 50176: at R = 128 two slabs beat one in every round (14.5 against 15.7 us), at R = 256 no count beat
+ * one, and 4 or 8 slabs lost at both; other row counts were not measured and fall on the side of the nearer measured one.  workspace: pcg_prob_head_workspace_bytes(R, slabs) bytes (0 for an R or a slab
+ * count the entry refuses), 4-byte aligned, all zero at the first call and left all zero.  R >= 1, even in mode D; F % 4 == 0; a and w
+ * 16-byte aligned; 0 < eps < 1.  The backward of this head is pcg_logit_head_bwd with dlogit as it stands.                             */
+typedef struct pcg_prob_head_fwd_args {
+  const float* a;       /* [R][F] */
+  const float* w;       /* [F], packed (h,w,c) */
+  const float* bias;    /* [1] */
+  float* logits;        /* [R] */
+  float* prob;          /* [R] */
+  float* loss;          /* [1] */
+  float* dlogit;        /* [R] */
+  float* db;            /* [1] */
+  void* workspace;
+  size_t workspace_bytes;
+  float eps;
+  int32_t R, F, mode, slabs;
+} pcg_prob_head_fwd_args;
+size_t pcg_prob_head_workspace_bytes(int32_t R, int32_t slabs);
+int pcg_prob_head_fwd(const pcg_prob_head_fwd_args* args, pcg_stream_t stream);
+
+/* The same loss on given probabilities p [R] (countergan2.py:188 in mode PCG_PROB_HEAD_D, :198 in mode PCG_PROB_HEAD_G), for the op
+ * chain that ends in pcg_act_fwd's sigmoid.  loss [1] (nullable); dp [R] (nullable, out of place) = d loss / d p, before the sigmoid:
+ * real rows -(1/half) / (p + eps), fake rows +(1/half) / ((1 - p) + eps), times grad_out[0] where grad_out (nullable, device) is given.
+ * One workgroup; thread t takes b = t, t + 256, ... below half, the term of b in mode D being log(p_b + eps) + log((1 - p_{half+b}) +
+ * eps), then a 256-wide tree: the order of pcg_prob_head_fwd, so fed that entry's prob it returns that entry's loss bit for bit.       */
+typedef struct pcg_log_eps_loss_args {
+  const float* p;          /* [R] */
+  const float* grad_out;   /* nullable: [1], device */
+  float* loss;             /* nullable: [1] */
+  float* dp;               /* nullable: [R] */
+  float eps;
+  int32_t R, mode;
+} pcg_log_eps_loss_args;
+int pcg_log_eps_loss_fwd_bwd(const pcg_log_eps_loss_args* args, pcg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

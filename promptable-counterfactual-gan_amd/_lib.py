@@ -285,9 +285,22 @@ class DeltaGanTargetDrawArgs(ctypes.Structure):
     _fields_ = [("target", _P), ("counter", _P), ("seed", ctypes.c_uint64), ("offset", ctypes.c_uint64), ("B", _I), ("K", _I)]
 
 
+class ProbHeadFwdArgs(ctypes.Structure):
+    """pcg_prob_head_fwd_args."""
+    _fields_ = ([(n, _P) for n in ("a", "w", "bias", "logits", "prob", "loss", "dlogit", "db", "workspace")] +
+                [("workspace_bytes", ctypes.c_size_t), ("eps", _F)] + [(n, _I) for n in ("R", "F", "mode", "slabs")])
+
+
+class LogEpsLossArgs(ctypes.Structure):
+    """pcg_log_eps_loss_args."""
+    _fields_ = [(n, _P) for n in ("p", "grad_out", "loss", "dp")] + [("eps", _F), ("R", _I), ("mode", _I)]
+
+
 DELTA_GAN_BUILD, DELTA_GAN_REGATHER = 0, 1               # PCG_DELTA_GAN_* (include/pcgan_hip.h)
 LOGIT_HEAD_D, LOGIT_HEAD_G = 0, 1                        # PCG_LOGIT_HEAD_*
 DELTA_GAN_CHUNK = 1024                                   # PCG_DELTA_GAN_CHUNK
+PROB_HEAD_D, PROB_HEAD_G = 0, 1                          # PCG_PROB_HEAD_*
+PROB_HEAD_MAX_SLABS = 16                                 # PCG_PROB_HEAD_MAX_SLABS
 
 # typedef name in include/pcgan_hip.h -> its class here (pcg_abi_struct_bytes checks the sizes: tests/test_house_abi_host.py)
 STRUCTS = {"pcg_conv_geom": ConvGeom, "pcg_in_xform": InXform, "pcg_wgrad_item": WgradItem, "pcg_sn_fwd_batch": SnFwdBatch,
@@ -306,7 +319,8 @@ STRUCTS = {"pcg_conv_geom": ConvGeom, "pcg_in_xform": InXform, "pcg_wgrad_item":
            "pcg_delta_gan_tail_fwd_args": DeltaGanTailFwdArgs, "pcg_logit_head_fwd_args": LogitHeadFwdArgs,
            "pcg_logit_head_bwd_args": LogitHeadBwdArgs, "pcg_delta_gan_tail_bwd_args": DeltaGanTailBwdArgs,
            "pcg_delta_cf_entry_args": DeltaCfEntryArgs, "pcg_delta_cf_tail_args": DeltaCfTailArgs,
-           "pcg_delta_gan_target_draw_args": DeltaGanTargetDrawArgs}
+           "pcg_delta_gan_target_draw_args": DeltaGanTargetDrawArgs, "pcg_prob_head_fwd_args": ProbHeadFwdArgs,
+           "pcg_log_eps_loss_args": LogEpsLossArgs}
 
 _c = ctypes
 _vp, _f, _i, _i64, _sz = _c.c_void_p, _c.c_float, _c.c_int, _c.c_int64, _c.c_size_t
@@ -550,6 +564,9 @@ PROTOTYPES = {
     "pcg_delta_cf_entry": (_i, [_c.POINTER(DeltaCfEntryArgs), _vp]),
     "pcg_delta_cf_tail": (_i, [_c.POINTER(DeltaCfTailArgs), _vp]),
     "pcg_delta_gan_target_draw": (_i, [_c.POINTER(DeltaGanTargetDrawArgs), _vp]),
+    "pcg_prob_head_workspace_bytes": (_sz, [_i32, _i32]),
+    "pcg_prob_head_fwd": (_i, [_c.POINTER(ProbHeadFwdArgs), _vp]),
+    "pcg_log_eps_loss_fwd_bwd": (_i, [_c.POINTER(LogEpsLossArgs), _vp]),
     "pcg_spectral_norm_fwd": (_i, [_vp, _i32, _i32, _vp, _vp, _f, _i, _vp, _vp, _vp, _vp, _vp]),
     "pcg_spectral_norm_bwd": (_i, [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _i, _vp]),
 }

@@ -1905,6 +1905,69 @@ def delta_gan_tail_bwd(dD, dC, delta, lambda_cls, lambda_reg, dD_stride=1, out=N
     return out
 
 
+# ---- the full-resolution MNIST CounteRGAN's head and losses (csrc/prob_head.hip) ---------------------------------------
+LOG_EPS = 1e-6                                           # countergan2.py:188,198
+
+
+def prob_head_workspace(R, device, slabs=0):
+    """A zeroed workspace for prob_head_fwd on R rows (arrival counter + one partial per row and slab).  Allocate it outside any graph
+    capture; the kernel leaves it zero."""
+    need = _lib.load().pcg_prob_head_workspace_bytes(int(R), int(slabs))
+    if need == 0:
+        raise _lib.PcgError(f"prob_head_workspace: {R} rows in {slabs} slabs: 1..65535 rows, 0..{_lib.PROB_HEAD_MAX_SLABS} slabs")
+    return torch.zeros(need, dtype=torch.uint8, device=device)
+
+
+def _prob_head_ws(R, slabs, device):
+    """The current stream's cached head workspace, grown on demand (never while the stream captures: the zero fill would replay)."""
+    stream = torch.cuda.current_stream(device).cuda_stream
+    key = (device.type, device.index, stream, "prob_head")
+    ws = _ws_cache.get(key)
+    need = _lib.load().pcg_prob_head_workspace_bytes(int(R), int(slabs))
+    if need and (ws is None or ws.numel() < need):
+        if torch.cuda.is_current_stream_capturing():
+            raise _lib.PcgError("prob_head_fwd: pass a workspace from ops.prob_head_workspace() made before the capture")
+        if ws is not None:
+            _ws_retired.append(ws)
+        ws = _ws_cache[key] = prob_head_workspace(R, device, slabs)
+    return ws if ws is not None else torch.zeros(16, dtype=torch.uint8, device=device)     # an R / slabs the entry itself refuses
+
+
+def prob_head_fwd(a, w, bias, mode_g=False, eps=LOG_EPS, slabs=0, logits=None, prob=None, loss=None, dlogit=None, db=None, ws=None):
+    """pcg_prob_head_fwd: logits [R] = a [R, F] . w [F] + bias, prob = sigmoid(logits), the log-eps loss of countergan2.py:188 (mode D:
+    rows 0..R/2 are D(real), the rest D(fake)) or :198 (mode_g: every row), its gradient dlogit [R] and db [1] = sum dlogit.  slabs: the
+    column slabs a row is cut into (0: the library's choice).  Returns (logits, prob, loss, dlogit, db)."""
+    _chk(a, "a"); _chk(w, "w"); _chk(bias, "bias")
+    R = a.shape[0]
+    F = a.numel() // R
+    if w.numel() != F or bias.numel() != 1:
+        raise _lib.PcgError(f"prob_head_fwd: a [R, F] {tuple(a.shape)}, w {tuple(w.shape)}, bias {tuple(bias.shape)} do not agree")
+    f32 = lambda n: torch.empty(n, dtype=torch.float32, device=a.device)      # noqa: E731
+    outs = []
+    for t, name, n in ((logits, "logits", R), (prob, "prob", R), (loss, "loss", 1), (dlogit, "dlogit", R), (db, "db", 1)):
+        t = t if t is not None else f32(n)
+        if _chk(t, name).numel() != n:
+            raise _lib.PcgError(f"prob_head_fwd: {name} holds {t.numel()} floats, {n} needed")
+        outs.append(t)
+    ws = ws if ws is not None else _prob_head_ws(R, slabs, a.device)
+    args = _lib.ProbHeadFwdArgs(_p(a), _p(w), _p(bias), *[_p(t) for t in outs], _p(ws), ws.numel(), float(eps), R, F,
+                                _lib.PROB_HEAD_G if mode_g else _lib.PROB_HEAD_D, int(slabs))
+    check(_lib.load().pcg_prob_head_fwd(ctypes.byref(args), _stream()), "pcg_prob_head_fwd")
+    return tuple(outs)
+
+
+def log_eps_loss_fwd_bwd(p, mode_g=False, eps=LOG_EPS, need_loss=True, need_grad=True, grad_out=None, loss_out=None):
+    """pcg_log_eps_loss_fwd_bwd on probabilities p [R]: the loss of countergan2.py:188 (rows 0..R/2 real, the rest fake) or :198
+    (mode_g).  Returns (loss [1] or None, dp [R] or None); dp is the gradient with respect to p, times the one-element device tensor
+    grad_out where given."""
+    _chk(p, "p")
+    loss = (loss_out if loss_out is not None else torch.empty(1, dtype=torch.float32, device=p.device)) if need_loss else None
+    dp = torch.empty_like(p) if need_grad else None
+    args = _lib.LogEpsLossArgs(_p(p), _p(grad_out), _p(loss), _p(dp), float(eps), p.numel(), _lib.PROB_HEAD_G if mode_g else _lib.PROB_HEAD_D)
+    check(_lib.load().pcg_log_eps_loss_fwd_bwd(ctypes.byref(args), _stream()), "pcg_log_eps_loss_fwd_bwd")
+    return loss, dp
+
+
 # ---- the additive-delta CounteRGAN's prompted queries and random-target draw (csrc/delta_cf_eval.hip; DESIGN.md §3.20) ------------------
 def delta_cf_entry(x, target, table, T=1, q0=0, nq=None, out=None, target_host=None):
     """pcg_delta_cf_entry: [nq, HW, 2] with channels (x[b], table[target(q)]) for the queries q = t * B + b of the window; x [B, HW];
