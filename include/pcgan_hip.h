@@ -1678,6 +1678,56 @@ typedef struct pcg_log_eps_loss_args {
 } pcg_log_eps_loss_args;
 int pcg_log_eps_loss_fwd_bwd(const pcg_log_eps_loss_args* args, pcg_stream_t stream);
 
+/* ---- the numbers and pixels of the MNIST CounteRGAN's report figures (conditional_counteRGAN/mnist/eval_utils.py:113-201, gr.py and
+ * gradio_app.py:346-441, :498-568; csrc/cf_report.hip) ---------------------------------------------------------
+ * All fp32, gfx950 only; every entry takes a stream, may be captured into a HIP graph and validates its arguments before it touches HIP:
+ * PCG_ERR_INVALID and a pcg_last_error text otherwise.  The only atomics are integer maxima, so no result depends on an order.        */
+#define PCG_CLASS_PICK_FIRST 0    /* the first row of every class (eval_utils.py:146-147)                                              */
+#define PCG_CLASS_PICK_BEST 1     /* the row the classifier is most confident about, the lowest such row on a tie (:142-144)           */
+#define PCG_CLASS_PICK_KMAX 64    /* classes a pick keeps per workgroup                                                                */
+#define PCG_CF_PANELS_GRID 0
+#define PCG_CF_PANELS_PANELS 1
+
+/* One source row per class over a data set walked in chunks (replaces the per-row loop of eval_utils.py:139-149: one batch-1 classifier
+ * forward and one host read per row).  A call folds the n rows [row0, row0 + n) of one chunk into state (uint64 [K], 8-byte aligned,
+ * zeroed by the caller before the first chunk):
+ *   key(row) = (uint64(hi) << 32) | (0xFFFFFFFF - row)          state[labels[row]] = max(state[labels[row]], key(row))
+ *   mode BEST:  hi = the bits of conf = softmax(logits[row][0..K))[labels[row]], fp32, max-subtracted: the arithmetic (and the device
+ *               function, csrc/softmax_label.h) of pcg_mnist_cf_score's own-label probabilities.  conf >= 0, and non-negative floats
+ *               order as their bit patterns, so the maximum key is the highest confidence and, among equal confidences, the lowest row:
+ *               the strict `conf > best_conf[idx]` scan of :143 in data-set order.  A row whose conf is not finite is skipped (a NaN
+ *               never wins that `>` either).
+ *   mode FIRST: hi = 1 and logits is not read (it may be null): the lowest row of the class, the early exit of :146-149.
+ * A row whose label is outside [0, K) is skipped.  logits [n][kp] (kp >= K, a multiple of 4: the layout of the padded classifier
+ * logits), labels [n] int64, both indexed from the chunk's first row.  K <= PCG_CLASS_PICK_KMAX; row0 + n <= 2^32 - 1 (a larger row does
+ * not fit the key and is refused).  One thread per row; a workgroup keeps K keys in LDS (64-bit LDS maxima) and then issues at most K
+ * global 64-bit atomicMax.  A maximum does not depend on the order of its operands: the state after all chunks is the same for ANY order
+ * of chunks, workgroups and threads, bit for bit.                                                                                       */
+int pcg_class_pick(const float* logits /*nullable in mode FIRST*/, const int64_t* labels, uint64_t* state, int32_t n, int32_t kp, int32_t K,
+                   int64_t row0, int32_t mode, pcg_stream_t stream);
+
+/* Decodes the state of pcg_class_pick (the `samples` / `best_conf` lists of eval_utils.py:136-137 after the loop): rows [K] int64 = the
+ * picked row of each class, -1 where the state word is 0 (no row of that class); conf [K] = its confidence (0 in mode FIRST and for an
+ * absent class).  X [N][HW] (nullable, with sources): the data set resident on the device; sources [K][HW] = X[rows[k]] (zeros for an
+ * absent class or a row >= N, which is never read).                                                                                     */
+int pcg_class_pick_gather(const uint64_t* state, const float* X /*nullable*/, int64_t* rows, float* conf, float* sources /*nullable*/,
+                          int32_t K, int64_t N, int32_t HW, int32_t mode, pcg_stream_t stream);
+
+/* The pixels of the figures.  Every operation is a single fp32 rounding (cf_report.hip compiles its kernels under
+ * `#pragma clang fp contract(off)`: a multiply is never fused with the add that follows it): the output is bit-identical to the same
+ * expressions in NumPy fp32.
+ * mode PCG_CF_PANELS_GRID (eval_utils.py:167-195): x = sources [n][HW] (n = K source classes), x_cf [T][n][HW] (the [target][row] layout
+ *   of the one-pass sweep), both in [-1, 1].  out (nullable) [n*H][T*W] float: cell (r, c) = (x_cf[c][r] + 1) / 2 (:190), the diagonal
+ *   r == c = (sources[r] + 1) / 2 (:175).  out_u8 (nullable) the same image as uint8, min(255, max(0, floor(v * 255 + 0.5))): the
+ *   convention of torchvision's save_image (countergan2.py:222).  mask, mask_mode, vmax are not read.
+ * mode PCG_CF_PANELS_PANELS (gr.py:370-372, :399, :533-535): x, x_cf [n][HW] in [-1, 1]; mask [HW] (PCG_MASK_SHARED) or [n][HW]
+ *   (PCG_MASK_PER_ROW).  out [n][4][H][W] = xv = (x + 1) / 2, cv = (x_cf + 1) / 2, |cv - xv| (from the two rounded values), mask.
+ *   vmax [1]: zeroed by the caller; the launch raises it to the maximum of the third panel with an atomicMax on the float's bits (the
+ *   values are >= 0).  T and out_u8 are not read.                                                                                      */
+int pcg_cf_panels(int32_t mode, const float* x, const float* x_cf, const float* mask /*nullable in grid mode*/, int32_t mask_mode, float* out,
+                  uint8_t* out_u8 /*nullable*/, float* vmax /*nullable in grid mode*/, int32_t n, int32_t T, int32_t H, int32_t W,
+                  pcg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

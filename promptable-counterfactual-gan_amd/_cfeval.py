@@ -1,7 +1,7 @@
 """What the counterfactual-evaluation front ends share on the host side (moons_countergan over csrc/moons_cf_eval.hip, house over
 csrc/house_cf_eval.hip, and the CSV text of countergan's classifier evaluation): the argument guards that run before anything touches
-the GPU, the fold of the kernels' group sums into the reference's metric table, and the CSV writers.  Pure host code: nothing here
-loads the library.  Where the ports differ, the difference is a keyword."""
+the GPU, the fold of the kernels' group sums into the reference's metric table, the CSV writers and the grayscale PNG writer of the
+counterfactual grid.  Pure host code: nothing here loads the library.  Where the ports differ, the difference is a keyword."""
 import math
 import os
 
@@ -106,6 +106,25 @@ def confusion_csv(cm):
 
 def csv_value(v):
     return "" if isinstance(v, float) and math.isnan(v) else (repr(v) if isinstance(v, float) else str(v))
+
+
+def write_png_gray(path, u8):
+    """An [H][W] uint8 array as an 8-bit grayscale PNG (zlib + struct only): signature, IHDR, one IDAT of the rows each behind a
+    filter byte 0, IEND."""
+    import struct
+    import zlib
+    a = np.asarray(u8)
+    if a.ndim != 2 or a.dtype != np.uint8 or a.shape[0] < 1 or a.shape[1] < 1:
+        raise PcgError(f"write_png_gray: expected a non-empty [H][W] uint8 array, got {a.shape} {a.dtype}")
+    h, w = a.shape
+
+    def block(tag, data):
+        return struct.pack(">I", len(data)) + tag + data + struct.pack(">I", zlib.crc32(tag + data) & 0xFFFFFFFF)
+    raw = np.concatenate([np.zeros((h, 1), np.uint8), a], axis=1).tobytes()
+    os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
+    with open(path, "wb") as f:
+        f.write(b"\x89PNG\r\n\x1a\n" + block(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, 0, 0, 0, 0)) + block(b"IDAT", zlib.compress(raw, 9)) +
+                block(b"IEND", b""))
 
 
 def save_table(rows, save_path, columns):

@@ -301,6 +301,9 @@ LOGIT_HEAD_D, LOGIT_HEAD_G = 0, 1                        # PCG_LOGIT_HEAD_*
 DELTA_GAN_CHUNK = 1024                                   # PCG_DELTA_GAN_CHUNK
 PROB_HEAD_D, PROB_HEAD_G = 0, 1                          # PCG_PROB_HEAD_*
 PROB_HEAD_MAX_SLABS = 16                                 # PCG_PROB_HEAD_MAX_SLABS
+CLASS_PICK_FIRST, CLASS_PICK_BEST = 0, 1                 # PCG_CLASS_PICK_*
+CLASS_PICK_KMAX = 64                                     # PCG_CLASS_PICK_KMAX
+CF_PANELS_GRID, CF_PANELS_PANELS = 0, 1                  # PCG_CF_PANELS_*
 
 # typedef name in include/pcgan_hip.h -> its class here (pcg_abi_struct_bytes checks the sizes: tests/test_house_abi_host.py)
 STRUCTS = {"pcg_conv_geom": ConvGeom, "pcg_in_xform": InXform, "pcg_wgrad_item": WgradItem, "pcg_sn_fwd_batch": SnFwdBatch,
@@ -567,6 +570,9 @@ PROTOTYPES = {
     "pcg_prob_head_workspace_bytes": (_sz, [_i32, _i32]),
     "pcg_prob_head_fwd": (_i, [_c.POINTER(ProbHeadFwdArgs), _vp]),
     "pcg_log_eps_loss_fwd_bwd": (_i, [_c.POINTER(LogEpsLossArgs), _vp]),
+    "pcg_class_pick": (_i, [_vp, _vp, _vp, _i32, _i32, _i32, _i64, _i32, _vp]),
+    "pcg_class_pick_gather": (_i, [_vp, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _i32, _vp]),
+    "pcg_cf_panels": (_i, [_i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
     "pcg_spectral_norm_fwd": (_i, [_vp, _i32, _i32, _vp, _vp, _f, _i, _vp, _vp, _vp, _vp, _vp]),
     "pcg_spectral_norm_bwd": (_i, [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _i, _vp]),
 }

@@ -12,6 +12,9 @@
     trainer.py           train_classifier  :8-39            train_classifier (fused=True: ClassifierFit, one graph replay per step)
     trainer.py           build_mask        :45-72           build_mask (same draws from torch's RNG)
     trainer.py           train_countergan  :76-123          make_optimizers + train_step (+ train_countergan loop)
+    eval_utils.py        visualize_counterfactual_grid :113-201   pick_sources, counterfactual_grid (the data, not the figure)
+    gr.py                make_and_save_heatmaps :346-441, save_user_modification_example :498-568
+                                                            heatmap_batch, user_modification_example (likewise)
 
 The torch layer objects are kept as parameter containers (identical `state_dict()` keys: `embed.weight`,
 `conv_in.*`, `resblocks.{0..5}.{conv1,bn1,conv2,bn2}.*`, `conv_mid.*`, `conv_out.*`; `cond_embed.weight`, `main.{0,2,4,6}.weight`,
@@ -25,7 +28,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import ops
-from ._cfeval import confusion_csv
+from ._cfeval import confusion_csv, write_png_gray
 from ._lib import ACT_LRELU, ACT_NONE, ACT_RELU, PcgError
 from .nn import weighted_sum, FlatModule, FrozenClassifier, in_conv_precision
 from .optim import Adam
@@ -1767,10 +1770,184 @@ def evaluate_classifier(classifier, dataloader, device, save_dir=None, prefix="c
     return acc, cm
 
 
-def evaluate_pipeline(generator, classifier, full_dataset, test_loader, config, verbose=True):
+# ---- the report figures' numbers and pixels (eval_utils.py:113-201, gr.py:346-441, :498-568; csrc/cf_report.hip) ------
+def _dataset_chunks(dataset, chunk, device):
+    """(N, H, W, resident, chunks, fetch) of a data set given as a pair of tensors (X [N,1,H,W] / [N,H,W], Y [N]), on the host or the
+    device, or as anything with __len__ / __getitem__ that yields (x, y).  chunks(stop, with_x) yields (row0, rows [n, H*W] fp32 on
+    the GPU or None, labels [n] int64 on the GPU) over the rows below `stop`; fetch(rows) returns those rows [len(rows), H*W] on the
+    GPU; resident: X as [N, H*W] rows where the whole data set already lies on the GPU, else None."""
+    chunk = int(chunk)
+    if chunk < 1:
+        raise PcgError(f"chunk {chunk}: a chunk holds at least one row")
+    if isinstance(dataset, (tuple, list)) and len(dataset) == 2 and all(torch.is_tensor(t) for t in dataset):
+        X, Y = dataset
+        N = X.shape[0]
+        if N < 1 or X.dim() < 3 or Y.numel() != N or Y.dtype.is_floating_point:
+            raise PcgError(f"dataset: expected (X [N,1,H,W], Y [N] integers) with N >= 1, got {tuple(X.shape)} and {tuple(Y.shape)} {Y.dtype}")
+        H, W = X.shape[-2], X.shape[-1]
+        if X.numel() != N * H * W:
+            raise PcgError(f"dataset: one-channel images expected, got {tuple(X.shape)}")
+        Xr, Yr = _as_rows(X, N), Y.reshape(-1).to(torch.int64)
+
+        def chunks(stop, with_x=True):
+            for r0 in range(0, stop, chunk):
+                r1 = min(stop, r0 + chunk)
+                yield r0, (Xr[r0:r1].to(device).contiguous() if with_x else None), Yr[r0:r1].to(device).contiguous()
+
+        def fetch(rows):
+            return Xr[torch.as_tensor(rows, dtype=torch.int64)].to(device).contiguous()      # (host rows: a host gather)
+        return N, H, W, (Xr if Xr.is_cuda else None), chunks, fetch
+    if not (hasattr(dataset, "__len__") and hasattr(dataset, "__getitem__")):
+        raise PcgError(f"dataset: expected a pair of tensors (X, Y) or a map-style data set, got {type(dataset).__name__}")
+    N = len(dataset)
+    if N < 1:
+        raise PcgError("dataset: no rows")
+    x0 = torch.as_tensor(dataset[0][0])
+    H, W = x0.shape[-2], x0.shape[-1]
+
+    def fetch(rows):
+        return torch.stack([torch.as_tensor(dataset[int(i)][0], dtype=torch.float32).reshape(H * W) for i in rows]).to(device).contiguous()
+
+    def chunks(stop, with_x=True):
+        for r0 in range(0, stop, chunk):
+            items = [dataset[i] for i in range(r0, min(stop, r0 + chunk))]
+            xs = torch.stack([torch.as_tensor(x, dtype=torch.float32).reshape(H * W) for x, _ in items]) if with_x else None
+            ys = torch.as_tensor([int(y) for _, y in items], dtype=torch.int64)
+            yield r0, (xs.to(device).contiguous() if with_x else None), ys.to(device)
+    return N, H, W, None, chunks, fetch
+
+
+def _pick_words(state, K, what):
+    """One host read of a pick's K keys -> the picked row per class; a class without a row raises."""
+    words = state.cpu().numpy().view("uint64")
+    absent = [k for k in range(K) if words[k] == 0]
+    if absent:
+        raise PcgError(f"{what}: the data set has no row of class(es) {absent}")
+    return [int(0xFFFFFFFF - (int(w) & 0xFFFFFFFF)) for w in words]
+
+
+def pick_sources(classifier, dataset, pick_best_source=False, chunk=2048, full_scan=False):
+    """The source pick of visualize_counterfactual_grid (eval_utils.py:135-149): one row per class, the first one of the data set or,
+    with pick_best_source, the one whose own label the classifier is most confident about (ties: the lowest row, the strict `>` of
+    :143).  The data set is walked in chunks of `chunk` rows, each folded into ONE device state (ops.class_pick): "best" runs the
+    classifier's padded logits per chunk, "first" does no classifier work at all.
+    The reference's `break` (:148-149) stands after the if / else, so its "best" scan too ends at the row that completes the set of
+    classes: the most confident row is chosen among the rows up to there.  That is the default here: a "first" pass over the labels
+    finds where the scan ends (one host read of K keys), the "best" pass covers those rows only (a second read at the end).
+    full_scan=True scans the whole data set instead — what the reference's docstring promises — with one host read at the end.
+    dataset: see _dataset_chunks.  Returns (sources [K,1,H,W], rows [K] int64, conf [K] fp32 — 0 in "first" mode), all on the GPU.
+    A class without a row raises (the reference fails on None.to)."""
+    K = classifier.num_classes
+    device = next(classifier.parameters()).device
+    if device.type != "cuda":
+        raise PcgError(f"pick_sources: the classifier is on {device}; libpcgan_hip has no CPU path")
+    mode = "best" if pick_best_source else "first"
+    classifier.eval()                                                                                               # :125
+    N, H, W, resident, chunks, fetch = _dataset_chunks(dataset, chunk, device)
+    if N > ops.PICK_MAX_ROW:
+        raise PcgError(f"pick_sources: {N} rows do not fit the 32-bit row of a key")
+    with torch.no_grad():
+        stop = N
+        if pick_best_source and not full_scan:
+            first = ops.class_pick_state(K, device)
+            for r0, _, y in chunks(N, with_x=False):
+                ops.class_pick(first, y, K, row0=r0, mode="first")
+            stop = max(_pick_words(first, K, "pick_sources")) + 1                                                   # :148-149
+        state = ops.class_pick_state(K, device)
+        for r0, xr, y in chunks(stop, with_x=pick_best_source):
+            ops.class_pick(state, y, K, row0=r0, logits=_padded_logits(classifier, xr) if pick_best_source else None, mode=mode)
+        rows, conf, sources = ops.class_pick_gather(state, K, mode, X=resident)
+    picked = _pick_words(state, K, "pick_sources")
+    if sources is None:
+        sources = fetch(picked)
+    return sources.view(K, 1, H, W), rows, conf
+
+
+def _grid_report(sources, rows, conf, sweep):
+    """The grid of a sweep over the K sources: the [source][target] views of the sweep's [target][row] results, the reference's own
+    annotation on the diagonal (eval_utils.py:176-178: pred = the class, conf = 1.0) and the two images (ops.cf_panels, grid mode)."""
+    import numpy as np
+    K, _, H, W = sources.shape
+    x_cf = sweep["x_cf"]
+    T = x_cf.shape[0]
+    image, image_u8 = ops.cf_panels(sources.view(K, H * W), x_cf.view(T, K, H * W), H, W, mode="grid")
+    pred = sweep["pred"].cpu().numpy().T.copy()                                                                     # [source][target]
+    cf = sweep["conf"].cpu().numpy().T.copy()
+    hit = pred == np.arange(T)[None, :]                                                                              # :193
+    d = np.arange(min(K, T))
+    pred[d, d], cf[d, d], hit[d, d] = d, 1.0, True                                                                   # :176-178
+    return {"sources": sources, "source_rows": rows, "source_conf": conf, "x_cf": x_cf.transpose(0, 1), "pred": pred, "conf": cf, "hit": hit,
+            "image": image, "image_u8": image_u8}
+
+
+def counterfactual_grid(generator, classifier, dataset, pick_best_source=False, patches=None, mask=None, chunk=2048, full_scan=False):
+    """visualize_counterfactual_grid (eval_utils.py:113-201) without the figure: pick_sources, ONE counterfactual_sweep over the K
+    sources (K x K queries; the default prompt is the all-ones mask of :183) and the grid image.  Returns sources [K,1,H,W],
+    source_rows, source_conf [K]; x_cf [K,K,1,H,W] (a view, [source][target]); pred, conf, hit [K,K] (host arrays, [source][target],
+    the diagonal as the reference annotates it: pred = r, conf = 1.0, hit); image [K*H, K*W] fp32 in [0, 1] with the sources on the
+    diagonal, and image_u8."""
+    generator.eval()                                                                                                # :124
+    sources, rows, conf = pick_sources(classifier, dataset, pick_best_source, chunk, full_scan)
+    with torch.no_grad():
+        sweep = counterfactual_sweep(generator, classifier, sources, patches=patches, mask=mask)
+    return _grid_report(sources, rows, conf, sweep)
+
+
+def grid_csv(grid):
+    """The text of cf_grid.csv: one line per cell, columns source, target, pred, conf, hit."""
+    K, T = grid["pred"].shape
+    lines = ["source,target,pred,conf,hit"]
+    lines += [f"{r},{c},{int(grid['pred'][r, c])},{float(grid['conf'][r, c])!r},{int(grid['hit'][r, c])}" for r in range(K) for c in range(T)]
+    return "\n".join(lines) + "\n"
+
+
+def heatmap_batch(x, x_cf, mask, classifier=None, max_samples=16):
+    """The data half of make_and_save_heatmaps (gr.py:346-441): for the first max_samples rows the four panels original,
+    counterfactual, |difference| and mask, [n,4,H,W] in [0, 1] (:370-372), and vmax [1], the batch maximum of the difference (:399),
+    both on the GPU.  x, x_cf [B,1,H,W] in [-1, 1]; mask [1,1,H,W] (shared) or [B,1,H,W].  With a classifier also pred (int64) and
+    conf [n] of the counterfactuals."""
+    if not (torch.is_tensor(x) and x.is_cuda and x.dim() == 4):
+        raise PcgError(f"x: expected a [B,1,H,W] tensor on the GPU, got {getattr(x, 'device', type(x))}")
+    B, _, H, W = x.shape
+    n = min(int(max_samples), B)
+    if n < 1 or tuple(x_cf.shape) != tuple(x.shape):
+        raise PcgError(f"heatmap_batch: max_samples {max_samples}, x {tuple(x.shape)}, x_cf {tuple(x_cf.shape)}")
+    HW = H * W
+    xr, cr = _as_rows(x, B)[:n], _as_rows(x_cf, B)[:n]
+    m = mask.reshape(-1, HW) if torch.is_tensor(mask) else None
+    if m is None or m.shape[0] not in (1, B):
+        raise PcgError(f"mask: expected [1,1,{H},{W}] or [{B},1,{H},{W}] on the GPU, got {getattr(mask, 'shape', type(mask))}")
+    m = (m if m.shape[0] == 1 else m[:n]).contiguous()
+    panels, vmax = ops.cf_panels(xr, cr, H, W, mask=m, mode="panels")
+    out = {"panels": panels, "vmax": vmax}
+    if classifier is not None:
+        with torch.no_grad():
+            res = ops.mnist_cf_score(_padded_logits(classifier, cr), classifier.num_classes, n, 1, target=None, outputs=("pred", "conf"),
+                                     group_sums=False)
+        out.update(pred=res["pred"], conf=res["conf"])
+    return out
+
+
+def user_modification_example(x, patches, generator, classifier, target, patch_size=Config.patch_size):
+    """save_user_modification_example (gr.py:498-568) without the figure: the first row of x, "turn it into `target`, touching only
+    `patches`" (counterfactuals(..., patches=patches), :498-530), then its four panels.  Returns panels [1,4,H,W], vmax [1], pred,
+    conf [1], mask [1,1,H,W] and x_cf [1,1,H,W], on the GPU."""
+    if not (torch.is_tensor(x) and x.is_cuda and x.dim() == 4):
+        raise PcgError(f"x: expected a [B,1,H,W] tensor on the GPU, got {getattr(x, 'device', type(x))}")
+    x1 = x[0:1].contiguous()
+    with torch.no_grad():
+        res = counterfactuals(generator, classifier, x1, int(target), patches=list(patches), patch_size=patch_size)
+    out = heatmap_batch(x1, res["x_cf"], res["mask"], max_samples=1)
+    out.update(pred=res["pred"], conf=res["conf"], mask=res["mask"], x_cf=res["x_cf"])
+    return out
+
+
+def evaluate_pipeline(generator, classifier, full_dataset, test_loader, config, verbose=True, grid=False):
     """eval_utils.py:572-647, the live lines (:577-610, :643): a patch prompt per sample of the first test batch, targets that differ
     from the labels, the counterfactuals, evaluate_counterfactuals on that batch (countergan_metrics.csv) and the per-target table.
-    The plots (cf_grid.png, the heat maps) are left out; `full_dataset` is what they would read.  Returns (metrics, per-target table)."""
+    grid=True: also the counterfactual grid of :626-629 over `full_dataset` (counterfactual_grid, pick_best_source=False as there):
+    cf_grid.npy (the float image), cf_grid.png (8-bit grayscale) and cf_grid.csv (source, target, pred, conf, hit) under
+    config.save_dir; rendering the annotated figure stays out.  Returns (metrics, per-target table)."""
     device = torch.device(config.device)
     x, y = next(iter(test_loader))                                                                                  # :577
     x, y = x.to(device), y.to(device)
@@ -1789,4 +1966,13 @@ def evaluate_pipeline(generator, classifier, full_dataset, test_loader, config, 
         f.write(per_class_csv({0: metrics_without_mask}))                                                           # :643
     if verbose:
         print(f"Countergan metrics: {metrics_without_mask}\nSaved to: {path}")
+    if grid:                                                                                                        # :626-629
+        import numpy as np
+        g = counterfactual_grid(generator, classifier, full_dataset)
+        np.save(os.path.join(config.save_dir, "cf_grid.npy"), g["image"].cpu().numpy())
+        write_png_gray(os.path.join(config.save_dir, "cf_grid.png"), g["image_u8"].cpu().numpy())
+        with open(os.path.join(config.save_dir, "cf_grid.csv"), "w") as f:
+            f.write(grid_csv(g))
+        if verbose:
+            print(f"Saved CF grid: {os.path.join(config.save_dir, 'cf_grid.png')}")
     return metrics_without_mask, table

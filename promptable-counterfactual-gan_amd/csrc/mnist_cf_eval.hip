@@ -11,6 +11,7 @@
 // inputs and outputs relative to q0.  x and the mask are never replicated.  fp32, wave64, no atomics; every sum has one fixed order.
 #include <cstdint>
 #include "pcg_common.h"
+#include "softmax_label.h"
 
 namespace pcg {
 namespace {
@@ -145,18 +146,7 @@ __global__ void __launch_bounds__(NT) mnist_cf_score_kernel(const pcg_mnist_cf_s
       }
       const float conf = 1.f / den;                          // exp(mx - mx) / den
       float p_o = 0.f;
-      if (a.logits_orig && yt >= 0) {
-        const float* lo_ = a.logits_orig + (size_t)b * a.ld;
-        float mo = lo_[0];
-        for (int k = 1; k < a.K; ++k) mo = fmaxf(mo, lo_[k]);
-        float d = 0.f, e_y = 0.f;
-        for (int k = 0; k < a.K; ++k) {
-          const float e = expf(lo_[k] - mo);
-          d += e;
-          if (k == (int)yt) e_y = e;
-        }
-        p_o = e_y / d;
-      }
+      if (a.logits_orig && yt >= 0) p_o = softmax_prob_at(a.logits_orig + (size_t)b * a.ld, a.K, (int)yt);
       const float flip = arg == (int)tg ? 1.f : 0.f;
       if (a.pred) a.pred[r] = arg;
       if (a.conf) a.conf[r] = conf;

@@ -26,7 +26,7 @@ import torch.nn as nn
 from . import ops
 from ._lib import ACT_LRELU, ACT_NONE, ACT_RELU, PcgError
 from .countergan import (PER_CLASS_FIELDS, BCEWithLogitsLoss, Classifier, CrossEntropyLoss, _as_rows, _conv_fwd, _conv_wgrad, _dgrad_act, _geom,
-                         _labels, _padded_logits, abs_mean, metrics_from_sums)
+                         _grid_report, _labels, _padded_logits, abs_mean, metrics_from_sums, pick_sources)
 from .nn import FlatModule, in_conv_precision, linear_dgrad, linear_fwd, linear_wgrad, weighted_sum
 from .optim import Adam
 
@@ -755,6 +755,14 @@ def counterfactual_sweep(G, C, imgs, y_true=None, query_chunk=2048, group_rows=N
     out = {"x_cf": res["x_cf"].view(shp), "delta": res["delta"].view(shp), "sums": res["sums"].view(T, B, 3), "group_sums": res["group_sums"]}
     out.update({k: res[k].view(T, B) for k in ops.SCORE_FIELDS})
     return out
+
+
+def counterfactual_grid(G, C, dataset, pick_best_source=False, chunk=2048, full_scan=False):
+    """The source-by-target grid of eval_utils.py:113-201 for the additive-delta generator (and countergan2.Generator, which inherits
+    it), each cell gan_train_copy.py:161-172: countergan.pick_sources, ONE counterfactual_sweep over the K sources, the grid image
+    (ops.cf_panels).  Returns what countergan.counterfactual_grid returns."""
+    sources, rows, conf = pick_sources(C, dataset, pick_best_source, chunk, full_scan)
+    return _grid_report(sources, rows, conf, counterfactual_sweep(G, C, sources))
 
 
 def evaluate_examples(G, C, imgs, targets=None, rng=None):

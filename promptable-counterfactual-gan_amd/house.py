@@ -1402,6 +1402,133 @@ def analyze_feature_shift_importance(X_orig, X_cf, feature_names, scaler=None):
     return rows
 
 
+SAMPLE_FIELDS = ("sample_idx_in_vis", "source_pred", "intended_target", "cf_pred", "success", "prediction_gain", "num_changed",
+                 "frac_changed", "sparsity", "L1_sum_norm", "L1_mean_norm", "L2_norm", "topk_features", "topk_vals_pct_of_range")
+AGGREGATE_FIELDS = ("n_samples_used", "class_flip_rate", "mean_prediction_gain", "median_prediction_gain", "mean_L1_sum_norm", "mean_L2_norm",
+                    "mean_num_changed", "mean_frac_changed", "mean_sparsity", "topk_features_global", "topk_features_global_mean_pct")
+
+
+def case_study_rows(N, n_samples=20, random_seed=42):
+    """The rows generate_case_study_report_from_vis draws (eval_utils.py:528-530): the same call, so the same rows."""
+    n = min(int(n_samples), int(N))
+    return np.random.default_rng(random_seed).choice(np.arange(int(N)), size=n, replace=False)
+
+
+def case_study_tables(probs_orig, probs_cf, originals, cfs, feature_names, scaler=None, n_samples=20, eps=1e-3, random_seed=42,
+                      top_k_features=5):
+    """eval_utils.py:525-660 on the host, NumPy only, the reference's own expressions on the arrays' own dtypes.  probs_orig, probs_cf
+    [n][NC]: the classifier's probabilities of the CHOSEN rows (case_study_rows) of originals / cfs [N][d].  Returns
+    (sample_rows, feature_rows, aggregate, per_sample_feature_tables) as lists of dicts (aggregate: one dict): the rows of
+    case_study_sample_summary.csv (SAMPLE_FIELDS), of case_study_feature_summary.csv sorted by mean_abs_delta_norm descending, the
+    aggregate (AGGREGATE_FIELDS), and per chosen row {"sample_idx", "source_pred", "intended_target", "rows"}.
+    Two departures from the reference, both on purpose: the feature summary's mean_abs_delta_denorm is each row's own feature's value
+    (the reference assigns the column after sort_values, in unsorted order, :636-638), and both sorts are stable."""
+    originals, cfs, names = np.asarray(originals), np.asarray(cfs), list(feature_names)
+    if originals.ndim != 2 or originals.shape != cfs.shape or originals.shape[0] < 1 or originals.shape[1] != len(names):
+        raise PcgError(f"case_study_tables: originals {originals.shape} and cfs {cfs.shape} must be [N][{len(names)}] with N >= 1")
+    N, d = originals.shape
+    idxs = case_study_rows(N, n_samples, random_seed)                                                              # :528-530
+    n = len(idxs)
+    probs_orig, probs_cf = np.asarray(probs_orig), np.asarray(probs_cf)
+    if probs_orig.ndim != 2 or probs_orig.shape != probs_cf.shape or probs_orig.shape[0] != n:
+        raise PcgError(f"case_study_tables: probs_orig {probs_orig.shape} and probs_cf {probs_cf.shape} must be [{n}][classes]: the chosen rows'")
+    preds_orig, preds_cf = np.argmax(probs_orig, axis=1), np.argmax(probs_cf, axis=1)                              # :544-545
+    intended = np.argmax(probs_cf - probs_orig, axis=1)                                                            # :548-549
+    abs_diff = np.abs(cfs[idxs] - originals[idxs])                                                                 # :551
+    num_changed = (abs_diff > eps).sum(axis=1)
+    frac_changed = num_changed / float(d)
+    sparsity = 1.0 - frac_changed
+    L1_sum, L1_mean, L2 = np.sum(abs_diff, axis=1), np.mean(abs_diff, axis=1), np.linalg.norm(abs_diff, axis=1)    # :555-557
+    gain = probs_cf[np.arange(n), intended] - probs_orig[np.arange(n), intended]                                   # :559
+    success = (preds_cf == intended).astype(int)
+    orig_dn = cf_dn = abs_dn = frange = None
+    if scaler is not None:                                                                                         # :564-572
+        try:
+            orig_dn, cf_dn = scaler.inverse_transform(originals[idxs]), scaler.inverse_transform(cfs[idxs])
+            abs_dn = np.abs(cf_dn - orig_dn)
+            if hasattr(scaler, "data_max_") and hasattr(scaler, "data_min_"):
+                frange = (np.asarray(scaler.data_max_) - np.asarray(scaler.data_min_)).astype(float)
+        except Exception:
+            orig_dn = cf_dn = abs_dn = frange = None
+    sample_rows, per_sample = [], []
+    for i, g in enumerate(idxs):                                                                                   # :575-620
+        topk = np.argsort(-abs_diff[i], kind="stable")[:top_k_features]                                            # :597
+        sample_rows.append({
+            "sample_idx_in_vis": int(g), "source_pred": int(preds_orig[i]), "intended_target": int(intended[i]), "cf_pred": int(preds_cf[i]),
+            "success": int(success[i]), "prediction_gain": float(gain[i]), "num_changed": int(num_changed[i]),
+            "frac_changed": float(frac_changed[i]), "sparsity": float(sparsity[i]), "L1_sum_norm": float(L1_sum[i]),
+            "L1_mean_norm": float(L1_mean[i]), "L2_norm": float(L2[i]), "topk_features": ";".join(names[j] for j in topk),
+            "topk_vals_pct_of_range": ";".join(map(str, (abs_diff[i, topk] * 100.0).round(6).tolist()))})           # :599-601
+        cols = {"orig_norm": originals[g], "cf_norm": cfs[g], "abs_delta_norm": abs_diff[i], "pct_of_range": abs_diff[i] * 100.0}   # :604-610
+        if orig_dn is not None:
+            cols.update(orig_denorm=orig_dn[i], cf_denorm=cf_dn[i], abs_delta_denorm=abs_dn[i])
+            if frange is not None:
+                cols["pct_of_range_denorm"] = (abs_dn[i] / (frange + 1e-12)) * 100.0                               # :616
+        rows = [dict({"feature": names[j]}, **{k: float(v[j]) for k, v in cols.items()}) for j in range(d)]
+        per_sample.append({"sample_idx": int(g), "source_pred": int(preds_orig[i]), "intended_target": int(intended[i]), "rows": rows})
+    mean_abs = abs_diff.mean(axis=0)                                                                               # :625-627
+    change_freq = (abs_diff > eps).mean(axis=0)
+    mean_abs_dn = abs_dn.mean(axis=0) if abs_dn is not None else None
+    feature_rows = []
+    for j in np.argsort(-mean_abs, kind="stable"):                                                                 # :634
+        row = {"feature": names[j], "mean_abs_delta_norm": float(mean_abs[j]), "mean_pct_of_range": float(mean_abs[j] * 100.0),
+               "change_freq": float(change_freq[j])}
+        if mean_abs_dn is not None:
+            row["mean_abs_delta_denorm"] = float(mean_abs_dn[j])
+        feature_rows.append(row)
+    col = lambda k: np.asarray([r[k] for r in sample_rows], dtype=np.float64)     # noqa: E731
+    aggregate = {"n_samples_used": int(n), "class_flip_rate": float(col("success").mean()),                        # :644-654
+                 "mean_prediction_gain": float(col("prediction_gain").mean()), "median_prediction_gain": float(np.median(col("prediction_gain"))),
+                 "mean_L1_sum_norm": float(col("L1_sum_norm").mean()), "mean_L2_norm": float(col("L2_norm").mean()),
+                 "mean_num_changed": float(col("num_changed").mean()), "mean_frac_changed": float(col("frac_changed").mean()),
+                 "mean_sparsity": float(col("sparsity").mean())}
+    top = np.argsort(-mean_abs, kind="stable")[:top_k_features]                                                    # :657-659
+    aggregate["topk_features_global"] = ",".join(names[j] for j in top)
+    aggregate["topk_features_global_mean_pct"] = ",".join(f"{(mean_abs[j] * 100.0):.3f}" for j in top)
+    return sample_rows, feature_rows, aggregate, per_sample
+
+
+def _csv_quote(v):
+    return '"' + v.replace('"', '""') + '"' if isinstance(v, str) and any(c in v for c in ',"\n') else v
+
+
+def case_studies(classifier, originals, cfs, config, scaler=None, n_samples=20, eps=1e-3, random_seed=42, top_k_features=5, save_dir=None):
+    """generate_case_study_report_from_vis (eval_utils.py:496-664): the chosen rows' probabilities from ONE fused classifier launch
+    (originals and counterfactuals stacked, the softmax of the 2n x NC logits on the host in fp32), then case_study_tables.  With
+    save_dir the reference's tree: case_study_sample_summary.csv, case_study_feature_summary.csv, case_study_aggregate_summary.csv and
+    samples/src{S}_tgt{T}/sample_{i}_features.csv.  Returns what case_study_tables returns."""
+    import os
+    originals, cfs = np.asarray(originals), np.asarray(cfs)
+    if originals.ndim != 2 or originals.shape != cfs.shape or originals.shape[0] < 1:
+        raise PcgError(f"case_studies: originals {originals.shape} and cfs {cfs.shape} must be the same [N][d] with N >= 1")
+    names = config.get("feature_names", [f"feat_{i}" for i in range(originals.shape[1])])
+    idxs = case_study_rows(originals.shape[0], n_samples, random_seed)
+    n = len(idxs)
+    classifier.eval()
+    dev = next(classifier.parameters()).device
+    with torch.no_grad():
+        both = np.concatenate([originals[idxs], cfs[idxs]], axis=0)
+        logits = classifier(torch.as_tensor(both, dtype=torch.float32).to(dev).contiguous()).cpu().numpy().astype(np.float32)
+    e = np.exp(logits - logits.max(axis=1, keepdims=True))                                                         # :542-543
+    probs = e / e.sum(axis=1, keepdims=True)
+    tables = case_study_tables(probs[:n], probs[n:], originals, cfs, names, scaler=scaler, n_samples=n_samples, eps=eps,
+                               random_seed=random_seed, top_k_features=top_k_features)
+    if save_dir:
+        sample_rows, feature_rows, aggregate, per_sample = tables
+        quoted = lambda rows: [{k: _csv_quote(v) for k, v in r.items()} for r in rows]     # noqa: E731
+        save_table(quoted(sample_rows), os.path.join(save_dir, "case_study_sample_summary.csv"), SAMPLE_FIELDS)
+        save_table(quoted(feature_rows), os.path.join(save_dir, "case_study_feature_summary.csv"), tuple(feature_rows[0].keys()))
+        save_table(quoted([aggregate]), os.path.join(save_dir, "case_study_aggregate_summary.csv"), AGGREGATE_FIELDS)
+        for s in per_sample:
+            path = os.path.join(save_dir, "samples", f"src{s['source_pred']}_tgt{s['intended_target']}", f"sample_{s['sample_idx']}_features.csv")
+            save_table(quoted(s["rows"]), path, tuple(s["rows"][0].keys()))
+        print(f"[case_study] Saved {n} per-sample CSVs (grouped by src->tgt), sample_summary, feature_summary and aggregate to {save_dir}")
+    return tables
+
+
+_case_studies = case_studies      # evaluate_pipeline's keyword has the function's name
+
+
 def weighted_scores(cm):
     """Pure host.  accuracy and sklearn's precision / recall / f1 with average='weighted', zero_division=0, from a confusion matrix
     (rows true, columns predicted): per class tp / column sum, tp / row sum and their harmonic mean (0 where a denominator is 0),
@@ -1441,11 +1568,12 @@ def evaluate_classifier(classifier, X_test, y_test, class_names=None):
     return dict(sc, confusion_matrix=cm, report="\n".join(lines) + "\n")
 
 
-def evaluate_pipeline(generator, classifier, X_test, y_test, config):
+def evaluate_pipeline(generator, classifier, X_test, y_test, config, case_studies=False):
     """eval_utils.py:673-728 — compute_metrics_per_target on the one-launch path -> <out_dir>/countergan_metrics.csv (the
     reference's layout); the feature-shift table -> feature_shift_importance.csv and the class-pair sensitivity array ->
-    class_pair_sensitivity/deltas.npy, where the reference saves their pictures.  Plots, the case-study HTML and t-SNE stay out
-    (DESIGN.md §7).  Returns the metric rows."""
+    class_pair_sensitivity/deltas.npy, where the reference saves their pictures.  case_studies=True: also the case-study tables of
+    :711-719 under <out_dir>/case_studies (case_studies(), config["case_study_n"] rows, 20 by default).  Figure rendering and t-SNE
+    stay out.  Returns the metric rows."""
     import os
     out = config.get("out_dir", ".")
     os.makedirs(out, exist_ok=True)
@@ -1459,6 +1587,9 @@ def evaluate_pipeline(generator, classifier, X_test, y_test, config):
     deltas = analyze_class_pair_sensitivity(generator, classifier, X_test, y_test, config)                               # :700-708
     os.makedirs(os.path.join(out, "class_pair_sensitivity"), exist_ok=True)
     np.save(os.path.join(out, "class_pair_sensitivity", "deltas.npy"), deltas)
+    if case_studies:                                                                                                     # :711-719
+        _case_studies(classifier, originals, cfs, config, scaler=config.get("scaler", None), n_samples=config.get("case_study_n", 20),
+                      save_dir=os.path.join(out, "case_studies"))
     return rows
 
 

@@ -2430,3 +2430,107 @@ def mnist_cf_score(logits_cf, K, B, T=1, target=None, y_true=None, logits_orig=N
                               *(ptr(res.get(n)) for n in SCORE_FIELDS), ptr(res.get("group_sums")), B, T, K, ld, group_rows, q0, nq)
     check(_lib.load().pcg_mnist_cf_score(ctypes.byref(a), _stream()), "pcg_mnist_cf_score")
     return res
+
+
+# ---- MNIST CounteRGAN: the report figures' numbers and pixels (csrc/cf_report.hip) --------------------------------
+PICK_MODES = {"first": _lib.CLASS_PICK_FIRST, "best": _lib.CLASS_PICK_BEST}
+PICK_MAX_ROW = (1 << 32) - 1          # rows must stay below this: a key holds 0xFFFFFFFF - row
+
+
+def _pick_mode(mode, K):
+    if mode not in PICK_MODES:
+        raise _lib.PcgError(f"mode {mode!r} is not one of {sorted(PICK_MODES)}")
+    if not 1 <= int(K) <= _lib.CLASS_PICK_KMAX:
+        raise _lib.PcgError(f"K {K} is outside [1, {_lib.CLASS_PICK_KMAX}]")
+    return PICK_MODES[mode]
+
+
+def class_pick_state(K, device):
+    """The zeroed uint64 [K] state of a pick, held as int64 (the same bits)."""
+    _pick_mode("first", K)
+    return torch.zeros(int(K), dtype=torch.int64, device=device)
+
+
+def class_pick(state, labels, K, row0=0, logits=None, mode="first"):
+    """Folds one chunk — labels [n] int64 and, in "best" mode, logits [n, kp] — whose first row is the data set's row `row0` into
+    state (class_pick_state): per class the maximum of (confidence bits << 32) | (0xFFFFFFFF - row).  Returns state."""
+    code = _pick_mode(mode, K)
+    _chk(state, "state", torch.int64)
+    if state.numel() != K:
+        raise _lib.PcgError(f"state: expected {K} words, got shape {tuple(state.shape)}")
+    _chk_idx(labels, K, "labels")
+    n, kp = labels.numel(), 0
+    if n < 1 or labels.dim() != 1:
+        raise _lib.PcgError(f"labels: expected [n] with n >= 1, got shape {tuple(labels.shape)}")
+    row0 = int(row0)
+    if row0 < 0 or row0 + n > PICK_MAX_ROW:
+        raise _lib.PcgError(f"rows [{row0}, {row0} + {n}) do not stay below 2^32 - 1")
+    if mode == "best":
+        if logits is None:
+            raise _lib.PcgError("mode 'best' reads the classifier's logits")
+        _chk(logits, "logits")
+        kp = logits.shape[-1]
+        if logits.dim() != 2 or logits.shape[0] != n or kp < K or kp % 4:
+            raise _lib.PcgError(f"logits: expected [{n}, kp] with kp >= {K} a multiple of 4, got {tuple(logits.shape)}")
+    check(_lib.load().pcg_class_pick(_p(logits) if mode == "best" else None, _p(labels), _p(state), n, kp, int(K), row0, code, _stream()),
+          "pcg_class_pick")
+    return state
+
+
+def class_pick_gather(state, K, mode="first", X=None):
+    """state -> (rows [K] int64, -1 for a class without a row; conf [K], 0 in "first" mode; sources [K, HW] = X[rows] for a data set
+    X [N, HW] resident on the GPU, else None)."""
+    code = _pick_mode(mode, K)
+    _chk(state, "state", torch.int64)
+    if state.numel() != K:
+        raise _lib.PcgError(f"state: expected {K} words, got shape {tuple(state.shape)}")
+    dev = state.device
+    rows, conf = torch.empty(K, dtype=torch.int64, device=dev), torch.empty(K, dtype=torch.float32, device=dev)
+    sources, N, HW = None, 0, 0
+    if X is not None:
+        _chk(X, "X")
+        if X.dim() != 2 or X.shape[0] < 1 or X.shape[1] < 1:
+            raise _lib.PcgError(f"X: expected [N, HW], got {tuple(X.shape)}")
+        N, HW = X.shape
+        sources = torch.empty((K, HW), dtype=torch.float32, device=dev)
+    check(_lib.load().pcg_class_pick_gather(_p(state), _p(X), _p(rows), _p(conf), _p(sources), int(K), int(N), int(HW), code, _stream()),
+          "pcg_class_pick_gather")
+    return rows, conf, sources
+
+
+def cf_panels(x, x_cf, H, W, mask=None, mode="panels"):
+    """mode "grid": x = sources [K, HW], x_cf [T, K, HW] -> (image [K*H, T*W] float in [0, 1], the same image as uint8).
+    mode "panels": x, x_cf [n, HW], mask [HW] (shared) or [n, HW] -> (panels [n, 4, H, W] = (x + 1) / 2, (x_cf + 1) / 2, their
+    |difference|, mask; vmax [1], the maximum of the third panel)."""
+    _chk(x, "x"); _chk(x_cf, "x_cf")
+    H, W = int(H), int(W)
+    HW = H * W
+    if H < 1 or W < 1 or x.dim() != 2 or x.shape[1] != HW:
+        raise _lib.PcgError(f"x: expected [n, {H} * {W}], got {tuple(x.shape)}")
+    n, dev = x.shape[0], x.device
+    lib = _lib.load()
+    if mode == "grid":
+        if x_cf.dim() != 3 or x_cf.shape[1] != n or x_cf.shape[2] != HW:
+            raise _lib.PcgError(f"x_cf: expected [T, {n}, {HW}] ([target][row]), got {tuple(x_cf.shape)}")
+        T = x_cf.shape[0]
+        image = torch.empty((n * H, T * W), dtype=torch.float32, device=dev)
+        image_u8 = torch.empty((n * H, T * W), dtype=torch.uint8, device=dev)
+        check(lib.pcg_cf_panels(_lib.CF_PANELS_GRID, _p(x), _p(x_cf), None, 0, _p(image), _p(image_u8), None, n, T, H, W, _stream()),
+              "pcg_cf_panels")
+        return image, image_u8
+    if mode != "panels":
+        raise _lib.PcgError(f"mode {mode!r} is not 'grid' or 'panels'")
+    if tuple(x_cf.shape) != (n, HW):
+        raise _lib.PcgError(f"x_cf: expected [{n}, {HW}], got {tuple(x_cf.shape)}")
+    if mask is None:
+        raise _lib.PcgError("mode 'panels' takes a mask")
+    _chk(mask, "mask")
+    if mask.numel() not in (HW, n * HW):
+        raise _lib.PcgError(f"mask: expected {HW} (shared) or {n * HW} (per row) values, got shape {tuple(mask.shape)}")
+    mm = _lib.MASK_SHARED if mask.numel() == HW else _lib.MASK_PER_ROW
+    panels = torch.empty((n, 4, H, W), dtype=torch.float32, device=dev)
+    vmax = torch.empty(1, dtype=torch.float32, device=dev)
+    fill(vmax, 0.0)
+    check(lib.pcg_cf_panels(_lib.CF_PANELS_PANELS, _p(x), _p(x_cf), _p(mask), mm, _p(panels), None, _p(vmax), n, 1, H, W, _stream()),
+          "pcg_cf_panels")
+    return panels, vmax
