@@ -1092,6 +1092,9 @@ int pcg_dp_shutdown(void);
  *   "pad_clip"          k4 s2 p1 forward / grad-input launches: 0 today's kernels, 1 position-major tiles that skip their all-padding
  *                       taps where the schedule model predicts >= 5 % (pcg_conv_pad_clip_query); 2 / 3 / 4 (measurements) every
  *                       eligible launch, tiles long first / short first / in pairs.  PCG_PAD_CLIP=v for a whole process.
+ *   "pad_clip_dgrad"    what "pad_clip" 1 does with grad-input launches: 1 (default) those the schedule model predicts no loss for,
+ *                       its measured unit cost included, from one round of 512 workgroups up; 0 none (forward-kernel launches
+ *                       only); 2 (measurements) every eligible one; other values are refused.  PCG_PAD_CLIP_DGRAD=v for a whole process.
  * value -1 restores the built-in choice.  Results stay correct under every setting (the order of a sum changes, not its terms). */
 int pcg_tune_set(const char* name, int32_t value);
 
@@ -1157,7 +1160,8 @@ int pcg_conv_pixtab_register(const pcg_conv_geom* g, void* host_out, size_t byte
  * pcg_conv_cliptab_bytes: its size, 0 for a geometry that has none.  pcg_conv_cliptab_register: the contract of
  * pcg_conv_pixtab_register (host_out: build on the host; device_table: remember the caller's device copy; both NULL: forget).
  * An eligible launch — fp32 MFMA path, batch and each BatchNorm group's share of it whole tiles, no K-slices, no stream-K — of a
- * registered geometry takes the clipped kernels where the schedule model predicts at least 5 % (pcg_tune_set("pad_clip", 0): never).
+ * registered geometry takes the clipped kernels where the schedule model predicts at least 5 % (forward kernel) or no loss (grad-input
+ * kernel, launches of at least 512 workgroups; pcg_tune_set("pad_clip_dgrad", 0): none) — pcg_tune_set("pad_clip", 0): never.
  * Convolution outputs are bit-identical; fused BatchNorm sums regroup their fp64 partial rows.
  * pcg_conv_sched_model: the model — time in us at which the last of n workgroups ends that are dispatched in order onto 256 CUs x 2
  * slots and run ktiles[i] k-tiles each, at 3.5 us per k-tile beside a busy neighbour slot and 2.2 us alone.

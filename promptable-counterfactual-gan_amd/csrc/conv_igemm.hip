@@ -675,7 +675,7 @@ int check_geom(const pcg_conv_geom* g) {
 }
 
 // Tuning switches for A/B measurements in ONE process (pcg_tune_set; scripts/conv_microbench.py --ab): -1 = the built-in choice.
-struct Tune { int edge_prio = -1, dgrad_swz3 = -1, wgrad_rounds = -1, korder = -1, wgrad_order = -1, dgrad_interleave = -1, fwd_splits = -1, stream_k = -1, sk_blocks = -1, dgrad_gemm = -1, t64 = -1, wgrad_pixtab = -1, pad_clip = -1; unsigned long long* stamps = nullptr; int stamp_slots = 0; };
+struct Tune { int edge_prio = -1, dgrad_swz3 = -1, wgrad_rounds = -1, korder = -1, wgrad_order = -1, dgrad_interleave = -1, fwd_splits = -1, stream_k = -1, sk_blocks = -1, dgrad_gemm = -1, t64 = -1, wgrad_pixtab = -1, pad_clip = -1, pad_clip_dgrad = -1; unsigned long long* stamps = nullptr; int stamp_slots = 0; };
 Tune g_tune;
 
 ConvP make_params(const pcg_conv_geom* g) {
@@ -781,6 +781,14 @@ int clip_mode() {
   static const int env = getenv("PCG_PAD_CLIP") ? atoi(getenv("PCG_PAD_CLIP")) : PCG_PAD_CLIP_DEFAULT;
   return g_tune.pad_clip >= 0 ? g_tune.pad_clip : env;
 }
+// What switch 1 of pad_clip does with grad-input launches.  1 (default): those the schedule model takes.  0: none, forward-kernel
+// launches only (the A/B's other side and an escape hatch).  2 (measurements): every eligible one, in the model's best order.  The
+// forced modes 2-7 of pad_clip are not affected.  pcg_tune_set("pad_clip_dgrad", v) or PCG_PAD_CLIP_DGRAD=v.
+int clip_dgrad_mode() {
+  static const int env0 = getenv("PCG_PAD_CLIP_DGRAD") ? atoi(getenv("PCG_PAD_CLIP_DGRAD")) : 1;
+  static const int env = env0 >= 0 && env0 <= 2 ? env0 : 1;       // (anything else in the environment: the default)
+  return g_tune.pad_clip_dgrad >= 0 ? g_tune.pad_clip_dgrad : env;
+}
 const uint32_t* cliptab_of(const pcg_conv_geom* g) {
   std::lock_guard<std::mutex> lock(g_clip_mutex);
   if (g_cliptab_n == 0) return nullptr;
@@ -796,10 +804,21 @@ struct ClipShape { int form, OH, OW, B, tilesN, interleave, bm0, alt64; };
 struct ClipPlan { bool take; int order, bm; double ratio; };   // ratio: predicted time of the chosen clipped launch / today's
 constexpr double CLIP_UNIT64 = 254.0 / (479.0 / 2.0) / 2.0;    // a 64-row tile's k-tile in units of a 128-row tile's
 constexpr double CLIP_TAKE = 0.95;
-// The clipped grad-input kernel measured 19-22 % SLOWER than today's at equal work (D3 / D4 at batch 512 and 1024, every order: 0.2514 ->
-// 0.3053 ms on D4; profiles/pad_clip_ab.json): its rows no longer share dy pixels between the taps of a tile or between the phases of
-// one tile.  The model carries that cost, so no grad-input launch is taken unless clipping removes more than a quarter of its time.
-constexpr double CLIP_DGRAD_COST = 1.21;
+// The clipped grad-input kernel's k-tile in units of today's: the median, over D3 / D4 at batch 512 and 1024 and the three orders, of
+// (clipped / today's time) / (the model's ratio without this factor) — 0.927 .. 0.984, profiles/dgrad_clip_ab.json.  It was 1.21 (D4:
+// 0.2514 -> 0.3053 ms) while the tap walk's early-return chain kept both loaders in private memory, 304-352 bytes read and written in
+// every k-tile of the producers' loop; with the walk in registers (conv_loaders.h, DgradTapIterT<true>::advance) the clipped kernel is
+// the faster one at equal work.
+constexpr double CLIP_DGRAD_COST = 0.98;
+// The grad-input form is taken wherever the prediction, unit cost included, is no loss — not only below CLIP_TAKE: the model saw no round
+// to save in D3 / D4 at either batch (ratio 1.000 in every order) where the clipped launches measured 2-7 % faster, and the DCGAN step
+// gains 0.035 ms with CLIP_TAKE and 0.137 ms with every grad-input launch clipped (profiles/dgrad_clip_ab.json).  Only launches of at
+// least one round of 512 workgroups, the smallest measured (D4 at batch 512); below that nothing was measured and the launch stays.
+// With a unit cost below 1 the ratio test is at present VACUOUS for this form — the model's best ratio never exceeds 1.0, so 0.98 times it
+// never exceeds CLIP_TAKE_DGRAD — and the rule comes down to "at least 512 workgroups"; it is kept so that a re-measured cost above 1
+// decides again.  Launches of 512 workgroups or more that are not whole rounds were not measured.
+constexpr double CLIP_TAKE_DGRAD = 1.0;
+constexpr int CLIP_DGRAD_MIN_TILES = 512;
 double clip_predict(const ClipShape& c, int bm, int order) {     // order < 0: today's launch (every tile iterates every tap)
   const int npos = c.OH * c.OW, tpp = c.B / bm, tilesM = npos * tpp, nph = c.form ? 4 : 1;
   const int per = (c.form && c.interleave ? nph : 1) * c.tilesN, gx = tilesM * per, gy = c.form && !c.interleave ? nph : 1;
@@ -838,7 +857,8 @@ ClipPlan plan_clip(const ClipShape& c) {
         if (r < best.ratio - 1e-9) best = ClipPlan{false, order, bm, r};
       }
     }
-    best.take = best.ratio <= CLIP_TAKE + 1e-9;
+    const int blocks = c.OH * c.OW * (c.B / best.bm) * c.tilesN * (c.form ? 4 : 1);
+    best.take = c.form ? best.ratio <= CLIP_TAKE_DGRAD + 1e-9 && blocks >= CLIP_DGRAD_MIN_TILES : best.ratio <= CLIP_TAKE + 1e-9;
   }
   cache[key] = best;
   return best;
@@ -1315,10 +1335,13 @@ static ClipPlan clip_fwd_plan(const pcg_conv_geom* g, int groups, bool t64, bool
 }
 static ClipPlan clip_dgrad_plan(const pcg_conv_geom* g, int groups, bool interleave, bool plain) {
   const ClipPlan none{false, 0, 0, 1.0};
-  if (clip_mode() == 0 || conv_bf16() || !plain || !mfma_layer(g) || g->Cin % 4 || g->Cout % 4 || !clip_shape_ok(g, groups, 128)) return none;
+  if (clip_mode() == 0 || (clip_mode() == 1 && clip_dgrad_mode() == 0) || conv_bf16() || !plain || !mfma_layer(g) || g->Cin % 4 || g->Cout % 4 ||
+      !clip_shape_ok(g, groups, 128)) return none;
   const int N = g->Cin;
   const ClipShape c{1, g->OH, g->OW, g->B, ceil_div(N, N > 64 ? 128 : 64), interleave ? 1 : 0, 128, 0};
-  return plan_clip(c);
+  ClipPlan cp = plan_clip(c);
+  if (clip_mode() == 1 && clip_dgrad_mode() == 2) cp.take = true;
+  return cp;
 }
 static void clip_apply(const pcg_conv_geom* g, const ClipPlan& cp, int groups, const uint32_t* tab, ConvP* p) {
   p->cliptab = tab; p->clip_order = cp.order; p->clip_tpp = g->B / cp.bm; p->clip_tpg = p->clip_tpp / groups; p->clip_npos = g->OH * g->OW;
@@ -2088,11 +2111,15 @@ extern "C" int pcg_tune_set(const char* name, int32_t value) {
   else if (!strcmp(name, "t64")) g_tune.t64 = value;
   else if (!strcmp(name, "wgrad_pixtab")) g_tune.wgrad_pixtab = value;   // A/B: 0 the weight gradient derives its pixels per k-tile, 1 reads the geometry's table
   else if (!strcmp(name, "pad_clip")) g_tune.pad_clip = value;           // A/B: 0 today's forward / grad-input launches, 1 the clipped ones the model takes
+  else if (!strcmp(name, "pad_clip_dgrad")) {
+    PCG_REQUIRE(value >= -1 && value <= 2, "pcg_tune_set: pad_clip_dgrad is 0, 1 or 2 (-1: built-in), not %d", (int)value);
+    g_tune.pad_clip_dgrad = value;
+  }  // A/B: pad_clip 1 takes 0 no grad-input launch, 1 those the model takes, 2 every eligible one
   else {
     // The parenthesised list is compared word for word by tests/test_host_logic.py::test_tune_switches, written before wgrad_pixtab
     // existed: the later switches are named behind it.  Follow-up: put them into the list and extend that test's list with them.
     set_error("pcg_tune_set: unknown switch '%s' (korder, edge_prio, dgrad_swz3, wgrad_rounds, wgrad_order, dgrad_interleave, fwd_splits, "
-              "stream_k, sk_blocks, dgrad_gemm, t64); the loader switches wgrad_pixtab and pad_clip are accepted as well", name);
+              "stream_k, sk_blocks, dgrad_gemm, t64); the loader switches wgrad_pixtab, pad_clip and pad_clip_dgrad are accepted as well", name);
     return PCG_ERR_INVALID;
   }
   return PCG_OK;

@@ -317,16 +317,31 @@ struct DgradTapIterT {
   }
   __device__ __forceinline__ void advance() {
     if constexpr (CLIP) {
+      // Locals in, values selected, every field stored once.  Written like the unclipped walk below — or with selects, but each mode
+      // updating the fields in place — the two modes end in "load a field, add, store it" on different fields (jh / co0); the compiler
+      // merges those tails into ONE increment through a selected pointer, and that address-taken access keeps the whole loader object
+      // in private memory: 304-352 bytes of scratch, read and written in every k-tile of the producers' loop.
+      // Precondition: the rectangle is not empty (hlo < hhi, wlo < whi) — every position of a k4 s2 p1 phase grid keeps at least one
+      // tap; for an empty one this form moves co0 where the early-return chain left the state alone (such a tile has no k-tile anyway).
+      int w = jw, h = jh, c = co0;
       if (mode == 0) {
-        co0 += IG_BK;
-        if (co0 >= Cout) { co0 = 0; if (++jw == whi) { jw = wlo; ++jh; } }
+        const int c1 = c + IG_BK;
+        const bool wc = c1 >= Cout;
+        const int w1 = w + (wc ? 1 : 0);
+        const bool ww = w1 == whi;
+        c = wc ? 0 : c1;
+        w = ww ? wlo : w1;
+        h += ww ? 1 : 0;
       } else {
-        if (++jw < whi) return;
-        jw = wlo;
-        if (++jh < hhi) return;
-        jh = hlo;
-        co0 += IG_BK;
+        const int w1 = w + 1;
+        const bool ww = w1 >= whi;
+        const int h1 = h + (ww ? 1 : 0);
+        const bool wh = h1 >= hhi;
+        w = ww ? wlo : w1;
+        h = wh ? hlo : h1;
+        c += wh ? IG_BK : 0;
       }
+      jw = w; jh = h; co0 = c;    // every field stored once, outside the mode branch: nothing to merge into a store through a pointer
       return;
     }
     if (mode == 0) {
