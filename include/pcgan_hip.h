@@ -1125,9 +1125,32 @@ int pcg_conv_plan_describe(const pcg_conv_geom* g, int32_t op, int32_t assume_sc
  *                                                                 "float4 lanes: 8192 blocks of 256: 2 passes" | "scalar lanes: ..."
  *   PCG_PLAN_ELEMENTWISE              (family, n work items)      the grid-stride launch of one thread per item, "4096 blocks of 256:
  *                                      2 passes"; family: PCG_PLAN_EW_TABULAR (tabular.hip), PCG_PLAN_EW_CF_OPS (cf_ops.hip),
- *                                      PCG_PLAN_EW_POINTWISE (pcg_add_bias_rows), PCG_PLAN_EW_GATHER_CHANNEL (pcg_gather_channel)  */
+ *                                      PCG_PLAN_EW_POINTWISE (pcg_add_bias_rows), PCG_PLAN_EW_GATHER_CHANNEL (pcg_gather_channel)
+ * The normalisation layer (csrc/batchnorm.hip, instnorm.hip, spectral_norm_body.h); "aligned": every tensor pointer of the call is
+ * 16-byte aligned:
+ *   PCG_PLAN_BN_COLREDUCE             (rows, C, aligned)          the column reduction of pcg_bn_train_stats / pcg_bn_act_bwd* / pcg_colsum:
+ *                                                                 "float4: 8 x 32 threads, 2 channel passes, 8 blocks of 128 rows" |
+ *                                                                 "scalar: ..." (threads: channel groups x row lanes)
+ *   PCG_PLAN_BN_APPLY                 (pass, rows, C, aligned)    pass 0 pcg_bn_apply_act, 1 the apply of pcg_bn_act_bwd* / pcg_bn_bwd_partial,
+ *                                                                 2 the same with fused column sums (dcol):
+ *                                                                 "fast<2>: 500 blocks, temporal stores, thread 0: 0 main trips + tail of 1"
+ *                                                                 (<loads in flight>; "non-temporal stores"; the trips of the grid-stride
+ *                                                                 loop as thread 0 walks it) | "float4 lanes: 9 blocks of 256: 1 pass" |
+ *                                                                 "scalar lanes: ..."; reads PCG_BN_DEPTH / PCG_BN_NT / PCG_BN_BLOCKS
+ *   PCG_PLAN_BN_FINALIZE              (nparts)                    the finalize over nparts partial rows: "256 threads, 1 eight-deep trip" |
+ *                                                                 "1024 threads, 0 eight-deep trips" | "presum: 228 chunks of 9 rows, 256
+ *                                                                 threads, 1 eight-deep trip" (the two-level form of pcg_bn_bwd_partial* and
+ *                                                                 the conv epilogues' statistics; trips of slice 0 through the batched loop)
+ *   PCG_PLAN_INSTNORM                 (pass, B, HW, C, aligned)   pass 0 pcg_instnorm_fwd, 1 pcg_instnorm_bwd*, 2 pcg_instnorm_bwd_bwd*:
+ *                                                                 "reg<6>: 32 channels x 32 lanes, grid 2 x 2" | "stream<4>: ..." |
+ *                                                                 "stream<1>: ..." (channels per block x position-lanes, grid B x blocks)
+ *   PCG_PLAN_SPECTRAL_NORM            (pass, O, I)                pass 0 forward: "LDS image: 12192 of 12288 floats, row stride 127" |
+ *                                                                 "global memory: 12384 floats exceed 12288, row stride 129"; pass 1
+ *                                                                 backward (pcg_spectral_norm_bwd*): "one burst: 8192 of 8192 elements" |
+ *                                                                 "loops: 8320 elements exceed 8192"  */
 enum { PCG_PLAN_GEMM_ACT = 0, PCG_PLAN_GEMM = 1, PCG_PLAN_LINEAR_WGRAD = 2, PCG_PLAN_LINEAR_WGRAD_GROUPED = 3, PCG_PLAN_MEAN = 4,
-       PCG_PLAN_ABS_MEAN = 5, PCG_PLAN_CROSS_ENTROPY = 6, PCG_PLAN_EMBED_CONCAT_BWD = 7, PCG_PLAN_ACT = 8, PCG_PLAN_ELEMENTWISE = 9 };
+       PCG_PLAN_ABS_MEAN = 5, PCG_PLAN_CROSS_ENTROPY = 6, PCG_PLAN_EMBED_CONCAT_BWD = 7, PCG_PLAN_ACT = 8, PCG_PLAN_ELEMENTWISE = 9,
+       PCG_PLAN_BN_COLREDUCE = 10, PCG_PLAN_BN_APPLY = 11, PCG_PLAN_BN_FINALIZE = 12, PCG_PLAN_INSTNORM = 13, PCG_PLAN_SPECTRAL_NORM = 14 };
 enum { PCG_PLAN_EW_TABULAR = 0, PCG_PLAN_EW_CF_OPS = 1, PCG_PLAN_EW_POINTWISE = 2, PCG_PLAN_EW_GATHER_CHANNEL = 3 };
 int pcg_launch_plan_describe(int32_t op, const int64_t* args, int32_t n_args, char* out, size_t out_bytes);
 size_t pcg_conv_scratch_parts_bytes(void);

@@ -5,6 +5,7 @@
 // float atomics).  Replaces nn.BatchNorm2d + nn.ReLU/nn.LeakyReLU at mnist_dcgan.py:77-87,103-110 and
 // conditional_counteRGAN/mnist/models/generator.py:12-20; [torch] semantics cited in pcgan_hip.h.
 #include "pcg_common.h"
+#include "launch_plan.h"
 #include <cstdlib>
 
 namespace pcg {
@@ -452,6 +453,7 @@ static const BnTune& bn_tune() {
   return t;
 }
 static bool bn_use_nt(size_t n4) { const BnTune& t = bn_tune(); return t.nt < 0 ? n4 * 16 >= t.nt_bytes : t.nt != 0; }
+static int bn_apply_depth() { return bn_tune().depth == 4 ? 4 : 2; }   // loads in flight per thread of the forward apply (the backward has 2)
 template <bool NT>
 __device__ __forceinline__ void bn_store4(float4* at, const float4& v) {
   typedef float nt_f32x4 __attribute__((ext_vector_type(4)));
@@ -500,10 +502,10 @@ __global__ void __launch_bounds__(256) bn_apply_act_fast_kernel(const float4* __
 }
 template <class... A>
 static void launch_bn_apply_fast(dim3 grid, hipStream_t s, size_t n4_all, A... a) {
-  const BnTune& t = bn_tune();
+  const int depth = bn_apply_depth();
   const bool nt = bn_use_nt(n4_all);
-  if (t.depth == 4 && nt) hipLaunchKernelGGL((bn_apply_act_fast_kernel<4, true>), grid, dim3(256), 0, s, a...);
-  else if (t.depth == 4) hipLaunchKernelGGL((bn_apply_act_fast_kernel<4, false>), grid, dim3(256), 0, s, a...);
+  if (depth == 4 && nt) hipLaunchKernelGGL((bn_apply_act_fast_kernel<4, true>), grid, dim3(256), 0, s, a...);
+  else if (depth == 4) hipLaunchKernelGGL((bn_apply_act_fast_kernel<4, false>), grid, dim3(256), 0, s, a...);
   else if (nt) hipLaunchKernelGGL((bn_apply_act_fast_kernel<2, true>), grid, dim3(256), 0, s, a...);
   else hipLaunchKernelGGL((bn_apply_act_fast_kernel<2, false>), grid, dim3(256), 0, s, a...);
 }
@@ -542,9 +544,12 @@ __global__ void __launch_bounds__(256) bn_bwd_apply_fast_kernel(const float4* __
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       if (premask) yy[e] = fmaf(xx[e], msc[e], msh[e]);
-      const float dz = dy_scale * gg[e] * (has_act ? act_grad_from_out(yy[e], act, slope) : 1.f);
+      // k0 * (dz - k1 - xh * k2) with dz = dy_scale * g * act', its two multiply-adds written out: left to the compiler, the
+      // temporal-store instantiation contracted both and the non-temporal one only some (its dx differed by up to 2 ulp, found by
+      // tests/test_hip_norm_branches.py::test_bn_environment_knobs).  These are the temporal instantiation's bits.
+      const float grad = has_act ? act_grad_from_out(yy[e], act, slope) : 1.f;
       const float xh = (xx[e] - mu[e]) * is[e];
-      gg[e] = k0[e] * (dz - k1[e] - xh * k2[e]);
+      gg[e] = k0[e] * fmaf(-xh, k2[e], fmaf(dy_scale * gg[e], grad, -k1[e]));
     }
     return make_float4(gg[0], gg[1], gg[2], gg[3]);
   };
@@ -608,6 +613,27 @@ unsigned ew_blocks(size_t nv) {
 }
 
 bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+// The element-wise pass behind the statistics, one decision for pcg_bn_apply_act, bn_act_bwd_impl, bn_bwd_partial_impl and the describe
+// piece at the end of this file: fast (register coefficients) / float4 / scalar lanes, loads in flight, store kind, grid.
+constexpr int COL_MAX_BLOCKS = 4096;   // grid cap of the fast apply kernels
+constexpr int COL_SUM_BLOCKS = 1024;   // ... when the pass also leaves column sums (one fp64 partial row per block): the finalize behind it
+                                       // walks the rows in a latency-bound loop (12 us at 4096 rows, r04 census of the CounteRGAN step)
+enum { BN_PASS_APPLY = 0, BN_PASS_BWD = 1, BN_PASS_BWD_COLSUM = 2 };
+enum { BN_LANES_FAST = 0, BN_LANES_FLOAT4 = 1, BN_LANES_SCALAR = 2 };
+struct ApplyPlan { int lanes, depth; bool nt; unsigned blocks; };
+ApplyPlan plan_apply(int pass, int64_t rows, int C, bool aligned) {
+  const size_t n = (size_t)rows * C;
+  if (fast_channels(C) && aligned) {
+    const unsigned cap = pass == BN_PASS_APPLY ? (unsigned)bn_tune().blocks : pass == BN_PASS_BWD_COLSUM ? COL_SUM_BLOCKS : COL_MAX_BLOCKS;
+    unsigned blocks = (unsigned)((n / 4 + 511) / 512);
+    if (blocks > cap) blocks = cap;
+    if (blocks < 1) blocks = 1;
+    return ApplyPlan{BN_LANES_FAST, pass == BN_PASS_APPLY ? bn_apply_depth() : 2, bn_use_nt(n / 4), blocks};
+  }
+  if (C % 4 == 0 && aligned) return ApplyPlan{BN_LANES_FLOAT4, 1, false, ew_blocks(n / 4)};
+  return ApplyPlan{BN_LANES_SCALAR, 1, false, ew_blocks(n)};
+}
 
 }  // namespace
 }  // namespace pcg
@@ -715,23 +741,18 @@ extern "C" int pcg_bn_apply_act(const float* x, int64_t rows, int32_t C, const f
   PCG_REQUIRE(x && y && mean && invstd && rows > 0 && C > 0, "pcg_bn_apply_act: bad arguments");
   hipStream_t s = (hipStream_t)stream;
   const size_t n = (size_t)rows * C;
-  if (fast_channels(C) && al16(x) && al16(y) && al16(residual)) {
-    unsigned blocks = (unsigned)((n / 4 + 511) / 512);
-    if (blocks > (unsigned)bn_tune().blocks) blocks = (unsigned)bn_tune().blocks;
-    if (blocks < 1) blocks = 1;
-    launch_bn_apply_fast(dim3(blocks), s, n / 4, reinterpret_cast<const float4*>(x), n / 4, C, mean,
+  const ApplyPlan ap = plan_apply(BN_PASS_APPLY, rows, C, al16(x) && al16(y) && al16(residual));
+  if (ap.lanes == BN_LANES_FAST) {
+    launch_bn_apply_fast(dim3(ap.blocks), s, n / 4, reinterpret_cast<const float4*>(x), n / 4, C, mean,
                          invstd, var_eps, gamma, beta, act, slope, reinterpret_cast<const float4*>(residual), alpha,
                          reinterpret_cast<float4*>(y), (size_t)0);
-  } else if (C % 4 == 0 && al16(x) && al16(y) && al16(residual))
-    hipLaunchKernelGGL(bn_apply_act_kernel<4>, dim3(ew_blocks(n / 4)), dim3(256), 0, s, x, n, C, mean, invstd, var_eps, gamma, beta, act, slope, residual, alpha, y);
+  } else if (ap.lanes == BN_LANES_FLOAT4)
+    hipLaunchKernelGGL(bn_apply_act_kernel<4>, dim3(ap.blocks), dim3(256), 0, s, x, n, C, mean, invstd, var_eps, gamma, beta, act, slope, residual, alpha, y);
   else
-    hipLaunchKernelGGL(bn_apply_act_kernel<1>, dim3(ew_blocks(n)), dim3(256), 0, s, x, n, C, mean, invstd, var_eps, gamma, beta, act, slope, residual, alpha, y);
+    hipLaunchKernelGGL(bn_apply_act_kernel<1>, dim3(ap.blocks), dim3(256), 0, s, x, n, C, mean, invstd, var_eps, gamma, beta, act, slope, residual, alpha, y);
   return launch_status("bn_apply_act_kernel");
 }
 
-constexpr int COL_MAX_BLOCKS = 4096;   // grid cap of the fast apply kernels
-constexpr int COL_SUM_BLOCKS = 1024;   // ... when the pass also leaves column sums (one fp64 partial row per block): the finalize behind it
-                                       // walks the rows in a latency-bound loop (12 us at 4096 rows, r04 census of the CounteRGAN step)
 static size_t colpart_bytes(int32_t C) { return (size_t)COL_MAX_BLOCKS * C * sizeof(double); }
 
 static int bn_act_bwd_impl(const float* dy, const float* x, const float* y, int64_t rows, int32_t C, const float* mean,
@@ -771,10 +792,9 @@ static int bn_act_bwd_impl(const float* dy, const float* x, const float* y, int6
   if (int e = launch_status("bn_bwd_finalize_kernel")) return e;
   const size_t n = (size_t)rows * C;
   const bool fused_col = dcol != nullptr;
-  if (fast_channels(C) && aligned) {
-    unsigned blocks = (unsigned)((n / 4 + 511) / 512);
-    if (blocks > (fused_col ? COL_SUM_BLOCKS : COL_MAX_BLOCKS)) blocks = fused_col ? COL_SUM_BLOCKS : COL_MAX_BLOCKS;
-    if (blocks < 1) blocks = 1;
+  const ApplyPlan ap = plan_apply(fused_col ? BN_PASS_BWD_COLSUM : BN_PASS_BWD, rows, C, aligned);
+  if (ap.lanes == BN_LANES_FAST) {
+    const unsigned blocks = ap.blocks;
     launch_bn_bwd_apply_fast(dim3(blocks), s, n / 4, reinterpret_cast<const float4*>(dy),
                              reinterpret_cast<const float4*>(x), reinterpret_cast<const float4*>(y), n / 4, C, mean, invstd,
                              (const float*)coef, act, slope, dy_scale, reinterpret_cast<float4*>(dx), gamma, beta, fused_col ? colpart : (double*)nullptr,
@@ -785,11 +805,11 @@ static int bn_act_bwd_impl(const float* dy, const float* x, const float* y, int6
                          (int)blocks, C, dcol, accumulate_col);
       return launch_status("colsum_finalize_kernel");
     }
-  } else if (C % 4 == 0 && aligned)
-    hipLaunchKernelGGL(bn_bwd_apply_kernel<4>, dim3(ew_blocks(n / 4)), dim3(256), 0, s, dy, x, y, n, C, mean, invstd,
+  } else if (ap.lanes == BN_LANES_FLOAT4)
+    hipLaunchKernelGGL(bn_bwd_apply_kernel<4>, dim3(ap.blocks), dim3(256), 0, s, dy, x, y, n, C, mean, invstd,
                        (const float*)coef, act, slope, dy_scale, dx, gamma, beta);
   else
-    hipLaunchKernelGGL(bn_bwd_apply_kernel<1>, dim3(ew_blocks(n)), dim3(256), 0, s, dy, x, y, n, C, mean, invstd,
+    hipLaunchKernelGGL(bn_bwd_apply_kernel<1>, dim3(ap.blocks), dim3(256), 0, s, dy, x, y, n, C, mean, invstd,
                        (const float*)coef, act, slope, dy_scale, dx, gamma, beta);
   if (int e = launch_status("bn_bwd_apply_kernel")) return e;
   if (dcol) {   // generic shapes: the separate reduction over the dx just written (the partial rows are free again)
@@ -858,10 +878,9 @@ static int bn_bwd_partial_impl(const float* dm, const float* x, int64_t rows, in
   const bool aligned = al16(dm) && al16(x) && al16(dx);
   const size_t n = (size_t)rows * C;
   double* colpart = reinterpret_cast<double*>(reinterpret_cast<char*>(workspace) + (((size_t)3 * C * sizeof(float) + 7) & ~(size_t)7));
-  if (fast_channels(C) && aligned) {
-    unsigned blocks = (unsigned)((n / 4 + 511) / 512);
-    if (blocks > (dcol ? COL_SUM_BLOCKS : COL_MAX_BLOCKS)) blocks = dcol ? COL_SUM_BLOCKS : COL_MAX_BLOCKS;
-    if (blocks < 1) blocks = 1;
+  const ApplyPlan ap = plan_apply(dcol ? BN_PASS_BWD_COLSUM : BN_PASS_BWD, rows, C, aligned);
+  if (ap.lanes == BN_LANES_FAST) {
+    const unsigned blocks = ap.blocks;
     launch_bn_bwd_apply_fast(dim3(blocks), s, n / 4, reinterpret_cast<const float4*>(dm),
                              reinterpret_cast<const float4*>(x), (const float4*)nullptr, n / 4, C, mean, invstd, (const float*)coef, (int)PCG_ACT_NONE,
                              0.f, dm_scale, reinterpret_cast<float4*>(dx), gamma, (const float*)nullptr, dcol ? colpart : (double*)nullptr, (size_t)0);
@@ -872,11 +891,11 @@ static int bn_bwd_partial_impl(const float* dm, const float* x, int64_t rows, in
       return launch_status("colsum_finalize_kernel");
     }
     return PCG_OK;
-  } else if (C % 4 == 0 && aligned)
-    hipLaunchKernelGGL(bn_bwd_apply_kernel<4>, dim3(ew_blocks(n / 4)), dim3(256), 0, s, dm, x, (const float*)nullptr, n, C, mean, invstd,
+  } else if (ap.lanes == BN_LANES_FLOAT4)
+    hipLaunchKernelGGL(bn_bwd_apply_kernel<4>, dim3(ap.blocks), dim3(256), 0, s, dm, x, (const float*)nullptr, n, C, mean, invstd,
                        (const float*)coef, PCG_ACT_NONE, 0.f, dm_scale, dx, gamma, (const float*)nullptr);
   else
-    hipLaunchKernelGGL(bn_bwd_apply_kernel<1>, dim3(ew_blocks(n)), dim3(256), 0, s, dm, x, (const float*)nullptr, n, C, mean, invstd,
+    hipLaunchKernelGGL(bn_bwd_apply_kernel<1>, dim3(ap.blocks), dim3(256), 0, s, dm, x, (const float*)nullptr, n, C, mean, invstd,
                        (const float*)coef, PCG_ACT_NONE, 0.f, dm_scale, dx, gamma, (const float*)nullptr);
   if (int e = launch_status("bn_bwd_apply_kernel")) return e;
   if (dcol) {
@@ -1046,4 +1065,48 @@ extern "C" int pcg_colsum(const float* dy, int64_t rows, int32_t C, float* db, i
   if (int e = launch_colreduce(fn, rows, C, cp, partial, s)) return e;
   hipLaunchKernelGGL(colsum_finalize_kernel, dim3((C + FIN_CH - 1) / FIN_CH), dim3(fin_threads(cp.nblocks)), 0, s, (const double*)partial, cp.nblocks, C, db, accumulate);
   return launch_status("colsum_finalize_kernel");
+}
+
+// this file's part of pcg_launch_plan_describe (tabular.hip): plan_cols, plan_apply, plan_presum and fin_threads, as the launchers call them
+int pcg::describe_batchnorm_plan(int32_t op, const int64_t* a, int32_t n_args, char* buf, size_t bytes) {
+  switch (op) {
+    case PCG_PLAN_BN_COLREDUCE: {
+      PCG_REQUIRE(n_args == 3 && a[0] > 0 && a[1] > 0 && a[1] <= INT32_MAX, "pcg_launch_plan_describe: bn_colreduce takes (rows, C, aligned)");
+      const ColPlan p = plan_cols(a[0], (int)a[1], a[2] != 0);
+      const int passes = (p.CG + p.TX - 1) / p.TX;
+      snprintf(buf, bytes, "%s: %d x %d threads, %d channel %s, %d %s of %d rows", p.vec == 4 ? "float4" : "scalar", p.TX, p.TY, passes,
+               passes == 1 ? "pass" : "passes", p.nblocks, p.nblocks == 1 ? "block" : "blocks", p.rows_per_block);
+      return PCG_OK;
+    }
+    case PCG_PLAN_BN_APPLY: {
+      PCG_REQUIRE(n_args == 4 && a[0] >= BN_PASS_APPLY && a[0] <= BN_PASS_BWD_COLSUM && a[1] > 0 && a[2] > 0 && a[2] <= INT32_MAX,
+                  "pcg_launch_plan_describe: bn_apply takes (pass 0 apply | 1 backward | 2 backward with column sums, rows, C, aligned)");
+      const ApplyPlan p = plan_apply((int)a[0], a[1], (int)a[2], a[3] != 0);
+      const size_t n = (size_t)a[1] * (size_t)a[2];
+      if (p.lanes == BN_LANES_FAST) {
+        // what the grid-stride loop of thread 0 does: trips of the DEPTH-deep main loop, then single steps
+        const size_t n4 = n / 4, stride = (size_t)p.blocks * 256, reach = (size_t)(p.depth - 1) * stride;
+        const size_t trips = n4 > reach ? (n4 - reach - 1) / (p.depth * stride) + 1 : 0;
+        const size_t done = trips * p.depth * stride, tail = n4 > done ? (n4 - done + stride - 1) / stride : 0;
+        snprintf(buf, bytes, "fast<%d>: %u %s, %s stores, thread 0: %zu main %s + tail of %zu", p.depth, p.blocks, p.blocks == 1 ? "block" : "blocks",
+                 p.nt ? "non-temporal" : "temporal", trips, trips == 1 ? "trip" : "trips", tail);
+        return PCG_OK;
+      }
+      const int k = snprintf(buf, bytes, "%s", p.lanes == BN_LANES_FLOAT4 ? "float4 lanes: " : "scalar lanes: ");
+      describe_ew_grid(buf + k, bytes - k, p.lanes == BN_LANES_FLOAT4 ? n / 4 : n, p.blocks);
+      return PCG_OK;
+    }
+    case PCG_PLAN_BN_FINALIZE: {
+      PCG_REQUIRE(n_args == 1 && a[0] > 0 && a[0] <= INT32_MAX, "pcg_launch_plan_describe: bn_finalize takes (nparts)");
+      const PrePlan q = plan_presum((int)a[0]);
+      const int rows = q.nchunks ? q.nchunks : (int)a[0], threads = fin_threads(rows), SL = threads / FIN_CH;
+      const int deep = rows > 7 * SL ? (rows - 7 * SL - 1) / (8 * SL) + 1 : 0;      // trips of slice 0 through the 8-loads-in-flight loop
+      int k = 0;
+      if (q.nchunks) k = snprintf(buf, bytes, "presum: %d chunks of %d rows, ", q.nchunks, q.rpc);
+      snprintf(buf + k, bytes - k, "%d threads, %d eight-deep %s", threads, deep, deep == 1 ? "trip" : "trips");
+      return PCG_OK;
+    }
+    default:
+      return PCG_PLAN_NOT_MINE;
+  }
 }

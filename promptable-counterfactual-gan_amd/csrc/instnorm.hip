@@ -13,6 +13,7 @@
 // (derivation checked against torch autograd in float64: tests/test_hip_wgan.py)
 #include <initializer_list>
 #include "pcg_common.h"
+#include "launch_plan.h"
 
 namespace pcg {
 namespace {
@@ -627,13 +628,17 @@ unsigned ew_blocks(size_t n) {
 // Channels per block of the register-resident form are chosen so that the position-lanes match the map: 4 lanes x 256 channels for a
 // 2x2 map, 16 x 64 for 6x6, 32 x 32 for 13x13 (`wide13`: the backward-of-backward keeps 16 x 64 there — with three tensors in
 // registers the 32-lane form measured 80 against 61 us).  `launch(kernel, grid, tc)` issues the chosen instantiation.
-template <template <int> class Reg, template <int> class Stream, class Launch>
-void instnorm_dispatch(bool vec, int B, int HW, int C, bool wide13, Launch launch) {
+// The decision itself is instnorm_plan, which the describe piece at the end of this file calls as well.
+struct InstnormPlan { int reg;   // NP of the register-resident form, 0: streaming
+                      int vec;   // channels per thread (4 | 1)
+                      int tc;    // channels per block
+                      int lanes; // position-lanes of a block
+                      int grid_y; };
+InstnormPlan instnorm_plan(bool vec, int HW, int C, bool wide13) {
   if (!vec) {
     int tc = 1;
     while (tc < C && tc < 64) tc <<= 1;
-    launch(Stream<1>::fn(), dim3(B, (C + tc - 1) / tc), tc);
-    return;
+    return InstnormPlan{0, 1, tc, IN_THREADS / tc, (C + tc - 1) / tc};
   }
   const int tc = pick_tc(C);
   int tcr = tc;
@@ -641,14 +646,23 @@ void instnorm_dispatch(bool vec, int B, int HW, int C, bool wide13, Launch launc
   else if (HW <= 8 && C % 128 == 0) tcr = 128;
   else if (wide13 && HW > 48 && C % 32 == 0 && tc >= 32) tcr = 32;
   const int th = IN_THREADS / (tcr / 4), np = (HW + th - 1) / th;     // positions per lane
-  const dim3 grid(B, (C + tcr - 1) / tcr);
-  if (np <= 1) launch(Reg<1>::fn(), grid, tcr);
-  else if (np <= 2) launch(Reg<2>::fn(), grid, tcr);
-  else if (np <= 3) launch(Reg<3>::fn(), grid, tcr);
-  else if (np <= 6) launch(Reg<6>::fn(), grid, tcr);
-  else if (np <= 12) launch(Reg<12>::fn(), grid, tcr);
-  else launch(Stream<4>::fn(), dim3(B, (C + tc - 1) / tc), tc);
+  const int reg = np <= 1 ? 1 : np <= 2 ? 2 : np <= 3 ? 3 : np <= 6 ? 6 : np <= 12 ? 12 : 0;
+  if (reg) return InstnormPlan{reg, 4, tcr, th, (C + tcr - 1) / tcr};
+  return InstnormPlan{0, 4, tc, IN_THREADS / (tc / 4), (C + tc - 1) / tc};
 }
+template <template <int> class Reg, template <int> class Stream, class Launch>
+void instnorm_dispatch(bool vec, int B, int HW, int C, bool wide13, Launch launch) {
+  const InstnormPlan p = instnorm_plan(vec, HW, C, wide13);
+  const dim3 grid(B, p.grid_y);
+  if (p.reg == 1) launch(Reg<1>::fn(), grid, p.tc);
+  else if (p.reg == 2) launch(Reg<2>::fn(), grid, p.tc);
+  else if (p.reg == 3) launch(Reg<3>::fn(), grid, p.tc);
+  else if (p.reg == 6) launch(Reg<6>::fn(), grid, p.tc);
+  else if (p.reg == 12) launch(Reg<12>::fn(), grid, p.tc);
+  else if (p.vec == 4) launch(Stream<4>::fn(), grid, p.tc);
+  else launch(Stream<1>::fn(), grid, p.tc);
+}
+constexpr bool wide13_of(int pass) { return pass != 2; }     // forward and backward take 32-channel blocks on 13x13 maps; the backward-of-backward does not
 template <int NP> struct FwdReg { static auto fn() { return instnorm_fwd_reg_kernel<NP>; } };
 template <int V> struct FwdStream { static auto fn() { return instnorm_fwd_kernel<V>; } };
 template <int NP> struct BwdReg { static auto fn() { return instnorm_bwd_reg_kernel<NP>; } };
@@ -664,7 +678,7 @@ using namespace pcg;
 extern "C" int pcg_instnorm_fwd(const float* x, int32_t B, int32_t HW, int32_t C, const float* gamma, const float* beta, float eps, int act,
                                 float slope, float* y, float* mean, float* invstd, pcg_stream_t stream) {
   PCG_REQUIRE(x && gamma && beta && y && mean && invstd && B > 0 && HW > 0 && C > 0, "pcg_instnorm_fwd: bad arguments");
-  instnorm_dispatch<FwdReg, FwdStream>(vec4(C, {x, gamma, beta, y, mean, invstd}), B, HW, C, true, [&](auto kernel, dim3 grid, int tc) {
+  instnorm_dispatch<FwdReg, FwdStream>(vec4(C, {x, gamma, beta, y, mean, invstd}), B, HW, C, wide13_of(0), [&](auto kernel, dim3 grid, int tc) {
     hipLaunchKernelGGL(kernel, grid, dim3(IN_THREADS), 0, (hipStream_t)stream, x, HW, C, tc, gamma, beta, eps, act, slope, y, mean, invstd);
   });
   return launch_status("instnorm_fwd_kernel");
@@ -676,7 +690,7 @@ extern "C" int pcg_instnorm_bwd_fused(const float* dy, const float* act_y, float
   PCG_REQUIRE(dy && x && mean && invstd && gamma && (dx || dgamma_partial) && B > 0 && HW > 0 && C > 0, "pcg_instnorm_bwd: bad arguments");
   PCG_REQUIRE((!dn_out || act_y) && (!addend || dx) && (!dxsum_partial || dx), "pcg_instnorm_bwd_fused: dn_out needs act_y; addend / dxsum_partial need dx");
   instnorm_dispatch<BwdReg, BwdStream>(vec4(C, {dy, act_y, x, mean, invstd, gamma, dn_out, addend, dx, dgamma_partial, dbeta_partial, dxsum_partial}),
-                                       B, HW, C, true, [&](auto kernel, dim3 grid, int tc) {
+                                       B, HW, C, wide13_of(1), [&](auto kernel, dim3 grid, int tc) {
     hipLaunchKernelGGL(kernel, grid, dim3(IN_THREADS), 0, (hipStream_t)stream, dy, act_y, neg_slope, x, HW, C, tc, mean, invstd, gamma, dn_out, addend, dx,
                        dgamma_partial, dbeta_partial, dxsum_partial);
   });
@@ -692,7 +706,7 @@ extern "C" int pcg_instnorm_bwd_bwd_act(const float* r, const float* dy, const f
                                         float* dgamma_partial, pcg_stream_t stream) {
   PCG_REQUIRE(r && dy && x && mean && invstd && gamma && (ddy || ez || dgamma_partial) && B > 0 && HW > 0 && C > 0,
               "pcg_instnorm_bwd_bwd: bad arguments");
-  instnorm_dispatch<BwdBwdReg, BwdBwdStream>(vec4(C, {r, dy, x, mean, invstd, gamma, ddy, ez, dgamma_partial, act_y}), B, HW, C, false,
+  instnorm_dispatch<BwdBwdReg, BwdBwdStream>(vec4(C, {r, dy, x, mean, invstd, gamma, ddy, ez, dgamma_partial, act_y}), B, HW, C, wide13_of(2),
                                              [&](auto kernel, dim3 grid, int tc) {
     hipLaunchKernelGGL(kernel, grid, dim3(IN_THREADS), 0, (hipStream_t)stream, r, dy, x, HW, C, tc, mean, invstd, gamma, ddy, ez, dgamma_partial, act_y,
                        neg_slope);
@@ -751,4 +765,18 @@ extern "C" int pcg_gradient_penalty_bwd(const float* grads, const float* norms, 
   hipLaunchKernelGGL(gp_bwd_kernel, dim3(ew_blocks(n)), dim3(256), 0, (hipStream_t)stream, grads, norms, grad_out_dev, 2.f * lambda / (float)B,
                      per_sample, n, dgrads);
   return launch_status("gp_bwd_kernel");
+}
+
+// this file's part of pcg_launch_plan_describe (tabular.hip): instnorm_plan, as instnorm_dispatch calls it
+int pcg::describe_instnorm_plan(int32_t op, const int64_t* a, int32_t n_args, char* buf, size_t bytes) {
+  if (op != PCG_PLAN_INSTNORM) return PCG_PLAN_NOT_MINE;
+  PCG_REQUIRE(n_args == 5 && a[0] >= 0 && a[0] <= 2 && a[1] > 0 && a[2] > 0 && a[3] > 0 && a[1] <= INT32_MAX && a[2] <= INT32_MAX && a[3] <= INT32_MAX,
+              "pcg_launch_plan_describe: instnorm takes (pass 0 forward | 1 backward | 2 backward of the backward, B, HW, C, aligned)");
+  const int C = (int)a[3];
+  const InstnormPlan p = instnorm_plan(a[4] != 0 && C % 4 == 0, (int)a[2], C, wide13_of((int)a[0]));
+  int k;
+  if (p.reg) k = snprintf(buf, bytes, "reg<%d>", p.reg);
+  else k = snprintf(buf, bytes, "stream<%d>", p.vec);
+  snprintf(buf + k, bytes - k, ": %d channels x %d lanes, grid %d x %d", p.tc, p.lanes, (int)a[1], p.grid_y);
+  return PCG_OK;
 }

@@ -56,6 +56,11 @@ __device__ __forceinline__ float sn_matvec(const float* M, int lm, const float* 
 // The matrix is staged once in LDS (row stride made odd: the row-wise products then hit 32 different banks) and the
 // matrix-vector products read it from there; matrices beyond 48 KB take the global-memory form.
 constexpr int SN_LDS_FLOATS = 12288;
+// The two decisions the bodies take themselves (block-uniform), shared with pcg_launch_plan_describe (tabular.hip):
+__host__ __device__ constexpr int sn_fwd_ld(int I) { return (I & 1) ? I : I + 1; }                              // odd row stride of the LDS image
+__host__ __device__ constexpr bool sn_fwd_in_lds(int O, int I) { return O * sn_fwd_ld(I) <= SN_LDS_FLOATS; }    // else the global-memory forward
+constexpr int SN_BURST_ELEMS = 32 * 256;
+__host__ __device__ constexpr bool sn_bwd_one_burst(int O, int I) { return O * I <= SN_BURST_ELEMS; }           // else the plain loops
 struct SnFwdLds { float red[256]; float su[256], sv[256]; float sW[SN_LDS_FLOATS]; };     // 51 KB: a block's LDS for the forward body
 struct SnBwdLds { float red[256]; float su[256], sv[256]; };
 __device__ __forceinline__ void spectral_norm_fwd_body(const float* __restrict__ W, int O, int I, float* __restrict__ u,
@@ -63,8 +68,8 @@ __device__ __forceinline__ void spectral_norm_fwd_body(const float* __restrict__
                                                        float* const* sigma_r, float* const* uu_r, float* const* vu_r, int reps, int rstride,
                                                        SnFwdLds& lds) {
   float* red = lds.red; float* su = lds.su; float* sv = lds.sv; float* sW = lds.sW;      // O, I <= 256 (host-checked)
-  const int ld = (I & 1) ? I : I + 1;
-  const bool in_lds = O * ld <= SN_LDS_FLOATS;      // block-uniform
+  const int ld = sn_fwd_ld(I);
+  const bool in_lds = sn_fwd_in_lds(O, I);          // block-uniform
   if (in_lds) {
     // one burst: u, v and the whole matrix are requested before the first LDS store (a load-then-store loop pays one memory
     // latency per trip: 32 trips for the 128 x 64 layer); the register copy of the matrix also feeds the W / sigma writes
@@ -159,7 +164,7 @@ __device__ __forceinline__ void spectral_norm_bwd_body(const float* __restrict__
   // schedule of the tabular step) give the same bits
 #pragma clang fp contract(off)
   float* red = lds.red;
-  if (!LOWREG && O * I <= 32 * 256) {       // (block-uniform) every operand of the layer in ONE burst: 32 elements per thread at most
+  if (!LOWREG && sn_bwd_one_burst(O, I)) {       // (block-uniform) every operand of the layer in ONE burst: 32 elements per thread at most
     float* su = lds.su; float* sv = lds.sv;
     constexpr int PER = 32;
     float a[PER], b[PER], w0[PER];
@@ -184,7 +189,7 @@ __device__ __forceinline__ void spectral_norm_bwd_body(const float* __restrict__
     __syncthreads();             // su / sv / red are reused by the next pass of a sequence
     return;
   }
-  if (LOWREG && O * I <= 32 * 256) {
+  if (LOWREG && sn_bwd_one_burst(O, I)) {
     float* su = lds.su; float* sv = lds.sv;
     constexpr int CH = 16, NCH = 32 / CH;
     const float uv = u[min((int)threadIdx.x, O - 1)], vv = v[min((int)threadIdx.x, I - 1)], sg = sigma[0];

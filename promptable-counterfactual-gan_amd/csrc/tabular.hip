@@ -1347,7 +1347,8 @@ extern "C" int pcg_ce_weighted_tally(const float* logits, const int64_t* target,
 }
 
 // Which route a non-convolution launch takes, as text: the predicates and planners the launchers above call (rowdot_takes,
-// skinny_takes, plan_linear_wgrad, plan_wgrad_mfma, mean_one_block, ew_blocks) and their counterparts in cf_ops.hip / pointwise.hip
+// skinny_takes, plan_linear_wgrad, plan_wgrad_mfma, mean_one_block, ew_blocks, sn_fwd_in_lds, sn_bwd_one_burst) and their counterparts in
+// cf_ops.hip / pointwise.hip / batchnorm.hip / instnorm.hip
 // (launch_plan.h) — host logic, no device.  The argument lists are in include/pcgan_hip.h.
 extern "C" int pcg_launch_plan_describe(int32_t op, const int64_t* args, int32_t n_args, char* out, size_t out_bytes) {
   PCG_REQUIRE(out && out_bytes > 0 && args && n_args > 0, "pcg_launch_plan_describe: bad arguments");
@@ -1383,6 +1384,19 @@ extern "C" int pcg_launch_plan_describe(int32_t op, const int64_t* args, int32_t
       if (mean_one_block(a[0])) say("%s", "one block of 1024");
       else say("%d partials + finish", MEAN_BLOCKS);
       break;
+    case PCG_PLAN_SPECTRAL_NORM: {     // the bodies of spectral_norm_body.h decide with these predicates themselves
+      PCG_REQUIRE(n_args == 3 && (a[0] == 0 || a[0] == 1) && a[1] > 0 && a[1] <= 256 && a[2] > 0 && a[2] <= 256,
+                  "pcg_launch_plan_describe: spectral_norm takes (pass 0 forward | 1 backward, O, I), dimensions 1..256");
+      const int O = (int)a[1], I = (int)a[2];
+      if (a[0] == 0) {
+        if (sn_fwd_in_lds(O, I)) say("LDS image: %d of %d floats, row stride %d", O * sn_fwd_ld(I), SN_LDS_FLOATS, sn_fwd_ld(I));
+        else say("global memory: %d floats exceed %d, row stride %d", O * sn_fwd_ld(I), SN_LDS_FLOATS, sn_fwd_ld(I));
+      } else {
+        if (sn_bwd_one_burst(O, I)) say("one burst: %d of %d elements", O * I, SN_BURST_ELEMS);
+        else say("loops: %d elements exceed %d", O * I, SN_BURST_ELEMS);
+      }
+      break;
+    }
     case PCG_PLAN_ELEMENTWISE:
       PCG_REQUIRE(n_args == 2 && a[1] > 0, "pcg_launch_plan_describe: elementwise takes (family, n)");
       if (a[0] == PCG_PLAN_EW_TABULAR) { describe_ew_grid(buf, sizeof(buf), (size_t)a[1], ew_blocks((size_t)a[1])); break; }
@@ -1390,6 +1404,8 @@ extern "C" int pcg_launch_plan_describe(int32_t op, const int64_t* args, int32_t
     default: {
       int e = describe_cf_ops_plan(op, a, n_args, buf, sizeof(buf));
       if (e == PCG_PLAN_NOT_MINE) e = describe_pointwise_plan(op, a, n_args, buf, sizeof(buf));
+      if (e == PCG_PLAN_NOT_MINE) e = describe_batchnorm_plan(op, a, n_args, buf, sizeof(buf));
+      if (e == PCG_PLAN_NOT_MINE) e = describe_instnorm_plan(op, a, n_args, buf, sizeof(buf));
       PCG_REQUIRE(e != PCG_PLAN_NOT_MINE, "pcg_launch_plan_describe: unknown op %d (or element-wise family)", op);
       if (e) return e;
     }
