@@ -215,6 +215,13 @@ class DeviceLoader:
     def __len__(self):
         return (self.x.shape[0] + self.batch_size - 1) // self.batch_size
 
+    def state_dict(self):
+        """The state of the generator the epoch orders are drawn from (a uint8 CPU tensor): what decides the next epoch's batches."""
+        return {"generator": self._gen.get_state()}
+
+    def load_state_dict(self, state):
+        self._gen.set_state(torch.as_tensor(state["generator"], dtype=torch.uint8).cpu())
+
     def epoch_order(self):
         """The next epoch's row order (host tensor; None without shuffling): the one draw an iteration makes from the loader's
         generator, so a consumer that walks the rows itself (countergan.ClassifierFit) sees the batches __iter__ would yield."""

@@ -14,8 +14,11 @@ import numpy as np
 import torch
 import torch.nn as nn
 
+from . import checkpoint as _ckpt
 from . import ops
 from . import nn as _nn
+from ._lib import PcgError
+from .data import DeviceLoader
 from .nn import BCELoss, SequentialConvNet
 from .optim import Adam
 
@@ -205,7 +208,8 @@ def build(cfg=None, device="cuda", seed=None):
     return netG, netD
 
 
-def train(dataloader, cfg=None, netG=None, netD=None, device="cuda", log=print, device_rng=None, dp=None):
+def train(dataloader, cfg=None, netG=None, netD=None, device="cuda", log=print, device_rng=None, dp=None, checkpoint=None, checkpoint_every=1,
+          resume=None):
     """The reference's training script from the fixed viz noise to the per-epoch loss averages (mnist_dcgan.py:129-198) with
     its plotting left out: `dataloader` yields (images, ...) batches (:143,148), per iteration one `train_step`, every 200
     iterations the log line (:178-181), every 500 iterations and at the very end a forward of the generator on the fixed
@@ -217,11 +221,34 @@ def train(dataloader, cfg=None, netG=None, netD=None, device="cuda", log=print, 
     seed-for-seed the draws of the reference's CPU path), or on the GPU from `device_rng` (an ops.DeviceRNG).
     Host syncs: the reference calls .item() six times per iteration; here the loss tensors are read once per epoch (and at the log
     lines), summed in the same order, so the averages are the same numbers.
+    checkpoint (a path): the run's whole state (pcgan_amd.checkpoint, DESIGN.md §3.23: both nets with their BatchNorm statistics, both
+    optimizers, `viz_noise`, `iters`, device_rng, a data.DeviceLoader's generator, torch's CPU generator -- host noise and a shuffling
+    DataLoader draw from it -- and the per-epoch losses) is written there after every checkpoint_every-th epoch.  resume (a path or a
+    loaded checkpoint): nets, optimizers and viz noise are made as always, the stored state is restored over them, and training
+    continues with the next epoch; cfg["epochs"] may be larger than when the checkpoint was written, batch size, number of rows and
+    device_rng's seed must be the same.  After a resume the loss lists include the epochs before the interruption, `iters` counts
+    from the run's start, and `img_list` holds only the batches made after the resume (the earlier ones were returned by the
+    interrupted call and are not stored).  The viz forward at "the very end" belongs to the last epoch of cfg["epochs"]: a run that
+    is to be continued bit for bit is one that was interrupted, not one that ended at a smaller cfg["epochs"].  With dp (data
+    parallel) both arguments are refused: checkpoints of a data-parallel run are not implemented.
     Returns a dict: netG, netD, epoch_G_losses, epoch_D_losses, img_list, iters."""
     c = _cfg(cfg)
+    _ckpt.check_args("dcgan.train", checkpoint, checkpoint_every, resume)
+    if dp is not None and (checkpoint is not None or resume is not None):
+        raise PcgError("dcgan.train: checkpoint= / resume= with dp: checkpoints of a data-parallel run are not implemented")
     dev = torch.device(device)
     if netG is None or netD is None:
         netG, netD = build(c, device=dev)                                     # :119-122
+    run = {"batch_size": int(c["batch_size"]), "n_rows": _ckpt.loader_rows(dataloader), "seed": device_rng.seed if device_rng is not None else None}
+    extra = {"loader": dataloader} if isinstance(dataloader, DeviceLoader) else {}
+    if device_rng is not None:
+        extra["device_rng"] = device_rng
+    state = None
+    if resume is not None:
+        state = _ckpt.open_resume(resume, "dcgan.train", **run)
+        if _ckpt.value(state, "epoch") >= c["epochs"]:                        # nothing left to run: no launch
+            _ckpt.restore(state, netG=netG, netD=netD)
+            return dict(_ckpt.value(state, "history"), netG=netG, netD=netD, img_list=[], iters=_ckpt.value(state, "iters"))
     criterion, optimizerD, optimizerG = make_optimizers(netG, netD, c)        # :125-127
 
     def randn(b):
@@ -233,8 +260,13 @@ def train(dataloader, cfg=None, netG=None, netD=None, device="cuda", log=print, 
     img_list, epoch_G_losses, epoch_D_losses = [], [], []
     iters = 0
     nbatches = len(dataloader)
+    first = 0
+    if state is not None:
+        vals = _ckpt.restore(state, netG=netG, netD=netD, optimizerD=optimizerD, optimizerG=optimizerG, viz_noise=viz_noise, **extra)
+        first, iters = vals["epoch"], vals["iters"]
+        epoch_G_losses, epoch_D_losses = vals["history"]["epoch_G_losses"], vals["history"]["epoch_D_losses"]
     log("Starting Training Loop...")                                          # :139
-    for epoch in range(c["epochs"]):                                          # :140
+    for epoch in range(first, c["epochs"]):                                   # :140
         pending = []                                                          # (errD_real, errD_fake, errG) device scalars of the epoch
         for i, data in enumerate(dataloader):                                 # :143
             real = data[0].to(dev)                                            # :148
@@ -259,6 +291,10 @@ def train(dataloader, cfg=None, netG=None, netD=None, device="cuda", log=print, 
             running_D_loss += float(np.float32(e_real.item()) + np.float32(e_fake.item()))   # errD is an fp32 sum (:163)
         epoch_G_losses.append(running_G_loss / nbatches)                      # :195-198
         epoch_D_losses.append(running_D_loss / nbatches)
+        if _ckpt.due(checkpoint, checkpoint_every, epoch):
+            _ckpt.save(checkpoint, _ckpt.capture(netG=netG, netD=netD, optimizerD=optimizerD, optimizerG=optimizerG, viz_noise=viz_noise,
+                                                 epoch=epoch + 1, iters=iters, run=run,
+                                                 history={"epoch_G_losses": epoch_G_losses, "epoch_D_losses": epoch_D_losses}, **extra))
     if dp is not None:
         dp.wait_all()
     return {"netG": netG, "netD": netD, "epoch_G_losses": epoch_G_losses, "epoch_D_losses": epoch_D_losses, "img_list": img_list,

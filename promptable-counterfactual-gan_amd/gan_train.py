@@ -23,10 +23,12 @@ network sequencing C-ABI calls on NHWC activations (csrc/delta_gan.hip holds the
 import torch
 import torch.nn as nn
 
+from . import checkpoint as _ckpt
 from . import ops
 from ._lib import ACT_LRELU, ACT_NONE, ACT_RELU, PcgError
 from .countergan import (PER_CLASS_FIELDS, BCEWithLogitsLoss, Classifier, CrossEntropyLoss, _as_rows, _conv_fwd, _conv_wgrad, _dgrad_act, _geom,
                          _grid_report, _labels, _padded_logits, abs_mean, metrics_from_sums, pick_sources)
+from .data import DeviceLoader
 from .nn import FlatModule, in_conv_precision, linear_dgrad, linear_fwd, linear_wgrad, weighted_sum
 from .optim import Adam
 
@@ -607,7 +609,18 @@ def train_gan(G, D, C, train_loader, params=params, fused=False, rng=None, targe
     epoch, so an epoch makes ONE host read and none inside it.  fused=True: the iterations run through GraphedTrainStep (one replay
     each); nets or a conv_precision the fused step does not take warn once and run the op chain.  params without "target_class"
     (params_random_target) is gan_train_copy.py's loop: every iteration's class is drawn on the device from rng (ops.DeviceRNG; inside
-    the replayed step when fused), or taken from `targets`, an iterable of ints, one per iteration.  Returns {"g_losses", "d_losses"}."""
+    the replayed step when fused), or taken from `targets`, an iterable of ints, one per iteration.
+    Three optional keys of `params` (this function's argument list is the reference-shaped one and stays as it is; the other trainers
+    take the same three as keyword arguments): params["checkpoint"] (a path): the run's whole state (pcgan_amd.checkpoint, DESIGN.md
+    §3.23: both nets, both optimizers, rng, a data.DeviceLoader's generator, torch's CPU generator, the histories) is written there
+    after every params["checkpoint_every"]-th (default 1) epoch.  params["resume"] (a path or a loaded checkpoint): rng is restored
+    first, so that the fused step's device counter starts at the stored offset; the optimizers (and the fused stepper) are built as
+    always, the stored state is restored over them, and training continues with the next epoch.  params["epochs_gan"] may be larger than when the checkpoint was written; batch size, number of
+    rows and rng's seed must be the same; `targets`, if given, holds the classes of the remaining iterations.  A resume at or past
+    the last epoch returns the stored histories without a launch.
+    Returns {"g_losses", "d_losses"}, after a resume the epochs before the interruption included."""
+    checkpoint, checkpoint_every, resume = params.get("checkpoint"), params.get("checkpoint_every", 1), params.get("resume")
+    _ckpt.check_args("train_gan", checkpoint, checkpoint_every, resume)
     _check_classifier(C)
     dev = next(G.parameters()).device
     if dev.type != "cuda":
@@ -615,6 +628,16 @@ def train_gan(G, D, C, train_loader, params=params, fused=False, rng=None, targe
     for p in C.parameters():
         p.requires_grad_(False)                                                        # :99-100
     drawn = params.get("target_class") is None and targets is None
+    run = {"batch_size": int(params["batch_size"]), "n_rows": _ckpt.loader_rows(train_loader), "seed": rng.seed if rng is not None else None}
+    loader = {"loader": train_loader} if isinstance(train_loader, DeviceLoader) else {}
+    state = None
+    if resume is not None:
+        state = _ckpt.open_resume(resume, "train_gan", **run)
+        if _ckpt.value(state, "epoch") >= params["epochs_gan"]:                        # nothing left to run: no launch
+            _ckpt.restore(state, G=G, D=D)
+            return dict(_ckpt.value(state, "history"))
+        if rng is not None:
+            _ckpt.restore(state, rng=rng)                                              # before the stepper makes its device counter from it
     stepper = None
     if fused:
         why = GraphedTrainStep.unsupported(G, D, C)
@@ -628,7 +651,11 @@ def train_gan(G, D, C, train_loader, params=params, fused=False, rng=None, targe
     opt_g, opt_d = (stepper.opt_g, stepper.opt_d) if stepper is not None else make_optimizers(G, D, params)
     source = _TargetSource(params, G.label_embed.num_embeddings, dev, rng=rng, targets=targets, in_step=stepper is not None)
     g_losses, d_losses = [], []
-    for epoch in range(params["epochs_gan"]):
+    first = 0
+    if state is not None:
+        vals = _ckpt.restore(state, G=G, D=D, opt_g=opt_g, opt_d=opt_d, **loader)
+        first, g_losses, d_losses = vals["epoch"], vals["history"]["g_losses"], vals["history"]["d_losses"]
+    for epoch in range(first, params["epochs_gan"]):
         out = None
         for x, y in train_loader:
             x, y = x.to(dev), y.to(dev)                                                # :117-118
@@ -644,6 +671,10 @@ def train_gan(G, D, C, train_loader, params=params, fused=False, rng=None, targe
             print(f"[GAN] Epoch {epoch + 1}/{params['epochs_gan']} | D_loss: {ld:.4f} | G_loss: {lg:.4f}")
         d_losses.append(ld)
         g_losses.append(lg)
+        if _ckpt.due(checkpoint, checkpoint_every, epoch):
+            objs = dict(loader, rng=rng) if rng is not None else loader
+            _ckpt.save(checkpoint, _ckpt.capture(G=G, D=D, opt_g=opt_g, opt_d=opt_d, epoch=epoch + 1,
+                                                 history={"g_losses": g_losses, "d_losses": d_losses}, run=run, **objs))
     return {"g_losses": g_losses, "d_losses": d_losses}
 
 

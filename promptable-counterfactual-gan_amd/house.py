@@ -28,6 +28,7 @@ import torch.nn as nn
 from torch.nn.utils import spectral_norm
 
 from . import _cfeval, ops
+from . import checkpoint as _ckpt
 from ._cfeval import confusion_matrix, metric_rows, save_table, upload  # noqa: F401  (public here: the host side is _cfeval's)
 from ._lib import ACT_LRELU, ACT_NONE, ACT_RELU, PcgError
 from .countergan import CrossEntropyLoss, abs_mean, grad_norm  # noqa: F401  (same loss kernels)
@@ -2110,7 +2111,7 @@ def epoch_permutation(n):
 
 
 def train_countergan(generator, config, X_train, y_train, clf_model, *, rng=None, draws=None, graph=None, log_every=100, verbose=True,
-                     save=True, discriminator=None):
+                     save=True, discriminator=None, checkpoint=None, checkpoint_every=1, resume=None):
     """house_sales_kc_usa/trainer.py:186-378 `train_countergan(generator, config, X_train, y_train, clf_model)` on the HIP kernels —
     same signature, same body:
 
@@ -2133,8 +2134,16 @@ def train_countergan(generator, config, X_train, y_train, clf_model, *, rng=None
 
     graph (default: when the batch size divides into full batches and no `draws` hook is given): every full-size iteration is ONE
     HIP-graph replay (GraphedTrainStep(dataset=..., diag=...)) — the benched rate through the reference-shaped API.
+    checkpoint (a path): the run's whole state (pcgan_amd.checkpoint, DESIGN.md §3.23: both nets, both optimizers, `rng`, torch's CPU
+    generator that epoch_permutation draws from, the histories) is written there after every checkpoint_every-th epoch, which reads
+    the epochs' results at that point.  resume (a path or a loaded checkpoint): everything is built as always -- the seeding and the
+    Discriminator's construction included -- the stored state is restored over it BEFORE the graphed step is built (its device
+    counter starts at the restored offset, its warm-up leaves the loaded Adam state alone), and training continues with the next
+    epoch.  config['epochs'] may be larger than when the checkpoint was written; batch size, number of rows and seed must be the
+    same.  A resume at or past the last epoch returns the stored histories without a launch.
     Returns {"d_losses", "g_losses", "pred_gain", "sparsity", "l2_reg", "class_flip_rate", "G_grad", "D_grad", "discriminator"}
-    (per-epoch lists; the reference returns None)."""
+    (per-epoch lists, after a resume the epochs before the interruption included; the reference returns None)."""
+    _ckpt.check_args("train_countergan", checkpoint, checkpoint_every, resume)
     device = torch.device(config.get("cuda", "cuda"))
     if device.type != "cuda":
         raise PcgError(f"train_countergan: config['cuda'] = {device}; libpcgan_hip has no CPU path")
@@ -2161,6 +2170,17 @@ def train_countergan(generator, config, X_train, y_train, clf_model, *, rng=None
     clf_model.eval()                                                                           # :234
     frozen = not any(p.requires_grad for p in clf_model.parameters())
     rng = rng if rng is not None else ops.DeviceRNG(seed=seed)
+    epochs = int(config["epochs"])
+    names = ("d_losses", "g_losses", "pred_gain", "sparsity", "l2_reg", "class_flip_rate")
+    hist = {k: [] for k in names + ("G_grad", "D_grad")}
+    first = 0
+    if resume is not None:
+        state = _ckpt.open_resume(resume, "train_countergan", batch_size=bs, n_rows=N, seed=seed)
+        vals = _ckpt.restore(state, G=G, D=D, opt_g=opt_g, opt_d=opt_d, rng=rng)
+        first, hist = vals["epoch"], {k: list(vals["history"][k]) for k in hist}
+        if first >= epochs:                                                                    # nothing left to run: no launch
+            hist["discriminator"] = D
+            return hist
     # the classifier on the original rows (:320): frozen, so ONE evaluation for the whole training set serves every iteration
     with torch.no_grad():
         logits_orig = torch.cat([clf_model(X_dev[i:i + 65536]).detach() for i in range(0, N, 65536)]).contiguous()
@@ -2174,13 +2194,12 @@ def train_countergan(generator, config, X_train, y_train, clf_model, *, rng=None
             raise PcgError("train_countergan(graph=True): supplied draws cannot be replayed from a captured step; use graph=False")
         gs = GraphedTrainStep(G, D, clf_model, opt_g, opt_d, norm_vals, bs, cfg, rng=rng, dataset=(X_dev, y_dev), diag=diag,
                               with_critic_wgrad_variant=True)
-    epochs = int(config["epochs"])
-    # per-epoch results stay on the device until someone needs them: verbose prints (and reads) every epoch like the reference,
-    # otherwise ONE read after the last epoch — the host never waits for the GPU inside the loop
+    # per-epoch results stay on the device until someone needs them: verbose prints (and reads) every epoch like the reference, a
+    # checkpoint reads the epochs since the last one, otherwise ONE read after the last epoch — the host never waits for the GPU
+    # inside the loop
     acc_hist = torch.zeros((epochs, 8), dtype=torch.float64, device=device)
     gn_hist = torch.zeros((epochs, 2), dtype=torch.float32, device=device)
-    names = ("d_losses", "g_losses", "pred_gain", "sparsity", "l2_reg", "class_flip_rate")
-    hist = {k: [] for k in names + ("G_grad", "D_grad")}
+    unread = first                                                                             # first epoch whose results are still on the device
 
     def read_epochs(lo, hi):
         a, gn = acc_hist[lo:hi].cpu().numpy(), gn_hist[lo:hi].cpu().numpy()
@@ -2191,7 +2210,7 @@ def train_countergan(generator, config, X_train, y_train, clf_model, *, rng=None
             hist["G_grad"].append(float(gn[e, 0])); hist["D_grad"].append(float(gn[e, 1]))
 
     sched = "inline" if (frozen and not clf_model.training) else None
-    for epoch in range(epochs):                                                                # :237
+    for epoch in range(first, epochs):                                                         # :237
         perm = epoch_permutation(N)[:steps * bs]                                               # :241 (the loader's order)
         perm_dev = perm.to(device)
         ops.fill(acc.view(torch.float32), 0.0)
@@ -2221,11 +2240,18 @@ def train_countergan(generator, config, X_train, y_train, clf_model, *, rng=None
         grad_norm_sum(G, out=gn_hist[epoch, 0:1]); grad_norm_sum(D, out=gn_hist[epoch, 1:2])   # :362
         if verbose:
             read_epochs(epoch, epoch + 1)
+            unread = epoch + 1
             print(f"[{epoch + 1}/{epochs}] D: {hist['d_losses'][-1]:.4f}, G: {hist['g_losses'][-1]:.4f}, "
                   f"pred_gain={hist['pred_gain'][-1]:.4f}, sparsity={hist['sparsity'][-1]:.4f}, l2_reg={hist['l2_reg'][-1]:.4f}, "
                   f"class_flip_rate={hist['class_flip_rate'][-1]:.4f} | G_grad: {hist['G_grad'][-1]:.4f}, D_grad: {hist['D_grad'][-1]:.4f}")
-    if not verbose:
-        read_epochs(0, epochs)
+        if _ckpt.due(checkpoint, checkpoint_every, epoch):
+            if unread <= epoch:
+                read_epochs(unread, epoch + 1)
+                unread = epoch + 1
+            _ckpt.save(checkpoint, _ckpt.capture(G=G, D=D, opt_g=opt_g, opt_d=opt_d, rng=rng, epoch=epoch + 1, history=hist,
+                                                 run={"batch_size": bs, "n_rows": N, "seed": seed}))
+    if unread < epochs:
+        read_epochs(unread, epochs)
     if save and config.get("generator_path"):
         import os
         os.makedirs(os.path.dirname(os.path.abspath(config["generator_path"])) or ".", exist_ok=True)

@@ -31,6 +31,7 @@ import torch.nn as nn
 from torch.nn.utils import spectral_norm
 
 from . import _cfeval, _epoch, ops
+from . import checkpoint as _ckpt
 from ._cfeval import confusion_csv, confusion_matrix, metric_rows, upload  # noqa: F401  (public here: the host side is _cfeval's)
 from ._epoch import no_autograd, on_gpu
 from ._lib import (MoonsCfDesc, MoonsCfEvalArgs, MoonsCfFwdArgs, MoonsCfTrainArgs, MoonsClfFitArgs, MoonsClfFitDesc, PcgError,
@@ -461,7 +462,8 @@ def log_now(epoch, batch_idx, epochs):
     return (epoch + 1) % (epochs * 0.1) == 0 and batch_idx % 5 == 0
 
 
-def train_countergan(generator, config, X_train, y_train, clf_model, *, draws=None, log_every=5, verbose=True, save=True):
+def train_countergan(generator, config, X_train, y_train, clf_model, *, draws=None, log_every=5, verbose=True, save=True,
+                     checkpoint=None, checkpoint_every=1, resume=None):
     """trainer.py:31-128 `train_countergan(generator, config, X_train, y_train, clf_model)` — same signature, same body order:
 
       :32-35   device = config['cuda']; torch.manual_seed / np.random.seed(config['seed'])
@@ -476,8 +478,16 @@ def train_countergan(generator, config, X_train, y_train, clf_model, *, draws=No
       :109-119 the reference's print lines and conditions (log_every: the `batch_idx % 5` of :109)
       :127-128 torch.save(G.state_dict(), config['generator_path'])  (the loss-curve PNG is plotting: left out)
 
-    Returns {"d_losses", "g_losses" (per-epoch means, as the reference collects them), "logs" (the last epoch's [iterations][9]),
-    "discriminator"}.  The parameters' .grad are not specified afterwards (see TrainSteps)."""
+    checkpoint (a path): the run's whole state (pcgan_amd.checkpoint) is written there after every checkpoint_every-th
+    epoch.  resume (a path or a loaded checkpoint): everything above is built as always -- the seeding and the Discriminator's
+    construction included -- then the stored state is restored over it and training continues with the next epoch;
+    config['epochs'] may be larger than when the checkpoint was written; batch size, number of rows and seed must be the same.  The
+    kernel's Adam counters are the optimizers' own segments, so restoring the optimizers restores them.
+
+    Returns {"d_losses", "g_losses" (per-epoch means, as the reference collects them; after a resume the epochs before the
+    interruption included), "logs" (the last epoch's [iterations][9]; None if a resume found nothing left to do), "discriminator"}.
+    The parameters' .grad are not specified afterwards (see TrainSteps)."""
+    _ckpt.check_args("train_countergan", checkpoint, checkpoint_every, resume)
     device = torch.device(config.get("cuda", "cuda"))
     if device.type != "cuda":
         raise PcgError(f"train_countergan: config['cuda'] = {device}; libpcgan_hip has no CPU path")
@@ -499,13 +509,21 @@ def train_countergan(generator, config, X_train, y_train, clf_model, *, draws=No
     opt_D = Adam(D.parameters(), lr=config["lr_D"])                            # :48
     clf_model = clf_model.to(device)                                           # :50
     clf_model.eval()                                                           # :51
-    runner = TrainSteps(G, D, clf_model, opt_G, opt_D, X_t.numpy(), y_np, config)
     rng = ops.DeviceRNG(seed=seed)
-    y_cpu = torch.as_tensor(y_np, dtype=torch.int64)
     epochs = config["epochs"]
     d_losses, g_losses = [], []
     logs = None
-    for epoch in range(epochs):                                                # :56
+    first = 0
+    if resume is not None:
+        # the optimizers have no segments yet: the loaded moments wait in them until TrainSteps asks for the flat segments below
+        state = _ckpt.open_resume(resume, "train_countergan", batch_size=bs, n_rows=N, seed=seed)
+        vals = _ckpt.restore(state, G=G, D=D, opt_G=opt_G, opt_D=opt_D, rng=rng)
+        first, d_losses, g_losses = vals["epoch"], vals["history"]["d_losses"], vals["history"]["g_losses"]
+        if first >= epochs:                                                    # nothing left to run: no launch
+            return {"d_losses": d_losses, "g_losses": g_losses, "logs": None, "discriminator": D}
+    runner = TrainSteps(G, D, clf_model, opt_G, opt_D, X_t.numpy(), y_np, config)
+    y_cpu = torch.as_tensor(y_np, dtype=torch.int64)
+    for epoch in range(first, epochs):                                         # :56
         perm = epoch_permutation(N)[:steps * bs]                               # :58 (the loader's order)
         rows = perm.view(steps, bs)
         if draws is None:
@@ -532,6 +550,10 @@ def train_countergan(generator, config, X_train, y_train, clf_model, *, draws=No
         g_losses.append(np.mean([float(v) for v in L[:, 1]]))                  # :116
         if verbose and (epoch + 1) % (epochs * 0.2) == 0:                      # :118
             print(f"[{epoch+1}/{config['epochs']}] D: {d_losses[-1]:.4f}, G: {g_losses[-1]:.4f}")
+        if _ckpt.due(checkpoint, checkpoint_every, epoch):
+            _ckpt.save(checkpoint, _ckpt.capture(G=G, D=D, opt_G=opt_G, opt_D=opt_D, rng=rng, epoch=epoch + 1,
+                                                 history={"d_losses": d_losses, "g_losses": g_losses},
+                                                 run={"batch_size": bs, "n_rows": N, "seed": seed}))
     if save:
         os.makedirs(config["out_dir"], exist_ok=True)                          # :121
         torch.save({k: v.detach().cpu().contiguous() for k, v in G.state_dict().items()}, config["generator_path"])   # :127

@@ -2072,6 +2072,19 @@ class DeviceRNG:
         self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
         self.offset = 0
 
+    def get_state(self):
+        """{"seed", "offset"}: the whole stream position.  The graphed steppers advance device counters of their own and mirror them
+        into `offset` after every replay, so this is the position at any point between two steps."""
+        return {"seed": self.seed, "offset": self.offset}
+
+    def set_state(self, state):
+        """Continue the stream of get_state().  A device counter is made from `offset` when a stepper is built (device_counter), so
+        restore the stream BEFORE building the stepper that draws from it."""
+        seed, offset = int(state["seed"]), int(state["offset"])
+        if offset < 0:
+            raise _lib.PcgError(f"DeviceRNG.set_state: offset {offset}")
+        self.seed, self.offset = seed & 0xFFFFFFFFFFFFFFFF, offset
+
     def _advance(self, n):
         # the Philox offset is a kernel ARGUMENT held on the host: a draw captured into a HIP graph would replay the same numbers
         # on every launch.  Draw outside the captured step and feed the result in as a static input (GraphedStep.load), or use the
