@@ -1126,6 +1126,10 @@ int pcg_conv_plan_describe(const pcg_conv_geom* g, int32_t op, int32_t assume_sc
  *   PCG_PLAN_ELEMENTWISE              (family, n work items)      the grid-stride launch of one thread per item, "4096 blocks of 256:
  *                                      2 passes"; family: PCG_PLAN_EW_TABULAR (tabular.hip), PCG_PLAN_EW_CF_OPS (cf_ops.hip),
  *                                      PCG_PLAN_EW_POINTWISE (pcg_add_bias_rows), PCG_PLAN_EW_GATHER_CHANNEL (pcg_gather_channel)
+ *   PCG_PLAN_ADAM                     (n, every pointer 16-byte aligned, capturable)   pcg_adam_step (capturable 0) /
+ *                                      pcg_adam_step_capturable (1, at most 256 blocks: PCG_ADAM_TICK_BLOCKS, at least 1, for the
+ *                                      float4 lanes): "float4 lanes: 256 blocks of 256: 2 passes, tail of 3" (the 1..3 elements behind
+ *                                      the 16-byte lanes, on block 0) | "scalar lanes: 256 blocks of 256: 3 passes"
  * The normalisation layer (csrc/batchnorm.hip, instnorm.hip, spectral_norm_body.h); "aligned": every tensor pointer of the call is
  * 16-byte aligned:
  *   PCG_PLAN_BN_COLREDUCE             (rows, C, aligned)          the column reduction of pcg_bn_train_stats / pcg_bn_act_bwd* / pcg_colsum:
@@ -1150,7 +1154,8 @@ int pcg_conv_plan_describe(const pcg_conv_geom* g, int32_t op, int32_t assume_sc
  *                                                                 "loops: 8320 elements exceed 8192"  */
 enum { PCG_PLAN_GEMM_ACT = 0, PCG_PLAN_GEMM = 1, PCG_PLAN_LINEAR_WGRAD = 2, PCG_PLAN_LINEAR_WGRAD_GROUPED = 3, PCG_PLAN_MEAN = 4,
        PCG_PLAN_ABS_MEAN = 5, PCG_PLAN_CROSS_ENTROPY = 6, PCG_PLAN_EMBED_CONCAT_BWD = 7, PCG_PLAN_ACT = 8, PCG_PLAN_ELEMENTWISE = 9,
-       PCG_PLAN_BN_COLREDUCE = 10, PCG_PLAN_BN_APPLY = 11, PCG_PLAN_BN_FINALIZE = 12, PCG_PLAN_INSTNORM = 13, PCG_PLAN_SPECTRAL_NORM = 14 };
+       PCG_PLAN_BN_COLREDUCE = 10, PCG_PLAN_BN_APPLY = 11, PCG_PLAN_BN_FINALIZE = 12, PCG_PLAN_INSTNORM = 13, PCG_PLAN_SPECTRAL_NORM = 14,
+       PCG_PLAN_ADAM = 15 };
 enum { PCG_PLAN_EW_TABULAR = 0, PCG_PLAN_EW_CF_OPS = 1, PCG_PLAN_EW_POINTWISE = 2, PCG_PLAN_EW_GATHER_CHANNEL = 3 };
 int pcg_launch_plan_describe(int32_t op, const int64_t* args, int32_t n_args, char* out, size_t out_bytes);
 size_t pcg_conv_scratch_parts_bytes(void);

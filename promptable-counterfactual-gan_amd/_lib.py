@@ -18,7 +18,7 @@ ACT_NONE, ACT_RELU, ACT_LRELU, ACT_TANH, ACT_SIGMOID = 0, 1, 2, 3, 4
 # pcg_launch_plan_describe: ops and element-wise families (include/pcgan_hip.h)
 (PLAN_GEMM_ACT, PLAN_GEMM, PLAN_LINEAR_WGRAD, PLAN_LINEAR_WGRAD_GROUPED, PLAN_MEAN, PLAN_ABS_MEAN, PLAN_CROSS_ENTROPY,
  PLAN_EMBED_CONCAT_BWD, PLAN_ACT, PLAN_ELEMENTWISE, PLAN_BN_COLREDUCE, PLAN_BN_APPLY, PLAN_BN_FINALIZE, PLAN_INSTNORM,
- PLAN_SPECTRAL_NORM) = range(15)
+ PLAN_SPECTRAL_NORM, PLAN_ADAM) = range(16)
 PLAN_EW_TABULAR, PLAN_EW_CF_OPS, PLAN_EW_POINTWISE, PLAN_EW_GATHER_CHANNEL = range(4)
 
 

@@ -3,6 +3,7 @@
 // next to each prototype in include/pcgan_hip.h.
 #include <cstdlib>
 #include <cstdio>
+#include <cstring>
 #include "epoch_wg.h"
 #include "launch_plan.h"
 
@@ -246,28 +247,42 @@ __global__ void __launch_bounds__(1024) norm_sum_kernel(const float* __restrict_
   }
 }
 
-int adam_launch(float* param, const float* grad, float* m, float* v, int64_t n, double lr, double beta1, double beta2, double eps,
-                double wd, int decoupled, AdamHyper hy, int64_t* step_dev, AdamCache* cache_dev, hipStream_t s) {
-  const bool al = al16(param) && al16(grad) && al16(m) && al16(v);
-  const AdamConst k{(float)lr, adam_k(beta1, beta2, eps), (float)wd, decoupled};
-  // 16-byte lanes over the bulk, the 1..3 trailing elements on three threads of block 0 (a flat buffer that ends in a bias of one
-  // element — the WGAN-GP critic's Linear(1024, 1) — used to send all 25 M parameters down the scalar kernel)
-  const int64_t bulk = al ? (n & ~(int64_t)3) : 0;
-  AdamTick tk{step_dev, cache_dev, lr, beta1, beta2, step_dev ? 1 : 0};
+// The Adam launch, decided once for adam_launch and for PCG_PLAN_ADAM: 16-byte lanes over the bulk, the 1..3 trailing elements on
+// three threads of block 0 (a flat buffer that ends in a bias of one element — the WGAN-GP critic's Linear(1024, 1) — used to send
+// all 25 M parameters down the scalar kernel); scalar lanes when a pointer is off a 16-byte boundary or n < 4.
+struct AdamPlan { bool float4_lanes; int64_t bulk; int tail; unsigned blocks; };
+
+AdamPlan adam_plan(int64_t n, bool all_aligned16, bool capturable) {
+  const int64_t bulk = all_aligned16 ? (n & ~(int64_t)3) : 0;
   if (bulk) {
     unsigned blocks = ew_blocks((size_t)bulk / 4);
-    if (tk.mode) {
+    if (capturable) {
       // every block takes a ticket at the SAME address, and device-scope atomics on one address complete ~9 ns apart (measured: 3494
-      // blocks made an 16 us update 48 us): a grid-stride loop over at most 256 blocks instead (21 us)
-      static const unsigned cap = [] { const char* e = getenv("PCG_ADAM_TICK_BLOCKS"); return e ? (unsigned)atoi(e) : 256u; }();
+      // blocks made an 16 us update 48 us): a grid-stride loop over at most 256 blocks instead (21 us).  The knob is clamped to at
+      // least one block: "0" or a non-number would otherwise ask for an empty grid.
+      static const unsigned cap = [] {
+        const char* e = getenv("PCG_ADAM_TICK_BLOCKS");
+        const int c = e ? atoi(e) : 256;
+        return (unsigned)(c < 1 ? 1 : c);
+      }();
       if (blocks > cap) blocks = cap;
     }
-    hipLaunchKernelGGL(adam_kernel<4>, dim3(blocks), dim3(256), 0, s, param, grad, m, v, (size_t)bulk, (int)(n - bulk), k, hy, tk);
-  } else {
-    unsigned blocks = ew_blocks((size_t)n);
-    if (tk.mode && blocks > 256u) blocks = 256u;
-    hipLaunchKernelGGL(adam_kernel<1>, dim3(blocks), dim3(256), 0, s, param, grad, m, v, (size_t)n, 0, k, hy, tk);
+    return AdamPlan{true, bulk, (int)(n - bulk), blocks};
   }
+  unsigned blocks = ew_blocks((size_t)n);
+  if (capturable && blocks > 256u) blocks = 256u;
+  return AdamPlan{false, n, 0, blocks};
+}
+
+int adam_launch(float* param, const float* grad, float* m, float* v, int64_t n, double lr, double beta1, double beta2, double eps,
+                double wd, int decoupled, AdamHyper hy, int64_t* step_dev, AdamCache* cache_dev, hipStream_t s) {
+  const AdamConst k{(float)lr, adam_k(beta1, beta2, eps), (float)wd, decoupled};
+  AdamTick tk{step_dev, cache_dev, lr, beta1, beta2, step_dev ? 1 : 0};
+  const AdamPlan pl = adam_plan(n, al16(param) && al16(grad) && al16(m) && al16(v), tk.mode != 0);
+  if (pl.float4_lanes)
+    hipLaunchKernelGGL(adam_kernel<4>, dim3(pl.blocks), dim3(256), 0, s, param, grad, m, v, (size_t)pl.bulk, pl.tail, k, hy, tk);
+  else
+    hipLaunchKernelGGL(adam_kernel<1>, dim3(pl.blocks), dim3(256), 0, s, param, grad, m, v, (size_t)pl.bulk, 0, k, hy, tk);
   return launch_status("adam_kernel");
 }
 
@@ -385,6 +400,15 @@ int pcg::describe_pointwise_plan(int32_t op, const int64_t* a, int32_t n_args, c
     const size_t items = v4 ? (size_t)a[0] / 4 : (size_t)a[0];
     const int k = snprintf(buf, bytes, "%s: ", v4 ? "float4 lanes" : "scalar lanes");
     describe_ew_grid(buf + k, bytes - k, items, ew_blocks(items));
+    return PCG_OK;
+  }
+  if (op == PCG_PLAN_ADAM) {
+    PCG_REQUIRE(n_args == 3 && a[0] > 0, "pcg_launch_plan_describe: adam takes (n, every pointer 16-byte aligned, capturable)");
+    const AdamPlan pl = adam_plan(a[0], a[1] != 0, a[2] != 0);
+    int k = snprintf(buf, bytes, "%s: ", pl.float4_lanes ? "float4 lanes" : "scalar lanes");
+    describe_ew_grid(buf + k, bytes - k, pl.float4_lanes ? (size_t)pl.bulk / 4 : (size_t)pl.bulk, pl.blocks);
+    k = (int)strlen(buf);
+    if (pl.tail) snprintf(buf + k, bytes - k, ", tail of %d", pl.tail);
     return PCG_OK;
   }
   if (op == PCG_PLAN_ELEMENTWISE && n_args == 2 && a[1] > 0 && a[0] == PCG_PLAN_EW_POINTWISE) {

@@ -37,6 +37,19 @@ def test_ctypes_table_matches_header():
     assert sorted(_lib.PROTOTYPES) == _declared()
 
 
+def test_plan_constants_match_header():
+    """Every PCG_PLAN_* enumerator of the header has its PLAN_* twin in _lib with the same value, and the other way round: the describe
+    ops (PCG_PLAN_ADAM the latest) and the element-wise families."""
+    from pcgan_amd import _lib
+    text = open(os.path.join(ROOT, "include", "pcgan_hip.h")).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    header = {name: int(value) for name, value in re.findall(r"\bPCG_(PLAN_[A-Z0-9_]+)\s*=\s*(\d+)", text)}
+    mine = {k: v for k, v in vars(_lib).items() if k.startswith("PLAN_")}
+    assert header == mine
+    ops_only = sorted(v for k, v in header.items() if not k.startswith("PLAN_EW_"))
+    assert ops_only == list(range(len(ops_only))) and header["PLAN_ADAM"] == ops_only[-1] == 15
+
+
 def test_no_compute_without_gpu_and_no_fallback():
     """The product path must fail loudly when it cannot run on the GPU: no CPU / PyTorch fallback."""
     import torch

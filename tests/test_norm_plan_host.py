@@ -29,7 +29,7 @@ def test_launch_plan_describe_refuses_bad_norm_arguments():
     bad = [(_lib.PLAN_BN_COLREDUCE, 0, 8, 1), (_lib.PLAN_BN_COLREDUCE, 5, 8), (_lib.PLAN_BN_APPLY, 3, 5, 8, 1), (_lib.PLAN_BN_APPLY, 0, 5, 0, 1),
            (_lib.PLAN_BN_APPLY, 0, 5, 8), (_lib.PLAN_BN_FINALIZE, 0), (_lib.PLAN_BN_FINALIZE, 4, 4), (_lib.PLAN_INSTNORM, 3, 2, 4, 4, 1),
            (_lib.PLAN_INSTNORM, 0, 2, 0, 4, 1), (_lib.PLAN_INSTNORM, 0, 2, 4, 4), (_lib.PLAN_SPECTRAL_NORM, 2, 8, 8), (_lib.PLAN_SPECTRAL_NORM, 0, 257, 8),
-           (_lib.PLAN_SPECTRAL_NORM, 1, 8, 257), (_lib.PLAN_SPECTRAL_NORM, 0, 8), (_lib.PLAN_SPECTRAL_NORM + 1, 1)]
+           (_lib.PLAN_SPECTRAL_NORM, 1, 8, 257), (_lib.PLAN_SPECTRAL_NORM, 0, 8), (_lib.PLAN_ADAM + 1, 1)]
     for args in bad:
         with pytest.raises(pcgan_amd.PcgError, match="pcg_launch_plan_describe"):
             ops.launch_plan(*args)

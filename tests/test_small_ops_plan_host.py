@@ -25,7 +25,7 @@ def test_launch_plan_describe_refuses_what_it_does_not_know():
     from pcgan_amd import _lib, ops
     for args in ((77, 1), (_lib.PLAN_ELEMENTWISE, 9, 100), (_lib.PLAN_GEMM_ACT, 0, 1, 512, 17), (_lib.PLAN_MEAN, 0),
                  (_lib.PLAN_EMBED_CONCAT_BWD, 64, 0, 0), (_lib.PLAN_BN_COLREDUCE, 0, 8, 1), (_lib.PLAN_BN_APPLY, 3, 5, 8, 1),
-                 (_lib.PLAN_BN_FINALIZE, 0), (_lib.PLAN_INSTNORM, 0, 2, 0, 4, 1), (_lib.PLAN_SPECTRAL_NORM, 0, 257, 8)):
+                 (_lib.PLAN_BN_FINALIZE, 0), (_lib.PLAN_INSTNORM, 0, 2, 0, 4, 1), (_lib.PLAN_SPECTRAL_NORM, 0, 257, 8), (_lib.PLAN_ADAM, 0, 1, 1), (_lib.PLAN_ADAM, 8, 1)):
         with pytest.raises(pcgan_amd.PcgError, match="pcg_launch_plan_describe"):
             ops.launch_plan(*args)
     # pcg_gemm has no skinny launch: the shape pcg_gemm_act sends there stays on the tile
