@@ -43,7 +43,7 @@ struct GBufs {
   float* inp;                     // [B][D + NC + D]   (x, onehot, mask): also the cond operand of the FiLM weight gradients
   float* H;                       // [NBLK+1][B][HH]  block inputs h_0..h_5
   float* Z1; float* Z2;           // [NBLK][B][HH]    pre-BatchNorm activations
-  float* P;                       // [2*NBLK][nblocks][2][HH]  partial column sums (sum, sum of squares) per BatchNorm
+  float* P;                       // [2*NBLK][nblocks][2][HH]  partial column sums of (z - p), (z - p)^2, p = the block's first row of z
   float* SM;                      // [2*NBLK][2][HH]  saved mean / invstd
   float* running;                 // BatchNorm buffers are separate tensors: pointers per layer come in RS
   float* cont; float* logits; float* soft; float* hard;   // outputs ([B][ncont], [B][T] x3; hard nullable)
@@ -82,6 +82,21 @@ __device__ __forceinline__ void pload(PRegs& r, const float* __restrict__ P, int
   for (int b = part; b < nblocks; b += NPART) { s += (double)P[(size_t)b * 2 * HH + c]; q += (double)P[(size_t)b * 2 * HH + HH + c]; }
   r.s = s; r.q = q;
 }
+// The forward's partial sums are PIVOTED (colsums_m): block b holds the sums of (z - p_b) and (z - p_b)^2 over its n_b live rows,
+// p_b = its first row of Z as stored.  The pivot is folded back here, in fp64: sum z = s_b + n_b p_b, sum z^2 = q_b + p_b (2 s_b +
+// n_b p_b).  (Plain fp32 sums of z and z^2 left var = E[z^2] - mean^2 with an error of ~14 u (mean / std)^2 relative: 2e-5 at a
+// ratio of 4.9, and the shipped nets reach 5.2 on their first BatchNorm.)
+__device__ __forceinline__ void pload_piv(PRegs& r, const float* __restrict__ P, const float* __restrict__ Z, int nblocks, int B) {
+  const int c = threadIdx.x & (HH - 1), part = threadIdx.x >> 5;
+  double s = 0.0, q = 0.0;
+#pragma unroll 8
+  for (int b = part; b < nblocks; b += NPART) {
+    const double sb = (double)P[(size_t)b * 2 * HH + c], qb = (double)P[(size_t)b * 2 * HH + HH + c];
+    const double pv = (double)Z[(size_t)b * FT * HH + c], n = (double)min(FT, B - b * FT);
+    s += sb + n * pv; q += qb + pv * (2.0 * sb + n * pv);
+  }
+  r.s = s; r.q = q;
+}
 struct CondRegs { float v[(MAXCOND + NQ - 1) / NQ]; };
 // cond = (one-hot target, mask): wave q brings in elements q, q+4, ... of its rows
 __device__ __forceinline__ void cload(CondRegs& r, const float* __restrict__ onehot, const float* __restrict__ mask, size_t row, bool on, int q) {
@@ -112,6 +127,7 @@ struct alignas(16) SmemM {
   float C[MK_C * PRM_];                     // cond, k-major (rows 21 .. 23 zero)
   float A[HH * PRM_];                       // the Linear's input, k-major
   float ws[NQ][2][HH];                      // per-wave column sums
+  float pv[NQ][HH];                         // per-wave pivots
   double fin[NPART][2][HH];
 };
 // registers -> LDS as stored with pitch PWM, pad columns zero
@@ -159,22 +175,35 @@ __device__ __forceinline__ void bn_finish_m(SmemM& s, int B, float eps, float mo
   }
   __syncthreads();
 }
-// column sums of v and v*v over the block's 64 rows from the accumulator layout (lane: rows 4 lq + r of its wave, column ct * 16 + li):
-// in-lane over r, across lq at distances 16 and 32, the four waves through LDS in wave order
-__device__ __forceinline__ void colsums_m(SmemM& s, const m16_t (&v)[2], const bool (&ok)[4], int wave, int li, int lq, float* part) {
+// pivoted column sums of the block's live rows from the accumulator layout (lane: rows 4 lq + r of its wave, column ct * 16 + li):
+// every wave subtracts ITS first row (lane li's register 0, one shuffle: no barrier) before it adds and squares — in-lane over r,
+// across lq at distances 16 and 32 —, and the 64 threads that add the four waves in wave order first move each wave's pair to the
+// block's pivot p = wave 0's (d = p_w - p: sum + n_w d, squares + d (2 sum + n_w d)); part = sums of (v - p), (v - p)^2, and p is
+// row 0 of the block as the caller stores it (pload_piv reads it back from there).
+template <class Smem>
+__device__ __forceinline__ void colsums_m(Smem& s, const m16_t (&v)[2], const bool (&ok)[4], int wave, int li, int lq, int live, float* part) {
 #pragma unroll
   for (int ct = 0; ct < 2; ++ct) {
+    const float pv = __shfl(v[ct][0], li);
     float s1 = 0.f, s2 = 0.f;
 #pragma unroll
-    for (int r = 0; r < 4; ++r) { const float x = ok[r] ? v[ct][r] : 0.f; s1 += x; s2 += x * x; }
+    for (int r = 0; r < 4; ++r) { const float x = ok[r] ? v[ct][r] - pv : 0.f; s1 += x; s2 += x * x; }
     s1 += __shfl_xor(s1, 16); s2 += __shfl_xor(s2, 16);
     s1 += __shfl_xor(s1, 32); s2 += __shfl_xor(s2, 32);
-    if (lq == 0) { s.ws[wave][0][ct * 16 + li] = s1; s.ws[wave][1][ct * 16 + li] = s2; }
+    if (lq == 0) { s.ws[wave][0][ct * 16 + li] = s1; s.ws[wave][1][ct * 16 + li] = s2; s.pv[wave][ct * 16 + li] = pv; }
   }
   __syncthreads();
   if (threadIdx.x < 2 * HH) {
     const int st = threadIdx.x >> 5, c = threadIdx.x & (HH - 1);
-    part[st * HH + c] = (s.ws[0][st][c] + s.ws[1][st][c]) + (s.ws[2][st][c] + s.ws[3][st][c]);
+    const float p0 = s.pv[0][c];
+    float t[NQ];
+#pragma unroll
+    for (int w = 0; w < NQ; ++w) {
+      const int nw = min(max(live - 16 * w, 0), 16);
+      const float n = (float)nw, d = nw ? s.pv[w][c] - p0 : 0.f, sw = s.ws[w][0][c];
+      t[w] = st == 0 ? fmaf(n, d, sw) : fmaf(d, fmaf(2.f, sw, n * d), s.ws[w][1][c]);
+    }
+    part[st * HH + c] = (t[0] + t[1]) + (t[2] + t[3]);
   }
 }
 
@@ -186,6 +215,7 @@ struct alignas(16) SmemF {
   float IN[MK_IN * PRM_];
   float A[HH * PRM_];
   float ws[NQ][2][HH];
+  float pv[NQ][HH];
 };
 __global__ void __launch_bounds__(NT) g_fwd_first4_kernel(const float* __restrict__ PRM, GBufs a, GDesc d) {
   __shared__ SmemF s;
@@ -252,21 +282,7 @@ __global__ void __launch_bounds__(NT) g_fwd_first4_kernel(const float* __restric
 #pragma unroll
     for (int r = 0; r < 4; ++r)
       if (ok[r]) a.Z1[(rowA + r) * HH + ct * 16 + li] = z[ct][r];
-  // column sums (as colsums_m, on this kernel's own LDS block)
-#pragma unroll
-  for (int ct = 0; ct < 2; ++ct) {
-    float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) { const float x = ok[r] ? z[ct][r] : 0.f; s1 += x; s2 += x * x; }
-    s1 += __shfl_xor(s1, 16); s2 += __shfl_xor(s2, 16);
-    s1 += __shfl_xor(s1, 32); s2 += __shfl_xor(s2, 32);
-    if (lq == 0) { s.ws[wave][0][ct * 16 + li] = s1; s.ws[wave][1][ct * 16 + li] = s2; }
-  }
-  __syncthreads();
-  if (threadIdx.x < 2 * HH) {
-    const int st = threadIdx.x >> 5, c = threadIdx.x & (HH - 1);
-    a.P[(size_t)blockIdx.x * 2 * HH + st * HH + c] = (s.ws[0][st][c] + s.ws[1][st][c]) + (s.ws[2][st][c] + s.ws[3][st][c]);
-  }
+  colsums_m(s, z, ok, wave, li, lq, min(FT, a.B - (int)blockIdx.x * FT), a.P + (size_t)blockIdx.x * 2 * HH);
 }
 
 // kind A (block k): bn1 statistics -> a1 = relu(film(bn1(z1))) ; z2 = fc2(a1), partial statistics
@@ -296,7 +312,7 @@ __global__ void __launch_bounds__(NT) g_fwd_a4_kernel(const float* __restrict__ 
     g_bn = PRM[f.bn_g + threadIdx.x]; b_bn = PRM[f.bn_b + threadIdx.x];
     if (f.rmean) { rm_old = f.rmean[threadIdx.x]; rv_old = f.rvar[threadIdx.x]; }     // every block: no block-0 detour in the burst
   }
-  pload(pr, a.P + (size_t)lyr * a.nblocks * 2 * HH, a.nblocks);
+  pload_piv(pr, a.P + (size_t)lyr * a.nblocks * 2 * HH, Zk, a.nblocks, a.B);
   PCG_T(1);
   // ---- into LDS
   wstore_m<MAXCOND>(s.Wg, s.bg, w_g);
@@ -345,7 +361,7 @@ __global__ void __launch_bounds__(NT) g_fwd_a4_kernel(const float* __restrict__ 
 #pragma unroll
     for (int r = 0; r < 4; ++r)
       if (ok[r]) Z2k[(rowA + r) * HH + ct * 16 + li] = z2[ct][r];
-  colsums_m(s, z2, ok, wave, li, lq, a.P + ((size_t)(lyr + 1) * a.nblocks + blockIdx.x) * 2 * HH);
+  colsums_m(s, z2, ok, wave, li, lq, min(FT, a.B - (int)blockIdx.x * FT), a.P + ((size_t)(lyr + 1) * a.nblocks + blockIdx.x) * 2 * HH);
   PCG_T(7);
 }
 
@@ -380,7 +396,7 @@ __global__ void __launch_bounds__(NT) g_fwd_b4_kernel(const float* __restrict__ 
     g_bn = PRM[f.bn_g + threadIdx.x]; b_bn = PRM[f.bn_b + threadIdx.x];
     if (f.rmean) { rm_old = f.rmean[threadIdx.x]; rv_old = f.rvar[threadIdx.x]; }
   }
-  pload(pr, a.P + (size_t)lyr * a.nblocks * 2 * HH, a.nblocks);
+  pload_piv(pr, a.P + (size_t)lyr * a.nblocks * 2 * HH, Zk, a.nblocks, a.B);
   wstore_m<MAXCOND>(s.Wg, s.bg, w_g);
   wstore_m<MAXCOND>(s.Wb, s.bb, w_b);
   if (more) wstore_m<HH>(s.Wf, s.bf, w_fc);
@@ -424,7 +440,7 @@ __global__ void __launch_bounds__(NT) g_fwd_b4_kernel(const float* __restrict__ 
 #pragma unroll
     for (int r = 0; r < 4; ++r)
       if (ok[r]) Z1n[(rowA + r) * HH + ct * 16 + li] = z1[ct][r];
-  colsums_m(s, z1, ok, wave, li, lq, a.P + ((size_t)(lyr + 1) * a.nblocks + blockIdx.x) * 2 * HH);
+  colsums_m(s, z1, ok, wave, li, lq, min(FT, a.B - (int)blockIdx.x * FT), a.P + ((size_t)(lyr + 1) * a.nblocks + blockIdx.x) * 2 * HH);
 }
 
 // ---- output heads ----------------------------------------------------------------------------------------------------------------
@@ -1019,8 +1035,24 @@ using namespace pcg;
 
 static bool heads_at_most_32_wide(const GDesc& d) {      // a lane keeps its half of a head's columns (<= 16) in registers
   for (int h = 0; h < d.nheads; ++h)
-    if (d.seg[h + 1] - d.seg[h] > 32) return false;
+    if (d.seg[h + 1] - d.seg[h] < 1 || d.seg[h + 1] - d.seg[h] > 32) return false;
   return true;
+}
+
+// What the segment and head kernels are built for, asked by the forward AND the backward entry before any launch.  nheads >= 1:
+// with no categorical column tile_walk divides by T = 0 and tile_load clamps to element -1.  ncont >= 1: nothing faults without a
+// continuous column (every division by ncont sits under e < rows * ncont), but the kernels have never run that shape and the module
+// sends it to the op chain; it is refused here rather than left untested.
+static int desc_ok(const GDesc& d, const char* entry) {
+  PCG_REQUIRE(d.hidden == 32 && d.nblocks == 5, "%s: built for hidden width 32 and 5 residual blocks (got %d, %d)", entry, d.hidden, d.nblocks);
+  PCG_REQUIRE(d.D == DIN && d.NC == NCLS, "%s: built for input_dim 17 and 4 classes (got %d, %d)", entry, d.D, d.NC);
+  PCG_REQUIRE(d.nheads >= 1 && d.nheads <= MAXHEADS, "%s: nheads = %d, built for 1 .. %d categorical heads", entry, d.nheads, MAXHEADS);
+  PCG_REQUIRE(d.ncont >= 1 && d.ncont <= HH, "%s: ncont = %d, built for 1 .. %d continuous columns", entry, d.ncont, HH);
+  PCG_REQUIRE(d.seg[0] == 0 && heads_at_most_32_wide(d), "%s: every head is 1 .. 32 columns wide and the first starts at column 0", entry);
+  PCG_REQUIRE(d.seg[d.nheads] <= MAXT && d.seg[d.nheads] + d.ncont <= MAXCOLS,
+              "%s: T = %d packed categorical columns (<= %d), T + ncont = %d output columns (<= %d)", entry, d.seg[d.nheads], MAXT,
+              d.seg[d.nheads] + d.ncont, MAXCOLS);
+  return PCG_OK;
 }
 
 // C-side mirrors of the argument blocks (plain arrays of offsets / pointers: see include/pcgan_hip.h)
@@ -1029,10 +1061,7 @@ extern "C" int pcg_house_g_fwd(const pcg_house_g_desc* desc, const pcg_house_g_f
   static_assert(sizeof(pcg_house_g_desc) == sizeof(GDesc), "descriptor layouts differ");
   GDesc d;
   std::memcpy(&d, desc, sizeof(d));
-  PCG_REQUIRE(desc->hidden == 32 && desc->nblocks == 5, "pcg_house_g_fwd: built for hidden width 32 and 5 residual blocks");
-  PCG_REQUIRE(d.D == DIN && d.NC == NCLS && d.nheads >= 0 && d.nheads <= MAXHEADS && d.ncont >= 0 &&
-                  d.ncont <= HH && d.seg[d.nheads] <= MAXT && d.seg[d.nheads] + d.ncont <= MAXCOLS && heads_at_most_32_wide(d),
-              "pcg_house_g_fwd: built for input_dim 17, 4 classes, <= 8 heads, <= 96 packed categorical + continuous output columns");
+  if (int e = desc_ok(d, "pcg_house_g_fwd")) return e;
   PCG_REQUIRE(args->B > 0 && args->params && args->x && args->onehot && args->mask && args->noise && args->inp && args->H && args->Z1 &&
                   args->Z2 && args->P && args->SM && args->cont && args->logits && args->soft,
               "pcg_house_g_fwd: null buffer");
@@ -1065,9 +1094,10 @@ extern "C" int pcg_house_g_fwd(const pcg_house_g_desc* desc, const pcg_house_g_f
 
 extern "C" int pcg_house_g_bwd(const pcg_house_g_desc* desc, const pcg_house_g_bwd_args* args, pcg_stream_t stream) {
   PCG_REQUIRE(desc && args, "pcg_house_g_bwd: null argument block");
+  static_assert(sizeof(pcg_house_g_desc) == sizeof(GDesc), "descriptor layouts differ");
   GDesc d;
   std::memcpy(&d, desc, sizeof(d));
-  PCG_REQUIRE(desc->hidden == 32 && desc->nblocks == 5 && d.D == DIN && d.NC == NCLS, "pcg_house_g_bwd: built for hidden width 32, 5 residual blocks, input_dim 17, 4 classes");
+  if (int e = desc_ok(d, "pcg_house_g_bwd")) return e;
   PCG_REQUIRE(args->B > 0 && args->params && args->grads && args->onehot && args->mask && args->H && args->Z1 && args->Z2 && args->SM &&
                   args->soft && args->DH && args->DZ1 && args->DZ2 && args->A1 && args->DN1 && args->DG && args->DB && args->DZIN &&
                   args->DL && args->DC && args->Q,

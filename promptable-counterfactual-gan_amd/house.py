@@ -124,16 +124,16 @@ class ResidualGenerator(FlatModule):
         """The dimensions of _fused_ok (below) without its training clause: what the one-launch evaluation kernel is built for."""
         bn = self.blocks[0].bn1 if len(self.blocks) else None
         return (self.hidden_dim == 32 and len(self.blocks) == 5 and bn is not None
-                and self.input_dim == 17 and self.num_classes == 4 and self.total_cat <= 96 and len(self.cat_idx) <= 8
+                and self.input_dim == 17 and self.num_classes == 4 and 1 <= self.total_cat <= 96 and len(self.cat_idx) <= 8
                 and self.total_cat + len(self.continuous_idx) <= 96 and all(b_ - a_ <= 32 for a_, b_ in zip(self.seg, self.seg[1:]))
-                and len(self.continuous_idx) <= 32 and all(b_.bn1.eps == bn.eps and b_.bn2.eps == bn.eps for b_ in self.blocks))
+                and 1 <= len(self.continuous_idx) <= 32 and all(b_.bn1.eps == bn.eps and b_.bn2.eps == bn.eps for b_ in self.blocks))
 
     def _fused_ok(self):
         bn = self.blocks[0].bn1 if len(self.blocks) else None
         return (self.use_fused and self.hidden_dim == 32 and len(self.blocks) == 5 and self.training and bn is not None
-                and self.input_dim == 17 and self.num_classes == 4 and self.total_cat <= 96 and len(self.cat_idx) <= 8
+                and self.input_dim == 17 and self.num_classes == 4 and 1 <= self.total_cat <= 96 and len(self.cat_idx) <= 8
                 and self.total_cat + len(self.continuous_idx) <= 96 and all(b_ - a_ <= 32 for a_, b_ in zip(self.seg, self.seg[1:]))
-                and len(self.continuous_idx) <= 32 and all(b_.bn1.momentum == bn.momentum and b_.bn2.eps == bn.eps for b_ in self.blocks))
+                and 1 <= len(self.continuous_idx) <= 32 and all(b_.bn1.momentum == bn.momentum and b_.bn2.eps == bn.eps for b_ in self.blocks))
 
     def _fused_desc(self):
         """Element offsets of every parameter in the flat buffer (rebuilt when the module is re-flattened)."""
@@ -237,6 +237,7 @@ class ResidualGenerator(FlatModule):
         for s_, f in enumerate(self.cat_idx):
             add(self.fc_cat_logits[str(f)], h_last, g["DL"][:, self.seg[s_]:], ldy=T)
         ops.linear_wgrad_grouped(items, B, onehot.device)
+        return g
 
     # -- small device-side index tables (seg offsets, column indices) -------------------------------------------------
     def index_tables(self, device):

@@ -122,3 +122,69 @@ def test_graphed_step_refuses_unknown_overlap_values(overlap):
     from pcgan_amd import PcgError, house as H
     with pytest.raises(PcgError, match="overlap must be"):
         H.GraphedTrainStep(None, None, None, None, None, None, 128, overlap=overlap)
+
+
+def _g_desc(_lib, widths, ncont, **over):
+    d = _lib.HouseGDesc(nheads=len(widths), ncont=ncont, D=17, NC=4, hidden=32, nblocks=5)
+    for s, w in enumerate(widths):
+        d.seg[s + 1] = d.seg[s] + w
+    for k, v in over.items():
+        setattr(d, k, v)
+    return d
+
+
+# descriptors pcg_house_g_fwd and pcg_house_g_bwd refuse before any launch (csrc/house_fused.hip: desc_ok), and a word of the message
+BAD_G_DESCS = [
+    ("nheads = 0", [], 10, "nheads = 0"),                      # T = 0: tile_walk would divide by it
+    ("ncont = 0", [9, 30], 0, "ncont = 0"),                    # never run by the fused kernels: the module takes the op chain
+    ("9 heads", [2] * 8, 1, "nheads = 9"),                     # (made 9 below: seg has 9 entries)
+    ("a 33-wide head", [33, 5], 4, "1 .. 32 columns wide"),
+    ("an empty head", [5, 0, 5], 4, "1 .. 32 columns wide"),
+    ("T = 97", [32, 32, 32, 1], 1, "T = 97"),
+    ("T + ncont = 97", [32, 32, 31], 2, "T + ncont = 97"),
+    ("ncont = 33", [9], 33, "ncont = 33"),
+]
+
+
+@pytest.mark.parametrize("what,widths,ncont,word", BAD_G_DESCS, ids=[b[0] for b in BAD_G_DESCS])
+def test_generator_descriptor_refused_by_forward_and_backward(what, widths, ncont, word):
+    """Every pointer is a fake non-null address and B = 5: a call that got past the descriptor checks would launch on them."""
+    from pcgan_amd import _lib
+    lib = _lib.load()
+    d = _g_desc(_lib, widths, ncont)
+    if what == "9 heads":
+        d.nheads = 9
+    f = _fill(_lib.HouseGFwdArgs(), B=5, running_mean=_ptrs(10), running_var=_ptrs(10), num_batches_tracked=_ptrs(10))
+    b = _fill(_lib.HouseGBwdArgs(), B=5, accumulate=0)
+    for entry, args in (("pcg_house_g_fwd", f), ("pcg_house_g_bwd", b)):
+        assert word in _refused(lib, getattr(lib, entry)(d, args, None), entry), (what, entry)
+
+
+def test_generator_descriptor_fixed_dimensions_refused_by_forward_and_backward():
+    from pcgan_amd import _lib
+    lib = _lib.load()
+    f = _fill(_lib.HouseGFwdArgs(), B=5, running_mean=_ptrs(10), running_var=_ptrs(10), num_batches_tracked=_ptrs(10))
+    b = _fill(_lib.HouseGBwdArgs(), B=5, accumulate=0)
+    for over, word in ((dict(hidden=64), "hidden width 32"), (dict(nblocks=4), "5 residual blocks"), (dict(D=16), "input_dim 17"),
+                       (dict(NC=3), "4 classes")):
+        d = _g_desc(_lib, [9, 30, 6, 2, 5, 5, 13], 10, **over)
+        for entry, args in (("pcg_house_g_fwd", f), ("pcg_house_g_bwd", b)):
+            assert word in _refused(lib, getattr(lib, entry)(d, args, None), entry), (over, entry)
+    # and the null-buffer check behind them still answers for a descriptor that passes
+    d = _g_desc(_lib, [9, 30, 6, 2, 5, 5, 13], 10)
+    f.soft = None
+    b.Q = None
+    assert "null buffer" in _refused(lib, lib.pcg_house_g_fwd(d, f, None), "pcg_house_g_fwd")
+    assert "null buffer" in _refused(lib, lib.pcg_house_g_bwd(d, b, None), "pcg_house_g_bwd")
+
+
+@pytest.mark.parametrize("cont,cats", [([], {0: 9, 1: 30}), (list(range(17)), {})], ids=["no continuous column", "no categorical head"])
+def test_generator_without_heads_or_continuous_columns_takes_the_chain(cont, cats):
+    """Neither _fused_ok nor _eval_dims_ok may send T = 0 or ncont = 0 to the fused kernels; the house configuration still goes."""
+    from pcgan_amd import house as H
+    G = H.ResidualGenerator(17, 32, 4, cont, cats)
+    G.train()
+    assert not G._fused_ok() and not G._eval_dims_ok()
+    G = H.ResidualGenerator(17, 32, 4, H.CONFIG["continuous_idx"], H.CONFIG["categorical_info"])
+    G.train()
+    assert G._fused_ok() and G._eval_dims_ok()
