@@ -94,7 +94,8 @@ def _step1(T, B, path):
         for k, v in fused.items():
             fwd["step." + k] = v.cpu()
     torch.cuda.synchronize()
-    res = {"losses": {k: float(out[k].cpu()) for k in RS.LOSSES}, "fwd": fwd, "pins": pins, "grad_G": _grads(G), "grad_D": _grads(D)}
+    res = {"losses": {k: float(out[k].cpu()) for k in RS.LOSSES}, "fwd": fwd, "pins": pins, "grad_G": _grads(G), "grad_D": _grads(D),
+           "nets": (G, D)}                                                      # after the step: D as the G step saw it
     _cache[(B, path)] = res
     return res
 

@@ -98,7 +98,7 @@ def _run_head(ops, d, tally0=(1.5, 2.0, 3.0)):
 
 
 @pytest.mark.parametrize("K", [3, 10, 16])
-@pytest.mark.parametrize("R", [1, 5, 8, 128])
+@pytest.mark.parametrize("R", [1, 5, 8, 15, 16, 17, 127, 128])           # 15, 16, 17, 127: the 16-row m-tile edges of mnist_clf_head_kernel
 def test_head_against_float64(ops, R, K):
     d = _head_data(R, K, 17 * R + K)
     r64 = RS.head(d["h"].double(), d["m1"], 0.5, d["W2"].double(), d["b2"].double(), d["y"])
