@@ -29,6 +29,7 @@ import torch.nn.functional as F
 
 from . import ops
 from ._cfeval import confusion_csv, write_png_gray
+from ._graphed import BatchWalkFit
 from ._lib import ACT_LRELU, ACT_NONE, ACT_RELU, PcgError
 from .nn import weighted_sum, FlatModule, FrozenClassifier, in_conv_precision
 from .optim import Adam
@@ -1002,7 +1003,7 @@ def _warn_fused_fallback(why):
         _fused_fallback_warned = True
 
 
-class ClassifierFit:
+class ClassifierFit(BatchWalkFit):
     """The classifier pre-training step (trainer.py:16-21) with fused launches around the three convolutions (csrc/mnist_clf.hip;
     DESIGN.md §3.17): the batch gather with the two Dropout masks, conv1..3 with their ReLU, Dropout2d + Flatten, fc1 with its ReLU,
     the head (Dropout, fc2, loss, tally and their backward down to fc1's pre-activation), fc1's weight gradient and grad-input, the
@@ -1010,7 +1011,8 @@ class ClassifierFit:
     graph, so a step is one replay.  The training set, the epoch's permutation, the activations and the tally (sum of loss * rows,
     correct rows, rows) live on the device; nothing is read back inside an epoch.  One graph for the full batch, one for the tail
     N % batch_size (a tail of one row is valid: there is no BatchNorm).  Gradients are overwritten every step: no zero_grad.
-    graph=False: the same entries called eagerly with by-value draws (what the replays must equal)."""
+    graph=False: the same entries called eagerly with by-value draws (what the replays must equal).  The walk over the epoch, the
+    capture and the tally readers are _graphed.BatchWalkFit's."""
 
     CHANNELS = [1, 32, 64, 128]
     HW_IN, FEAT, HIDDEN, MAX_K, MAX_ROWS = 28, 128 * 7 * 7, 256, 16, 128
@@ -1043,9 +1045,9 @@ class ClassifierFit:
         dev = next(classifier.parameters()).device
         if dev.type != "cuda":
             raise PcgError(f"ClassifierFit: the classifier is on {dev}; libpcgan_hip has no CPU path")
-        self.classifier, self.B = classifier, int(batch_size)
+        self.classifier = classifier
         X = torch.as_tensor(x_train).to(dev, torch.float32)
-        self.N = int(X.shape[0])
+        super().__init__(X.shape[0], batch_size)
         D = self.HW_IN * self.HW_IN
         if self.N < 1 or self.B < 1 or X.numel() != self.N * D:
             raise PcgError(f"ClassifierFit: need x [N, 1, {self.HW_IN}, {self.HW_IN}] and y [N]")
@@ -1053,7 +1055,6 @@ class ClassifierFit:
         self.Y = torch.as_tensor(y_train).to(dev, torch.int64).contiguous()
         if self.Y.shape != (self.N,):
             raise PcgError(f"ClassifierFit: need x [N, 1, {self.HW_IN}, {self.HW_IN}] and y [N]")
-        self.tail = self.N % self.B
         self.rng = rng if rng is not None else ops.DeviceRNG(seed=0)
         classifier.train()
         classifier._ensure_flat()
@@ -1063,24 +1064,20 @@ class ClassifierFit:
         self._fc1, self._fc2 = classifier.fc[1], classifier.fc[4]
         self._p2d, self._p1 = classifier.conv[6].p, classifier.fc[3].p
         self.K = self._fc2.out_features
-        self._tallies = torch.zeros(6, dtype=torch.float64, device=dev)
-        self.tally, self.val_tally = self._tallies[:3], self._tallies[3:]
-        self.perm = torch.arange(self.N, dtype=torch.int64, device=dev)               # identity until new_epoch()
-        self._cur = 0
-        self._ctr = self.rng.device_counter(dev, cursor=True)
+        self._start(classifier, dev, graph)
+
+    def _buffers(self, R):
+        dev = self.X.device
         f32 = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev)      # noqa: E731
         C = self.CHANNELS
-        self._bufs = {}
-        for R in sorted({self.B if self.N >= self.B else 0, self.tail} - {0}):
-            geoms, hw = [], self.HW_IN
-            for conv in self._convs:
-                geoms.append(_geom(conv, R, hw, hw))
-                hw = geoms[-1].OH
-            self._bufs[R] = {"x": f32(R, D), "y": torch.zeros((R,), dtype=torch.int64, device=dev), "m": [f32(R, C[3]), f32(R, self.HIDDEN)],
-                             "g": geoms, "a": [f32(R, g.OH, g.OW, g.Cout) for g in geoms], "flat": f32(R, self.FEAT), "h": f32(R, self.HIDDEN),
-                             "logits": f32(R, self.K), "loss": f32(1), "dh": f32(R, self.HIDDEN), "dflat": f32(R, self.FEAT),
-                             "d3": f32(R, geoms[2].OH, geoms[2].OW, C[3])}
-        self._graphs = self._capture() if graph else None
+        geoms, hw = [], self.HW_IN
+        for conv in self._convs:
+            geoms.append(_geom(conv, R, hw, hw))
+            hw = geoms[-1].OH
+        return {"x": f32(R, self.HW_IN * self.HW_IN), "y": torch.zeros((R,), dtype=torch.int64, device=dev), "m": [f32(R, C[3]), f32(R, self.HIDDEN)],
+                "g": geoms, "a": [f32(R, g.OH, g.OW, g.Cout) for g in geoms], "flat": f32(R, self.FEAT), "h": f32(R, self.HIDDEN),
+                "logits": f32(R, self.K), "loss": f32(1), "dh": f32(R, self.HIDDEN), "dflat": f32(R, self.FEAT),
+                "d3": f32(R, geoms[2].OH, geoms[2].OW, C[3])}
 
     def _span(self, R):
         return ops.DeviceRNG.mnist_clf_batch_span(R, [self.CHANNELS[3], self.HIDDEN])
@@ -1125,101 +1122,6 @@ class ClassifierFit:
             ops.colsum(d.numel() // conv.out_channels, conv.out_channels, d, conv.bias.grad, False)
             if i > 0:
                 d = _dgrad_act(g, d, ops.ohwi(conv.weight.data), below, ACT_RELU, 0.0)
-
-    def _capture(self):
-        """Capture needs one real execution of every launch first; the parameters, the Adam state, the tally and the counter are put
-        back afterwards."""
-        net = self.classifier
-        params0 = net.flat_params.clone()
-        ctr0, tal0 = self._ctr.clone(), self._tallies.clone()
-        snap = self.optimizer.snapshot()
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for R, b in self._bufs.items():
-                self._launches(b)
-                self._ctr.copy_(ctr0)
-        torch.cuda.current_stream().wait_stream(side)
-        # no finalizer may run while the stream captures (see nn._HipGraphCapture.begin): the cyclic collector is held off.  It is not
-        # run first: what is garbage now stays so until the collector is back on.
-        import gc
-        gc_on = gc.isenabled()
-        gc.disable()
-        graphs = {}
-        try:
-            for R, b in self._bufs.items():
-                graphs[R] = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(graphs[R]):
-                    self._launches(b)
-        finally:
-            if gc_on:
-                gc.enable()
-        net.flat_params.copy_(params0)
-        self.optimizer.restore(snap)
-        self._ctr.copy_(ctr0); self._tallies.copy_(tal0)
-        return graphs
-
-    def new_epoch(self, perm):
-        """Upload this epoch's row order (N entries) and rewind the cursor: one small copy per EPOCH."""
-        if perm.numel() != self.N:
-            raise PcgError(f"ClassifierFit.new_epoch: permutation of {perm.numel()} entries, {self.N} needed")
-        self.perm.copy_(perm.to(torch.int64))
-        self._ctr[2:3].zero_()
-        self._cur = 0
-
-    @property
-    def steps_per_epoch(self):
-        return self.N // self.B + (1 if self.tail else 0)
-
-    def step(self, record=None):
-        """The next batch of the epoch: one replay (Adam is inside it).  record (a dict): receives clones of the batch's rows ("x",
-        "y"), its masks ("masks") and its loss ("loss", a [1] device tensor)."""
-        left = self.N - self._cur
-        if left <= 0:
-            raise PcgError("ClassifierFit.step: the epoch is used up; call new_epoch(perm)")
-        R = self.B if left >= self.B else left
-        b = self._bufs[R]
-        if self._graphs is not None:
-            self._graphs[R].replay()
-            self.rng.offset += self._span(R)                  # the host-side mirror of the device counter
-        else:
-            self._launches(b, cursor=self._cur)
-        self._cur += R
-        if record is not None:
-            record.update(x=b["x"].clone(), y=b["y"].clone(), masks=[m.clone() for m in b["m"]], loss=b["loss"].clone())
-        return R
-
-    def run_batch(self, x, y, masks):
-        """Forward, loss and backward of one GIVEN batch with GIVEN Dropout masks (runs that must reproduce recorded draws), called
-        eagerly: the gradients land in the flat gradient buffer, the tally counts the batch; no Adam.  Returns the loss ([1], device)."""
-        R = int(x.shape[0])
-        if R not in self._bufs:
-            raise PcgError(f"ClassifierFit.run_batch: {R} rows; this fit holds buffers for {sorted(self._bufs)}")
-        b = self._bufs[R]
-        b["x"].copy_(x.reshape(R, -1)); b["y"].copy_(y)
-        for dst, src in zip(b["m"], masks):
-            dst.copy_(src.reshape(dst.shape))
-        self._forward_backward(b)
-        return b["loss"]
-
-    def epoch(self, perm):
-        """All steps of one epoch in the order perm, with no host read."""
-        self.new_epoch(perm)
-        for _ in range(self.steps_per_epoch):
-            self.step()
-
-    def read_tally(self):
-        """(sum of loss * rows, correct rows, rows) of the training steps since the last read; clears it.  One host read."""
-        t = self.tally.cpu().tolist()
-        self.tally.zero_()
-        return tuple(t)
-
-    def read_tallies(self):
-        """The training tally and val_tally (same layout; train_classifier's validation launches add to it) in ONE host read; clears
-        both."""
-        t = self._tallies.cpu().tolist()
-        self._tallies.zero_()
-        return tuple(t)
 
 
 VAL_CHUNK = 4096   # rows per eval-mode forward of train_classifier(fused=True)'s validation

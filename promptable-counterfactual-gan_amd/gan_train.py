@@ -25,6 +25,7 @@ import torch.nn as nn
 
 from . import checkpoint as _ckpt
 from . import ops
+from ._graphed import Held, capture_steps
 from ._lib import ACT_LRELU, ACT_NONE, ACT_RELU, PcgError
 from .countergan import (PER_CLASS_FIELDS, BCEWithLogitsLoss, Classifier, CrossEntropyLoss, _as_rows, _conv_fwd, _conv_wgrad, _dgrad_act, _geom,
                          _grid_report, _labels, _padded_logits, abs_mean, metrics_from_sums, pick_sources)
@@ -309,19 +310,6 @@ def train_step(G, D, C, opt_g, opt_d, x, y, target, params=params):
             "loss_reg": loss_reg.detach()}
 
 
-_warmup_streams = {}
-
-
-def _warmup_stream(dev):
-    """ONE side stream per device for the warm-up execution of every capture.  A stream's first convolution hands it 64 MiB of stream-K
-    scratch for the life of the process (ops._conv_scratch), so a fresh stream per capture -- one per batch size per stepper -- pinned
-    that much per graph."""
-    key = dev.index if dev.index is not None else torch.cuda.current_device()
-    if key not in _warmup_streams:
-        _warmup_streams[key] = torch.cuda.Stream(dev)
-    return _warmup_streams[key]
-
-
 class GraphedTrainStep:
     """The iteration of gan_train.py:117-144 on the fused launches of csrc/delta_gan.hip around the library's convolutions, captured
     once per batch size as a single-stream, strictly linear HIP graph: a step is two small copies (the batch into the graph's input
@@ -490,33 +478,8 @@ class GraphedTrainStep:
     def _capture(self, b, draw=False):
         """Capture needs one real execution of every launch first; the parameters, the Adam state and the draw's device counter are put
         back afterwards."""
-        G, D = self.G, self.D
-        p0 = G.flat_params.clone(), D.flat_params.clone()
-        ctr0 = self._ctr.clone() if draw else None
-        snaps = self.opt_g.snapshot(), self.opt_d.snapshot()
-        side = _warmup_stream(self.dev)
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            self._launches(b, draw)
-        torch.cuda.current_stream().wait_stream(side)
-        if snaps[0] is None:                                  # the first execution built the Adam state: capture sees it at step 0 again
-            self.opt_g.restore(None); self.opt_d.restore(None)
-        # no finalizer may run while the stream captures (see nn._HipGraphCapture.begin): the cyclic collector is held off
-        import gc
-        gc_on = gc.isenabled()
-        gc.disable()
-        try:
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph):
-                self._launches(b, draw)
-        finally:
-            if gc_on:
-                gc.enable()
-        G.flat_params.copy_(p0[0]); D.flat_params.copy_(p0[1])
-        self.opt_g.restore(snaps[0]); self.opt_d.restore(snaps[1])
-        if draw:
-            self._ctr.copy_(ctr0)                             # the warm-up execution drew from the counter: back to the stream's position
-        return graph
+        held = Held((self.G, self.D), (self.opt_g, self.opt_d), (self._ctr if draw else None,))
+        return capture_steps([(lambda: self._launches(b, draw), 1)], held, self.dev)[0][0]
 
     def step(self, x, y, target=None):
         """One iteration on the batch (x [R,1,28,28] or [R,784], y [R], target [R]).  target None (a stepper built with rng): the

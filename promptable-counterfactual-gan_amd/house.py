@@ -30,6 +30,7 @@ from torch.nn.utils import spectral_norm
 from . import _cfeval, ops
 from . import checkpoint as _ckpt
 from ._cfeval import confusion_matrix, metric_rows, save_table, upload  # noqa: F401  (public here: the host side is _cfeval's)
+from ._graphed import BatchWalkFit, Held, capture_steps
 from ._lib import ACT_LRELU, ACT_NONE, ACT_RELU, PcgError
 from .countergan import CrossEntropyLoss, abs_mean, grad_norm  # noqa: F401  (same loss kernels)
 from .nn import FlatModule, FrozenClassifier, affine_fwd, in_conv_precision, linear_dgrad as _lin_dgrad, linear_fwd as _lin_fwd, linear_wgrad as _lin_wgrad, mean, weighted_sum  # noqa: F401
@@ -1632,11 +1633,8 @@ class GraphedTrainStep:
         self.target_y = torch.ones((batch,), dtype=torch.int64, device=dev)
         self.mask = torch.ones((batch, D_in), dtype=torch.float32, device=dev)
         self.noise = torch.zeros((batch, T), dtype=torch.float32, device=dev)
-        nets = (generator, discriminator)
-        for n in nets:
+        for n in (generator, discriminator):
             n._ensure_flat()
-        saved = [(n.flat_params.clone(), [b.clone() for b in n.buffers()]) for n in nets]
-        osnap = [o.snapshot() for o in (opt_g, opt_d)]
 
         nc = config["num_classes"]
         # one-hot rows of target_y and y: static inputs of the scheduled step (draw_batch_randoms(onehots=self.onehots) fills them with
@@ -1658,14 +1656,12 @@ class GraphedTrainStep:
             self.src = torch.zeros((batch,), dtype=torch.int64, device=dev)
             self.perm = torch.arange((X.shape[0] // batch) * batch, dtype=torch.int64, device=dev)      # identity until new_epoch()
             self._imm = torch.tensor(list(config.get("immutable_idx", [])), dtype=torch.int32, device=dev)
-        ctr0 = self._ctr.clone() if rng is not None else None
         sdiag = None
         if diag is not None:
             sdiag = dict(diag)
             if dataset is not None and diag["logits_orig"].shape[0] != batch:
                 sdiag["src_rows"] = self.src
         self._diag = sdiag
-        acc0 = sdiag["acc"].clone() if sdiag is not None and sdiag.get("acc") is not None else None
 
         def step(skip_dead=True):
             if dataset is not None:
@@ -1678,40 +1674,11 @@ class GraphedTrainStep:
                               config, gumbel=self.noise, branch=self.branch, onehots=self.onehots if self.branch is not None else None,
                               diag=sdiag, skip_dead_d_wgrad=skip_dead)
         self._nc = nc
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for _ in range(max(1, warmup)):
-                step()
-            if with_critic_wgrad_variant:
-                step(False)
-        torch.cuda.current_stream().wait_stream(side)
-        import gc
-        gc.collect()                 # no finalizer may run while the stream captures (see nn._HipGraphCapture.begin)
-        gc_on = gc.isenabled()
-        gc.disable()
-        try:
-            self.graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.graph):
-                self.out = step()
-            self.graph_full = self.out_full = None
-            if with_critic_wgrad_variant:
-                self.graph_full = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(self.graph_full):
-                    self.out_full = step(False)
-        finally:
-            if gc_on:
-                gc.enable()
-        for n, (fp, bufs) in zip(nets, saved):
-            n.flat_params.copy_(fp)
-            for b, b0 in zip(n.buffers(), bufs):
-                b.copy_(b0)
-        for o, sn in zip((opt_g, opt_d), osnap):
-            o.restore(sn)
-        if rng is not None:
-            self._ctr.copy_(ctr0)        # the warm-up steps drew from the counter (and walked the cursor): back to the stream's position
-        if acc0 is not None:
-            sdiag["acc"].copy_(acc0)     # ... and added to the epoch accumulators
+        # the warm-up steps draw from the counter (and walk the cursor) and add to the epoch accumulators: held with the nets and Adam
+        held = Held((generator, discriminator), (opt_g, opt_d), (self._ctr, sdiag.get("acc") if sdiag is not None else None))
+        runs = [(step, max(1, warmup))] + ([(lambda: step(False), 1)] if with_critic_wgrad_variant else [])
+        got = capture_steps(runs, held, dev, collect=True)
+        (self.graph, self.out), (self.graph_full, self.out_full) = got[0], got[1] if with_critic_wgrad_variant else (None, None)
 
     def new_epoch(self, perm):
         """dataset mode: upload this epoch's row order (int64, at least steps * batch entries; only whole batches are used —
@@ -1786,14 +1753,15 @@ def _warn_fused_fallback(why):
         _fused_fallback_warned = True
 
 
-class ClassifierFit:
+class ClassifierFit(BatchWalkFit):
     """The classifier pre-training step (trainer.py:78-91) as whole-batch dense launches (csrc/dense_rows.hip): the batch
     gather with the three Dropout masks, four post-activation forward stages, the logits, the loss head with its tally, four stage
     backwards, five weight gradients -- 16 launches captured once as a single-stream, strictly linear HIP graph -- and AdamW, launched
     eagerly after each replay (its lr is a by-value argument that ReduceLROnPlateau changes).  The training set, the epoch's
     permutation, the saved activations and the tally (sum of loss * rows, correct rows, rows) live on the device; nothing is read
     back inside an epoch.  One graph for the full batch, one for the tail N % batch_size; a tail of one row is refused, as
-    BatchNorm1d refuses it.  graph=False: the same entries called eagerly with by-value draws (what the replays must equal)."""
+    BatchNorm1d refuses it.  graph=False: the same entries called eagerly with by-value draws (what the replays must equal).  The walk
+    over the epoch, the capture and the tally readers are _graphed.BatchWalkFit's."""
 
     DIMS = [17, 256, 256, 128, 64, 4]
 
@@ -1815,13 +1783,12 @@ class ClassifierFit:
         dev = next(model.parameters()).device
         if dev.type != "cuda":
             raise PcgError(f"ClassifierFit: the model is on {dev}; libpcgan_hip has no CPU path")
-        self.model, self.B = model, int(batch_size)
+        self.model = model
         self.X = torch.as_tensor(np.asarray(X_train), dtype=torch.float32).to(dev).contiguous()
         self.Y = torch.as_tensor(np.asarray(y_train), dtype=torch.int64).to(dev).contiguous()
-        self.N = int(self.X.shape[0])
+        super().__init__(self.X.shape[0], batch_size)
         if self.X.dim() != 2 or self.X.shape[1] != self.DIMS[0] or self.Y.shape != (self.N,):
             raise PcgError(f"ClassifierFit: need X [N, {self.DIMS[0]}] and y [N]")
-        self.tail = self.N % self.B
         if self.B < 2 or self.N < 2 or self.tail == 1:
             raise PcgError(f"ClassifierFit: {self.N} rows in batches of {self.B} leave a batch of one row; training-mode BatchNorm1d "
                            "needs more than 1 row per batch")
@@ -1833,20 +1800,19 @@ class ClassifierFit:
         self.optimizer = AdamW(model.parameters(), lr=lr, weight_decay=weight_decay)
         self._stages, self._last = model._stages()
         self._slopes = [m.negative_slope for m in model.net if isinstance(m, nn.LeakyReLU)]
-        self._tallies = torch.zeros(6, dtype=torch.float64, device=dev)
-        self.tally, self.val_tally = self._tallies[:3], self._tallies[3:]
-        self.perm = torch.arange(self.N, dtype=torch.int64, device=dev)               # identity until new_epoch()
-        self._cur = 0
-        self._ctr = self.rng.device_counter(dev, cursor=True)
+        self._start(model, dev, graph)       # AdamW stays outside the graphs, and the warm-up: its state is held all the same
+
+    def _buffers(self, R):
+        dev = self.X.device
         f32 = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev)      # noqa: E731
         widths = self.DIMS[1:5]
-        self._bufs = {}
-        for R in sorted({self.B if self.N >= self.B else 0, self.tail} - {0}):
-            self._bufs[R] = {"x": f32(R, self.DIMS[0]), "y": torch.zeros((R,), dtype=torch.int64, device=dev),
-                             "m": [f32(R, w) for w in widths[:3]], "a": [f32(R, w) for w in widths], "h": [f32(R, w) for w in widths],
-                             "mean": [f32(w) for w in widths], "invstd": [f32(w) for w in widths], "d": [f32(R, w) for w in widths],
-                             "logits": f32(R, self.DIMS[5]), "dl": f32(R, self.DIMS[5]), "loss": f32(1)}
-        self._graphs = self._capture() if graph else None
+        return {"x": f32(R, self.DIMS[0]), "y": torch.zeros((R,), dtype=torch.int64, device=dev),
+                "m": [f32(R, w) for w in widths[:3]], "a": [f32(R, w) for w in widths], "h": [f32(R, w) for w in widths],
+                "mean": [f32(w) for w in widths], "invstd": [f32(w) for w in widths], "d": [f32(R, w) for w in widths],
+                "logits": f32(R, self.DIMS[5]), "dl": f32(R, self.DIMS[5]), "loss": f32(1)}
+
+    def _after_step(self):
+        self.optimizer.step()                # eagerly after every replay: the lr is a by-value argument
 
     def _span(self, R):
         return ops.DeviceRNG.house_clf_batch_span(R, self.DIMS[1:4])
@@ -1881,98 +1847,6 @@ class ClassifierFit:
         ops.dense_rows_wgrad(b["dl"], b["h"][-1], last.weight.grad, None)
         for s in range(len(st) - 1, -1, -1):
             ops.dense_rows_wgrad(b["d"][s], b["x"] if s == 0 else b["h"][s - 1], st[s][0].weight.grad, None)
-
-    def _capture(self):
-        """Capture needs one real execution of every launch first; the BatchNorm buffers, the tally and the counter are put back."""
-        bufs = [t.clone() for t in self.model.buffers()]
-        ctr0, tal0 = self._ctr.clone(), self._tallies.clone()
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for R, b in self._bufs.items():
-                self._launches(b)
-                self._ctr.copy_(ctr0)
-        torch.cuda.current_stream().wait_stream(side)
-        # no finalizer may run while the stream captures (see nn._HipGraphCapture.begin): the cyclic collector is held off.  It is not
-        # run first: what is garbage now stays so until the collector is back on, and a collection costs 60 ms, more than two epochs.
-        import gc
-        gc_on = gc.isenabled()
-        gc.disable()
-        graphs = {}
-        try:
-            for R, b in self._bufs.items():
-                graphs[R] = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(graphs[R]):
-                    self._launches(b)
-        finally:
-            if gc_on:
-                gc.enable()
-        for t, t0 in zip(self.model.buffers(), bufs):
-            t.copy_(t0)
-        self._ctr.copy_(ctr0); self._tallies.copy_(tal0)
-        return graphs
-
-    def new_epoch(self, perm):
-        """Upload this epoch's row order (N entries) and rewind the cursor: one small copy per EPOCH."""
-        if perm.numel() != self.N:
-            raise PcgError(f"ClassifierFit.new_epoch: permutation of {perm.numel()} entries, {self.N} needed")
-        self.perm.copy_(perm.to(torch.int64))
-        self._ctr[2:3].zero_()
-        self._cur = 0
-
-    @property
-    def steps_per_epoch(self):
-        return self.N // self.B + (1 if self.tail else 0)
-
-    def step(self, record=None):
-        """The next batch of the epoch: one replay, then AdamW.  record (a dict): receives clones of the batch's rows ("x", "y"), its
-        masks ("masks") and its loss ("loss", a [1] device tensor)."""
-        left = self.N - self._cur
-        if left <= 0:
-            raise PcgError("ClassifierFit.step: the epoch is used up; call new_epoch(perm)")
-        R = self.B if left >= self.B else left
-        b = self._bufs[R]
-        if self._graphs is not None:
-            self._graphs[R].replay()
-            self.rng.offset += self._span(R)                  # the host-side mirror of the device counter
-        else:
-            self._launches(b, cursor=self._cur)
-        self.optimizer.step()
-        self._cur += R
-        if record is not None:
-            record.update(x=b["x"].clone(), y=b["y"].clone(), masks=[m.clone() for m in b["m"]], loss=b["loss"].clone())
-        return R
-
-    def run_batch(self, x, y, masks):
-        """Forward, loss and backward of one GIVEN batch with GIVEN Dropout masks (runs that must reproduce recorded draws), called
-        eagerly: the gradients land in the flat gradient buffer, the tally counts the batch; no AdamW.  Returns the loss ([1], device)."""
-        R = int(x.shape[0])
-        if R not in self._bufs:
-            raise PcgError(f"ClassifierFit.run_batch: {R} rows; this fit holds buffers for {sorted(self._bufs)}")
-        b = self._bufs[R]
-        b["x"].copy_(x); b["y"].copy_(y)
-        for dst, src in zip(b["m"], masks):
-            dst.copy_(src)
-        self._forward_backward(b)
-        return b["loss"]
-
-    def epoch(self, perm):
-        """All steps of one epoch in the order perm, with no host read."""
-        self.new_epoch(perm)
-        for _ in range(self.steps_per_epoch):
-            self.step()
-
-    def read_tally(self):
-        """(sum of loss * rows, correct rows, rows) of the training steps since the last read; clears it.  One host read."""
-        t = self.tally.cpu().tolist()
-        self.tally.zero_()
-        return tuple(t)
-
-    def read_tallies(self):
-        """The training tally and val_tally (same layout; train_classifier's validation launch adds to it) in ONE host read; clears both."""
-        t = self._tallies.cpu().tolist()
-        self._tallies.zero_()
-        return tuple(t)
 
 
 def train_classifier(X_train_all, X_test, y_train_all, y_test, scaler, config, device=None, verbose=True, fused=False):

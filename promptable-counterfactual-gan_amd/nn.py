@@ -19,6 +19,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
+from ._graphed import Held, HipGraphCapture as _HipGraphCapture      # the backend's home is _graphed; it stays importable from here
 from ._lib import ACT_LRELU, ACT_NONE, ACT_RELU, ACT_SIGMOID, ACT_TANH, PcgError
 
 
@@ -1028,59 +1029,6 @@ class _CutDP:
         self._owner._cut(self._dp.wait_all)
 
 
-class _HipGraphCapture:
-    """Capture backend of GraphedStep: HIP graphs (torch.cuda.CUDAGraph), every segment in ONE memory pool."""
-
-    def __init__(self, device, tick=True):
-        self._pool = None
-        self._tick = torch.zeros(1, device=device) if tick else None     # tick=False: one segment holding the whole step, never empty
-
-    def warmup(self, run, n, dp):
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for _ in range(n):
-                run()
-            if dp is not None:
-                dp.wait_all()
-        torch.cuda.current_stream().wait_stream(side)
-
-    def begin(self):
-        # Python's cyclic collector must not run while a stream captures: freeing a graph, an event or a cached block from a finalizer
-        # is a HIP call the capture forbids, and an error raised inside a finalizer aborts the process.  Collect now, hold it off.
-        import gc
-        gc.collect()
-        self._gc_was_on = gc.isenabled()
-        gc.disable()
-        try:
-            self._g = torch.cuda.CUDAGraph()
-            # thread_local: calls made by other threads (the RCCL watchdog polling events) must not invalidate the capture
-            self._ctx = torch.cuda.graph(self._g, pool=self._pool, capture_error_mode="thread_local")
-            self._ctx.__enter__()
-        except BaseException:
-            self._gc_restore()         # the capture never began: end() will not run, the collector must not stay off
-            raise
-        if self._tick is not None:
-            self._tick.add_(1.0)   # no segment is ever empty (an empty capture cannot be instantiated)
-
-    def _gc_restore(self):
-        if getattr(self, "_gc_was_on", False):
-            import gc
-            gc.enable()
-        self._gc_was_on = False
-
-    def end(self):
-        try:
-            self._ctx.__exit__(None, None, None)
-        finally:
-            self._gc_restore()
-        if self._pool is None:
-            self._pool = self._g.pool()
-        return self._g             # .replay()
-
-    abort = end
-
-
 class GraphedStep:
     """A whole training step captured once in a HIP graph and replayed with one host call — the host then cannot starve the GPU,
     whether the step is short (small per-GPU batches, the tabular nets) or the host cores are slow or shared.
@@ -1110,8 +1058,7 @@ class GraphedStep:
                            "cannot be captured in a HIP graph: run the step eagerly")
         for m in modules:
             m._ensure_flat()
-        saved = [(m.flat_params.clone(), [b.clone() for b in m.buffers()]) for m in modules]
-        osnap = [o.snapshot() for o in optimizers]
+        held = Held(modules, optimizers)
         run = step_fn if dp is None else (lambda: step_fn(dp))
         if capture is None:
             # the segments of a data-parallel program may hold no launch (the paired step starts with wait(G)): they carry a one-element add;
@@ -1130,12 +1077,7 @@ class GraphedStep:
         if dp is not None:
             dp.wait_all()
         self.graph = self.program[0][0]
-        for m, (fp, bufs) in zip(modules, saved):
-            m.flat_params.copy_(fp)
-            for b, b0 in zip(m.buffers(), bufs):
-                b.copy_(b0)
-        for o, sn in zip(optimizers, osnap):
-            o.restore(sn)
+        held.restore()
 
     def _end(self, op):
         self.program.append((self._capture.end(), op))

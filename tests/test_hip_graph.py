@@ -151,6 +151,113 @@ def test_collector_is_handed_back_when_capture_cannot_begin(pcg, monkeypatch):
     assert gc.isenabled()
 
 
+def _adam_state(opt):
+    return [t.clone() for built in opt._segments or [] for st in built for t in (st["exp_avg"], st["exp_avg_sq"], st["step"])]
+
+
+def _house_fit(pcg):
+    from pcgan_amd import house as H
+    torch.manual_seed(3)
+    model = H.NNClassifier(17, 4).to(DEV)
+    rng = pcg.ops.DeviceRNG(9)
+    rng.rand((5,), DEV)                                      # the stream does not start at offset 0
+    X, y = torch.rand(5, 17).numpy(), torch.tensor([0, 1, 2, 3, 0]).numpy()
+    return {"nets": [model], "rng": rng, "opts": lambda s: [s.optimizer], "state": lambda s: [s._ctr, s._tallies],
+            "build": lambda: H.ClassifierFit(model, X, y, torch.tensor([0.5, 1.0, 1.5, 2.0], device=DEV), 3, rng=rng),
+            "graphs": lambda s: sorted(s._graphs) == [2, 3]}
+
+
+def _mnist_fit(pcg):
+    from pcgan_amd import countergan as K
+    torch.manual_seed(3)
+    model = K.CNNClassifier().to(DEV)
+    rng = pcg.ops.DeviceRNG(9)
+    rng.rand((5,), DEV)
+    X, y = (torch.rand(5, 1, 28, 28) * 2 - 1).numpy(), torch.tensor([3, 1, 4, 1, 5]).numpy()
+    return {"nets": [model], "rng": rng, "opts": lambda s: [s.optimizer], "state": lambda s: [s._ctr, s._tallies],
+            "build": lambda: K.ClassifierFit(model, X, y, 4, rng=rng), "graphs": lambda s: sorted(s._graphs) == [1, 4]}
+
+
+def _delta_gan_step(pcg):
+    """The stepper captures at the first step of a batch size: one step with a given target (the plain graph; Adam now stands at
+    step 1 with moments), then the capture under test is the DRAWN graph of the same batch size."""
+    from pcgan_amd import countergan as K, gan_train as T
+    torch.manual_seed(3)
+    G, D, C = T.Generator().to(DEV), T.Discriminator().to(DEV), K.Classifier().to(DEV).eval()
+    rng = pcg.ops.DeviceRNG(9)
+    rng.rand((5,), DEV)
+    stepper = T.GraphedTrainStep(G, D, C, 3, dict(T.params), rng=rng)
+    x, y = (torch.rand(3, 1, 28, 28) * 2 - 1).to(DEV), torch.tensor([3, 1, 4], device=DEV)
+    stepper.step(x, y, torch.tensor([7, 7, 7], device=DEV))
+
+    def build():
+        stepper._draw_graphs[3] = stepper._capture(stepper._bufs[3], draw=True)
+        return stepper
+    return {"nets": [G, D], "rng": rng, "opts": lambda s: [s.opt_g, s.opt_d], "state": lambda s: [s._ctr], "build": build,
+            "graphs": lambda s: sorted(s._draw_graphs) == sorted(s._graphs) == [3], "opts_before": [stepper.opt_g, stepper.opt_d],
+            "state_before": [stepper._ctr]}
+
+
+def _house_step(pcg):
+    """One eager step first, so that Adam holds moments and a step count that the warm-up would visibly advance."""
+    from pcgan_amd import house as H
+    B = 128
+    torch.manual_seed(3)
+    C = H.NNClassifier(17, 4).to(DEV).eval()
+    for p in C.parameters():
+        p.requires_grad = False
+    G = H.ResidualGenerator(17, 32, 4, H.CONFIG["continuous_idx"], H.CONFIG["categorical_info"], tau=0.5).to(DEV)
+    D = H.Discriminator(17, 32, 4).to(DEV)
+    opt_g, opt_d = H.make_optimizers(G, D)
+    norm = H.cat_norm_maps(G, H.CONFIG, torch.device(DEV))
+    rng = pcg.ops.DeviceRNG(9)
+    x, y = torch.rand(B, 17, device=DEV), torch.randint(0, 4, (B,), device=DEV)
+    t, m, noise = H.draw_batch_randoms(rng, G, y, H.CONFIG, torch.device(DEV))
+    H.train_step(G, D, C, opt_g, opt_d, x, y, t, m, norm, gumbel=noise)
+    diag = {"logits_orig": torch.randn(B, 4, device=DEV), "acc": torch.arange(1.0, 9.0, dtype=torch.float64, device=DEV), "eps": 1e-3}
+    return {"nets": [G, D], "rng": rng, "opts": lambda s: [opt_g, opt_d], "state": lambda s: [s._ctr, diag["acc"]],
+            "build": lambda: H.GraphedTrainStep(G, D, C, opt_g, opt_d, norm, B, rng=rng, diag=diag, with_critic_wgrad_variant=True),
+            "graphs": lambda s: s.graph is not None and s.graph_full is not None, "opts_before": [opt_g, opt_d], "state_before": [diag["acc"]]}
+
+
+@pytest.mark.parametrize("make", [_house_fit, _mnist_fit, _delta_gan_step, _house_step])
+def test_building_a_graphed_stepper_does_not_advance_training(pcg, make):
+    """Every stepper on _graphed.capture_steps, at the smallest shape its own tests build it with (a full batch plus a tail: both buffer
+    sets): warm-up and capture leave every parameter, module buffer, Adam moment and step count, the device counter, rng.offset and
+    the tallies / accumulators bit-identical to clones taken before; the collector is enabled afterwards; and a second stepper in the
+    same process warms up on the same one stream per device."""
+    import gc
+    from pcgan_amd import _graphed
+    case = make(pcg)
+    nets, rng = case["nets"], case["rng"]
+    before = {"params": [n.flat_params.clone() for n in nets], "bufs": [b.clone() for n in nets for b in n.buffers()], "offset": rng.offset,
+              "adam": [_adam_state(o) for o in case.get("opts_before", [])], "state": [t.clone() for t in case.get("state_before", [])]}
+    assert gc.isenabled()
+    stepper = case["build"]()
+    torch.cuda.synchronize()
+    assert gc.isenabled() and case["graphs"](stepper)
+    assert all(torch.equal(n.flat_params, p) for n, p in zip(nets, before["params"]))
+    assert all(torch.equal(b, b0) for b, b0 in zip([b for n in nets for b in n.buffers()], before["bufs"]))
+    assert rng.offset == before["offset"]
+    ctr = case["state"](stepper)[0]
+    assert ctr.tolist()[:2] == [rng.offset, 0] and not any(ctr.tolist()[2:])             # the stream's position, no ticket, cursor 0
+    if before["adam"]:                                       # the optimizers existed before: every moment and step count as it was
+        after = [_adam_state(o) for o in case["opts"](stepper)]
+        assert all(len(a) == len(b) > 0 and all(torch.equal(u, v) for u, v in zip(a, b)) for a, b in zip(after, before["adam"]))
+        assert all(int(a[2]) > 0 and a[0].any() for a in after)                     # ... and it was a state worth keeping
+    else:                                                    # built by the stepper: never stepped
+        assert all(not t.any() for o in case["opts"](stepper) for t in _adam_state(o))
+    if before["state"]:
+        assert all(torch.equal(u, v) for u, v in zip(case["state"](stepper)[-len(before["state"]):], before["state"]))
+    else:
+        assert not case["state"](stepper)[1].any()           # the tallies of a fit start at zero
+    streams = dict(_graphed._warmup_streams)
+    assert len(streams) == 1
+    case["build"]()
+    torch.cuda.synchronize()
+    assert _graphed._warmup_streams == streams and gc.isenabled()
+
+
 def test_native_rccl_exports_one_rank(pcg):
     """pcg_dp_* (RCCL behind the C ABI) on a one-rank communicator: in-stream average, side-stream begin / record / wait with
     follow-up work queued behind the reduction, float64 sum, broadcast — and the ordering against the producer stream."""
