@@ -1095,6 +1095,13 @@ int pcg_dp_shutdown(void);
  *   "pad_clip_dgrad"    what "pad_clip" 1 does with grad-input launches: 1 (default) those the schedule model predicts no loss for,
  *                       its measured unit cost included, from one round of 512 workgroups up; 0 none (forward-kernel launches
  *                       only); 2 (measurements) every eligible one; other values are refused.  PCG_PAD_CLIP_DGRAD=v for a whole process.
+ *   "wgrad_padskip"     fp32 weight gradients of k4 s2 p1 layers (pcg_conv_wgrad_padskip_query): 0 today's launches; 1 the consumer
+ *                       waves leave out the MFMAs whose x operand is all padding — same products otherwise, in the same order, so
+ *                       the result is bit-identical for finite dy (a non-finite dy at a padded position gives NaN under 0 and is
+ *                       ignored under 1), with the blocks ordered so that a skipping tile shares its CU with a full one, for the
+ *                       layer classes that measured a gain (OW = 4 and 8; default); 2 / 3 (measurements) every eligible launch, in
+ *                       that paired order / in today's order; other values are refused.  PCG_WGRAD_PADSKIP=v for a whole process (a value
+ *                       outside 0 .. 3 there means the default).
  * value -1 restores the built-in choice.  Results stay correct under every setting (the order of a sum changes, not its terms). */
 int pcg_tune_set(const char* name, int32_t value);
 
@@ -1202,6 +1209,17 @@ int pcg_conv_cliptab_register(const pcg_conv_geom* g, void* host_out, size_t byt
 double pcg_conv_sched_model(const int32_t* ktiles, int32_t n);
 int pcg_conv_pad_clip_query(const pcg_conv_geom* g, int32_t op, int32_t groups, int32_t assume_scratch, int32_t* taken, int32_t* order,
                             int32_t* tile_rows, double* predicted);
+/* The padding skip of the weight gradients (pcg_tune_set "wgrad_padskip"): plain host code, no device.  *applies 1 for op 2 (grad-weight)
+ * in fp32 operand precision on a k4 s2 p1 geometry with IH = 2 OH, IW = 2 OW, OH and OW powers of two >= 4 and Cin a multiple of 64, else
+ * 0 (ops 0 and 1, the bf16 mode and every other geometry launch what they always did); *fraction: the share of the launch's MFMAs left
+ * out — 1/8 for OW = 4 (one MFMA in four for the taps kw = 0 and 3), 1 / (2 OH) for OW >= 8 (one k-group in OH for kh = 0 and 3) —
+ * or 0.  The switch itself is not consulted.  Outputs may be NULL.                                                                 */
+int pcg_conv_wgrad_padskip_query(const pcg_conv_geom* g, int32_t op, int32_t* applies, double* fraction);
+/* What a plain fp32 weight-gradient launch of `g` does under the current switches, decided as pcg_conv2d_wgrad decides it (host code,
+ * no device): *mode 0 today's kernel, 1 the skipping consumers in today's block order, 2 in the paired order; *pair_bit: the bit m of
+ * the paired order (blocks b of every odd round of 256 work as block b ^ m), 0 where the order stays as it is.  assume_scratch as in
+ * pcg_conv_plan_describe.  Outputs may be NULL.                                                                                  */
+int pcg_conv_wgrad_padskip_plan(const pcg_conv_geom* g, int32_t assume_scratch, int32_t* mode, int32_t* pair_bit);
 /* Diagnostic builds only (`make -C csrc stamp`, -DPCG_CLOCK_STAMP): every conv kernel block leaves {shader-clock ticks, 100 MHz
  * ticks} of its main loop at buf[2*block], buf[2*block+1] (uint64) — the clock the chip holds inside the kernel.  Returns 1 when
  * this build stamps, 0 for the shipped library (which compiles no stamp code).  buf = NULL turns it off.                        */

@@ -353,6 +353,8 @@ PROTOTYPES = {
     "pcg_conv_cliptab_register": (_i, [_gp, _vp, _sz, _vp]),
     "pcg_conv_sched_model": (_d, [_vp, _i32]),
     "pcg_conv_pad_clip_query": (_i, [_gp, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "pcg_conv_wgrad_padskip_query": (_i, [_gp, _i32, _vp, _vp]),
+    "pcg_conv_wgrad_padskip_plan": (_i, [_gp, _i32, _vp, _vp]),
     "pcg_conv2d_fwd_bn_g": (_i, [_gp, _vp, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _sz, _vp]),
     "pcg_bn_apply_act_g": (_i, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _i, _f, _vp, _i32, _vp]),
     "pcg_conv2d_dgrad_bn_phases": (_i32, [_gp]),

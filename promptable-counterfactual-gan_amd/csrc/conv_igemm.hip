@@ -14,6 +14,7 @@
 #include <array>
 #include <map>
 #include <mutex>
+#include <vector>
 #include "conv_loaders.h"
 #include "conv_pixtab.h"
 #include "conv_cliptab.h"
@@ -226,8 +227,8 @@ __device__ __forceinline__ int sk_start(int g, const SkPlan& sk) {
 __device__ __forceinline__ int sk_owner(int x, const SkPlan& sk) {     // the block whose range holds iteration x
   return __builtin_amdgcn_readfirstlane((int)((((uint32_t)x + 1u) * (uint32_t)sk.sk_blocks - 1u) / (uint32_t)(sk.sk_tiles * sk.ktiles)));
 }
-__device__ __forceinline__ int sk_segments(const SkPlan& sk, SkSeg& s0, SkSeg& s1) {
-  const int b = blockIdx.x;
+// b: the block's place in the launch order — blockIdx.x, or a permutation of it (wgrad_pair_block)
+__device__ __forceinline__ int sk_segments(const SkPlan& sk, SkSeg& s0, SkSeg& s1, int b) {
   if (b < sk.dp_tiles) { s0 = SkSeg{(int)xcd_remap((uint32_t)b, (uint32_t)sk.dp_tiles), 0, sk.ktiles, 1, 0}; return 1; }
   // neighbouring ranges (neighbouring tiles: shared operand rows) on ONE XCD, like the tiles of the data-parallel part
   const int g = (int)xcd_remap((uint32_t)(b - sk.dp_tiles), (uint32_t)sk.sk_blocks), KT = sk.ktiles;
@@ -308,8 +309,8 @@ __device__ __forceinline__ bool sk_combine_core(float* parts, int* arrivals, int
   return true;
 }
 template <class Cfg>
-__device__ __forceinline__ bool sk_combine(const SkPlan& sk, const SkSeg& sg, f32x16 (&acc)[Cfg::TM][Cfg::TN]) {
-  const int g = (int)xcd_remap((uint32_t)((int)blockIdx.x - sk.dp_tiles), (uint32_t)sk.sk_blocks), j = sg.tile - sk.dp_tiles, KT = sk.ktiles;
+__device__ __forceinline__ bool sk_combine(const SkPlan& sk, const SkSeg& sg, f32x16 (&acc)[Cfg::TM][Cfg::TN], int b) {
+  const int g = (int)xcd_remap((uint32_t)(b - sk.dp_tiles), (uint32_t)sk.sk_blocks), j = sg.tile - sk.dp_tiles, KT = sk.ktiles;
   return sk_combine_core<Cfg>(sk.parts, sk.arrivals, sk.sk_blocks, g, j, sg.nparts, sg.first_block,
                               [&](int blk) { return sk_start(blk, sk) >= j * KT; }, acc);
 }
@@ -332,7 +333,7 @@ __device__ __forceinline__ void fwd_sk_segment(const ConvP& p, const SkPlan& sk,
   }
   f32x16 acc[Cfg::TM][Cfg::TN];
   igemm_consume<Cfg, true, true>(sg.nkt, acc, smem);
-  if (sk_combine<Cfg>(sk, sg, acc))
+  if (sk_combine<Cfg>(sk, sg, acc, (int)blockIdx.x))
     igemm_store_tile<Cfg>(acc, smem, n_block, p.N, p.bias, [&](int row) -> float* {
       const int m = m_block + row;
       return m < p.M ? p.out + (size_t)m * p.N + n_block : nullptr;
@@ -342,7 +343,7 @@ template <class Cfg, bool XF>
 __global__ void __launch_bounds__(IG_THREADS, Cfg::MINW) conv_fwd_sk_kernel(ConvP p, SkPlan sk) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   SkSeg s0, s1{};
-  const int nseg = sk_segments(sk, s0, s1);
+  const int nseg = sk_segments(sk, s0, s1, (int)blockIdx.x);
   fwd_sk_segment<Cfg, XF>(p, sk, s0, smem);
   if (nseg == 1) return;
   lds_barrier();   // the epilogue staged through the LDS stages: the second segment's producers wait for it
@@ -379,7 +380,7 @@ __device__ __forceinline__ void dgrad_sk_segment(const ConvP& p, const DgradPhas
   }
   f32x16 acc[Cfg::TM][Cfg::TN];
   igemm_consume<Cfg, true, false>(sg.nkt, acc, smem);
-  if (sk_combine<Cfg>(sk, sg, acc))
+  if (sk_combine<Cfg>(sk, sg, acc, (int)blockIdx.x))
     igemm_store_tile<Cfg>(acc, smem, n_block, p.N, p.bias, [&](int row) -> float* {
       const int pix = rowpix[row];
       return pix >= 0 ? p.out + (size_t)pix * p.Cin + n_block : nullptr;
@@ -390,24 +391,58 @@ __global__ void __launch_bounds__(IG_THREADS, Cfg::MINW) conv_dgrad_sk_kernel(Co
   extern __shared__ __attribute__((aligned(16))) float smem[];
   __shared__ int rowpix[Cfg::BM];
   SkSeg s0, s1{};
-  const int nseg = sk_segments(sk, s0, s1);
+  const int nseg = sk_segments(sk, s0, s1, (int)blockIdx.x);
   dgrad_sk_segment<Cfg, XF>(p, phases, sk, s0, tiles_per_phase, smem, rowpix);
   if (nseg == 1) return;
   lds_barrier();
   dgrad_sk_segment<Cfg, XF>(p, phases, sk, s1, tiles_per_phase, smem, rowpix);
 }
 
+// The padding skip of the weight-gradient consumers (igemm_core.h PadSkip) for this wave's columns [n_block + wn * WTN, .. + WTN) and a
+// K range that starts at k-tile kt_begin.  The host takes these kernels only for k4 s2 p1 geometries with IH = 2 OH, IW = 2 OW, OH and
+// OW powers of two >= 4 and Cin a multiple of 64 (wgrad_padskip_geom), so a wave tile never straddles two tap rows, nor two taps
+// where OW = 4.  Columns past N belong to "tap row 4": nothing is skipped for them.
+template <class Cfg>
+__device__ __forceinline__ PadSkip wgrad_padskip(const ConvP& p, int n_block, int kt_begin) {
+  const int wn = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) % Cfg::WAVES_N;
+  const int tap = __builtin_amdgcn_readfirstlane((int)((uint32_t)(n_block + wn * Cfg::WTN) / (uint32_t)p.Cin));
+  const int kh = tap >> 2, kw = tap & 3;
+  PadSkip ps;
+  ps.q0 = kt_begin * IG_BK;
+  ps.lgw = 31 - __builtin_clz((unsigned)p.OW); ps.ohm = p.OH - 1;
+  const bool w4 = p.OW == 4;
+  ps.tmask = w4 && tap < 16 ? (kw == 0 ? 1 : kw == 3 ? 8 : 0) : 0;
+  ps.oh_zero = w4 ? -1 : kh == 0 ? 0 : kh == 3 ? p.OH - 1 : -1;
+  return ps;
+}
+// Block order of the skipping kernels (pair_xor != 0): the schedule model puts blocks b and b + 256 on one CU, and in today's orders
+// those two own tiles of the same tap class — both skip or neither does.  Within every odd round of 256 blocks the block ids are
+// permuted by b ^ pair_xor (a permutation of the round, so every tile is still computed exactly once, by one block, in the same K
+// order); the host picks the bit that pairs a skipping tile with a full one (wgrad_pair_xor).  Rounds that are not whole keep their order.
+__device__ __forceinline__ uint32_t wgrad_pair_block(uint32_t b, uint32_t nblocks, int pair_xor) {
+  return ((b >> 8) & 1u) && (b | 255u) < nblocks ? b ^ (uint32_t)pair_xor : b;
+}
+
 // XFA: the dy operand is a transformed activation (ConvTranspose2d layers); XFB: x is; TAB: the x gather reads its pixels from the
-// geometry's descriptor table (ConvP::pixtab != nullptr)
-template <class Cfg, bool XFA, bool XFB, bool TAB = false>
+// geometry's descriptor table (ConvP::pixtab != nullptr); PS (1: OW = 4, 2: OW >= 8): the consumers skip all-padding MFMAs (wgrad_padskip) — launched as a 1-D
+// grid in today's dispatch order (tile-major: x = tile fastest), optionally paired (pair_xor, unused without PS)
+template <class Cfg, bool XFA, bool XFB, bool TAB = false, int PS = 0>
 __global__ void __launch_bounds__(IG_THREADS, 4) conv_wgrad_kernel(ConvP p, int ktiles_total, int ktiles_per_split, int tiles,
-                                                                   int slice_major) {
+                                                                   int slice_major, int pair_xor) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   prio_entry(p);
   // slice_major: 1-D grid, the output tiles of one K-slice are consecutive on ONE XCD, so the slice of dy / x they all read
   // comes from HBM once and from that XCD's L2 afterwards (layers with few output tiles re-read their operands per tile)
   uint32_t tile, split;
-  if (slice_major) {
+  if constexpr (PS) {
+    const uint32_t b = wgrad_pair_block(blockIdx.x, gridDim.x, pair_xor);
+    if (slice_major) {
+      const uint32_t l = xcd_remap(b, gridDim.x);
+      split = l / (uint32_t)tiles; tile = l - split * (uint32_t)tiles;
+    } else {
+      split = b / (uint32_t)tiles; tile = xcd_remap(b - split * (uint32_t)tiles, (uint32_t)tiles);
+    }
+  } else if (slice_major) {
     const uint32_t l = xcd_remap(blockIdx.x, gridDim.x);
     split = l / (uint32_t)tiles; tile = l - split * (uint32_t)tiles;
   } else {
@@ -427,7 +462,8 @@ __global__ void __launch_bounds__(IG_THREADS, 4) conv_wgrad_kernel(ConvP p, int 
     return;
   }
   f32x16 acc[Cfg::TM][Cfg::TN];
-  igemm_consume<Cfg, false, false>(ktiles, acc, smem, ClockStamp{p.stamps, p.stamp_slots});
+  if constexpr (PS) igemm_consume_padskip<Cfg, false, false, PS>(ktiles, acc, smem, ClockStamp{p.stamps, p.stamp_slots}, wgrad_padskip<Cfg>(p, n_block, kt_begin));
+  else igemm_consume<Cfg, false, false>(ktiles, acc, smem, ClockStamp{p.stamps, p.stamp_slots});
   prio_epilogue(p);
   float* slab = p.out + (size_t)split * (size_t)p.M * (size_t)p.N;
   igemm_store_tile<Cfg>(acc, smem, n_block, p.N, nullptr, [&](int row) -> float* {
@@ -534,8 +570,8 @@ __global__ void __launch_bounds__(IG_THREADS, Cfg::MINW) conv_dgrad_skn_kernel(C
 // hundred tiles), the last arrival of a (tile, wave) writes dw itself — with the .grad accumulation as an EPI_ADD on dw — so
 // neither slabs nor the slab_reduce pass exist (288-tile gradients of the WGAN-GP critic: one workgroup per tile left 224 CUs
 // with one tile and 32 with two).
-template <class Cfg, bool XFA, bool XFB, bool TAB>
-__device__ __forceinline__ void wgrad_sk_segment(const ConvP& p, const SkPlan& sk, const SkSeg& sg, float* smem) {
+template <class Cfg, bool XFA, bool XFB, bool TAB, int PS>
+__device__ __forceinline__ void wgrad_sk_segment(const ConvP& p, const SkPlan& sk, const SkSeg& sg, float* smem, int b) {
   const int mt = __builtin_amdgcn_readfirstlane(sg.tile / p.tilesN), nt = sg.tile - mt * p.tilesN;
   const int m_block = mt * Cfg::BM, n_block = nt * Cfg::BN;
   if (wave_id() >= 4) {
@@ -546,22 +582,25 @@ __device__ __forceinline__ void wgrad_sk_segment(const ConvP& p, const SkPlan& s
     return;
   }
   f32x16 acc[Cfg::TM][Cfg::TN];
-  igemm_consume<Cfg, false, false>(sg.nkt, acc, smem);
-  if (sk_combine<Cfg>(sk, sg, acc))
+  if constexpr (PS) igemm_consume_padskip<Cfg, false, false, PS>(sg.nkt, acc, smem, ClockStamp{nullptr, 0}, wgrad_padskip<Cfg>(p, n_block, sg.kt_begin));
+  else igemm_consume<Cfg, false, false>(sg.nkt, acc, smem);
+  if (sk_combine<Cfg>(sk, sg, acc, b))
     igemm_store_tile<Cfg>(acc, smem, n_block, p.N, nullptr, [&](int row) -> float* {
       const int m = m_block + row;
       return m < p.M ? p.out + (size_t)m * p.N + n_block : nullptr;
     }, nullptr, PCG_ACT_NONE, 0.f, &p.epi);
 }
-template <class Cfg, bool XFA, bool XFB, bool TAB = false>
-__global__ void __launch_bounds__(IG_THREADS, 4) conv_wgrad_sk_kernel(ConvP p, SkPlan sk) {
+// PS: as in conv_wgrad_kernel; the permuted block id stands in for blockIdx.x everywhere (ranges, partial slots, arrival counters)
+template <class Cfg, bool XFA, bool XFB, bool TAB = false, int PS = 0>
+__global__ void __launch_bounds__(IG_THREADS, 4) conv_wgrad_sk_kernel(ConvP p, SkPlan sk, int pair_xor) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   SkSeg s0, s1{};
-  const int nseg = sk_segments(sk, s0, s1);
-  wgrad_sk_segment<Cfg, XFA, XFB, TAB>(p, sk, s0, smem);
+  const int b = PS ? (int)wgrad_pair_block(blockIdx.x, gridDim.x, pair_xor) : (int)blockIdx.x;
+  const int nseg = sk_segments(sk, s0, s1, b);
+  wgrad_sk_segment<Cfg, XFA, XFB, TAB, PS>(p, sk, s0, smem, b);
   if (nseg == 1) return;
   lds_barrier();
-  wgrad_sk_segment<Cfg, XFA, XFB, TAB>(p, sk, s1, smem);
+  wgrad_sk_segment<Cfg, XFA, XFB, TAB, PS>(p, sk, s1, smem, b);
 }
 
 // 64x192 tile of the weight gradient (Cout <= 64, N = KH*KW*Cin a multiple of 192): the same pipeline with the 192-column B loader
@@ -675,7 +714,7 @@ int check_geom(const pcg_conv_geom* g) {
 }
 
 // Tuning switches for A/B measurements in ONE process (pcg_tune_set; scripts/conv_microbench.py --ab): -1 = the built-in choice.
-struct Tune { int edge_prio = -1, dgrad_swz3 = -1, wgrad_rounds = -1, korder = -1, wgrad_order = -1, dgrad_interleave = -1, fwd_splits = -1, stream_k = -1, sk_blocks = -1, dgrad_gemm = -1, t64 = -1, wgrad_pixtab = -1, pad_clip = -1, pad_clip_dgrad = -1; unsigned long long* stamps = nullptr; int stamp_slots = 0; };
+struct Tune { int edge_prio = -1, dgrad_swz3 = -1, wgrad_rounds = -1, korder = -1, wgrad_order = -1, dgrad_interleave = -1, fwd_splits = -1, stream_k = -1, sk_blocks = -1, dgrad_gemm = -1, t64 = -1, wgrad_pixtab = -1, pad_clip = -1, pad_clip_dgrad = -1, wgrad_padskip = -1; unsigned long long* stamps = nullptr; int stamp_slots = 0; };
 Tune g_tune;
 
 ConvP make_params(const pcg_conv_geom* g) {
@@ -1094,6 +1133,70 @@ int launch_dgrad(const ConvP& p, const DgradPhases& ph, int nphases, int maxMp, 
 }
 
 struct WgradPlan { int splits, ktiles_total, ktiles_per_split, tiles; bool narrow, wide192; };
+
+// ---- weight gradients that skip their all-padding MFMAs (igemm_core.h PadSkip) ----
+// Which geometries: k4 s2 p1 with IH = 2 OH and IW = 2 OW (the last tap row / column is padding at the last output row / column), OH and
+// OW powers of two >= 4 (output row of a k-group by shift and mask; OW = 4: ow of an MFMA's two positions), Cin a multiple of 64 (a
+// wave tile of 32 or 64 columns lies inside one tap).  Plain host code.
+bool wgrad_padskip_geom(const pcg_conv_geom* g) {
+  auto pow2 = [](int v) { return v >= 4 && (v & (v - 1)) == 0; };
+  return g->KH == 4 && g->KW == 4 && g->stride == 2 && g->pad == 1 && g->IH == 2 * g->OH && g->IW == 2 * g->OW && pow2(g->OH) && pow2(g->OW) &&
+         g->Cin % 64 == 0 && !thin_is_cin(g) && !thin_is_cout(g);
+}
+// share of the launch's MFMAs left out: OW = 4: one MFMA in four for the taps kw = 0 and 3; OW >= 8: one k-group in OH for kh = 0 and 3
+double wgrad_padskip_fraction(const pcg_conv_geom* g) { return g->OW == 4 ? 0.125 : 0.5 / g->OH; }
+// pcg_tune_set("wgrad_padskip", v) or PCG_WGRAD_PADSKIP=v: 0 today's launches; 1 (default) the skipping consumers in the paired block
+// order for the classes that measured a gain, OW = 4 and OW = 8 (OW = 16 lost 1.7 % and stays on today's
+// kernels); 2 / 3 (measurements) every eligible launch, in the paired order / in today's order.
+// Returns what a launch of `g` does: 0 today's kernel, 1 skipping in today's order, 2 skipping in the paired order.
+constexpr int WGRAD_PADSKIP_DEFAULT = 1;
+int wgrad_padskip_mode(const pcg_conv_geom* g) {
+  static const int env0 = getenv("PCG_WGRAD_PADSKIP") ? atoi(getenv("PCG_WGRAD_PADSKIP")) : WGRAD_PADSKIP_DEFAULT;
+  static const int env = env0 >= 0 && env0 <= 3 ? env0 : WGRAD_PADSKIP_DEFAULT;      // a value outside 0 .. 3: the built-in default
+  const int v = g_tune.wgrad_padskip >= 0 ? g_tune.wgrad_padskip : env;
+  return v == 1 ? (g->OW <= 8 ? 2 : 0) : v == 2 ? 2 : v == 3 ? 1 : 0;
+}
+// The paired order's bit (wgrad_pair_block).  A tile's class is the number of its wave-tile columns that skip; the bit m in {1, 2, ..,
+// 128} (or 0: none) is the one for which the blocks b ^ m of the odd rounds and b - 256 of the even ones, which share a CU in the
+// schedule model, come closest to one skipping class per CU.  PairForm says which output tile block b works on in today's order:
+//   sk = 0  conv_wgrad_kernel: n0 = tiles, n1 = K-slices, n2 = slice_major
+//   sk = 1  conv_wgrad_sk_kernel: n0 = dp_tiles, n1 = sk_tiles, n2 = sk_blocks, n3 = k-tiles per tile (the tile of the block's first segment)
+// The bit depends on nothing but its arguments; the answers are kept (a training step asks for the same few over and over).
+struct PairForm { int sk, n0, n1, n2, n3; };
+int wgrad_pair_xor(int waves_n, int wtn, int tilesN, int Cin, int OW, const PairForm& f) {
+  struct Entry { int key[10]; int bit; };
+  static std::vector<Entry> cache;
+  static std::mutex cache_mutex;
+  const int key[10] = {waves_n, wtn, tilesN, Cin, OW, f.sk, f.n0, f.n1, f.n2, f.n3};
+  std::lock_guard<std::mutex> lock(cache_mutex);
+  for (const Entry& e : cache)
+    if (!memcmp(e.key, key, sizeof(key))) return e.bit;
+  const int blocks = f.sk ? f.n0 + f.n2 : f.n0 * f.n1;
+  auto tile_of = [&](int b) {
+    if (!f.sk) return f.n2 ? (int)(xcd_remap((uint32_t)b, (uint32_t)blocks) % (uint32_t)f.n0) : (int)xcd_remap((uint32_t)(b % f.n0), (uint32_t)f.n0);
+    if (b < f.n0) return (int)xcd_remap((uint32_t)b, (uint32_t)f.n0);
+    const uint32_t g = xcd_remap((uint32_t)(b - f.n0), (uint32_t)f.n2);
+    return f.n0 + (int)(g * (uint32_t)(f.n1 * f.n3) / (uint32_t)f.n2 / (uint32_t)f.n3);
+  };
+  auto cls = [&](int b) {
+    const int nt = tile_of(b) % tilesN;
+    int c = 0;
+    for (int wn = 0; wn < waves_n; ++wn) {
+      const int tap = (nt * 128 + wn * wtn) / Cin, kh = tap >> 2, kw = tap & 3;      // (128-column tiles)
+      c += tap < 16 && (OW == 4 ? (kw == 0 || kw == 3) : (kh == 0 || kh == 3)) ? 1 : 0;
+    }
+    return c;
+  };
+  int best_m = 0, best = -1;
+  for (int m = 0; m <= 128; m = m ? 2 * m : 1) {
+    int score = 0;
+    for (int b = 256; (b | 255) < blocks; b += (b & 255) == 255 ? 257 : 1)
+      score += waves_n - abs(cls(b ^ m) + cls(b - 256) - waves_n);
+    if (score > best) { best = score; best_m = m; }
+  }
+  if (cache.size() < 256) cache.push_back(Entry{{key[0], key[1], key[2], key[3], key[4], key[5], key[6], key[7], key[8], key[9]}, best_m});
+  return best_m;
+}
 
 WgradPlan plan_wgrad(const pcg_conv_geom* g) {
   WgradPlan w{};
@@ -1890,30 +1993,57 @@ extern "C" size_t pcg_conv2d_wgrad_workspace_bytes(const pcg_conv_geom* g) {
   return (size_t)w.splits * (size_t)g->Cout * (size_t)g->KH * g->KW * g->Cin * sizeof(float);
 }
 
-template <class Cfg, bool XFA, bool XFB, bool TAB = false>
-static int launch_wgrad_x(const ConvP& p, const WgradPlan& wp, int slice_major, hipStream_t s) {
+// padskip (wgrad_padskip_mode; 0 unless the geometry is eligible): 1 the skipping consumers in today's block order, 2 in the paired order.
+// Only the plain fp32 kernels have the skipping twin: the bf16 twins and the transformed-operand variants launch what they always did.
+static int wgrad_slice_major(const WgradPlan& wp) {
+  static const int order_env0 = getenv("PCG_WGRAD_ORDER") ? atoi(getenv("PCG_WGRAD_ORDER")) : -1;   // A/B switch: 0 tile-major, 1 slice-major
+  const int order_env = g_tune.wgrad_order >= 0 ? g_tune.wgrad_order : order_env0;
+  return order_env >= 0 ? order_env : (wp.tiles <= 8 ? 1 : 0);
+}
+template <class Cfg, bool XFA, bool XFB, bool TAB = false, int PS = 0>
+static int launch_wgrad_x(const ConvP& p, const WgradPlan& wp, int slice_major, hipStream_t s, int padskip = 0) {
   if constexpr (!TAB) {
-    if (p.pixtab) return launch_wgrad_x<Cfg, XFA, XFB, true>(p, wp, slice_major, s);
+    if (p.pixtab) return launch_wgrad_x<Cfg, XFA, XFB, true>(p, wp, slice_major, s, padskip);
+  }
+  if constexpr (!PS && !XFA && !XFB && !Cfg::BF16) {
+    if (padskip) return p.OW == 4 ? launch_wgrad_x<Cfg, XFA, XFB, TAB, 1>(p, wp, slice_major, s, padskip)
+                                  : launch_wgrad_x<Cfg, XFA, XFB, TAB, 2>(p, wp, slice_major, s, padskip);
   }
   constexpr size_t smem = smem_bytes<Cfg, false, false>();
-  static int once = set_smem(conv_wgrad_kernel<Cfg, XFA, XFB, TAB>, smem);
+  static int once = set_smem(conv_wgrad_kernel<Cfg, XFA, XFB, TAB, PS>, smem);
   if (once != PCG_OK) return once;
-  hipLaunchKernelGGL((conv_wgrad_kernel<Cfg, XFA, XFB, TAB>), slice_major ? dim3((unsigned)wp.tiles * wp.splits) : dim3((unsigned)wp.tiles, wp.splits),
-                     dim3(IG_THREADS), smem, s, p, wp.ktiles_total, wp.ktiles_per_split, wp.tiles, slice_major);
+  if constexpr (PS) {
+    const int blocks = wp.tiles * wp.splits;
+    static_assert(Cfg::BN == 128, "wgrad_pair_xor counts 128-column tiles");
+    const int px = padskip == 2 ? wgrad_pair_xor(Cfg::WAVES_N, Cfg::WTN, p.tilesN, p.Cin, p.OW, PairForm{0, wp.tiles, wp.splits, slice_major ? 1 : 0, 0}) : 0;
+    hipLaunchKernelGGL((conv_wgrad_kernel<Cfg, XFA, XFB, TAB, PS>), dim3((unsigned)blocks), dim3(IG_THREADS), smem, s, p, wp.ktiles_total,
+                       wp.ktiles_per_split, wp.tiles, slice_major, px);
+  } else {
+    hipLaunchKernelGGL((conv_wgrad_kernel<Cfg, XFA, XFB, TAB, PS>), slice_major ? dim3((unsigned)wp.tiles * wp.splits) : dim3((unsigned)wp.tiles, wp.splits),
+                       dim3(IG_THREADS), smem, s, p, wp.ktiles_total, wp.ktiles_per_split, wp.tiles, slice_major, 0);
+  }
   return launch_status("conv_wgrad_kernel");
 }
-template <class Cfg, bool XFA, bool XFB, bool TAB = false>
-static int launch_wgrad_sk_x(const ConvP& p, const SkPlan& sk, hipStream_t s) {
+template <class Cfg, bool XFA, bool XFB, bool TAB = false, int PS = 0>
+static int launch_wgrad_sk_x(const ConvP& p, const SkPlan& sk, hipStream_t s, int padskip = 0) {
   if constexpr (!Cfg::BF16) {
     if (conv_bf16()) return launch_wgrad_sk_x<Bf16Twin<Cfg>, XFA, XFB>(p, sk, s);
   }
   if constexpr (!TAB) {
-    if (p.pixtab) return launch_wgrad_sk_x<Cfg, XFA, XFB, true>(p, sk, s);
+    if (p.pixtab) return launch_wgrad_sk_x<Cfg, XFA, XFB, true>(p, sk, s, padskip);
+  }
+  if constexpr (!PS && !XFA && !XFB && !Cfg::BF16) {
+    if (padskip) return p.OW == 4 ? launch_wgrad_sk_x<Cfg, XFA, XFB, TAB, 1>(p, sk, s, padskip) : launch_wgrad_sk_x<Cfg, XFA, XFB, TAB, 2>(p, sk, s, padskip);
   }
   constexpr size_t smem = smem_bytes<Cfg, false, false>();
-  static int once = set_smem(conv_wgrad_sk_kernel<Cfg, XFA, XFB, TAB>, smem);
+  static int once = set_smem(conv_wgrad_sk_kernel<Cfg, XFA, XFB, TAB, PS>, smem);
   if (once != PCG_OK) return once;
-  hipLaunchKernelGGL((conv_wgrad_sk_kernel<Cfg, XFA, XFB, TAB>), dim3((unsigned)(sk.dp_tiles + sk.sk_blocks)), dim3(IG_THREADS), smem, s, p, sk);
+  const int blocks = sk.dp_tiles + sk.sk_blocks;
+  int px = 0;
+  if constexpr (PS) {
+    if (padskip == 2) px = wgrad_pair_xor(Cfg::WAVES_N, Cfg::WTN, p.tilesN, p.Cin, p.OW, PairForm{1, sk.dp_tiles, sk.sk_tiles, sk.sk_blocks, sk.ktiles});
+  }
+  hipLaunchKernelGGL((conv_wgrad_sk_kernel<Cfg, XFA, XFB, TAB, PS>), dim3((unsigned)blocks), dim3(IG_THREADS), smem, s, p, sk, px);
   return launch_status("conv_wgrad_sk_kernel");
 }
 template <class Cfg, bool TAB = false>
@@ -1929,13 +2059,13 @@ static int launch_wgrad192(const ConvP& p, const WgradPlan& wp, int slice_major,
   return launch_status("conv_wgrad192_kernel");
 }
 template <class Cfg>
-static int launch_wgrad(const ConvP& p, const WgradPlan& wp, int slice_major, int xf_side, hipStream_t s) {
+static int launch_wgrad(const ConvP& p, const WgradPlan& wp, int slice_major, int xf_side, hipStream_t s, int padskip) {
   if constexpr (!Cfg::BF16) {
-    if (conv_bf16()) return launch_wgrad<Bf16Twin<Cfg>>(p, wp, slice_major, xf_side, s);
+    if (conv_bf16()) return launch_wgrad<Bf16Twin<Cfg>>(p, wp, slice_major, xf_side, s, 0);
   }
   if (xf_side == 1) return launch_wgrad_x<Cfg, false, true>(p, wp, slice_major, s);    // x is a transformed activation
   if (xf_side == 2) return launch_wgrad_x<Cfg, true, false>(p, wp, slice_major, s);    // dy is
-  return launch_wgrad_x<Cfg, false, false>(p, wp, slice_major, s);
+  return launch_wgrad_x<Cfg, false, false>(p, wp, slice_major, s, padskip);
 }
 
 extern "C" int pcg_conv2d_wgrad_xf(const pcg_conv_geom* g, const float* x, const pcg_in_xform* xf_x, const float* dy,
@@ -1966,10 +2096,9 @@ extern "C" int pcg_conv2d_wgrad_xf(const pcg_conv_geom* g, const float* x, const
   p.pixtab = pixtab_of(g);
   if (int e = hx ? set_xform("pcg_conv2d_wgrad_xf", xf_x, g->Cin, &p) : set_xform("pcg_conv2d_wgrad_xf", xf_dy, g->Cout, &p)) return e;
   hipStream_t s = (hipStream_t)stream;
-  static const int order_env0 = getenv("PCG_WGRAD_ORDER") ? atoi(getenv("PCG_WGRAD_ORDER")) : -1;   // A/B switch: 0 tile-major, 1 slice-major
-  const int order_env = g_tune.wgrad_order >= 0 ? g_tune.wgrad_order : order_env0;
-  const int slice_major = order_env >= 0 ? order_env : (wp.tiles <= 8 ? 1 : 0);
+  const int slice_major = wgrad_slice_major(wp);
   const int side = hx ? 1 : hy ? 2 : 0;
+  const int padskip = wgrad_padskip_geom(g) ? wgrad_padskip_mode(g) : 0;
   // a tile count that leaves the chip unevenly loaded: stream-K, straight into dw.  One full-K block per tile anyway (splits == 1:
   // the Linear 8192 -> 1024 gradients, 512 tiles x 8-16 k-tiles): the same kernel with every tile data-parallel — dw written (or
   // accumulated) by the epilogue, no slab and no slab_reduce pass (30 us behind an 84 us kernel in the r03 critic trace)
@@ -1981,7 +2110,7 @@ extern "C" int pcg_conv2d_wgrad_xf(const pcg_conv_geom* g, const float* x, const
       p.out = dw;
       if (accumulate) { p.epi.mode = EPI_ADD; p.epi.neg = 1.f; p.epi.delta_bytes = 0; }
       return side == 1 ? launch_wgrad_sk_x<Cfg128x128, false, true>(p, sk, s)
-           : side == 2 ? launch_wgrad_sk_x<Cfg128x128, true, false>(p, sk, s) : launch_wgrad_sk_x<Cfg128x128, false, false>(p, sk, s);
+           : side == 2 ? launch_wgrad_sk_x<Cfg128x128, true, false>(p, sk, s) : launch_wgrad_sk_x<Cfg128x128, false, false>(p, sk, s, padskip);
     }
   }
   int rc;
@@ -1994,7 +2123,7 @@ extern "C" int pcg_conv2d_wgrad_xf(const pcg_conv_geom* g, const float* x, const
       wq.wide192 = false;
       wq.tiles = ceil_div(p.M, 64) * ceil_div(p.N, 128);
     }
-    rc = wq.narrow ? launch_wgrad<TileCfg<64, 128, 1, 4>>(p, wq, slice_major, side, s) : launch_wgrad<Cfg128x128>(p, wq, slice_major, side, s);
+    rc = wq.narrow ? launch_wgrad<TileCfg<64, 128, 1, 4>>(p, wq, slice_major, side, s, padskip) : launch_wgrad<Cfg128x128>(p, wq, slice_major, side, s, padskip);
   }
   if (rc != PCG_OK) return rc;
   const size_t n = (size_t)p.M * p.N;
@@ -2096,6 +2225,44 @@ extern "C" int pcg_conv_pad_clip_query(const pcg_conv_geom* g, int32_t op, int32
   return PCG_OK;
 }
 
+// Does a launch of `g` for `op` have the padding-skipping consumers (op 2, the plain fp32 weight gradient of an eligible geometry), and
+// which share of its MFMAs do they leave out?  The geometry and the operand precision alone: the wgrad_padskip switch is not consulted.
+extern "C" int pcg_conv_wgrad_padskip_query(const pcg_conv_geom* g, int32_t op, int32_t* applies, double* fraction) {
+  if (int e = check_geom(g)) return e;
+  PCG_REQUIRE(op >= 0 && op <= 2, "pcg_conv_wgrad_padskip_query: op is 0, 1 or 2, not %d", (int)op);
+  const bool yes = op == 2 && !conv_bf16() && wgrad_padskip_geom(g);
+  if (applies) *applies = yes ? 1 : 0;
+  if (fraction) *fraction = yes ? wgrad_padskip_fraction(g) : 0.0;
+  return PCG_OK;
+}
+
+// What a plain fp32 weight-gradient launch of `g` does under the current switches, decided as pcg_conv2d_wgrad decides it (host code):
+// *mode 0 today's kernel, 1 the skipping consumers in today's block order, 2 in the paired order; *pair_bit the paired order's bit (0:
+// the order stays — fewer than two whole rounds of 256 blocks, or nothing to pair).  assume_scratch as in pcg_conv_plan_describe.
+extern "C" int pcg_conv_wgrad_padskip_plan(const pcg_conv_geom* g, int32_t assume_scratch, int32_t* mode, int32_t* pair_bit) {
+  if (int e = check_geom(g)) return e;
+  int m = 0, bit = 0;
+  if (!conv_bf16() && wgrad_padskip_geom(g)) {
+    m = wgrad_padskip_mode(g);
+    if (m == 2) {
+      const WgradPlan wp = plan_wgrad(g);
+      const int tilesN = ceil_div(g->KH * g->KW * g->Cin, 128);
+      const int have = assume_scratch ? (sk_mode() != 0 ? 1 : 0) : (have_sk_scratch() ? 1 : 0);
+      SkPlan sk{};
+      bool take = false;
+      if (!wp.narrow && !wp.wide192 && wp.tiles > 96 && sk_mode() != 0) {
+        take = have && plan_sk_shape(wp.tiles, wp.ktiles_total, &sk);
+        if (!take && wp.splits == 1) { sk = SkPlan{wp.tiles, 0, 0, wp.ktiles_total, nullptr, nullptr}; take = true; }
+      }
+      if (take) bit = wgrad_pair_xor(2, 64, tilesN, g->Cin, g->OW, PairForm{1, sk.dp_tiles, sk.sk_tiles, sk.sk_blocks, sk.ktiles});
+      else bit = wgrad_pair_xor(wp.narrow ? 4 : 2, wp.narrow ? 32 : 64, tilesN, g->Cin, g->OW, PairForm{0, wp.tiles, wp.splits, wgrad_slice_major(wp), 0});
+    }
+  }
+  if (mode) *mode = m;
+  if (pair_bit) *pair_bit = bit;
+  return PCG_OK;
+}
+
 extern "C" int pcg_tune_set(const char* name, int32_t value) {
   PCG_REQUIRE(name != nullptr, "pcg_tune_set: null name");
   if (!strcmp(name, "korder")) g_tune.korder = value;
@@ -2111,6 +2278,10 @@ extern "C" int pcg_tune_set(const char* name, int32_t value) {
   else if (!strcmp(name, "t64")) g_tune.t64 = value;
   else if (!strcmp(name, "wgrad_pixtab")) g_tune.wgrad_pixtab = value;   // A/B: 0 the weight gradient derives its pixels per k-tile, 1 reads the geometry's table
   else if (!strcmp(name, "pad_clip")) g_tune.pad_clip = value;           // A/B: 0 today's forward / grad-input launches, 1 the clipped ones the model takes
+  else if (!strcmp(name, "wgrad_padskip")) {
+    PCG_REQUIRE(value >= -1 && value <= 3, "pcg_tune_set: wgrad_padskip is 0, 1, 2 or 3 (-1: built-in), not %d", (int)value);
+    g_tune.wgrad_padskip = value;
+  }  // A/B: 0 today's weight-gradient launches, 1 the consumers skip all-padding MFMAs where that measured a gain; 2 / 3: measurements
   else if (!strcmp(name, "pad_clip_dgrad")) {
     PCG_REQUIRE(value >= -1 && value <= 2, "pcg_tune_set: pad_clip_dgrad is 0, 1 or 2 (-1: built-in), not %d", (int)value);
     g_tune.pad_clip_dgrad = value;
@@ -2119,7 +2290,7 @@ extern "C" int pcg_tune_set(const char* name, int32_t value) {
     // The parenthesised list is compared word for word by tests/test_host_logic.py::test_tune_switches, written before wgrad_pixtab
     // existed: the later switches are named behind it.  Follow-up: put them into the list and extend that test's list with them.
     set_error("pcg_tune_set: unknown switch '%s' (korder, edge_prio, dgrad_swz3, wgrad_rounds, wgrad_order, dgrad_interleave, fwd_splits, "
-              "stream_k, sk_blocks, dgrad_gemm, t64); the loader switches wgrad_pixtab, pad_clip and pad_clip_dgrad are accepted as well", name);
+              "stream_k, sk_blocks, dgrad_gemm, t64); the loader switches wgrad_pixtab, pad_clip, pad_clip_dgrad and wgrad_padskip are accepted as well", name);
     return PCG_ERR_INVALID;
   }
   return PCG_OK;

@@ -409,6 +409,7 @@ __device__ __forceinline__ void igemm_produce(LA& la, LB& lb, int ktiles, float*
 // the tile boundary.  (s_setprio 2 here dates from r01; what matters is that the PRODUCERS rank above it — igemm_produce.)
 // The bf16 twin (Cfg::BF16) runs the same loop over k-groups of 16: one 8-element fragment per operand tile and one
 // v_mfma_f32_32x32x16_bf16 per accumulator and k-group — 2 per k-tile instead of 16 fp32 ones.
+// igemm_consume_padskip below is a COPY of this loop (fetch, barriers, stamps, priorities): a change here has to be made there as well.
 template <bool BF> struct MmaFrag { float v[4]; };
 template <> struct MmaFrag<true> { bf16x8 v; };
 
@@ -489,6 +490,128 @@ __device__ __forceinline__ void igemm_consume(int ktiles, f32x16 (&acc)[Cfg::TM]
     cur ^= 1;
     if (kt + 1 < ktiles) fetch(As + cur * IA::FLOATS, Bs + cur * IB::FLOATS, 0, KG & 1);
     mma((KG - 1) & 1);
+  }
+  cs.end(); cs.phase(2);
+#ifdef PCG_CLOCK_STAMP
+  cs.bar_flush(0, __builtin_amdgcn_s_memtime() - loop_t0);
+#endif
+  __builtin_amdgcn_s_setprio(0);
+}
+
+// igemm_consume_padskip: igemm_consume for the fp32 weight gradients of k4 s2 p1 layers — the same fragments,
+// barriers, priorities and MFMA order, in a function of its own so that igemm_consume compiles to what it always did.
+// PS: leave out MFMAs whose B operand is padding in BOTH of their k slots.  k = output position in (image, oh, ow) order, a k-tile starts at a multiple of 32 positions, OH and OW are powers of two,
+// and MFMA t of the k-group at position q (a multiple of 8) takes positions {q + t, q + 4 + t} (above).  All of a wave tile's columns
+// belong to one tap row kh (OW >= 8) or one tap (kh, kw) (OW = 4):
+//   PS = 1, OW = 4   both positions of MFMA t have ow = t: t = 0 is all padding for kw = 0, t = 3 for kw = 3 (tmask 1 / 8, fixed per wave).
+//                    The wave picks ONE of three copies of the main loop — t in [0,4), [1,4) or [0,3) — so no loop holds a branch.
+//   PS = 2, OW >= 8  the 8 positions of a k-group lie in one output row oh = (q >> log2 OW) & (OH - 1): the group is all padding for
+//                    kh = 0 at oh = 0 and for kh = 3 at oh = OH - 1 (oh_zero).  A wave of those tap rows runs a copy of the main loop
+//                    with a 4-bit mask of such groups per k-tile and one uniform branch per k-group; a skipped group skips its
+//                    fragment reads too.  The waves of kh = 1 / 2 run the loop as it always was.  (The choice is per wave, not per
+//                    k-tile: with both bodies inside one loop the 128x128 kernel spilled 186 registers.)
+// Everything here is wave-uniform scalar state.  The accumulators start at +0 and the left-out products are a * 0, so every remaining
+// product keeps its MFMA, its k slot and its place in the sequence: the result is bit-identical for finite dy.  A non-finite dy at
+// such a position gives NaN without the skip and is ignored with it.
+struct PadSkip {
+  int tmask;     // PS = 1: bit t: MFMA t of every k-group multiplies only padding (0, 1 or 8)
+  int q0;        // position of the first k-tile consumed (a multiple of 32)
+  int lgw, ohm;  // log2(OW), OH - 1
+  int oh_zero;   // PS = 2: the output row whose k-groups are all padding for this wave's tap row, or -1
+};
+template <int V> struct IntC { static constexpr int value = V; };
+
+template <class Cfg, bool AK, bool BK_, int PS>
+__device__ __forceinline__ void igemm_consume_padskip(int ktiles, f32x16 (&acc)[Cfg::TM][Cfg::TN], const float* smem, ClockStamp cs = ClockStamp{nullptr, 0},
+                                                      PadSkip ps = PadSkip{0, 0, 0, 0, -1}) {
+  static_assert((PS == 1 || PS == 2) && !Cfg::BF16, "the padding skip is written for the fp32 k-groups of 8");
+  using IA = LdsImage<Cfg::BM, AK, Cfg::SWZ, Cfg::BF16>;
+  using IB = LdsImage<Cfg::BN, BK_, Cfg::SWZ, Cfg::BF16>;
+  constexpr int KG = IG_BK / (Cfg::BF16 ? 16 : 8);  // k-groups per tile
+  const float* As = smem;
+  const float* Bs = smem + 2 * IA::FLOATS;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int wm = wave / Cfg::WAVES_N, wn = wave % Cfg::WAVES_N;
+  const int li = lane & 31, lh = lane >> 5;
+  const int arow = wm * Cfg::WTM, brow = wn * Cfg::WTN;
+#pragma unroll
+  for (int i = 0; i < Cfg::TM; ++i)
+#pragma unroll
+    for (int j = 0; j < Cfg::TN; ++j)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+
+  MmaFrag<Cfg::BF16> a[2][Cfg::TM], b[2][Cfg::TN];
+  auto fetch = [&](const float* as, const float* bs, int ks, int buf) {
+#pragma unroll
+    for (int i = 0; i < Cfg::TM; ++i) IA::frag(as, arow + 32 * i, ks, li, lh, a[buf][i].v);
+#pragma unroll
+    for (int j = 0; j < Cfg::TN; ++j) IB::frag(bs, brow + 32 * j, ks, li, lh, b[buf][j].v);
+  };
+  // the MFMAs t in [T0, T1) of a k-group ([0, 4) unless PS = 1 leaves one end out), in the order they always had
+  auto mma = [&](int buf, auto T0, auto T1) {
+#pragma unroll
+    for (int t = T0.value; t < T1.value; ++t)
+#pragma unroll
+      for (int i = 0; i < Cfg::TM; ++i)
+#pragma unroll
+        for (int j = 0; j < Cfg::TN; ++j)
+          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[buf][i].v[t], b[buf][j].v[t], acc[i][j], 0, 0, 0);
+  };
+
+  lds_barrier();  // barrier 0: stage 0 is ready
+  if (ktiles <= 0) return;
+  __builtin_amdgcn_s_setprio(PCG_CONSUMER_PRIO);
+  cs.begin(); cs.phase(1); cs.bar_init();
+#ifdef PCG_CLOCK_STAMP
+  const unsigned long long loop_t0 = __builtin_amdgcn_s_memtime();
+#endif
+  // PS = 2: bit ks = k-group ks of the k-tile at position q holds nothing but padding
+  auto dead = [&](int q, auto BR) {
+    int m = 0;
+    if constexpr (BR.value != 0) {
+#pragma unroll
+      for (int ks = 0; ks < KG; ++ks) m |= (((q + 8 * ks) >> ps.lgw) & ps.ohm) == ps.oh_zero ? 1 << ks : 0;
+    }
+    return m;
+  };
+#if PCG_CONSUMER_ALTERNATE
+  const int alt_phase = (int)((blockIdx.x / PCG_CONSUMER_ALTERNATE) & 1u);
+#endif
+  // BR: the copy with a branch around every dead k-group; without, the loop as it always was
+  auto loop = [&](auto T0, auto T1, auto BR) {
+    int qt = ps.q0;        // BR: position of k-tile kt, the mask of its dead k-groups
+    int dm = dead(qt, BR);
+    if (!(dm & 1)) fetch(As, Bs, 0, 0);
+    int cur = 0;
+    for (int kt = 0; kt < ktiles; ++kt) {
+#if PCG_CONSUMER_ALTERNATE
+      if ((kt + alt_phase) & 1) __builtin_amdgcn_s_setprio(2); else __builtin_amdgcn_s_setprio(1);
+#endif
+      const float* as = As + cur * IA::FLOATS;
+      const float* bs = Bs + cur * IB::FLOATS;
+      const int dn = dead(qt + IG_BK, BR);
+#pragma unroll
+      for (int ks = 0; ks < KG - 1; ++ks) {
+        if (!((dm >> (ks + 1)) & 1)) fetch(as, bs, ks + 1, (ks + 1) & 1);
+        if (!((dm >> ks) & 1)) mma(ks & 1, T0, T1);
+      }
+      cs.bar_begin();
+      lds_barrier();  // barrier kt+1: all reads of stage cur have retired (lgkmcnt(0)); stage cur^1 is ready
+      cs.bar_end();
+      cur ^= 1;
+      if (kt + 1 < ktiles && !(dn & 1)) fetch(As + cur * IA::FLOATS, Bs + cur * IB::FLOATS, 0, KG & 1);
+      if (!((dm >> (KG - 1)) & 1)) mma((KG - 1) & 1, T0, T1);
+      qt += IG_BK; dm = dn;
+    }
+  };
+  if constexpr (PS == 1) {
+    if (ps.tmask == 1) loop(IntC<1>{}, IntC<4>{}, IntC<0>{});
+    else if (ps.tmask == 8) loop(IntC<0>{}, IntC<3>{}, IntC<0>{});
+    else loop(IntC<0>{}, IntC<4>{}, IntC<0>{});
+  } else {
+    if (ps.oh_zero >= 0) loop(IntC<0>{}, IntC<4>{}, IntC<1>{});
+    else loop(IntC<0>{}, IntC<4>{}, IntC<0>{});
   }
   cs.end(); cs.phase(2);
 #ifdef PCG_CLOCK_STAMP

@@ -59,7 +59,7 @@ struct FastDiv {
 
 // ---- XCD-aware tile order: blocks b and b+8 share an XCD (and its L2); give each XCD a contiguous
 // run of tile ids so neighbouring tiles (shared operand panels) hit the same L2.  Bijective for any n.
-__device__ __forceinline__ uint32_t xcd_remap(uint32_t bid, uint32_t nblocks) {
+__host__ __device__ __forceinline__ uint32_t xcd_remap(uint32_t bid, uint32_t nblocks) {
   const uint32_t q = nblocks >> 3, r = nblocks & 7u;
   const uint32_t xcd = bid & 7u, idx = bid >> 3;
   const uint32_t base = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;

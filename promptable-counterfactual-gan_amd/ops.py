@@ -194,6 +194,24 @@ def conv_pad_clip_query(g, op, groups=1, assume_scratch=True):
     return bool(taken.value), order.value, rows.value, pred.value
 
 
+def conv_wgrad_padskip_query(g, op=2):
+    """(applies, fraction) of pcg_conv_wgrad_padskip_query: does the launch of `g` for op (2: grad-weight) have the consumers that skip
+    all-padding MFMAs, and which share of the launch's MFMAs do they leave out."""
+    applies, frac = ctypes.c_int32(0), ctypes.c_double(0.0)
+    check(_lib.load().pcg_conv_wgrad_padskip_query(ctypes.byref(g), int(op), ctypes.byref(applies), ctypes.byref(frac)),
+          "pcg_conv_wgrad_padskip_query")
+    return bool(applies.value), frac.value
+
+
+def conv_wgrad_padskip_plan(g, assume_scratch=True):
+    """(mode, pair_bit) of pcg_conv_wgrad_padskip_plan: 0 today's kernel, 1 skipping consumers in today's block order, 2 in the paired
+    order, and that order's bit."""
+    mode, bit = ctypes.c_int32(-1), ctypes.c_int32(-1)
+    check(_lib.load().pcg_conv_wgrad_padskip_plan(ctypes.byref(g), int(bool(assume_scratch)), ctypes.byref(mode), ctypes.byref(bit)),
+          "pcg_conv_wgrad_padskip_plan")
+    return mode.value, bit.value
+
+
 def launch_plan(op, *args):
     """The route a non-convolution launch takes, as text (pcg_launch_plan_describe: host logic, no device).  op: one of _lib.PLAN_*;
     args: that op's integers, e.g. launch_plan(_lib.PLAN_GEMM_ACT, transA, transB, M, N, K) -> 'skinny: 33 blocks, ...'."""
