@@ -1778,6 +1778,50 @@ int pcg_cf_panels(int32_t mode, const float* x, const float* x_cf, const float* 
                   uint8_t* out_u8 /*nullable*/, float* vmax /*nullable in grid mode*/, int32_t n, int32_t T, int32_t H, int32_t W,
                   pcg_stream_t stream);
 
+/* ---- the normalised image sheets of the trainers: torchvision's make_grid and the pixels of save_image on CPU fp32 tensors, as called
+ * at dconv_gan/mnist/mnist_dcgan.py:190 (padding 2) and :222 (padding 5), simple_gan/mnist/mnist_gan.py:141 (nrow 5),
+ * conditional_counteRGAN/mnist/gan_train.py:161-163 and countergan2.py:222-224 (nrow 4; the delta as deltas * 0.5 + 0.5),
+ * conditional_gan/mnist/mnist_wgan_conditional.py:123-125 and :181-182 (csrc/image_sheet.hip) ------------------
+ * All fp32, gfx950 only; both entries take a stream, may be captured into one HIP graph and validate their arguments before they touch
+ * HIP.  Every pixel operation is a single fp32 rounding (no contraction), the division is a true fp32 division.  Pixels of a NaN input
+ * are unspecified; a NaN cannot fault.                                                                                                   */
+
+/* Bytes of the workspace of pcg_image_range: a ticket and one (min, max) pair per workgroup.  The caller zeroes it ONCE, when it is
+ * allocated; every launch leaves the ticket zero, so nothing is reset between calls.  One launch at a time per workspace.              */
+size_t pcg_image_range_workspace_bytes(void);
+
+/* range[0] = min, range[1] = max of pre_scale * x[i] + pre_shift over the n floats of x (the product and the sum are two roundings;
+ * pre_scale 1 and pre_shift 0 read x as it is): the global minimum and maximum make_grid(normalize=True) takes when no value_range is
+ * given.  x 4-byte aligned: 16-byte loads from the first 16-byte boundary on, scalar ends.  Reduced as floats per wave (shuffles), per
+ * workgroup (LDS) and, by the workgroup that takes the last ticket, over the workgroups' pairs; a minimum does not depend on the order
+ * of its operands, so the result is the same bits for any order of workgroups.  n <= 2^31 - 1; range 4-byte, workspace 16-byte aligned. */
+int pcg_image_range(const float* x, int64_t n, float pre_scale, float pre_shift, float* range, void* workspace, size_t workspace_bytes,
+                    pcg_stream_t stream);
+
+/* make_grid(x [N][C][H][W], nrow, padding, normalize, value_range, pad_value) and the uint8 pixels of save_image in one launch.
+ *   every element first becomes e = pre_scale * x + pre_shift (two roundings; (1, 0): x as it is);
+ *   normalize: e = (min(max(e, lo), hi) - lo) / d.  range != null: lo = range[0], hi = range[1] are read on the DEVICE (what
+ *     pcg_image_range left there) and d = float(max(double(hi) - double(lo), 1e-5)) is formed there; range == null: the host gives
+ *     lo, hi and d (a value_range; d > 0, lo <= hi);
+ *   C == 1: the channel three times (C' = 3);
+ *   N == 1: the grid is the image, [C'][H][W]; else xmaps = min(nrow, N), ymaps = ceil(N / xmaps), the grid is
+ *     [C'][ymaps * (H + padding) + padding][xmaps * (W + padding) + padding], image k at row (k / xmaps) * (H + padding) + padding and
+ *     column (k % xmaps) * (W + padding) + padding, every other pixel pad_value (the unused cells of the last row too).
+ * grid (nullable): the float grid.  u8 (nullable): uint8(min(255, max(0, floor(g * 255 + 0.5)))) laid out [Hg][Wg][3], or [Hg][Wg]
+ * with gray != 0 (C == 1 only).  At least one of the two.  One thread per pixel of the grid plane.
+ * Refused: C outside {1, 3}; N, H, W or nrow < 1; padding < 0; N * C * H * W or 3 * Hg * Wg above 2^31 - 1; a range pointer that is not
+ * 4-byte aligned.                                                                                                                       */
+typedef struct pcg_image_sheet_args {
+  const float* x;          /* [N][C][H][W] */
+  const float* range;      /* nullable: [2] on the device, read when normalize != 0 */
+  float* grid;             /* nullable: [3][Hg][Wg] */
+  uint8_t* u8;             /* nullable: [Hg][Wg][3] or, gray, [Hg][Wg] */
+  float lo, hi, d;         /* read when normalize != 0 and range == null */
+  float pad_value, pre_scale, pre_shift;
+  int32_t N, C, H, W, nrow, padding, normalize, gray;
+} pcg_image_sheet_args;
+int pcg_image_sheet(const pcg_image_sheet_args* args, pcg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,7 +4,7 @@ and PyTorch nn.Module / optimizer drop-ins that call them.
 
 The directory name carries a hyphen; import it as `pcgan_amd` (the shim `pcgan_amd.py` at the repo root).
 """
-from . import _lib, ops  # noqa: F401
+from . import _lib, ops, sheets  # noqa: F401
 from ._lib import LIB_PATH, PcgError  # noqa: F401
 
 
@@ -17,4 +17,4 @@ def load():
         ops.prepare_conv_scratch()
     return lib
 
-__all__ = ["ops", "load", "LIB_PATH", "PcgError"]
+__all__ = ["ops", "sheets", "load","LIB_PATH", "PcgError"]

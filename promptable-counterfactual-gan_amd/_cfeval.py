@@ -127,6 +127,25 @@ def write_png_gray(path, u8):
                 block(b"IEND", b""))
 
 
+def write_png_rgb(path, u8):
+    """An [H][W][3] uint8 array as an 8-bit RGB PNG (colour type 2), built like write_png_gray's: what the image sheets
+    (pcgan_amd.sheets.save_image) write."""
+    import struct
+    import zlib
+    a = np.asarray(u8)
+    if a.ndim != 3 or a.shape[2] != 3 or a.dtype != np.uint8 or a.shape[0] < 1 or a.shape[1] < 1:
+        raise PcgError(f"write_png_rgb: expected a non-empty [H][W][3] uint8 array, got {a.shape} {a.dtype}")
+    h, w = a.shape[:2]
+
+    def block(tag, data):
+        return struct.pack(">I", len(data)) + tag + data + struct.pack(">I", zlib.crc32(tag + data) & 0xFFFFFFFF)
+    raw = np.concatenate([np.zeros((h, 1), np.uint8), a.reshape(h, 3 * w)], axis=1).tobytes()
+    os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
+    with open(path, "wb") as f:
+        f.write(b"\x89PNG\r\n\x1a\n" + block(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, 2, 0, 0, 0)) + block(b"IDAT", zlib.compress(raw, 9)) +
+                block(b"IEND", b""))
+
+
 def save_table(rows, save_path, columns):
     """DataFrame.to_csv(index=False) of a list of dicts: shortest float repr, nan as an empty field."""
     os.makedirs(os.path.dirname(save_path) or ".", exist_ok=True)

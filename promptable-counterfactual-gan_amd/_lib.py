@@ -297,7 +297,13 @@ class LogEpsLossArgs(ctypes.Structure):
     _fields_ = [(n, _P) for n in ("p", "grad_out", "loss", "dp")] + [("eps", _F), ("R", _I), ("mode", _I)]
 
 
-DELTA_GAN_BUILD, DELTA_GAN_REGATHER = 0, 1               # PCG_DELTA_GAN_* (include/pcgan_hip.h)
+class ImageSheetArgs(ctypes.Structure):
+    """pcg_image_sheet_args."""
+    _fields_ = ([(n, _P) for n in ("x", "range", "grid", "u8")] + [(n, _F) for n in ("lo", "hi", "d", "pad_value", "pre_scale", "pre_shift")] +
+                [(n, _I) for n in ("N", "C", "H", "W", "nrow", "padding", "normalize", "gray")])
+
+
+DELTA_GAN_BUILD, DELTA_GAN_REGATHER = 0, 1              # PCG_DELTA_GAN_* (include/pcgan_hip.h)
 LOGIT_HEAD_D, LOGIT_HEAD_G = 0, 1                        # PCG_LOGIT_HEAD_*
 DELTA_GAN_CHUNK = 1024                                   # PCG_DELTA_GAN_CHUNK
 PROB_HEAD_D, PROB_HEAD_G = 0, 1                          # PCG_PROB_HEAD_*
@@ -324,7 +330,7 @@ STRUCTS = {"pcg_conv_geom": ConvGeom, "pcg_in_xform": InXform, "pcg_wgrad_item":
            "pcg_logit_head_bwd_args": LogitHeadBwdArgs, "pcg_delta_gan_tail_bwd_args": DeltaGanTailBwdArgs,
            "pcg_delta_cf_entry_args": DeltaCfEntryArgs, "pcg_delta_cf_tail_args": DeltaCfTailArgs,
            "pcg_delta_gan_target_draw_args": DeltaGanTargetDrawArgs, "pcg_prob_head_fwd_args": ProbHeadFwdArgs,
-           "pcg_log_eps_loss_args": LogEpsLossArgs}
+           "pcg_log_eps_loss_args": LogEpsLossArgs, "pcg_image_sheet_args": ImageSheetArgs}
 
 _c = ctypes
 _vp, _f, _i, _i64, _sz = _c.c_void_p, _c.c_float, _c.c_int, _c.c_int64, _c.c_size_t
@@ -576,6 +582,9 @@ PROTOTYPES = {
     "pcg_class_pick": (_i, [_vp, _vp, _vp, _i32, _i32, _i32, _i64, _i32, _vp]),
     "pcg_class_pick_gather": (_i, [_vp, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _i32, _vp]),
     "pcg_cf_panels": (_i, [_i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
+    "pcg_image_range_workspace_bytes": (_sz, []),
+    "pcg_image_range": (_i, [_vp, _i64, _f, _f, _vp, _vp, _sz, _vp]),
+    "pcg_image_sheet": (_i, [_c.POINTER(ImageSheetArgs), _vp]),
     "pcg_spectral_norm_fwd": (_i, [_vp, _i32, _i32, _vp, _vp, _f, _i, _vp, _vp, _vp, _vp, _vp]),
     "pcg_spectral_norm_bwd": (_i, [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _i, _vp]),
 }

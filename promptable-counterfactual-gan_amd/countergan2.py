@@ -385,6 +385,14 @@ def counterfactual_batch(G, x, target):
     return _gt.counterfactual_batch(G, x, target)
 
 
+def save_examples(G, x, target, output_dir):
+    """countergan2.py:213-224 -- the counterfactuals of one batch towards `target` and the files original.png, counterfactual.png,
+    delta.png in output_dir (gan_train._example_sheets: the delta's `* 0.5 + 0.5` rides in the sheet's launches, from the raw delta).
+    Returns (original, counterfactual, delta) as uint8 arrays."""
+    cf, delta = counterfactual_batch(G, x, target)
+    return _gt._example_sheets(x, cf, delta, output_dir)
+
+
 def delta_image(delta):
     """countergan2.py:224 -- delta * 0.5 + 0.5, the picture of the change."""
     _need_gpu(delta, "delta_image")

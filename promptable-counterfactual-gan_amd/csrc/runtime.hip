@@ -38,6 +38,7 @@ int launch_status(const char* what) {
 //   + pcg_delta_cf_entry, pcg_delta_cf_tail, pcg_delta_gan_target_draw (csrc/delta_cf_eval.hip).
 //   + pcg_prob_head_fwd (+ _workspace_bytes), pcg_log_eps_loss_fwd_bwd (csrc/prob_head.hip).
 //   + pcg_class_pick, pcg_class_pick_gather, pcg_cf_panels (csrc/cf_report.hip).
+//   + pcg_image_range (+ _workspace_bytes), pcg_image_sheet (csrc/image_sheet.hip).
 // v5, additive: + pcg_conv_precision_set / _get (thread-local bf16-operand mode of the implicit-GEMM convolutions).
 // v5 (r04): + grouped batches (pcg_conv2d_fwd_bn_g, pcg_bn_apply_act_g, pcg_conv2d_dgrad_bn_phases, pcg_conv2d_dgrad_bnbwd_g,
 //   pcg_bn_bwd_partial_g(+_workspace_bytes), pcg_bn_act_bwd_premask_g(+pcg_bn_act_bwd_g_workspace_bytes), pcg_bce_pair),
@@ -64,7 +65,7 @@ extern "C" size_t pcg_abi_struct_bytes(const char* name) {
       PCG_STRUCT(pcg_delta_gan_entry_args), PCG_STRUCT(pcg_delta_gan_tail_fwd_args), PCG_STRUCT(pcg_logit_head_fwd_args),
       PCG_STRUCT(pcg_logit_head_bwd_args), PCG_STRUCT(pcg_delta_gan_tail_bwd_args), PCG_STRUCT(pcg_delta_cf_entry_args),
       PCG_STRUCT(pcg_delta_cf_tail_args), PCG_STRUCT(pcg_delta_gan_target_draw_args), PCG_STRUCT(pcg_prob_head_fwd_args),
-      PCG_STRUCT(pcg_log_eps_loss_args)};
+      PCG_STRUCT(pcg_log_eps_loss_args), PCG_STRUCT(pcg_image_sheet_args)};
 #undef PCG_STRUCT
   if (name)
     for (const auto& t : table)

@@ -16,6 +16,7 @@ import torch.nn as nn
 
 from . import checkpoint as _ckpt
 from . import ops
+from . import sheets
 from . import nn as _nn
 from ._lib import PcgError
 from .data import DeviceLoader
@@ -209,7 +210,7 @@ def build(cfg=None, device="cuda", seed=None):
 
 
 def train(dataloader, cfg=None, netG=None, netD=None, device="cuda", log=print, device_rng=None, dp=None, checkpoint=None, checkpoint_every=1,
-          resume=None):
+          resume=None, grid=False):
     """The reference's training script from the fixed viz noise to the per-epoch loss averages (mnist_dcgan.py:129-198) with
     its plotting left out: `dataloader` yields (images, ...) batches (:143,148), per iteration one `train_step`, every 200
     iterations the log line (:178-181), every 500 iterations and at the very end a forward of the generator on the fixed
@@ -231,6 +232,9 @@ def train(dataloader, cfg=None, netG=None, netD=None, device="cuda", log=print, 
     interrupted call and are not stored).  The viz forward at "the very end" belongs to the last epoch of cfg["epochs"]: a run that
     is to be continued bit for bit is one that was interrupted, not one that ended at a smaller cfg["epochs"].  With dp (data
     parallel) both arguments are refused: checkpoints of a data-parallel run are not implemented.
+    grid=True: `img_list` holds what the reference's holds, `vutils.make_grid(fake, padding=2, normalize=True)` (:190) of every viz
+    batch, made on the device (pcgan_amd.sheets) and copied to the CPU: [3, 530, 530] for 64 images of 64 x 64.  The
+    grids are not part of the numerical path: losses, nets and resume behave as with grid=False.
     Returns a dict: netG, netD, epoch_G_losses, epoch_D_losses, img_list, iters."""
     c = _cfg(cfg)
     _ckpt.check_args("dcgan.train", checkpoint, checkpoint_every, resume)
@@ -283,7 +287,8 @@ def train(dataloader, cfg=None, netG=None, netD=None, device="cuda", log=print, 
                 if dp is not None:
                     dp.wait(netG)                                             # Adam(G) of this iteration runs on the side stream
                 with torch.no_grad():
-                    img_list.append(netG(viz_noise).detach().cpu())           # :188-189 (train mode: updates running stats)
+                    fake = netG(viz_noise).detach()                           # :188-189 (train mode: updates running stats)
+                    img_list.append((sheets.make_grid(fake.contiguous(), padding=2, normalize=True) if grid else fake).cpu())   # :190
             iters += 1                                                        # :193
         running_G_loss = running_D_loss = 0.0                                 # :141-142, :184-185 (same order of additions)
         for e_real, e_fake, e_g in pending:
@@ -299,3 +304,9 @@ def train(dataloader, cfg=None, netG=None, netD=None, device="cuda", log=print, 
         dp.wait_all()
     return {"netG": netG, "netD": netD, "epoch_G_losses": epoch_G_losses, "epoch_D_losses": epoch_D_losses, "img_list": img_list,
             "iters": iters}
+
+
+def real_grid(real_batch, device="cuda"):
+    """mnist_dcgan.py:222 -- `vutils.make_grid(real_batch[0][:64], padding=5, normalize=True)`: the grid of the first 64 rows of a batch
+    of real images, made on `device` (the batch is uploaded if it is not there); the float grid on the device."""
+    return sheets.make_grid(real_batch[:64].to(device, torch.float32).contiguous(), padding=5, normalize=True)

@@ -20,11 +20,14 @@ The torch layer objects are kept as parameter containers (`label_embed`, and `ne
 `state_dict()` keys and shapes are the reference's in both directions with strict=True.  Forward and backward are one autograd node per
 network sequencing C-ABI calls on NHWC activations (csrc/delta_gan.hip holds the fused launches around the convolutions; DESIGN.md
 §3.19; csrc/delta_cf_eval.hip the query windows and the class draw, §3.20)."""
+import os
+
 import torch
 import torch.nn as nn
 
 from . import checkpoint as _ckpt
 from . import ops
+from . import sheets
 from ._graphed import Held, capture_steps
 from ._lib import ACT_LRELU, ACT_NONE, ACT_RELU, PcgError
 from .countergan import (PER_CLASS_FIELDS, BCEWithLogitsLoss, Classifier, CrossEntropyLoss, _as_rows, _conv_fwd, _conv_wgrad, _dgrad_act, _geom,
@@ -649,6 +652,26 @@ def counterfactual_batch(G, imgs, target):
         B = imgs.shape[0]
         cf = ops.clamp_add_fwd(_as_rows(imgs, B), delta.reshape(B, HW), -1.0, 1.0)
     return cf.view(B, 1, H, W), delta
+
+
+def _example_sheets(imgs, cf, delta, output_dir):
+    """The three sheets of gan_train.py:161-163 / countergan2.py:222-224 -- save_image(..., nrow=4, normalize=True) of the images, the
+    counterfactuals and `deltas * 0.5 + 0.5` (the affine rides in the sheet's own launches: pre=(0.5, 0.5) on the raw delta) --
+    made on the device (pcgan_amd.sheets), one uint8 download each.  Returns the three [Hg, Wg, 3] uint8 arrays."""
+    B = imgs.shape[0]
+    return tuple(sheets.save_image(t.detach().reshape(B, 1, H, W).contiguous(), os.path.join(output_dir, name + ".png"), nrow=4, normalize=True,
+                                   pre=pre)
+                 for name, t, pre in (("original", imgs, (1.0, 0.0)), ("counterfactual", cf, (1.0, 0.0)), ("delta", delta, (0.5, 0.5))))
+
+
+def save_examples(G, imgs, target, output_dir):
+    """gan_train.py:155-163 -- the counterfactuals of one batch towards `target` (a class for every row, or one class per row) and
+    the files original.png, counterfactual.png, delta.png in output_dir.  Returns (original, counterfactual, delta) as uint8 arrays."""
+    _need_gpu(imgs, "save_examples")
+    if not torch.is_tensor(target):
+        target = torch.full((imgs.shape[0],), int(target), dtype=torch.int64, device=imgs.device)      # :155
+    cf, delta = counterfactual_batch(G, imgs, target)
+    return _example_sheets(imgs, cf, delta, output_dir)
 
 
 # ---- the promptable half: queries, the all-targets sweep, per-target evaluation (gan_train_copy.py:161-172; DESIGN.md §3.20) -------------

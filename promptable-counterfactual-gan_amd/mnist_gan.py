@@ -10,11 +10,14 @@ grad-input GEMM whose epilogue is the activation derivative and BatchNorm backwa
 the weight + bias gradient (`ops.dense_rows_wgrad`).  `use_fused = False` on a net runs the same layers as a chain of the older ops
 (linear_fwd / linear_dgrad / linear_wgrad, bn_train_stats / bn_apply_act / bn_act_bwd, act_fwd / act_bwd): the in-project baseline.
 """
+import os
+
 import numpy as np
 import torch
 import torch.nn as nn
 
 from . import ops
+from . import sheets
 from ._lib import ACT_LRELU, ACT_NONE, ACT_SIGMOID, ACT_TANH, PcgError
 from .nn import FlatModule, GraphedStep, linear_dgrad, linear_fwd, linear_wgrad
 from .optim import Adam
@@ -303,12 +306,15 @@ def train_step(generator, discriminator, opt_g, opt_d, real, z, record=None):
     return g_loss, d_loss
 
 
-def train(generator, discriminator, loader, cfg=config, opt_g=None, opt_d=None, epochs=None, seed=0, draws=None, graphed=False):
+def train(generator, discriminator, loader, cfg=config, opt_g=None, opt_d=None, epochs=None, seed=0, draws=None, graphed=False,
+          image_dir=None):
     """The epochs loop (:111-139) over a `data.DeviceLoader` (reshuffled every epoch, last short batch kept, like the reference's
     DataLoader).  z is drawn on the device (pcg_randn); `draws(epoch, i, rows)` overrides it with a host array or tensor
     [rows, latent_dim] — the reference draws z with np.random.normal on the host (:122), parity runs pass the same numbers.
-    graphed: replay the step through nn.GraphedStep, one graph per distinct batch size.  Returns the per-epoch
-    (generator_loss, discriminator_loss) of the epoch's last batch (:139), read back once at the end."""
+    graphed: replay the step through nn.GraphedStep, one graph per distinct batch size.  image_dir (a path): after every epoch the
+    first 25 rows of the epoch's last generated batch are written to `{image_dir}/{epoch}.png` as the reference does (:140-141:
+    `save_image(generated_images.data[:25], ..., nrow=5, normalize=True)`), the sheet made on the device (pcgan_amd.sheets).  Returns
+    the per-epoch (generator_loss, discriminator_loss) of the epoch's last batch (:139), read back once at the end."""
     G, D = generator, discriminator
     if opt_g is None or opt_d is None:
         opt_g, opt_d = make_optimizers(G, D, cfg)
@@ -339,6 +345,9 @@ def train(generator, discriminator, loader, cfg=config, opt_g=None, opt_d=None, 
                 last = train_step(G, D, opt_g, opt_d, real, z)
         if last is not None:
             losses.append((last[0].clone(), last[1].clone()))                                # :139
+            if image_dir is not None:                                                        # :140-141; the step left the batch in X[R:]
+                generated = _workspace(G, D, R, dev).X[R:2 * R][:25].view(-1, *img_shape(cfg))
+                sheets.save_image(generated, os.path.join(image_dir, f"{epoch}.png"), nrow=5, normalize=True)
     return [(float(a.item()), float(b.item())) for a, b in losses]
 
 

@@ -25,6 +25,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
+from . import sheets
 from ._lib import ACT_LRELU, PcgError
 from .nn import FlatModule, GraphedStep, SequentialConvNet, _compile, in_conv_precision, linear_dgrad, linear_fwd, linear_wgrad, mean, weighted_sum
 from .optim import AdamW
@@ -485,16 +486,44 @@ class GraphedSteps:
         return self._generator.replay()
 
 
-def train(critic, generator, dataloader, hp, device, rng=None, epochs=None, graphed=False):
+def class_grid(generator, hp, fixed_noise=None, per_class=8):
+    """:123-125 and :181-182 -- the class grid: `per_class` fixed noises per class, labels [0] * per_class + [1] * per_class + ...,
+    the generator's images under no_grad and `vutils.make_grid(fake_images, padding=2, normalize=True)`, made on the device
+    (pcgan_amd.sheets): [3, 302, 242] for 80 images of 28 x 28.  fixed_noise [num_classes * per_class, latent_size] on the
+    generator's device; None draws it with torch.randn there (:124).  The generator runs in the mode it is in: in training mode,
+    as in the reference, the forward updates the BatchNorm running statistics.  Returns the float grid on the device."""
+    dev = next(generator.parameters()).device
+    n = hp.num_classes * int(per_class)
+    if fixed_noise is None:
+        fixed_noise = torch.randn((n, hp.latent_size), device=dev)                                                   # :124
+    if tuple(fixed_noise.shape) != (n, hp.latent_size):
+        raise PcgError(f"class_grid: fixed_noise must be [{n}, {hp.latent_size}], got {tuple(fixed_noise.shape)}")
+    classes = torch.arange(hp.num_classes, dtype=torch.int64, device=dev).repeat_interleave(int(per_class))           # :125
+    with torch.no_grad():
+        fake_images = generator(fixed_noise, ops.onehot(classes, hp.num_classes))                                    # :181
+    return sheets.make_grid(fake_images.contiguous(), padding=2, normalize=True)                                     # :182
+
+
+def train(critic, generator, dataloader, hp, device, rng=None, epochs=None, graphed=False, grid_every=None, img_list=None, fixed_noise=None):
     """:129-189 without the plotting tail: `dataloader` yields (images [B,1,28,28], class indices [B]); one-hot rows come from
     an identity table (:123,133); noise / alpha / fake labels are drawn on the device.  graphed=True: full batches of hp.batchsize
-    rows replay GraphedSteps (same numbers); a ragged last batch runs eagerly."""
+    rows replay GraphedSteps (same numbers); a ragged last batch runs eagerly.
+    grid_every (an int; None: no grids): the lines the reference keeps commented out (:180-182) -- when `iters % grid_every == 0` and
+    at the very last iteration one class_grid of `fixed_noise` (None: drawn once, :124) is appended to the list `img_list`, as a CPU
+    tensor.  That forward runs in training mode and updates the generator's BatchNorm running statistics, as the reference's would."""
     critic_optimizer, generator_optimizer = make_optimizers(critic, generator)
     gs = GraphedSteps(critic, generator, critic_optimizer, generator_optimizer, hp, hp.batchsize, device) if graphed else None
     rng = rng if rng is not None else ops.DeviceRNG(seed=1)
     history = []
     generator_loss = None
-    for epoch in range(hp.num_epochs if epochs is None else epochs):
+    n_epochs = hp.num_epochs if epochs is None else epochs
+    iters = 0
+    if grid_every is not None:
+        if int(grid_every) < 1 or img_list is None:
+            raise PcgError(f"train: grid_every {grid_every} must be >= 1 and needs a list img_list to append to")
+        if fixed_noise is None:
+            fixed_noise = torch.randn((hp.num_classes * 8, hp.latent_size), device=device)                           # :124
+    for epoch in range(n_epochs):
         d_sum = g_sum = 0.0
         n = 0
         for batch_idx, (images, labels) in enumerate(dataloader):
@@ -512,6 +541,9 @@ def train(critic, generator, dataloader, hp, device, rng=None, epochs=None, grap
                                   generator_step(critic, generator, generator_optimizer, fake_labels, noise))["generator_loss"]
             d_sum += out["critic_loss"].item(); g_sum += generator_loss.item()           # :177-178
             n += 1
+            if grid_every is not None and (iters % int(grid_every) == 0 or (epoch == n_epochs - 1 and batch_idx == len(dataloader) - 1)):
+                img_list.append(class_grid(generator, hp, fixed_noise).cpu())             # :180-182
+            iters += 1                                                                   # :184
         history.append((d_sum / max(n, 1), g_sum / max(n, 1)))
     return history
 
