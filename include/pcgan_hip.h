@@ -84,18 +84,11 @@ size_t pcg_conv2d_dgrad_workspace_bytes(const pcg_conv_geom* g);
 typedef enum pcg_precision { PCG_PREC_F32 = 0, PCG_PREC_BF16 = 1 } pcg_precision;
 int pcg_conv_precision_set(int32_t precision);
 int32_t pcg_conv_precision_get(void);
+/* The plain forms as positional calls (pcg_conv2d below with nothing but the operands and the workspace set). */
 int pcg_conv2d_fwd(const pcg_conv_geom* g, const float* x, const float* w, const float* bias /*nullable*/,
                    float* y, void* workspace /*nullable*/, size_t workspace_bytes, pcg_stream_t stream);
 int pcg_conv2d_dgrad(const pcg_conv_geom* g, const float* dy, const float* w, const float* bias_x /*nullable: added per Cin channel (ConvTranspose2d bias)*/,
                      float* dx, void* workspace /*nullable*/, size_t workspace_bytes, pcg_stream_t stream);
-/* The same with the activation that follows the layer fused into the output write — y = act(conv(x) + bias):
- * Conv2d + LeakyReLU (mnist_dcgan.py:100-101, counteRGAN models/discriminator.py:17-24, generator.py:36-37,50),
- * Conv2d + ReLU (models/classifier.py:7-12), Conv2d + Sigmoid (mnist_dcgan.py:110-111), ConvTranspose2d + Tanh
- * (mnist_dcgan.py:88-89, mnist_wgan_conditional.py:70-71).  The backward needs only y (pcg_act_bwd). */
-int pcg_conv2d_fwd_act(const pcg_conv_geom* g, const float* x, const float* w, const float* bias /*nullable*/, int act, float slope,
-                       float* y, void* workspace /*nullable*/, size_t workspace_bytes, pcg_stream_t stream);
-int pcg_conv2d_dgrad_act(const pcg_conv_geom* g, const float* dy, const float* w, const float* bias_x /*nullable*/, int act, float slope,
-                         float* dx, void* workspace /*nullable*/, size_t workspace_bytes, pcg_stream_t stream);
 size_t pcg_conv2d_wgrad_workspace_bytes(const pcg_conv_geom* g);
 /* Deferred slab reductions (r04).  A split-K weight gradient ends with a small launch that sums its K-slice slabs into dw; in a backward
  * sweep nothing reads dw before the sweep ends (optimizer.step(), mnist_dcgan.py:164,176; the gradient exchange).  Between
@@ -110,18 +103,10 @@ int32_t pcg_slab_defer_pending(void);
  * (the reference accumulates .grad over two backward() calls: mnist_dcgan.py:153,161).             */
 int pcg_conv2d_wgrad(const pcg_conv_geom* g, const float* x, const float* dy, float* dw, int accumulate,
                      void* workspace, size_t workspace_bytes, pcg_stream_t stream);
-/* Convolution + training-mode BatchNorm statistics of its output in one call (MFMA layers only): the per-channel sum /
- * sum of squares are taken from the accumulator tile in the conv epilogue (no extra pass over y), partial rows are
- * finalised in a fixed order.  Same outputs as pcg_conv2d_fwd (resp. _dgrad) followed by pcg_bn_train_stats.
- * workspace: pcg_conv2d_{fwd,dgrad}_bn_workspace_bytes (0 = layer not eligible: use the two separate calls).          */
+/* Partial-row buffers of the fused BatchNorm statistics (pcg_conv_args.stats) and of the add_bnsum / bnbwd epilogues
+ * (0 = layer not eligible: use the separate calls).                                                                     */
 size_t pcg_conv2d_fwd_bn_workspace_bytes(const pcg_conv_geom* g);
 size_t pcg_conv2d_dgrad_bn_workspace_bytes(const pcg_conv_geom* g);
-int pcg_conv2d_fwd_bn(const pcg_conv_geom* g, const float* x, const float* w, const float* bias, float* y,
-                      float eps, float momentum, float* save_mean, float* save_invstd, float* running_mean, float* running_var,
-                      int64_t* num_batches_tracked, void* workspace, size_t workspace_bytes, pcg_stream_t stream);
-int pcg_conv2d_dgrad_bn(const pcg_conv_geom* g, const float* dy, const float* w, const float* bias_x, float* dx,
-                        float eps, float momentum, float* save_mean, float* save_invstd, float* running_mean, float* running_var,
-                        int64_t* num_batches_tracked, void* workspace, size_t workspace_bytes, pcg_stream_t stream);
 /* ---- input transforms: BatchNorm + ReLU / LeakyReLU of the PRODUCING layer applied inside the consumer's gather ------------------
  * In `Conv -> BatchNorm(train) -> LeakyReLU -> Conv` (mnist_dcgan.py:102-110, G: :76-87) the activated tensor a = act(bn(z)) is
  * only ever read by the next convolution (forward, and again by that layer's weight gradient).  With a transform the consumer
@@ -129,89 +114,113 @@ int pcg_conv2d_dgrad_bn(const pcg_conv_geom* g, const float* dy, const float* w,
  * separate BatchNorm-apply pass and the activated copy of every such activation disappear.  scale / shift are the folded
  * BatchNorm (scale = gamma*invstd, shift = beta - mean*scale — exactly the expression pcg_bn_apply_act evaluates, so results are
  * bit-identical to the unfused sequence); zero padding stays zero.  MFMA layers only (Cin > 3, Cout > 3, channel counts % 4 == 0).
- *   _fwd_bn_xf / _dgrad_bn_xf : as pcg_conv2d_{fwd,dgrad}_bn with the transform `xf` (nullable) on the input operand (x resp. dy
- *                               — the forward input of a ConvTranspose2d layer) and, if coef_out != NULL, the folded scale / shift
- *                               [2][C] of THIS layer's BatchNorm (gamma, beta required) written by the statistics finalize —
- *                               ready to be the next consumer's transform;
- *   _fwd_xf / _dgrad_xf       : as pcg_conv2d_{fwd,dgrad}_act with a transform on the input operand;
- *   _wgrad_xf                 : weight gradient with the transform on x (Conv2d) or on dy (ConvTranspose2d, whose forward input
- *                               sits on the dy side of the adjoint geometry) — at most one of the two. */
+ * pcg_conv_args.xf puts one on the input operand of a forward or grad-input launch; pcg_conv2d_wgrad_xf takes one on x (Conv2d) or on
+ * dy (ConvTranspose2d, whose forward input sits on the dy side of the adjoint geometry) — at most one of the two. */
 typedef struct pcg_in_xform {
   const float* scale;   /* [C], 16-byte aligned; NULL: no transform */
   const float* shift;   /* [C] */
   int32_t act;          /* PCG_ACT_NONE / PCG_ACT_RELU / PCG_ACT_LRELU */
   float slope;
 } pcg_in_xform;
-int pcg_conv2d_fwd_bn_xf(const pcg_conv_geom* g, const float* x, const pcg_in_xform* xf, const float* w, const float* bias, float* y,
-                         float eps, float momentum, float* save_mean, float* save_invstd, float* running_mean, float* running_var,
-                         int64_t* num_batches_tracked, const float* gamma, const float* beta, float* coef_out /*nullable [2][Cout]*/,
-                         void* workspace, size_t workspace_bytes, pcg_stream_t stream);
-int pcg_conv2d_dgrad_bn_xf(const pcg_conv_geom* g, const float* dy, const pcg_in_xform* xf, const float* w, const float* bias_x, float* dx,
-                           float eps, float momentum, float* save_mean, float* save_invstd, float* running_mean, float* running_var,
-                           int64_t* num_batches_tracked, const float* gamma, const float* beta, float* coef_out /*nullable [2][Cin]*/,
-                           void* workspace, size_t workspace_bytes, pcg_stream_t stream);
-int pcg_conv2d_fwd_xf(const pcg_conv_geom* g, const float* x, const pcg_in_xform* xf, const float* w, const float* bias, int act,
-                      float slope, float* y, void* workspace /*nullable*/, size_t workspace_bytes, pcg_stream_t stream);
-int pcg_conv2d_dgrad_xf(const pcg_conv_geom* g, const float* dy, const pcg_in_xform* xf, const float* w, const float* bias_x, int act,
-                        float slope, float* dx, void* workspace /*nullable*/, size_t workspace_bytes, pcg_stream_t stream);
 int pcg_conv2d_wgrad_xf(const pcg_conv_geom* g, const float* x, const pcg_in_xform* xf_x, const float* dy, const pcg_in_xform* xf_dy,
                         float* dw, int accumulate, void* workspace, size_t workspace_bytes, pcg_stream_t stream);
-/* Backward-pass epilogues (MFMA layers).  In autograd's sweep through `Conv -> [BatchNorm] -> ReLU/LeakyReLU -> Conv` (D:
- * mnist_dcgan.py:100-110, G: :76-87) the gradient w.r.t. a layer's OUTPUT a = act(..) is produced by the grad-input kernel of the
- * layer above; these entry points apply the lower layer's activation derivative while that tile is still in registers:
- *   _mask  : dx = conv_dgrad(dy, w) * act'(a_below)            (a_below = the post-activation output, same shape as dx) —
- *            replaces the pcg_act_bwd pass of a Conv + LeakyReLU layer without BatchNorm (mnist_dcgan.py:100-101);
- *   _bnbwd : dx = conv_dgrad(dy, w) * act'(bn(z_below)) with the mask recomputed from the pre-BatchNorm output z_below as
- *            fma(z, gamma*invstd, beta - mean*gamma*invstd) > 0, and the per-channel sums of dx and dx*xhat written as partial
- *            rows ([pcg_conv2d_*_bn_partial_rows][2][C], buffer of pcg_conv2d_*_bn_workspace_bytes) — the reduction pass of
- *            BatchNorm's backward disappears; finish with pcg_bn_bwd_partial.
- * The `fwd` forms are the same for ConvTranspose2d layers (their grad-input is a forward convolution).  act: none / ReLU / LeakyReLU. */
-int pcg_conv2d_dgrad_mask(const pcg_conv_geom* g, const float* dy, const float* w, const float* a_below, int act, float slope,
-                          float* dx, void* workspace /*nullable*/, size_t workspace_bytes, pcg_stream_t stream);
-/* r04: pcg_conv2d_dgrad_mask also serves one-channel layers whose grad-input takes the row-block form (..._thin_ok: k3 / k4, Cout
- * <= 3, Cin a power-of-two multiple of 4): the mask is applied in the thin expand kernel (CounteRGAN conv_out, models/generator.py:50). */
-int32_t pcg_conv2d_dgrad_mask_thin_ok(const pcg_conv_geom* g);
 /* Thin layers that take an input transform (r04): a Cin = 1 geometry with Cout = 64 and <= 16 taps — DCGAN's last ConvTranspose2d(64, 1, 4, 2, 1)
- * (mnist_dcgan.py:88), whose input is BatchNorm2d + ReLU of the layer before (:86-87).  pcg_conv2d_dgrad_xf (its forward) and
+ * (mnist_dcgan.py:88), whose input is BatchNorm2d + ReLU of the layer before (:86-87).  A grad-input pcg_conv2d with xf (its forward) and
  * pcg_conv2d_wgrad_xf with xf_dy (its weight gradient) then read the PRE-BatchNorm tensor: the BatchNorm-apply pass and the activated
  * copy of that activation disappear (both kernels are HBM-bound: the transform is free).  Needs the workspace of
  * pcg_conv2d_dgrad_workspace_bytes / pcg_conv2d_wgrad_workspace_bytes.                                                              */
 int32_t pcg_conv2d_xf_thin_ok(const pcg_conv_geom* g);
-/* y = (conv(x, w) + addend) * act'(a_below) — pcg_conv2d_*_add followed by pcg_act_bwd in ONE epilogue: the last skip-add of a residual
- * chain arriving at the entry convolution's LeakyReLU (models/generator.py:76 backward).  a_below: the activated output, output's shape. */
-int pcg_conv2d_fwd_add_mask(const pcg_conv_geom* g, const float* x, const float* w, const float* addend, const float* a_below, int act,
-                            float slope, float* y, pcg_stream_t stream);
-int pcg_conv2d_dgrad_add_mask(const pcg_conv_geom* g, const float* dy, const float* w, const float* addend, const float* a_below, int act,
-                              float slope, float* dx, pcg_stream_t stream);
-int pcg_conv2d_fwd_mask(const pcg_conv_geom* g, const float* x, const float* w, const float* a_below, int act, float slope,
-                        float* y, void* workspace /*nullable*/, size_t workspace_bytes, pcg_stream_t stream);
-int pcg_conv2d_dgrad_bnbwd(const pcg_conv_geom* g, const float* dy, const float* w, const float* z_below, const float* mean,
-                           const float* invstd, const float* gamma, const float* beta, int act, float slope, float* dx,
-                           void* partial, size_t partial_bytes, pcg_stream_t stream);
-int pcg_conv2d_fwd_bnbwd(const pcg_conv_geom* g, const float* x, const float* w, const float* z_below, const float* mean,
-                         const float* invstd, const float* gamma, const float* beta, int act, float slope, float* y,
-                         void* partial, size_t partial_bytes, pcg_stream_t stream);
-/* dx = conv_dgrad(dy, w) + addend  (addend may be dx itself: in-place accumulation) — the skip connection of a residual block
- * in the backward sweep (`x + 0.1*out`, conditional_counteRGAN/mnist/models/generator.py:20): no separate add pass.  MFMA layers. */
-int pcg_conv2d_dgrad_add(const pcg_conv_geom* g, const float* dy, const float* w, const float* addend, float* dx,
-                         void* workspace /*nullable*/, size_t workspace_bytes, pcg_stream_t stream);
-/* pcg_conv2d_dgrad_add + the BatchNorm-backward column sums of the SUM for the next BatchNorm down the skip chain
- * (`x + 0.1*bn2(conv2(...))`, models/generator.py:18-20: the gradient arriving at block i-1's bn2 is the sum block i's backward just
- * formed): partial rows get sum(sum_scale*dx) and sum(sum_scale*dx*xhat) with xhat from z_next / mean / invstd of that BatchNorm;
- * dx itself is stored unscaled.  Finish with pcg_bn_bwd_partial_db(dm = dx, dm_scale = sum_scale).  partial: the buffer of
- * pcg_conv2d_dgrad_bn_workspace_bytes, pcg_conv2d_dgrad_bn_partial_rows rows.  addend == NULL (r04, both forms): the plain grad-input
- * with the sums — the head of the chain, conv_mid's grad-input above the last block's bn2 (generator.py:49,78). */
-int pcg_conv2d_dgrad_add_bnsum(const pcg_conv_geom* g, const float* dy, const float* w, const float* addend /*nullable*/, const float* z_next,
-                               const float* mean, const float* invstd, float sum_scale, float* dx, void* partial, size_t partial_bytes,
-                               pcg_stream_t stream);
-/* The `fwd` forms of the skip-add epilogues (a ConvTranspose2d's grad-input; or a stride-1 Conv2d's grad-input run as a forward
- * convolution of dy with the adjoint weight — pcg_conv_weight_adjoint: w[co][kh][kw][ci] -> w_adj[ci][KH-1-kh][KW-1-kw][co], geometry
- * {B, OH, OW, Cout -> IH, IW, Cin, pad' = K-1-pad} — which makes both GEMM operands K-major). */
-int pcg_conv2d_fwd_add(const pcg_conv_geom* g, const float* x, const float* w, const float* addend, float* y,
-                       void* workspace /*nullable*/, size_t workspace_bytes, pcg_stream_t stream);
-int pcg_conv2d_fwd_add_bnsum(const pcg_conv_geom* g, const float* x, const float* w, const float* addend, const float* z_next,
-                             const float* mean, const float* invstd, float sum_scale, float* y, void* partial, size_t partial_bytes,
-                             pcg_stream_t stream);
+/* One-channel layers whose grad-input takes the row-block form (k3 / k4, Cout <= 3, Cin a power-of-two multiple of 4) also take the
+ * mask epilogue (r04): it is applied in the thin expand kernel (CounteRGAN conv_out, models/generator.py:50). */
+int32_t pcg_conv2d_dgrad_mask_thin_ok(const pcg_conv_geom* g);
+
+/* ---- pcg_conv2d: every form of the forward and the grad-input convolution -------------------------------------------------------
+ * One launch = one pcg_conv_args.  A zero-filled struct with op, in, w and out set is the plain convolution; every other member
+ * switches one thing on.  Three families exist, and pcg_conv2d refuses every mixture of them before any HIP call:
+ *   - the convolution with its bias, output activation and input transform (act, slope, bias, xf);
+ *   - the same without activation + the training-mode BatchNorm statistics of its output (stats; bias and xf allowed);
+ *   - the bare convolution with a backward-pass epilogue (epi; no bias, activation, transform or statistics).
+ * A ConvTranspose2d layer runs the other direction (header comment): its forward is PCG_CONV_DGRAD, its grad-input PCG_CONV_FWD, so
+ * every epilogue exists in both directions.  A stride-1 Conv2d's grad-input may also run as a FORWARD convolution of dy with the adjoint
+ * weight — pcg_conv_weight_adjoint: w[co][kh][kw][ci] -> w_adj[ci][KH-1-kh][KW-1-kw][co], geometry {B, OH, OW, Cout -> IH, IW, Cin,
+ * pad' = K-1-pad} — which makes both GEMM operands K-major.                                                                        */
+typedef enum pcg_conv_op { PCG_CONV_FWD = 0, PCG_CONV_DGRAD = 1 } pcg_conv_op;
+/* Backward-pass epilogues (MFMA layers).  In autograd's sweep through `Conv -> [BatchNorm] -> ReLU/LeakyReLU -> Conv` (D:
+ * mnist_dcgan.py:100-110, G: :76-87) the gradient w.r.t. a layer's OUTPUT a = act(..) is produced by the grad-input kernel of the
+ * layer above; an epilogue applies the lower layer's activation derivative (epi_act: none / ReLU / LeakyReLU, epi_slope) or a skip
+ * connection's add while that tile is still in registers.  out = conv(in, w) in the launch's direction, then:                      */
+typedef enum pcg_conv_epi {
+  PCG_CONV_EPI_NONE = 0,
+  /* out *= act'(a_below)   (a_below = the post-activation output of the layer below, out's shape) — replaces the pcg_act_bwd pass of a
+   * Conv + LeakyReLU layer without BatchNorm (mnist_dcgan.py:100-101).  Also on pcg_conv2d_dgrad_mask_thin_ok geometries.          */
+  PCG_CONV_EPI_MASK = 1,
+  /* out += addend   (addend may be out itself: in-place accumulation) — the skip connection of a residual block in the backward
+   * sweep (`x + 0.1*out`, conditional_counteRGAN/mnist/models/generator.py:20): no separate add pass.                               */
+  PCG_CONV_EPI_ADD = 2,
+  /* out = (out + addend) * act'(a_below) — the add followed by pcg_act_bwd in ONE epilogue: the last skip-add of a residual chain
+   * arriving at the entry convolution's LeakyReLU (models/generator.py:76 backward).  a_below: the activated output, not out itself. */
+  PCG_CONV_EPI_ADD_MASK = 3,
+  /* The add + the BatchNorm-backward column sums of the SUM for the next BatchNorm down the skip chain (`x + 0.1*bn2(conv2(...))`,
+   * models/generator.py:18-20: the gradient arriving at block i-1's bn2 is the sum block i's backward just formed): the partial rows
+   * get sum(sum_scale*out) and sum(sum_scale*out*xhat) with xhat from z / mean / invstd of that BatchNorm (z = its pre-normalisation
+   * output z_next); out itself is stored unscaled.  Finish with pcg_bn_bwd_partial_db(dm = out, dm_scale = sum_scale).
+   * addend == NULL (r04): the plain result with the sums — the head of the chain, conv_mid's grad-input above the last block's bn2
+   * (generator.py:49,78).                                                                                                           */
+  PCG_CONV_EPI_ADD_BNSUM = 4,
+  /* out *= act'(bn(z)) with the mask recomputed from the pre-BatchNorm output z (= z_below) of the layer below as
+   * fma(z, gamma*invstd, beta - mean*gamma*invstd) > 0, and the per-channel sums of out and out*xhat written as partial rows — the
+   * reduction pass of BatchNorm's backward disappears; finish with pcg_bn_bwd_partial.                                              */
+  PCG_CONV_EPI_BNBWD = 5
+} pcg_conv_epi;
+typedef struct pcg_conv_args {
+  const float* in;              /* forward: x [B][IH][IW][Cin]; grad-input: dy [B][OH][OW][Cout] */
+  const float* w;               /* OHWI */
+  const float* bias;            /* nullable; grad-input: added per Cin channel (ConvTranspose2d bias) */
+  float* out;                   /* forward: y; grad-input: dx */
+  const pcg_in_xform* xf;       /* nullable: input transform on `in` (MFMA layers; the grad-input of pcg_conv2d_xf_thin_ok geometries) */
+  /* the epilogue's tensors — each epilogue reads the ones its enumerator names, all 16-byte aligned as `out` must then be */
+  const float* addend;
+  const float* a_below;
+  const float* z;               /* add_bnsum: z_next; bnbwd: z_below */
+  const float* mean;            /* add_bnsum, bnbwd: statistics of that BatchNorm, [C] ([groups][C] with groups) */
+  const float* invstd;
+  const float* gamma;           /* bnbwd: required.  stats: optional, with beta, for coef_out */
+  const float* beta;
+  void* partial;                /* add_bnsum, bnbwd: fp64 partial rows [pcg_conv2d_*_bn_partial_rows][2][C], the buffer of */
+  size_t partial_bytes;         /*   pcg_conv2d_{fwd,dgrad}_bn_workspace_bytes of the launch's direction                   */
+  /* Fused statistics (stats != 0; MFMA layers only): the per-channel sum / sum of squares are taken from the accumulator tile in the
+   * conv epilogue (no extra pass over out), partial rows are finalised in a fixed order.  Same outputs as the plain launch followed
+   * by pcg_bn_train_stats.  `workspace` is then the buffer of pcg_conv2d_{fwd,dgrad}_bn_workspace_bytes and is required.          */
+  float* save_mean;             /* [C]; [groups][C] with groups */
+  float* save_invstd;
+  float* running_mean;          /* nullable */
+  float* running_var;           /* nullable */
+  int64_t* num_batches_tracked; /* nullable: += 1 (+= groups) */
+  float* coef_out;              /* nullable [2][C]: the folded scale / shift of THIS layer's BatchNorm (gamma, beta required), written by
+                                   the statistics finalize — ready to be the next consumer's transform */
+  /* Optional scratch (pcg_conv2d_{fwd,dgrad}_workspace_bytes; NULL is always valid: a slower path is used); the statistics' buffer */
+  void* workspace;
+  size_t workspace_bytes;
+  int32_t op;                   /* pcg_conv_op */
+  /* The activation that follows the layer fused into the output write — out = act(conv(in) + bias): Conv2d + LeakyReLU
+   * (mnist_dcgan.py:100-101, counteRGAN models/discriminator.py:17-24, generator.py:36-37,50), Conv2d + ReLU (models/classifier.py:7-12),
+   * Conv2d + Sigmoid (mnist_dcgan.py:110-111), ConvTranspose2d + Tanh (mnist_dcgan.py:88-89, mnist_wgan_conditional.py:70-71).
+   * The backward needs only out (pcg_act_bwd).                                                                                   */
+  int32_t act;                  /* pcg_act */
+  float slope;
+  int32_t epi;                  /* pcg_conv_epi */
+  int32_t epi_act;              /* mask, add_mask, bnbwd: the layer below's activation (none / ReLU / LeakyReLU); add, add_bnsum: none */
+  float epi_slope;
+  float sum_scale;              /* add_bnsum */
+  int32_t stats;
+  float eps, momentum;          /* stats */
+  /* 0: one batch.  >= 1 (at most 8): `groups` batches of B / groups images side by side (grouped batches, below) — the forward with
+   * stats (no transform, no coef_out; (B / groups) * OH * OW a multiple of 128) and the grad-input with bnbwd (equal sub-pixel phases
+   * — pcg_conv2d_dgrad_bn_phases of them — whose rows split into whole 128-row tiles per group; the partial rows keep the ungrouped
+   * layout [phase][tile row]).  groups = 1 runs the grouped finalize on one group, not the ungrouped one.                          */
+  int32_t groups;
+} pcg_conv_args;
+int pcg_conv2d(const pcg_conv_geom* g, const pcg_conv_args* a, pcg_stream_t stream);
 int pcg_conv_weight_adjoint(const float* w, float* w_adj, int32_t Cout, int32_t KH, int32_t KW, int32_t Cin, pcg_stream_t stream);
 /* The same for n <= 16 layers of one shape in ONE launch (host arrays of device pointers). */
 int pcg_conv_weight_adjoint_many(const float* const* w, float* const* w_adj, int32_t n, int32_t Cout, int32_t KH, int32_t KW, int32_t Cin,
@@ -283,7 +292,7 @@ int pcg_bn_act_bwd_db(const float* dy, const float* x, const float* y /*nullable
                       size_t workspace_bytes, pcg_stream_t stream);
 size_t pcg_bn_bwd_partial_db_workspace_bytes(int32_t C);
 /* dm_scale: the partial sums already include this factor, the apply pass multiplies dm by it (1: plain) — the 0.1 of a residual
- * branch whose incoming gradient is the unscaled skip-path sum (pcg_conv2d_dgrad_add_bnsum).  dcol may be NULL. */
+ * branch whose incoming gradient is the unscaled skip-path sum (PCG_CONV_EPI_ADD_BNSUM).  dcol may be NULL. */
 int pcg_bn_bwd_partial_db(const float* dm, const float* x, int64_t rows, int32_t C, const float* mean, const float* invstd,
                           const float* gamma, const void* partial, int32_t nparts, float dm_scale, float* dx, float* dgamma,
                           float* dbeta, int accumulate, float* dcol /*nullable*/, int accumulate_col, void* workspace,
@@ -301,20 +310,12 @@ int pcg_bn_bwd_partial_db(const float* dm, const float* x, int64_t rows, int32_t
  * 2B images instead of two added results) — a few ulp, stated in tests/test_hip_groups.py.  Constraints: C / 4 a power of two
  * <= 256, (B / groups) * OH * OW a multiple of 128, equal sub-pixel phases; not available in the exact-BatchNorm data-parallel
  * mode.  Callers fall back to separate passes otherwise (pcgan_amd.nn.SequentialConvNet.supports_groups).                      */
-int pcg_conv2d_fwd_bn_g(const pcg_conv_geom* g, const float* x, const float* w, const float* bias /*nullable*/, float* y, float eps,
-                        float momentum, float* save_mean /*[groups][Cout]*/, float* save_invstd /*[groups][Cout]*/,
-                        float* running_mean /*nullable*/, float* running_var /*nullable*/, int64_t* num_batches_tracked /*nullable*/,
-                        int32_t groups, void* workspace /*pcg_conv2d_fwd_bn_workspace_bytes*/, size_t workspace_bytes, pcg_stream_t stream);
 /* y = act(bn_g(x)) with group g's statistics on group g's rows (training mode only: mean / invstd are save_mean / save_invstd) */
 int pcg_bn_apply_act_g(const float* x, int64_t rows, int32_t C, const float* mean /*[groups][C]*/, const float* invstd /*[groups][C]*/,
                        const float* gamma, const float* beta, int act, float slope, float* y, int32_t groups, pcg_stream_t stream);
-/* pcg_conv2d_dgrad_bnbwd on `groups` side-by-side batches: mean / invstd of the layer below are [groups][Cin]; the partial rows keep
- * the ungrouped layout ([phase][tile row], pcg_conv2d_dgrad_bn_partial_rows of them in pcg_conv2d_dgrad_bn_phases phases).       */
+/* the sub-pixel phases of a grad-input launch (pcg_conv_args.groups with the bnbwd epilogue; pcg_bn_bwd_partial_g's nphases) */
 int32_t pcg_conv2d_dgrad_bn_phases(const pcg_conv_geom* g);
-int pcg_conv2d_dgrad_bnbwd_g(const pcg_conv_geom* g, const float* dy, const float* w, const float* z_below, const float* mean,
-                             const float* invstd, const float* gamma, const float* beta, int act, float slope, float* dx,
-                             void* partial, size_t partial_bytes, int32_t groups, pcg_stream_t stream);
-/* pcg_bn_bwd_partial on `groups` side-by-side batches (partial rows from pcg_conv2d_dgrad_bnbwd_g; nphases = the phases of that launch) */
+/* pcg_bn_bwd_partial on `groups` side-by-side batches (partial rows from a grouped bnbwd grad-input; nphases = the phases of that launch) */
 size_t pcg_bn_bwd_partial_g_workspace_bytes(int32_t C, int32_t groups);
 int pcg_bn_bwd_partial_g(const float* dm, const float* x, int64_t rows, int32_t C, const float* mean, const float* invstd,
                          const float* gamma, const void* partial, int32_t nparts, int32_t nphases, float* dx, float* dgamma,

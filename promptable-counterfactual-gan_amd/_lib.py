@@ -73,6 +73,20 @@ class InXform(ctypes.Structure):
     _fields_ = [("scale", _P), ("shift", _P), ("act", _I), ("slope", ctypes.c_float)]
 
 
+class ConvArgs(ctypes.Structure):
+    """pcg_conv_args: one forward / grad-input convolution launch (pcg_conv2d)."""
+    _fields_ = ([(n, _P) for n in ("in_", "w", "bias", "out", "xf", "addend", "a_below", "z", "mean", "invstd", "gamma", "beta", "partial")] +
+                [("partial_bytes", ctypes.c_size_t)] +
+                [(n, _P) for n in ("save_mean", "save_invstd", "running_mean", "running_var", "num_batches_tracked", "coef_out", "workspace")] +
+                [("workspace_bytes", ctypes.c_size_t), ("op", _I), ("act", _I), ("slope", ctypes.c_float), ("epi", _I), ("epi_act", _I),
+                 ("epi_slope", ctypes.c_float), ("sum_scale", ctypes.c_float), ("stats", _I), ("eps", ctypes.c_float),
+                 ("momentum", ctypes.c_float), ("groups", _I)])
+
+
+CONV_FWD, CONV_DGRAD = 0, 1                                                          # pcg_conv_op
+CONV_EPIS = ("none", "mask", "add", "add_mask", "add_bnsum", "bnbwd")                # pcg_conv_epi, by value
+
+
 class MoonsCfDesc(ctypes.Structure):
     """pcg_moons_cf_desc (include/pcgan_hip.h)."""
     _fields_ = ([(n, _I) for n in ("hidden", "clf_hidden", "B", "N", "nG", "nD", "nC", "nG_adam", "nD_adam")] +
@@ -313,7 +327,7 @@ CLASS_PICK_KMAX = 64                                     # PCG_CLASS_PICK_KMAX
 CF_PANELS_GRID, CF_PANELS_PANELS = 0, 1                  # PCG_CF_PANELS_*
 
 # typedef name in include/pcgan_hip.h -> its class here (pcg_abi_struct_bytes checks the sizes: tests/test_house_abi_host.py)
-STRUCTS = {"pcg_conv_geom": ConvGeom, "pcg_in_xform": InXform, "pcg_wgrad_item": WgradItem, "pcg_sn_fwd_batch": SnFwdBatch,
+STRUCTS = {"pcg_conv_geom": ConvGeom, "pcg_conv_args": ConvArgs, "pcg_in_xform": InXform, "pcg_wgrad_item": WgradItem, "pcg_sn_fwd_batch": SnFwdBatch,
            "pcg_sn_bwd_batch": SnBwdBatch, "pcg_house_g_desc": HouseGDesc, "pcg_house_g_fwd_args": HouseGFwdArgs,
            "pcg_house_g_bwd_args": HouseGBwdArgs, "pcg_house_critic_fwd_args": HouseCriticFwdArgs,
            "pcg_house_critic_bwd_args": HouseCriticBwdArgs, "pcg_house_cls_fwd_args": HouseClsFwdArgs, "pcg_house_cls_bwd_args": HouseClsBwdArgs,
@@ -361,10 +375,8 @@ PROTOTYPES = {
     "pcg_conv_pad_clip_query": (_i, [_gp, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     "pcg_conv_wgrad_padskip_query": (_i, [_gp, _i32, _vp, _vp]),
     "pcg_conv_wgrad_padskip_plan": (_i, [_gp, _i32, _vp, _vp]),
-    "pcg_conv2d_fwd_bn_g": (_i, [_gp, _vp, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _sz, _vp]),
     "pcg_bn_apply_act_g": (_i, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _i, _f, _vp, _i32, _vp]),
     "pcg_conv2d_dgrad_bn_phases": (_i32, [_gp]),
-    "pcg_conv2d_dgrad_bnbwd_g": (_i, [_gp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _f, _vp, _vp, _sz, _i32, _vp]),
     "pcg_bn_bwd_partial_g_workspace_bytes": (_sz, [_i32, _i32]),
     "pcg_bn_bwd_partial_g": (_i, [_vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _i, _i32, _vp, _sz, _vp]),
     "pcg_bn_act_bwd_g_workspace_bytes": (_sz, [_i64, _i32, _i32]),
@@ -390,40 +402,23 @@ PROTOTYPES = {
     "pcg_calib_copy": (_i, [_vp, _vp, _i64, _vp]),
     "pcg_conv2d_fwd_workspace_bytes": (_sz, [_gp]),
     "pcg_conv2d_dgrad_workspace_bytes": (_sz, [_gp]),
+    "pcg_conv2d": (_i, [_gp, _c.POINTER(ConvArgs), _vp]),
     "pcg_conv2d_fwd": (_i, [_gp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "pcg_conv2d_dgrad": (_i, [_gp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "pcg_conv2d_fwd_act": (_i, [_gp, _vp, _vp, _vp, _i, _f, _vp, _vp, _sz, _vp]),
-    "pcg_conv2d_dgrad_act": (_i, [_gp, _vp, _vp, _vp, _i, _f, _vp, _vp, _sz, _vp]),
     "pcg_conv2d_fwd_bn_workspace_bytes": (_sz, [_gp]),
     "pcg_conv2d_dgrad_bn_workspace_bytes": (_sz, [_gp]),
-    "pcg_conv2d_fwd_bn": (_i, [_gp, _vp, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "pcg_conv2d_dgrad_bn": (_i, [_gp, _vp, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "pcg_conv2d_dgrad_mask": (_i, [_gp, _vp, _vp, _vp, _i, _f, _vp, _vp, _sz, _vp]),
     "pcg_conv2d_dgrad_mask_thin_ok": (_i32, [_gp]),
     "pcg_conv2d_xf_thin_ok": (_i32, [_gp]),
-    "pcg_conv2d_fwd_add_mask": (_i, [_gp, _vp, _vp, _vp, _vp, _i, _f, _vp, _vp]),
-    "pcg_conv2d_dgrad_add_mask": (_i, [_gp, _vp, _vp, _vp, _vp, _i, _f, _vp, _vp]),
-    "pcg_conv2d_fwd_mask": (_i, [_gp, _vp, _vp, _vp, _i, _f, _vp, _vp, _sz, _vp]),
-    "pcg_conv2d_dgrad_bnbwd": (_i, [_gp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _f, _vp, _vp, _sz, _vp]),
-    "pcg_conv2d_fwd_bnbwd": (_i, [_gp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _f, _vp, _vp, _sz, _vp]),
-    "pcg_conv2d_dgrad_add": (_i, [_gp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "pcg_conv2d_fwd_bn_partial_rows": (_c.c_int32, [_gp]),
     "pcg_conv2d_dgrad_bn_partial_rows": (_c.c_int32, [_gp]),
     "pcg_bn_bwd_partial_workspace_bytes": (_sz, [_c.c_int32]),
     "pcg_bn_bwd_partial": (_i, [_vp, _vp, _i64, _c.c_int32, _vp, _vp, _vp, _vp, _c.c_int32, _vp, _vp, _vp, _i, _vp, _sz, _vp]),
-    "pcg_conv2d_fwd_bn_xf": (_i, [_gp, _vp, _xp, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "pcg_conv2d_dgrad_bn_xf": (_i, [_gp, _vp, _xp, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "pcg_conv2d_fwd_xf": (_i, [_gp, _vp, _xp, _vp, _vp, _i, _f, _vp, _vp, _sz, _vp]),
-    "pcg_conv2d_dgrad_xf": (_i, [_gp, _vp, _xp, _vp, _vp, _i, _f, _vp, _vp, _sz, _vp]),
     "pcg_conv2d_wgrad_xf": (_i, [_gp, _vp, _xp, _vp, _xp, _vp, _i, _vp, _sz, _vp]),
     "pcg_bn_train_stats_coef": (_i, [_vp, _i64, _c.c_int32, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "pcg_bn_db_workspace_bytes": (_sz, [_i64, _c.c_int32]),
     "pcg_bn_act_bwd_db": (_i, [_vp, _vp, _vp, _i64, _c.c_int32, _vp, _vp, _vp, _vp, _i, _f, _f, _vp, _vp, _vp, _i, _vp, _i, _vp, _sz, _vp]),
     "pcg_bn_bwd_partial_db_workspace_bytes": (_sz, [_c.c_int32]),
     "pcg_bn_bwd_partial_db": (_i, [_vp, _vp, _i64, _c.c_int32, _vp, _vp, _vp, _vp, _c.c_int32, _f, _vp, _vp, _vp, _i, _vp, _i, _vp, _sz, _vp]),
-    "pcg_conv2d_dgrad_add_bnsum": (_i, [_gp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _sz, _vp]),
-    "pcg_conv2d_fwd_add": (_i, [_gp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "pcg_conv2d_fwd_add_bnsum": (_i, [_gp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _sz, _vp]),
     "pcg_conv_weight_adjoint": (_i, [_vp, _vp, _i32, _i32, _i32, _i32, _vp]),
     "pcg_conv_weight_adjoint_many": (_i, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
     "pcg_house_losses": (_i, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _f, _f, _f, _f, _vp, _vp]),

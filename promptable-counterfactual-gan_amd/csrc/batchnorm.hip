@@ -997,7 +997,7 @@ static int launch_bwd_finalize_apply_g(const float* dm, const float* x, int64_t 
 }
 
 // BatchNorm backward of G side-by-side batches from the column sums a grouped fused grad-input epilogue left in `partial`
-// (pcg_conv2d_dgrad_bnbwd_g; dm is already masked).  mean / invstd: [G][C]; nphases: sub-pixel phases of the launch that wrote the
+// (a grouped bnbwd grad-input of pcg_conv2d; dm is already masked).  mean / invstd: [G][C]; nphases: sub-pixel phases of the launch that wrote the
 // partial rows (pcg_conv2d_dgrad_bn_phases), 1 for a forward-kernel launch.
 extern "C" int pcg_bn_bwd_partial_g(const float* dm, const float* x, int64_t rows, int32_t C, const float* mean, const float* invstd,
                                     const float* gamma, const void* partial_, int32_t nparts, int32_t nphases, float* dx, float* dgamma,

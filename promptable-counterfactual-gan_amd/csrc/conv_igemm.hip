@@ -738,13 +738,18 @@ ConvP make_params(const pcg_conv_geom* g) {
 }
 
 // validate an input transform for an operand with C channels and put it into the kernel parameters
-int set_xform(const char* who, const pcg_in_xform* xf, int C, ConvP* p) {
+int check_xform(const char* who, const pcg_in_xform* xf, int C) {
   if (!xf || !xf->scale) return PCG_OK;
   PCG_REQUIRE(xf->shift != nullptr, "%s: input transform without shift", who);
   PCG_REQUIRE(xf->act == PCG_ACT_NONE || xf->act == PCG_ACT_RELU || xf->act == PCG_ACT_LRELU,
               "%s: input transform activation %d is not none / ReLU / LeakyReLU", who, xf->act);
   PCG_REQUIRE(C % 4 == 0 && (((uintptr_t)xf->scale | (uintptr_t)xf->shift) & 15) == 0,
               "%s: input transform needs a channel count %% 4 == 0 and 16-byte aligned scale / shift", who);
+  return PCG_OK;
+}
+int set_xform(const char* who, const pcg_in_xform* xf, int C, ConvP* p) {
+  if (!xf || !xf->scale) return PCG_OK;
+  if (int e = check_xform(who, xf, C)) return e;
   p->in_sc = xf->scale; p->in_sh = xf->shift; p->in_neg = act_neg_of(xf->act, xf->slope); p->in_c_bytes = (uint32_t)C * 4u;
   return PCG_OK;
 }
@@ -1450,21 +1455,36 @@ static void clip_apply(const pcg_conv_geom* g, const ClipPlan& cp, int groups, c
   p->cliptab = tab; p->clip_order = cp.order; p->clip_tpp = g->B / cp.bm; p->clip_tpg = p->clip_tpp / groups; p->clip_npos = g->OH * g->OW;
 }
 
-static int conv2d_fwd_impl(const pcg_conv_geom* g, const float* x, const float* w, const float* bias, float* y,
-                           double* stat_partial, void* workspace, size_t workspace_bytes, pcg_stream_t stream, int act = PCG_ACT_NONE,
-                           float slope = 0.f, const EpiAux* epi = nullptr, const pcg_in_xform* xf = nullptr, int groups = 1) {
-  if (int e = check_geom(g)) return e;
-  PCG_REQUIRE(x && w && y, "pcg_conv2d_fwd: null pointer");
-  PCG_REQUIRE(act >= PCG_ACT_NONE && act <= PCG_ACT_SIGMOID, "pcg_conv2d_fwd: unknown activation %d", act);
-  if (thin_is_cin(g) || thin_is_cout(g)) {
-    PCG_REQUIRE(!(xf && xf->scale), "pcg_conv2d_fwd: input transforms are only implemented on the MFMA path (Cin > 3 and Cout > 3)");
-    return thin_conv_fwd(g, x, w, bias, y, workspace, workspace_bytes, (hipStream_t)stream, act, slope);
-  }
-  PCG_REQUIRE(g->Cin % 4 == 0, "pcg_conv2d_fwd: Cin=%d must be a multiple of 4 for the MFMA path (1..3-channel layers take the thin path)", g->Cin);
+// A validated pcg_conv_args (conv_call_of below): what the two implementation functions launch.  epi is null for PCG_CONV_EPI_NONE — the
+// split-K and GEMM + col2im decisions read it.
+struct ConvCall {
+  const float *in, *w, *bias;
+  float* out;
+  double* stat_partial;      // partial rows of the fused statistics or of an add_bnsum / bnbwd epilogue
+  void* workspace;
+  size_t workspace_bytes;
+  int act;
+  float slope;
+  const EpiAux* epi;
+  const pcg_in_xform* xf;
+  int groups;                // BatchNorm groups of a forward launch (1: ungrouped); the grad-input's ride in epi->group_rows
+};
+
+static int conv2d_fwd_impl(const pcg_conv_geom* g, const ConvCall& c, pcg_stream_t stream) {
+  const float *x = c.in, *w = c.w, *bias = c.bias;
+  float* y = c.out;
+  double* stat_partial = c.stat_partial;
+  void* workspace = c.workspace;
+  const size_t workspace_bytes = c.workspace_bytes;
+  const int act = c.act, groups = c.groups;
+  const float slope = c.slope;
+  const EpiAux* epi = c.epi;
+  const pcg_in_xform* xf = c.xf;
+  if (thin_is_cin(g) || thin_is_cout(g)) return thin_conv_fwd(g, x, w, bias, y, workspace, workspace_bytes, (hipStream_t)stream, act, slope);
   ConvP p = make_params(g);
   p.x = x; p.w = w; p.bias = bias; p.out = y; p.stat_partial = stat_partial;
   if (epi) p.epi = *epi;
-  if (int e = set_xform("pcg_conv2d_fwd", xf, g->Cin, &p)) return e;
+  if (int e = set_xform("pcg_conv2d", xf, g->Cin, &p)) return e;
   p.M = g->B * g->OH * g->OW; p.N = g->Cout;
   p.ktiles = g->KH * g->KW * ceil_div(g->Cin, IG_BK);
   p.ktiles_per_split = p.ktiles;
@@ -1502,15 +1522,6 @@ static int conv2d_fwd_impl(const pcg_conv_geom* g, const float* x, const float* 
   return (fuse || act == PCG_ACT_NONE) ? PCG_OK : pcg_act_fwd(y, (int64_t)p.M * p.N, act, slope, y, stream);
 }
 
-extern "C" int pcg_conv2d_fwd(const pcg_conv_geom* g, const float* x, const float* w, const float* bias, float* y,
-                              void* workspace, size_t workspace_bytes, pcg_stream_t stream) {
-  return conv2d_fwd_impl(g, x, w, bias, y, nullptr, workspace, workspace_bytes, stream);
-}
-extern "C" int pcg_conv2d_fwd_act(const pcg_conv_geom* g, const float* x, const float* w, const float* bias, int act, float slope,
-                                  float* y, void* workspace, size_t workspace_bytes, pcg_stream_t stream) {
-  return conv2d_fwd_impl(g, x, w, bias, y, nullptr, workspace, workspace_bytes, stream, act, slope);
-}
-
 extern "C" size_t pcg_conv2d_fwd_bn_workspace_bytes(const pcg_conv_geom* g) {
   if (check_geom(g) != PCG_OK || !mfma_layer(g) || g->Cout % 4) return 0;
   return bn_partial_buffer_bytes(fwd_stat_rows(g), g->Cout);
@@ -1518,50 +1529,6 @@ extern "C" size_t pcg_conv2d_fwd_bn_workspace_bytes(const pcg_conv_geom* g) {
 extern "C" size_t pcg_conv2d_dgrad_bn_workspace_bytes(const pcg_conv_geom* g) {
   if (check_geom(g) != PCG_OK || !mfma_layer(g) || g->stride > 2 || g->Cin % 4) return 0;
   return bn_partial_buffer_bytes(dgrad_stat_rows(g), g->Cin);
-}
-
-extern "C" int pcg_conv2d_fwd_bn_xf(const pcg_conv_geom* g, const float* x, const pcg_in_xform* xf, const float* w, const float* bias,
-                                    float* y, float eps, float momentum, float* save_mean, float* save_invstd, float* running_mean,
-                                    float* running_var, int64_t* num_batches_tracked, const float* gamma, const float* beta,
-                                    float* coef_out, void* workspace, size_t workspace_bytes, pcg_stream_t stream) {
-  const size_t need = pcg_conv2d_fwd_bn_workspace_bytes(g);
-  PCG_REQUIRE(need > 0, "pcg_conv2d_fwd_bn: only MFMA layers (Cin > 3, Cout > 3, Cout %% 4 == 0); use pcg_conv2d_fwd + pcg_bn_train_stats");
-  PCG_REQUIRE(save_mean && save_invstd, "pcg_conv2d_fwd_bn: null statistics output");
-  PCG_REQUIRE(!coef_out || (gamma && beta), "pcg_conv2d_fwd_bn_xf: coef_out needs gamma and beta");
-  if (!workspace || workspace_bytes < need) { set_error("pcg_conv2d_fwd_bn: workspace %zu B < required %zu B", workspace_bytes, need); return PCG_ERR_WORKSPACE; }
-  if (int e = conv2d_fwd_impl(g, x, w, bias, y, (double*)workspace, nullptr, 0, stream, PCG_ACT_NONE, 0.f, nullptr, xf)) return e;
-  return launch_bn_stats_finalize((const double*)workspace, fwd_stat_rows(g), (int64_t)g->B * g->OH * g->OW, g->Cout, eps, momentum,
-                                  save_mean, save_invstd, running_mean, running_var, num_batches_tracked, (hipStream_t)stream, true,
-                                  gamma, beta, coef_out);
-}
-extern "C" int pcg_conv2d_fwd_bn(const pcg_conv_geom* g, const float* x, const float* w, const float* bias, float* y, float eps,
-                                 float momentum, float* save_mean, float* save_invstd, float* running_mean, float* running_var,
-                                 int64_t* num_batches_tracked, void* workspace, size_t workspace_bytes, pcg_stream_t stream) {
-  return pcg_conv2d_fwd_bn_xf(g, x, nullptr, w, bias, y, eps, momentum, save_mean, save_invstd, running_mean, running_var,
-                              num_batches_tracked, nullptr, nullptr, nullptr, workspace, workspace_bytes, stream);
-}
-// Grouped form (r04): `groups` independent batches of g->B / groups images side by side in ONE launch — the discriminator's real and
-// fake passes (mnist_dcgan.py:151-161) as one 2B-row convolution per layer.  The convolution itself does not care; BatchNorm does:
-// each group gets its own batch statistics (save_mean / save_invstd are [groups][Cout]) from its own partial rows, the running
-// statistics move once per group in group order and num_batches_tracked advances by `groups`, exactly what `groups` successive
-// training-mode forwards do.  Needs (B / groups) * OH * OW % 128 == 0 (whole tiles per group).
-extern "C" int pcg_conv2d_fwd_bn_g(const pcg_conv_geom* g, const float* x, const float* w, const float* bias, float* y, float eps,
-                                   float momentum, float* save_mean, float* save_invstd, float* running_mean, float* running_var,
-                                   int64_t* num_batches_tracked, int32_t groups, void* workspace, size_t workspace_bytes,
-                                   pcg_stream_t stream) {
-  const size_t need = pcg_conv2d_fwd_bn_workspace_bytes(g);
-  PCG_REQUIRE(need > 0, "pcg_conv2d_fwd_bn_g: only MFMA layers (Cin > 3, Cout > 3, Cout %% 4 == 0)");
-  PCG_REQUIRE(save_mean && save_invstd, "pcg_conv2d_fwd_bn_g: null statistics output");
-  PCG_REQUIRE(groups >= 1 && groups <= 8 && g->B % groups == 0 && ((int64_t)(g->B / groups) * g->OH * g->OW) % 128 == 0,
-              "pcg_conv2d_fwd_bn_g: %d images do not split into %d groups of whole 128-row tiles (%d x %d output)", g->B, groups, g->OH, g->OW);
-  if (!workspace || workspace_bytes < need) { set_error("pcg_conv2d_fwd_bn_g: workspace %zu B < required %zu B", workspace_bytes, need); return PCG_ERR_WORKSPACE; }
-  if (int e = conv2d_fwd_impl(g, x, w, bias, y, (double*)workspace, nullptr, 0, stream, PCG_ACT_NONE, 0.f, nullptr, nullptr, groups)) return e;
-  return launch_bn_stats_finalize_g((const double*)workspace, fwd_stat_rows(g), 1, groups, (int64_t)(g->B / groups) * g->OH * g->OW, g->Cout,
-                                    eps, momentum, save_mean, save_invstd, running_mean, running_var, num_batches_tracked, (hipStream_t)stream);
-}
-extern "C" int pcg_conv2d_fwd_xf(const pcg_conv_geom* g, const float* x, const pcg_in_xform* xf, const float* w, const float* bias,
-                                 int act, float slope, float* y, void* workspace, size_t workspace_bytes, pcg_stream_t stream) {
-  return conv2d_fwd_impl(g, x, w, bias, y, nullptr, workspace, workspace_bytes, stream, act, slope, nullptr, xf);
 }
 
 // the sub-pixel phases (ih % s, iw % s) of a grad-input: rows, first taps, taps per axis, partial-statistics rows
@@ -1591,26 +1558,28 @@ static int build_phases(const pcg_conv_geom* g, DgradPhases* php, int* maxMp_out
   return nph;
 }
 
-static int conv2d_dgrad_impl(const pcg_conv_geom* g, const float* dy, const float* w, const float* bias_x, float* dx,
-                             double* stat_partial, void* workspace, size_t workspace_bytes, pcg_stream_t stream, int act = PCG_ACT_NONE,
-                             float slope = 0.f, const EpiAux* epi = nullptr, const pcg_in_xform* xf = nullptr) {
-  if (int e = check_geom(g)) return e;
-  PCG_REQUIRE(dy && w && dx, "pcg_conv2d_dgrad: null pointer");
-  PCG_REQUIRE(act >= PCG_ACT_NONE && act <= PCG_ACT_SIGMOID, "pcg_conv2d_dgrad: unknown activation %d", act);
+static int conv2d_dgrad_impl(const pcg_conv_geom* g, const ConvCall& c, pcg_stream_t stream) {
+  const float *dy = c.in, *w = c.w, *bias_x = c.bias;
+  float* dx = c.out;
+  double* stat_partial = c.stat_partial;
+  void* workspace = c.workspace;
+  const size_t workspace_bytes = c.workspace_bytes;
+  const int act = c.act;
+  const float slope = c.slope;
+  const EpiAux* epi = c.epi;
+  const pcg_in_xform* xf = c.xf;
   const bool has_xf = xf && xf->scale;
   if (thin_is_cin(g) || thin_is_cout(g)) {
-    PCG_REQUIRE(!has_xf || thin_conv_xf_ok(g), "pcg_conv2d_dgrad: input transforms on the MFMA path (Cin > 3 and Cout > 3) and on the thin forms of pcg_conv2d_xf_thin_ok only");
-    PCG_REQUIRE(!has_xf || (xf->act == PCG_ACT_NONE || xf->act == PCG_ACT_RELU || xf->act == PCG_ACT_LRELU), "pcg_conv2d_dgrad: transform activation %d", has_xf ? xf->act : 0);
     const ThinXf tx{has_xf ? xf->scale : nullptr, has_xf ? xf->shift : nullptr, has_xf ? act_neg_of(xf->act, xf->slope) : 1.f};
     return thin_conv_dgrad(g, dy, w, bias_x, dx, workspace, workspace_bytes, (hipStream_t)stream, act, slope, &tx);
   }
-  PCG_REQUIRE(g->Cin % 4 == 0 && g->Cout % 4 == 0, "pcg_conv2d_dgrad: Cin=%d and Cout=%d must be multiples of 4", g->Cin, g->Cout);
-  PCG_REQUIRE(g->stride <= 2, "pcg_conv2d_dgrad: stride %d > 2 unsupported", g->stride);
   if (!epi && !stat_partial && !has_xf && dgrad_as_gemm(g, stream_has_sk((hipStream_t)stream)) && workspace && workspace_bytes >= dgrad_gemm_bytes(g) &&
       (((uintptr_t)workspace | (uintptr_t)dx) & 15) == 0) {
     pcg_conv_geom g1 = {g->B, g->OH, g->OW, g->KH * g->KW * g->Cin, g->OH, g->OW, g->Cout, 1, 1, 1, 0};
     float* dcol = (float*)workspace;
-    if (int e = conv2d_dgrad_impl(&g1, dy, w, nullptr, dcol, nullptr, nullptr, 0, stream)) return e;
+    ConvCall c1{};
+    c1.in = dy; c1.w = w; c1.out = dcol; c1.groups = 1;
+    if (int e = conv2d_dgrad_impl(&g1, c1, stream)) return e;
     const bool fuse_act = act_is_cheap(act);
     const int CQ = g->Cin / 4;
     const uint64_t total = (uint64_t)g->B * g->IH * g->IW * CQ;
@@ -1627,13 +1596,13 @@ static int conv2d_dgrad_impl(const pcg_conv_geom* g, const float* dy, const floa
   const bool fuse = act_is_cheap(act);
   p.dy = dy; p.w = w; p.bias = bias_x; p.out = dx; p.stat_partial = stat_partial;
   if (epi) p.epi = *epi;
-  if (int e = set_xform("pcg_conv2d_dgrad", xf, g->Cout, &p)) return e;
+  if (int e = set_xform("pcg_conv2d", xf, g->Cout, &p)) return e;
   p.act = fuse ? act : PCG_ACT_NONE; p.slope = act_neg_of(p.act, slope);
   p.N = g->Cin;
   DgradPhases ph{};
   int maxMp = 0;
   const int nph = build_phases(g, &ph, &maxMp);
-  PCG_REQUIRE(nph > 0, "pcg_conv2d_dgrad: empty problem");
+  PCG_REQUIRE(nph > 0, "pcg_conv2d: empty problem");
   hipStream_t st = (hipStream_t)stream;
   if (const uint32_t* tab = clip_mode() != 0 ? cliptab_of(g) : nullptr) {
     const int groups = p.epi.group_rows > 0 ? maxMp / p.epi.group_rows : 1;
@@ -1648,135 +1617,140 @@ static int conv2d_dgrad_impl(const pcg_conv_geom* g, const float* dy, const floa
   return fuse ? PCG_OK : pcg_act_fwd(dx, (int64_t)g->B * g->IH * g->IW * g->Cin, act, slope, dx, stream);
 }
 
-extern "C" int pcg_conv2d_dgrad(const pcg_conv_geom* g, const float* dy, const float* w, const float* bias_x, float* dx,
-                                void* workspace, size_t workspace_bytes, pcg_stream_t stream) {
-  return conv2d_dgrad_impl(g, dy, w, bias_x, dx, nullptr, workspace, workspace_bytes, stream);
-}
-extern "C" int pcg_conv2d_dgrad_act(const pcg_conv_geom* g, const float* dy, const float* w, const float* bias_x, int act, float slope,
-                                    float* dx, void* workspace, size_t workspace_bytes, pcg_stream_t stream) {
-  return conv2d_dgrad_impl(g, dy, w, bias_x, dx, nullptr, workspace, workspace_bytes, stream, act, slope);
-}
 
-extern "C" int pcg_conv2d_dgrad_bn_xf(const pcg_conv_geom* g, const float* dy, const pcg_in_xform* xf, const float* w, const float* bias_x,
-                                      float* dx, float eps, float momentum, float* save_mean, float* save_invstd, float* running_mean,
-                                      float* running_var, int64_t* num_batches_tracked, const float* gamma, const float* beta,
-                                      float* coef_out, void* workspace, size_t workspace_bytes, pcg_stream_t stream) {
-  const size_t need = pcg_conv2d_dgrad_bn_workspace_bytes(g);
-  PCG_REQUIRE(need > 0, "pcg_conv2d_dgrad_bn: only MFMA layers with stride <= 2; use pcg_conv2d_dgrad + pcg_bn_train_stats");
-  PCG_REQUIRE(save_mean && save_invstd, "pcg_conv2d_dgrad_bn: null statistics output");
-  PCG_REQUIRE(!coef_out || (gamma && beta), "pcg_conv2d_dgrad_bn_xf: coef_out needs gamma and beta");
-  if (!workspace || workspace_bytes < need) { set_error("pcg_conv2d_dgrad_bn: workspace %zu B < required %zu B", workspace_bytes, need); return PCG_ERR_WORKSPACE; }
-  if (int e = conv2d_dgrad_impl(g, dy, w, bias_x, dx, (double*)workspace, nullptr, 0, stream, PCG_ACT_NONE, 0.f, nullptr, xf)) return e;
-  return launch_bn_stats_finalize((const double*)workspace, dgrad_stat_rows(g), (int64_t)g->B * g->IH * g->IW, g->Cin, eps, momentum,
-                                  save_mean, save_invstd, running_mean, running_var, num_batches_tracked, (hipStream_t)stream, true,
-                                  gamma, beta, coef_out);
-}
-extern "C" int pcg_conv2d_dgrad_bn(const pcg_conv_geom* g, const float* dy, const float* w, const float* bias_x, float* dx, float eps,
-                                   float momentum, float* save_mean, float* save_invstd, float* running_mean, float* running_var,
-                                   int64_t* num_batches_tracked, void* workspace, size_t workspace_bytes, pcg_stream_t stream) {
-  return pcg_conv2d_dgrad_bn_xf(g, dy, nullptr, w, bias_x, dx, eps, momentum, save_mean, save_invstd, running_mean, running_var,
-                                num_batches_tracked, nullptr, nullptr, nullptr, workspace, workspace_bytes, stream);
-}
-extern "C" int pcg_conv2d_dgrad_xf(const pcg_conv_geom* g, const float* dy, const pcg_in_xform* xf, const float* w, const float* bias_x,
-                                   int act, float slope, float* dx, void* workspace, size_t workspace_bytes, pcg_stream_t stream) {
-  return conv2d_dgrad_impl(g, dy, w, bias_x, dx, nullptr, workspace, workspace_bytes, stream, act, slope, nullptr, xf);
-}
-
-// ---- backward-pass epilogues: the gradient w.r.t. the layer below's OUTPUT leaves the kernel already multiplied by that
-// layer's ReLU / LeakyReLU derivative, optionally with BatchNorm-backward's two column sums taken on the way -------------------
-static int epi_common(const char* who, const pcg_conv_geom* g, const float* out, const float* aux, int act, float slope, EpiAux* e) {
-  PCG_REQUIRE(mfma_layer(g), "%s: only MFMA layers (Cin > 3 and Cout > 3); use the unfused calls", who);
-  PCG_REQUIRE(aux && out, "%s: null pointer", who);
-  PCG_REQUIRE(act == PCG_ACT_NONE || act == PCG_ACT_RELU || act == PCG_ACT_LRELU, "%s: activation %d is not none / ReLU / LeakyReLU", who, act);
-  PCG_REQUIRE((((uintptr_t)aux | (uintptr_t)out) & 15) == 0, "%s: tensors must be 16-byte aligned", who);
-  e->neg = act_neg_of(act, slope);
-  e->delta_bytes = (int64_t)((intptr_t)aux - (intptr_t)out);
-  return PCG_OK;
-}
-
-// a Cin = 1 layer whose dy-side operand may carry an input transform (pcg_conv2d_dgrad_xf, pcg_conv2d_wgrad_xf with xf_dy): DCGAN's last
-// ConvTranspose2d(64, 1, 4, 2, 1) behind BatchNorm + ReLU (mnist_dcgan.py:85-88) — no BatchNorm-apply pass, no activated copy
+// a Cin = 1 layer whose dy-side operand may carry an input transform (pcg_conv2d grad-input with xf, pcg_conv2d_wgrad_xf with xf_dy): DCGAN's
+// last ConvTranspose2d(64, 1, 4, 2, 1) behind BatchNorm + ReLU (mnist_dcgan.py:85-88) — no BatchNorm-apply pass, no activated copy
 extern "C" int32_t pcg_conv2d_xf_thin_ok(const pcg_conv_geom* g) { return check_geom(g) == PCG_OK && thin_conv_xf_ok(g) ? 1 : 0; }
 extern "C" int32_t pcg_conv2d_dgrad_mask_thin_ok(const pcg_conv_geom* g) { return check_geom(g) == PCG_OK && thin_conv_dgrad_mask_ok(g) && g->Cin % 4 == 0 ? 1 : 0; }
-extern "C" int pcg_conv2d_dgrad_mask(const pcg_conv_geom* g, const float* dy, const float* w, const float* a_below, int act, float slope,
-                                     float* dx, void* workspace, size_t workspace_bytes, pcg_stream_t stream) {
-  EpiAux e{};
-  e.mode = EPI_MASK;
+// The phases of a grad-input launch: the partial rows of a bnbwd epilogue are [phase][tile row], pcg_bn_bwd_partial_g reads each group's
+// share of every phase.
+extern "C" int32_t pcg_conv2d_dgrad_bn_phases(const pcg_conv_geom* g) {
+  if (check_geom(g) != PCG_OK) return 0;
+  DgradPhases ph{};
+  int maxMp = 0;
+  return build_phases(g, &ph, &maxMp);
+}
+
+// ---- pcg_conv2d: the forward and grad-input forms behind one argument struct (include/pcgan_hip.h: pcg_conv_args) --------------------
+// Every refusal is made here, before any HIP call.  Fills the ConvCall the implementation functions launch; `e` is the storage of its
+// epilogue (c->epi stays null for PCG_CONV_EPI_NONE).  The backward-pass epilogues hand the gradient w.r.t. the layer below's OUTPUT out
+// of the kernel already multiplied by that layer's ReLU / LeakyReLU derivative, optionally with BatchNorm-backward's two column sums
+// taken on the way; aux tensors reach the kernel as byte distances from the output.
+static int conv_call_of(const pcg_conv_geom* g, const pcg_conv_args* a, ConvCall* c, EpiAux* e) {
   if (int rc = check_geom(g)) return rc;
-  if (pcg_conv2d_dgrad_mask_thin_ok(g)) {      // a one-channel layer's grad-input (r04): the mask in the row-block expand kernel
-    PCG_REQUIRE(dy && w && a_below && dx && (((uintptr_t)a_below | (uintptr_t)dx) & 15) == 0, "pcg_conv2d_dgrad_mask: null or misaligned tensor");
-    PCG_REQUIRE(act == PCG_ACT_NONE || act == PCG_ACT_RELU || act == PCG_ACT_LRELU, "pcg_conv2d_dgrad_mask: activation %d is not none / ReLU / LeakyReLU", act);
-    return thin_conv_dgrad_mask(g, dy, w, a_below, act, slope, dx, (hipStream_t)stream);
+  PCG_REQUIRE(a != nullptr, "pcg_conv2d: null argument struct");
+  const bool dgrad = a->op == PCG_CONV_DGRAD, mfma = mfma_layer(g), has_xf = a->xf && a->xf->scale;
+  auto act_masks = [](int act) { return act == PCG_ACT_NONE || act == PCG_ACT_RELU || act == PCG_ACT_LRELU; };
+  auto off16 = [](const void* p) { return ((uintptr_t)p & 15) != 0; };
+  PCG_REQUIRE(dgrad || a->op == PCG_CONV_FWD, "pcg_conv2d: unknown op %d", a->op);
+  PCG_REQUIRE(a->in && a->w && a->out, "pcg_conv2d: null pointer (in / w / out)");
+  PCG_REQUIRE(a->act >= PCG_ACT_NONE && a->act <= PCG_ACT_SIGMOID, "pcg_conv2d: unknown activation %d", a->act);
+  PCG_REQUIRE(a->epi >= PCG_CONV_EPI_NONE && a->epi <= PCG_CONV_EPI_BNBWD, "pcg_conv2d: unknown epilogue %d", a->epi);
+  // the forms that exist: an epilogue or the statistics ride on the bare convolution
+  PCG_REQUIRE(a->epi == PCG_CONV_EPI_NONE || (!a->stats && !has_xf && !a->bias && a->act == PCG_ACT_NONE),
+              "pcg_conv2d: an epilogue goes with no statistics, input transform, bias or output activation");
+  PCG_REQUIRE(!a->stats || a->act == PCG_ACT_NONE, "pcg_conv2d: statistics go with no output activation (they are taken of the sum itself)");
+  PCG_REQUIRE(a->groups == 0 || (a->groups > 0 && (dgrad ? a->epi == PCG_CONV_EPI_BNBWD : a->stats && !has_xf && !a->gamma && !a->beta && !a->coef_out)),
+              "pcg_conv2d: groups = %d goes with the forward's statistics (no transform, no gamma / beta / coef_out) or the grad-input's bnbwd epilogue only", a->groups);
+  if (!mfma) {
+    PCG_REQUIRE(!has_xf || (dgrad && thin_conv_xf_ok(g)), "pcg_conv2d: input transforms on the MFMA path (Cin > 3 and Cout > 3) and on the grad-input of pcg_conv2d_xf_thin_ok geometries only");
+    PCG_REQUIRE(!has_xf || act_masks(a->xf->act), "pcg_conv2d: input transform activation %d is not none / ReLU / LeakyReLU", has_xf ? a->xf->act : 0);
+  } else {
+    PCG_REQUIRE(g->Cin % 4 == 0 && (!dgrad || g->Cout % 4 == 0),
+                "pcg_conv2d: Cin=%d (grad-input: and Cout=%d) must be a multiple of 4 for the MFMA path (1..3-channel layers take the thin path)", g->Cin, g->Cout);
+    PCG_REQUIRE(!dgrad || g->stride <= 2, "pcg_conv2d: grad-input stride %d > 2 unsupported", g->stride);
+    if (int rc = check_xform("pcg_conv2d", a->xf, dgrad ? g->Cout : g->Cin)) return rc;
   }
-  if (int rc = epi_common("pcg_conv2d_dgrad_mask", g, dx, a_below, act, slope, &e)) return rc;
-  return conv2d_dgrad_impl(g, dy, w, nullptr, dx, nullptr, workspace, workspace_bytes, stream, PCG_ACT_NONE, 0.f, &e);
-}
-extern "C" int pcg_conv2d_fwd_mask(const pcg_conv_geom* g, const float* x, const float* w, const float* a_below, int act, float slope,
-                                   float* y, void* workspace, size_t workspace_bytes, pcg_stream_t stream) {
-  EpiAux e{};
-  e.mode = EPI_MASK;
-  if (int rc = check_geom(g)) return rc;
-  if (int rc = epi_common("pcg_conv2d_fwd_mask", g, y, a_below, act, slope, &e)) return rc;
-  return conv2d_fwd_impl(g, x, w, nullptr, y, nullptr, workspace, workspace_bytes, stream, PCG_ACT_NONE, 0.f, &e);
-}
-
-extern "C" int pcg_conv2d_dgrad_add(const pcg_conv_geom* g, const float* dy, const float* w, const float* addend, float* dx,
-                                    void* workspace, size_t workspace_bytes, pcg_stream_t stream) {
-  EpiAux e{};
-  e.mode = EPI_ADD;
-  if (int rc = check_geom(g)) return rc;
-  if (int rc = epi_common("pcg_conv2d_dgrad_add", g, dx, addend, PCG_ACT_NONE, 0.f, &e)) return rc;
-  return conv2d_dgrad_impl(g, dy, w, nullptr, dx, nullptr, workspace, workspace_bytes, stream, PCG_ACT_NONE, 0.f, &e);
-}
-
-extern "C" int pcg_conv2d_fwd_add(const pcg_conv_geom* g, const float* x, const float* w, const float* addend, float* y,
-                                  void* workspace, size_t workspace_bytes, pcg_stream_t stream) {
-  EpiAux e{};
-  e.mode = EPI_ADD;
-  if (int rc = check_geom(g)) return rc;
-  if (int rc = epi_common("pcg_conv2d_fwd_add", g, y, addend, PCG_ACT_NONE, 0.f, &e)) return rc;
-  return conv2d_fwd_impl(g, x, w, nullptr, y, nullptr, workspace, workspace_bytes, stream, PCG_ACT_NONE, 0.f, &e);
-}
-// skip-add followed by the ReLU / LeakyReLU backward of the layer whose activated output a_below the sum is a gradient of:
-// y = (conv(x, w) + addend) * (a_below > 0 ? 1 : slope) in ONE epilogue (was pcg_conv2d_*_add + a pcg_act_bwd pass over the tensor)
-static int add_mask_epi(const char* who, const pcg_conv_geom* g, const float* out, const float* addend, const float* a_below, int act,
-                        float slope, EpiAux* e) {
-  e->mode = EPI_ADD;
-  if (int rc = check_geom(g)) return rc;
-  if (int rc = epi_common(who, g, out, addend, act, slope, e)) return rc;      // e->neg = the activation's negative-side factor
-  PCG_REQUIRE(a_below && a_below != out && (((uintptr_t)a_below) & 15) == 0, "%s: a_below must be a 16-byte aligned tensor other than the output", who);
-  e->delta2_bytes = (int64_t)((intptr_t)a_below - (intptr_t)out);
+  *c = ConvCall{a->in, a->w, a->bias, a->out, nullptr, a->workspace, a->workspace_bytes, a->act, a->slope, nullptr, a->xf, 1};
+  const size_t need = dgrad ? pcg_conv2d_dgrad_bn_workspace_bytes(g) : pcg_conv2d_fwd_bn_workspace_bytes(g);   // partial rows of this direction
+  if (a->stats) {
+    PCG_REQUIRE(need > 0, "pcg_conv2d: statistics only on MFMA layers (Cin > 3, Cout > 3, output channels %% 4 == 0, grad-input stride <= 2); use pcg_conv2d + pcg_bn_train_stats");
+    PCG_REQUIRE(a->save_mean && a->save_invstd, "pcg_conv2d: null statistics output");
+    PCG_REQUIRE(!a->coef_out || (a->gamma && a->beta), "pcg_conv2d: coef_out needs gamma and beta");
+    PCG_REQUIRE(a->groups == 0 || (a->groups <= 8 && g->B % a->groups == 0 && ((int64_t)(g->B / a->groups) * g->OH * g->OW) % 128 == 0),
+                "pcg_conv2d: %d images do not split into %d groups of whole 128-row tiles (%d x %d output)", g->B, a->groups, g->OH, g->OW);
+    if (!a->workspace || a->workspace_bytes < need) { set_error("pcg_conv2d: workspace %zu B < required %zu B (statistics)", a->workspace_bytes, need); return PCG_ERR_WORKSPACE; }
+    c->stat_partial = (double*)a->workspace; c->workspace = nullptr; c->workspace_bytes = 0;
+    if (a->groups > 0) c->groups = a->groups;
+  }
+  if (a->epi == PCG_CONV_EPI_NONE) return PCG_OK;
+  // (a mask on a pcg_conv2d_dgrad_mask_thin_ok geometry is the one epilogue off the MFMA path: the thin expand kernel applies it)
+  PCG_REQUIRE(mfma || (dgrad && a->epi == PCG_CONV_EPI_MASK && pcg_conv2d_dgrad_mask_thin_ok(g)),
+              "pcg_conv2d: epilogues only on MFMA layers (Cin > 3 and Cout > 3); use the unfused calls");
+  const bool masks = a->epi == PCG_CONV_EPI_MASK || a->epi == PCG_CONV_EPI_ADD_MASK || a->epi == PCG_CONV_EPI_BNBWD;
+  PCG_REQUIRE(masks ? act_masks(a->epi_act) : a->epi_act == PCG_ACT_NONE, "pcg_conv2d: epilogue activation %d is not none / ReLU / LeakyReLU (add, add_bnsum: none)", a->epi_act);
+  const bool sums = a->epi == PCG_CONV_EPI_ADD_BNSUM || a->epi == PCG_CONV_EPI_BNBWD;
+  e->mode = a->epi == PCG_CONV_EPI_MASK ? EPI_MASK : a->epi == PCG_CONV_EPI_BNBWD ? EPI_BNBWD : sums ? EPI_ADDSUM : EPI_ADD;
+  e->no_addend = a->epi == PCG_CONV_EPI_ADD_BNSUM && !a->addend;          // (r04) nullable: the sums of the plain result
+  const float* aux = a->epi == PCG_CONV_EPI_MASK ? a->a_below : a->epi == PCG_CONV_EPI_BNBWD ? a->z : e->no_addend ? a->out : a->addend;
+  PCG_REQUIRE(aux, "pcg_conv2d: null pointer (the epilogue's %s)", a->epi == PCG_CONV_EPI_MASK ? "a_below" : a->epi == PCG_CONV_EPI_BNBWD ? "z" : "addend");
+  PCG_REQUIRE(!off16(aux) && !off16(a->out), "pcg_conv2d: tensors must be 16-byte aligned");
+  e->neg = a->epi == PCG_CONV_EPI_ADD_BNSUM ? a->sum_scale : act_neg_of(a->epi_act, a->epi_slope);
+  e->delta_bytes = (int64_t)((intptr_t)aux - (intptr_t)a->out);
+  if (a->epi == PCG_CONV_EPI_ADD_MASK) {
+    PCG_REQUIRE(a->a_below && a->a_below != a->out && !off16(a->a_below), "pcg_conv2d: a_below must be a 16-byte aligned tensor other than the output");
+    e->delta2_bytes = (int64_t)((intptr_t)a->a_below - (intptr_t)a->out);
+  }
+  if (sums) {
+    PCG_REQUIRE(need > 0, "pcg_conv2d: layer not eligible for the column sums (MFMA layers, stride <= 2, channel count %% 4 == 0)");
+    const bool bn = a->epi == PCG_CONV_EPI_BNBWD;
+    PCG_REQUIRE(a->mean && a->invstd && (bn ? a->gamma && a->beta : a->z != nullptr), "pcg_conv2d: null BatchNorm parameter (%s)", bn ? "mean / invstd / gamma / beta" : "z / mean / invstd");
+    PCG_REQUIRE(!off16(a->mean) && !off16(a->invstd) && (bn ? !off16(a->gamma) && !off16(a->beta) : !off16(a->z)), "pcg_conv2d: BatchNorm vectors and z must be 16-byte aligned");
+    if (!a->partial || a->partial_bytes < need) { set_error("pcg_conv2d: partial-sum buffer %zu B < required %zu B", a->partial_bytes, need); return PCG_ERR_WORKSPACE; }
+    e->mean = a->mean; e->invstd = a->invstd;
+    if (bn) { e->gamma = a->gamma; e->beta = a->beta; }
+    else e->delta2_bytes = (int64_t)((intptr_t)a->z - (intptr_t)a->out);
+    c->stat_partial = (double*)a->partial;
+  }
+  if (a->groups > 0) {      // the grad-input's bnbwd on side-by-side batches: equal sub-pixel phases with whole 128-row tiles per group
+    DgradPhases ph{};
+    int maxMp = 0;
+    const int nph = build_phases(g, &ph, &maxMp);
+    bool ok = a->groups <= 8 && g->B % a->groups == 0 && nph > 0;
+    for (int i = 0; i < nph && ok; ++i) ok = ph.p[i].Mp == maxMp;
+    ok = ok && (maxMp / a->groups) % 128 == 0 && maxMp % a->groups == 0;
+    PCG_REQUIRE(ok, "pcg_conv2d: needs equal sub-pixel phases whose rows split into %d groups of whole 128-row tiles", a->groups);
+    e->group_rows = a->groups > 1 ? maxMp / a->groups : 0;
+  }
+  c->epi = e;
   return PCG_OK;
 }
-extern "C" int pcg_conv2d_fwd_add_mask(const pcg_conv_geom* g, const float* x, const float* w, const float* addend, const float* a_below,
-                                       int act, float slope, float* y, pcg_stream_t stream) {
-  EpiAux e{};
-  if (int rc = add_mask_epi("pcg_conv2d_fwd_add_mask", g, y, addend, a_below, act, slope, &e)) return rc;
-  return conv2d_fwd_impl(g, x, w, nullptr, y, nullptr, nullptr, 0, stream, PCG_ACT_NONE, 0.f, &e);
+
+extern "C" int pcg_conv2d(const pcg_conv_geom* g, const pcg_conv_args* a, pcg_stream_t stream) {
+  ConvCall c{};
+  EpiAux epi{};
+  if (int rc = conv_call_of(g, a, &c, &epi)) return rc;
+  const bool dgrad = a->op == PCG_CONV_DGRAD;
+  if (c.epi && !mfma_layer(g))       // a one-channel layer's grad-input (r04): the mask in the row-block expand kernel
+    return thin_conv_dgrad_mask(g, a->in, a->w, a->a_below, a->epi_act, a->epi_slope, a->out, (hipStream_t)stream);
+  if (int rc = dgrad ? conv2d_dgrad_impl(g, c, stream) : conv2d_fwd_impl(g, c, stream)) return rc;
+  if (!a->stats) return PCG_OK;
+  // Side-by-side batches: each group gets its own batch statistics (save_mean / save_invstd are [groups][Cout]) from its own partial rows,
+  // the running statistics move once per group in group order and num_batches_tracked advances by `groups`, exactly what `groups`
+  // successive training-mode forwards do.  (groups == 1 is this launch too, not the ungrouped one.)
+  if (a->groups > 0)
+    return launch_bn_stats_finalize_g(c.stat_partial, fwd_stat_rows(g), 1, a->groups, (int64_t)(g->B / a->groups) * g->OH * g->OW, g->Cout, a->eps,
+                                      a->momentum, a->save_mean, a->save_invstd, a->running_mean, a->running_var, a->num_batches_tracked,
+                                      (hipStream_t)stream);
+  return launch_bn_stats_finalize(c.stat_partial, dgrad ? dgrad_stat_rows(g) : fwd_stat_rows(g), (int64_t)g->B * (dgrad ? g->IH * g->IW : g->OH * g->OW),
+                                  dgrad ? g->Cin : g->Cout, a->eps, a->momentum, a->save_mean, a->save_invstd, a->running_mean, a->running_var,
+                                  a->num_batches_tracked, (hipStream_t)stream, true, a->gamma, a->beta, a->coef_out);
 }
-extern "C" int pcg_conv2d_dgrad_add_mask(const pcg_conv_geom* g, const float* dy, const float* w, const float* addend, const float* a_below,
-                                         int act, float slope, float* dx, pcg_stream_t stream) {
-  EpiAux e{};
-  if (int rc = add_mask_epi("pcg_conv2d_dgrad_add_mask", g, dx, addend, a_below, act, slope, &e)) return rc;
-  return conv2d_dgrad_impl(g, dy, w, nullptr, dx, nullptr, nullptr, 0, stream, PCG_ACT_NONE, 0.f, &e);
+// the plain forms as positional C calls
+static pcg_conv_args plain_args(int op, const float* in, const float* w, const float* bias, float* out, void* workspace, size_t workspace_bytes) {
+  pcg_conv_args a{};
+  a.op = op; a.in = in; a.w = w; a.bias = bias; a.out = out; a.workspace = workspace; a.workspace_bytes = workspace_bytes;
+  return a;
 }
-extern "C" int pcg_conv2d_fwd_add_bnsum(const pcg_conv_geom* g, const float* x, const float* w, const float* addend, const float* z_next,
-                                        const float* mean, const float* invstd, float sum_scale, float* y, void* partial,
-                                        size_t partial_bytes, pcg_stream_t stream) {
-  EpiAux e{};
-  e.mode = EPI_ADDSUM;
-  if (int rc = check_geom(g)) return rc;
-  e.no_addend = addend == nullptr;          // (r04) nullable: the sums of the plain result
-  if (int rc = epi_common("pcg_conv2d_fwd_add_bnsum", g, y, addend ? addend : y, PCG_ACT_NONE, 0.f, &e)) return rc;
-  const size_t need = pcg_conv2d_fwd_bn_workspace_bytes(g);
-  PCG_REQUIRE(need > 0, "pcg_conv2d_fwd_add_bnsum: layer not eligible (MFMA layers, channel count %% 4 == 0)");
-  PCG_REQUIRE(z_next && mean && invstd && (((uintptr_t)z_next | (uintptr_t)mean | (uintptr_t)invstd) & 15) == 0,
-              "pcg_conv2d_fwd_add_bnsum: z_next / mean / invstd must be non-null and 16-byte aligned");
-  if (!partial || partial_bytes < need) { set_error("pcg_conv2d_fwd_add_bnsum: partial-sum buffer %zu B < required %zu B", partial_bytes, need); return PCG_ERR_WORKSPACE; }
-  e.neg = sum_scale;
-  e.delta2_bytes = (int64_t)((intptr_t)z_next - (intptr_t)y);
-  e.mean = mean; e.invstd = invstd;
-  return conv2d_fwd_impl(g, x, w, nullptr, y, (double*)partial, nullptr, 0, stream, PCG_ACT_NONE, 0.f, &e);
+extern "C" int pcg_conv2d_fwd(const pcg_conv_geom* g, const float* x, const float* w, const float* bias, float* y,
+                              void* workspace, size_t workspace_bytes, pcg_stream_t stream) {
+  const pcg_conv_args a = plain_args(PCG_CONV_FWD, x, w, bias, y, workspace, workspace_bytes);
+  return pcg_conv2d(g, &a, stream);
+}
+extern "C" int pcg_conv2d_dgrad(const pcg_conv_geom* g, const float* dy, const float* w, const float* bias_x, float* dx,
+                                void* workspace, size_t workspace_bytes, pcg_stream_t stream) {
+  const pcg_conv_args a = plain_args(PCG_CONV_DGRAD, dy, w, bias_x, dx, workspace, workspace_bytes);
+  return pcg_conv2d(g, &a, stream);
 }
 
 namespace pcg { namespace {
@@ -1830,81 +1804,7 @@ extern "C" int pcg_conv_weight_adjoint(const float* w, float* w_adj, int32_t Cou
   return launch_status("weight_adjoint_kernel");
 }
 
-extern "C" int pcg_conv2d_dgrad_add_bnsum(const pcg_conv_geom* g, const float* dy, const float* w, const float* addend, const float* z_next,
-                                          const float* mean, const float* invstd, float sum_scale, float* dx, void* partial,
-                                          size_t partial_bytes, pcg_stream_t stream) {
-  EpiAux e{};
-  e.mode = EPI_ADDSUM;
-  if (int rc = check_geom(g)) return rc;
-  e.no_addend = addend == nullptr;          // (r04) nullable: the sums of the plain result
-  if (int rc = epi_common("pcg_conv2d_dgrad_add_bnsum", g, dx, addend ? addend : dx, PCG_ACT_NONE, 0.f, &e)) return rc;
-  const size_t need = pcg_conv2d_dgrad_bn_workspace_bytes(g);
-  PCG_REQUIRE(need > 0, "pcg_conv2d_dgrad_add_bnsum: layer not eligible (MFMA layers, stride <= 2, channel count %% 4 == 0)");
-  PCG_REQUIRE(z_next && mean && invstd && (((uintptr_t)z_next | (uintptr_t)mean | (uintptr_t)invstd) & 15) == 0,
-              "pcg_conv2d_dgrad_add_bnsum: z_next / mean / invstd must be non-null and 16-byte aligned");
-  if (!partial || partial_bytes < need) { set_error("pcg_conv2d_dgrad_add_bnsum: partial-sum buffer %zu B < required %zu B", partial_bytes, need); return PCG_ERR_WORKSPACE; }
-  e.neg = sum_scale;
-  e.delta2_bytes = (int64_t)((intptr_t)z_next - (intptr_t)dx);
-  e.mean = mean; e.invstd = invstd;
-  return conv2d_dgrad_impl(g, dy, w, nullptr, dx, (double*)partial, nullptr, 0, stream, PCG_ACT_NONE, 0.f, &e);
-}
 
-static int bnbwd_epi(const char* who, const pcg_conv_geom* g, const float* out, const float* z_below, const float* mean, const float* invstd,
-                     const float* gamma, const float* beta, int act, float slope, size_t need, void* partial, size_t partial_bytes,
-                     EpiAux* e) {
-  PCG_REQUIRE(need > 0, "%s: layer not eligible (MFMA layers, stride <= 2, channel count %% 4 == 0)", who);
-  PCG_REQUIRE(mean && invstd && gamma && beta, "%s: null BatchNorm parameter", who);
-  PCG_REQUIRE((((uintptr_t)mean | (uintptr_t)invstd | (uintptr_t)gamma | (uintptr_t)beta) & 15) == 0, "%s: BatchNorm vectors must be 16-byte aligned", who);
-  if (!partial || partial_bytes < need) { set_error("%s: partial-sum buffer %zu B < required %zu B", who, partial_bytes, need); return PCG_ERR_WORKSPACE; }
-  e->mode = EPI_BNBWD;
-  e->mean = mean; e->invstd = invstd; e->gamma = gamma; e->beta = beta;
-  return epi_common(who, g, out, z_below, act, slope, e);
-}
-
-extern "C" int pcg_conv2d_dgrad_bnbwd(const pcg_conv_geom* g, const float* dy, const float* w, const float* z_below, const float* mean,
-                                      const float* invstd, const float* gamma, const float* beta, int act, float slope, float* dx,
-                                      void* partial, size_t partial_bytes, pcg_stream_t stream) {
-  EpiAux e{};
-  if (int rc = check_geom(g)) return rc;
-  if (int rc = bnbwd_epi("pcg_conv2d_dgrad_bnbwd", g, dx, z_below, mean, invstd, gamma, beta, act, slope,
-                         pcg_conv2d_dgrad_bn_workspace_bytes(g), partial, partial_bytes, &e)) return rc;
-  return conv2d_dgrad_impl(g, dy, w, nullptr, dx, (double*)partial, nullptr, 0, stream, PCG_ACT_NONE, 0.f, &e);
-}
-extern "C" int pcg_conv2d_fwd_bnbwd(const pcg_conv_geom* g, const float* x, const float* w, const float* z_below, const float* mean,
-                                    const float* invstd, const float* gamma, const float* beta, int act, float slope, float* y,
-                                    void* partial, size_t partial_bytes, pcg_stream_t stream) {
-  EpiAux e{};
-  if (int rc = check_geom(g)) return rc;
-  if (int rc = bnbwd_epi("pcg_conv2d_fwd_bnbwd", g, y, z_below, mean, invstd, gamma, beta, act, slope,
-                         pcg_conv2d_fwd_bn_workspace_bytes(g), partial, partial_bytes, &e)) return rc;
-  return conv2d_fwd_impl(g, x, w, nullptr, y, (double*)partial, nullptr, 0, stream, PCG_ACT_NONE, 0.f, &e);
-}
-// Grouped form of pcg_conv2d_dgrad_bnbwd: dy holds `groups` batches side by side; mean / invstd of the layer below are [groups][Cin].
-// The partial rows keep the layout of the ungrouped launch ([phase][tile row]); pcg_bn_bwd_partial_g reads each group's share of
-// every phase (pcg_conv2d_dgrad_bn_phases of them).  Needs equal sub-pixel phases with whole 128-row tiles per group.
-extern "C" int32_t pcg_conv2d_dgrad_bn_phases(const pcg_conv_geom* g) {
-  if (check_geom(g) != PCG_OK) return 0;
-  DgradPhases ph{};
-  int maxMp = 0;
-  return build_phases(g, &ph, &maxMp);
-}
-extern "C" int pcg_conv2d_dgrad_bnbwd_g(const pcg_conv_geom* g, const float* dy, const float* w, const float* z_below, const float* mean,
-                                        const float* invstd, const float* gamma, const float* beta, int act, float slope, float* dx,
-                                        void* partial, size_t partial_bytes, int32_t groups, pcg_stream_t stream) {
-  EpiAux e{};
-  if (int rc = check_geom(g)) return rc;
-  if (int rc = bnbwd_epi("pcg_conv2d_dgrad_bnbwd_g", g, dx, z_below, mean, invstd, gamma, beta, act, slope,
-                         pcg_conv2d_dgrad_bn_workspace_bytes(g), partial, partial_bytes, &e)) return rc;
-  DgradPhases ph{};
-  int maxMp = 0;
-  const int nph = build_phases(g, &ph, &maxMp);
-  bool ok = groups >= 1 && groups <= 8 && g->B % groups == 0 && nph > 0;
-  for (int i = 0; i < nph && ok; ++i) ok = ph.p[i].Mp == maxMp;
-  ok = ok && (maxMp / groups) % 128 == 0 && maxMp % groups == 0;
-  PCG_REQUIRE(ok, "pcg_conv2d_dgrad_bnbwd_g: needs equal sub-pixel phases whose rows split into %d groups of whole 128-row tiles", groups);
-  e.group_rows = groups > 1 ? maxMp / groups : 0;
-  return conv2d_dgrad_impl(g, dy, w, nullptr, dx, (double*)partial, nullptr, 0, stream, PCG_ACT_NONE, 0.f, &e);
-}
 // Thin forward (Cin = 1, k4) whose output is a gradient w.r.t. the activated output of  z -> BatchNorm(train) -> ReLU / LeakyReLU:
 // returns dz directly and adds dgamma / dbeta — the output tensor itself, the reduction pass over it and the re-read in the apply pass
 // disappear (thin_rows_expand_bn_kernel; DCGAN: G5's grad-input + G4's BatchNorm backward, mnist_dcgan.py:85-88 backward).

@@ -1,7 +1,7 @@
 // mnist_cf_eval.hip — the glue of the MNIST CounteRGAN's prompted queries and per-target evaluation:
 // conditional_counteRGAN/mnist eval_utils.py:46-110 (evaluate_counterfactuals, evaluate_generator_per_target), :204-288
 // (build_patch_mask_for_batch), :292-344 (compute_masked_metrics) and gradio_app.py:234-259 (one image, that digit, only these patches).
-// The convolutions stay the library's (pcg_conv2d_fwd_act); these four kernels are what surrounds them when ONE generator pass carries
+// The convolutions stay the library's (pcg_conv2d); these four kernels are what surrounds them when ONE generator pass carries
 // every (target class, row) query of a loader batch:
 //   patch_mask_bits   one 64-bit word per mask -> a dense [H][W] mask of whole patches
 //   entry             the generator's NHWC input (x[b], table[target(q)], mask[row(q)]) with the broadcast done by indexing

@@ -27,7 +27,10 @@ int launch_status(const char* what) {
 }
 }  // namespace pcg
 
-// ABI history.  v6: the tabular step's launches take argument structs, a rider is an optional struct pointer (eighteen entry points
+// ABI history.  v7: the forward and grad-input convolutions take one argument struct: pcg_conv2d(geom, pcg_conv_args) replaces the twenty
+//   positional entries pcg_conv2d_{fwd,dgrad}_{act,xf,bn,bn_xf,mask,add,add_mask,add_bnsum,bnbwd} and the grouped _fwd_bn_g / _dgrad_bnbwd_g;
+//   pcg_conv2d_fwd / pcg_conv2d_dgrad stay as positional conveniences.
+//   v6: the tabular step's launches take argument structs, a rider is an optional struct pointer (eighteen entry points
 //   became nine: pcg_spectral_norm_{fwd,bwd}_batched, pcg_house_critic_{fwd,bwd}, pcg_house_classifier_{fwd,bwd},
 //   pcg_house_residual_{fwd,bwd}, pcg_house_diag); + pcg_abi_struct_bytes.  v6, additive: + pcg_house_cf_eval;
 //   + pcg_patch_mask_bits, pcg_mnist_cf_entry, pcg_mnist_cf_tail, pcg_mnist_cf_score (csrc/mnist_cf_eval.hip);
@@ -40,7 +43,7 @@ int launch_status(const char* what) {
 //   + pcg_class_pick, pcg_class_pick_gather, pcg_cf_panels (csrc/cf_report.hip).
 //   + pcg_image_range (+ _workspace_bytes), pcg_image_sheet (csrc/image_sheet.hip).
 // v5, additive: + pcg_conv_precision_set / _get (thread-local bf16-operand mode of the implicit-GEMM convolutions).
-// v5 (r04): + grouped batches (pcg_conv2d_fwd_bn_g, pcg_bn_apply_act_g, pcg_conv2d_dgrad_bn_phases, pcg_conv2d_dgrad_bnbwd_g,
+// v5 (r04): + grouped batches (the grouped forward-statistics and bnbwd grad-input entries, part of pcg_conv2d since v7; pcg_bn_apply_act_g, pcg_conv2d_dgrad_bn_phases,
 //   pcg_bn_bwd_partial_g(+_workspace_bytes), pcg_bn_act_bwd_premask_g(+pcg_bn_act_bwd_g_workspace_bytes), pcg_bce_pair),
 //   pcg_conv2d_fwd_bnbwd_thin(+_ok, +_workspace_bytes), pcg_conv_weight_adjoint_many, pcg_conv_reset_scratch, pcg_dp_barrier,
 //   pcg_dp_rccl_version; the stream-K scratch registry is keyed by (device, stream).
@@ -49,11 +52,11 @@ int launch_status(const char* what) {
 //   critic-stage entry points.  v3 (r02): pcg_adam_step_capturable scratch is 48 bytes; pcg_linear_wgrad_grouped takes whole layers;
 //   + the pcg_house_* / spectral-norm reps / seq entry points.  v2 (r02): + pcg_conv2d_*_xf, pcg_bn_train_stats_coef, pcg_dp_*;
 //   pcg_bn_bwd_partial takes fp64 partial rows.
-extern "C" int pcg_abi_version(void) { return 6; }
+extern "C" int pcg_abi_version(void) { return 7; }
 extern "C" size_t pcg_abi_struct_bytes(const char* name) {
 #define PCG_STRUCT(T) {#T, sizeof(T)}
   static const struct { const char* name; size_t bytes; } table[] = {
-      PCG_STRUCT(pcg_conv_geom), PCG_STRUCT(pcg_in_xform), PCG_STRUCT(pcg_wgrad_item), PCG_STRUCT(pcg_sn_fwd_batch), PCG_STRUCT(pcg_sn_bwd_batch),
+      PCG_STRUCT(pcg_conv_geom), PCG_STRUCT(pcg_conv_args), PCG_STRUCT(pcg_in_xform), PCG_STRUCT(pcg_wgrad_item), PCG_STRUCT(pcg_sn_fwd_batch), PCG_STRUCT(pcg_sn_bwd_batch),
       PCG_STRUCT(pcg_house_g_desc), PCG_STRUCT(pcg_house_g_fwd_args), PCG_STRUCT(pcg_house_g_bwd_args), PCG_STRUCT(pcg_house_critic_fwd_args),
       PCG_STRUCT(pcg_house_critic_bwd_args), PCG_STRUCT(pcg_house_cls_fwd_args), PCG_STRUCT(pcg_house_cls_bwd_args),
       PCG_STRUCT(pcg_house_res_fwd_args), PCG_STRUCT(pcg_house_res_bwd_args), PCG_STRUCT(pcg_house_loss_args), PCG_STRUCT(pcg_house_diag_args),

@@ -344,6 +344,33 @@ def _xref(xf):
     return xf.ref() if xf is not None else None
 
 
+def _conv2d_call(g, op, **fields):
+    """Fill a pcg_conv_args (_lib.ConvArgs) from `fields` and launch it: tensors go in as their pointers, `xf` as the InputXform's
+    struct, `epi` by its name in _lib.CONV_EPIS; None leaves a member zero.  The label that PCG_TRACE_OPS logs names the entry, the op
+    and whatever is not default — the plain convolution, with or without an output activation, is exactly 'pcg_conv2d fwd'."""
+    a = _lib.ConvArgs(op=op)
+    for k, v in fields.items():
+        if v is None:
+            continue
+        if k == "epi":
+            a.epi = _lib.CONV_EPIS.index(v)
+        elif k == "xf":
+            a.xf = ctypes.addressof(v.c_struct)
+        else:
+            setattr(a, k, v.data_ptr() if torch.is_tensor(v) else v)
+    label = ["pcg_conv2d", "dgrad" if op else "fwd"] + [_lib.CONV_EPIS[a.epi]] * bool(a.epi) + ["stats"] * bool(a.stats) + ["xf"] * bool(a.xf)
+    check(_lib.load().pcg_conv2d(ctypes.byref(g), ctypes.byref(a), _stream()), " ".join(label + [f"g{a.groups}"] * bool(a.groups)))
+
+
+def _conv2d(g, op, **fields):
+    with _Timed(g, "dgrad" if op else "fwd"):
+        _conv2d_call(g, op, **fields)
+
+
+def _ws_fields(ws):
+    return dict(workspace=ws, workspace_bytes=ws.numel() if ws is not None else 0)
+
+
 def conv2d_fwd(g, x, w, bias=None, out=None, act=0, slope=0.0, xf=None):
     """y[B,OH,OW,Cout] = act(conv(x[B,IH,IW,Cin], w OHWI) (+ bias)); xf: input transform on x (InputXform)."""
     _chk(x, "x"); _chk(w, "w")
@@ -352,17 +379,13 @@ def conv2d_fwd(g, x, w, bias=None, out=None, act=0, slope=0.0, xf=None):
     lib = _lib.load()
     need = lib.pcg_conv2d_fwd_workspace_bytes(ctypes.byref(g))
     ws = workspace(need, x.device) if need else None
-    with _Timed(g, "fwd"):
-        if isinstance(xf, BnInput):
+    if isinstance(xf, BnInput):
+        with _Timed(g, "fwd"):
             check(lib.pcg_conv2d_fwd_bnin_full(ctypes.byref(g), _p(x), _p(xf.mean), _p(xf.invstd), _p(xf.gamma), _p(xf.beta), xf.act, xf.slope,
                                                xf.groups, _p(w), _p(bias), int(act), float(slope), _p(y), _stream()), "pcg_conv2d_fwd_bnin_full")
-        elif xf is not None:
-            assert xf.C == g.Cin
-            check(lib.pcg_conv2d_fwd_xf(ctypes.byref(g), _p(x), xf.ref(), _p(w), _p(bias), int(act), float(slope), _p(y), _p(ws),
-                                        ws.numel() if need else 0, _stream()), "pcg_conv2d_fwd_xf")
-        else:
-            check(lib.pcg_conv2d_fwd_act(ctypes.byref(g), _p(x), _p(w), _p(bias), int(act), float(slope), _p(y), _p(ws),
-                                         ws.numel() if need else 0, _stream()), "pcg_conv2d_fwd_act")
+        return y
+    assert xf is None or xf.C == g.Cin
+    _conv2d(g, _lib.CONV_FWD, in_=x, w=w, bias=bias, out=y, act=int(act), slope=float(slope), xf=xf, **_ws_fields(ws))
     return y
 
 
@@ -375,14 +398,8 @@ def conv2d_dgrad(g, dy, w, bias_x=None, out=None, act=0, slope=0.0, xf=None):
     lib = _lib.load()
     need = lib.pcg_conv2d_dgrad_workspace_bytes(ctypes.byref(g))
     ws = workspace(need, dy.device) if need else None
-    with _Timed(g, "dgrad"):
-        if xf is not None:
-            assert xf.C == g.Cout
-            check(lib.pcg_conv2d_dgrad_xf(ctypes.byref(g), _p(dy), xf.ref(), _p(w), _p(bias_x), int(act), float(slope), _p(dx), _p(ws),
-                                          ws.numel() if need else 0, _stream()), "pcg_conv2d_dgrad_xf")
-        else:
-            check(lib.pcg_conv2d_dgrad_act(ctypes.byref(g), _p(dy), _p(w), _p(bias_x), int(act), float(slope), _p(dx), _p(ws),
-                                           ws.numel() if need else 0, _stream()), "pcg_conv2d_dgrad_act")
+    assert xf is None or xf.C == g.Cout
+    _conv2d(g, _lib.CONV_DGRAD, in_=dy, w=w, bias=bias_x, out=dx, act=int(act), slope=float(slope), xf=xf, **_ws_fields(ws))
     return dx
 
 
@@ -407,11 +424,9 @@ def conv_bn_train(g, a, w, bias, transposed, eps, momentum, running_mean, runnin
     invstd = torch.empty(C, dtype=torch.float32, device=a.device)
     coef = torch.empty(2 * C, dtype=torch.float32, device=a.device) if want_coef else None
     ws = workspace(need, a.device)
-    fn = lib.pcg_conv2d_dgrad_bn_xf if transposed else lib.pcg_conv2d_fwd_bn_xf
-    with _Timed(g, "dgrad" if transposed else "fwd"):
-        check(fn(ctypes.byref(g), _p(a), _xref(xf), _p(w), _p(bias), _p(z), eps, momentum, _p(mean), _p(invstd), _p(running_mean),
-                 _p(running_var), _p(num_batches_tracked), _p(gamma), _p(beta), _p(coef), _p(ws), ws.numel(), _stream()),
-              "pcg_conv2d_*_bn_xf")
+    _conv2d(g, int(transposed), in_=a, w=w, bias=bias, out=z, xf=xf, stats=1, eps=eps, momentum=momentum, save_mean=mean, save_invstd=invstd,
+            running_mean=running_mean, running_var=running_var, num_batches_tracked=num_batches_tracked, gamma=gamma, beta=beta,
+            coef_out=coef, **_ws_fields(ws))
     return (z, mean, invstd, coef) if want_coef else (z, mean, invstd)
 
 
@@ -427,8 +442,7 @@ def conv_bwd_data_fused(g, d, w, transposed, below_act, below_slope, a_below=Non
         _chk(d, "d"); _chk(w, "w"); _chk(a_below, "a_below")
         out = torch.empty((g.B, g.IH, g.IW, g.Cin), dtype=torch.float32, device=d.device)
         assert a_below.numel() == out.numel()
-        check(lib.pcg_conv2d_dgrad_mask(ctypes.byref(g), _p(d), _p(w), _p(a_below), int(below_act), float(below_slope), _p(out), None, 0, _stream()),
-              "pcg_conv2d_dgrad_mask(thin)")
+        _conv2d_call(g, _lib.CONV_DGRAD, in_=d, w=w, out=out, epi="mask", a_below=a_below, epi_act=int(below_act), epi_slope=float(below_slope))
         return out, None, 0
     if g.Cin <= 3 or g.Cout <= 3 or g.Cin % 4 or g.Cout % 4 or g.stride > 2:
         return None
@@ -440,10 +454,7 @@ def conv_bwd_data_fused(g, d, w, transposed, below_act, below_slope, a_below=Non
     if bn is None:
         _chk(a_below, "a_below")
         assert a_below.numel() == out.numel()
-        fn = lib.pcg_conv2d_fwd_mask if transposed else lib.pcg_conv2d_dgrad_mask
-        with _Timed(g, "fwd" if transposed else "dgrad"):
-            check(fn(ctypes.byref(g), _p(d), _p(w), _p(a_below), int(below_act), float(below_slope), _p(out), None, 0, _stream()),
-                  "pcg_conv2d_*_mask")
+        _conv2d(g, int(not transposed), in_=d, w=w, out=out, epi="mask", a_below=a_below, epi_act=int(below_act), epi_slope=float(below_slope))
         return out, None, 0
     _chk(z_below, "z_below")
     assert z_below.numel() == out.numel()
@@ -453,10 +464,8 @@ def conv_bwd_data_fused(g, d, w, transposed, below_act, below_slope, a_below=Non
         return None
     nparts = (lib.pcg_conv2d_fwd_bn_partial_rows if transposed else lib.pcg_conv2d_dgrad_bn_partial_rows)(ctypes.byref(g))
     partial = torch.empty(need // 4, dtype=torch.float32, device=d.device)   # own tensor: lives until bn_bwd_partial has read it
-    fn = lib.pcg_conv2d_fwd_bnbwd if transposed else lib.pcg_conv2d_dgrad_bnbwd
-    with _Timed(g, "fwd" if transposed else "dgrad"):
-        check(fn(ctypes.byref(g), _p(d), _p(w), _p(z_below), _p(mean), _p(invstd), _p(gamma), _p(beta), int(below_act), float(below_slope),
-                 _p(out), _p(partial), need, _stream()), "pcg_conv2d_*_bnbwd")
+    _conv2d(g, int(not transposed), in_=d, w=w, out=out, epi="bnbwd", z=z_below, mean=mean, invstd=invstd, gamma=gamma, beta=beta,
+            epi_act=int(below_act), epi_slope=float(below_slope), partial=partial, partial_bytes=need)
     return out, partial, nparts
 
 
@@ -496,9 +505,7 @@ def conv2d_dgrad_add_mask(g, dy, w, addend, a_below, act, slope, out=None, trans
     n = shape[0] * shape[1] * shape[2] * shape[3]
     assert addend.numel() == n and a_below.numel() == n
     dx = out if out is not None else torch.empty(shape, dtype=torch.float32, device=dy.device)
-    fn = _lib.load().pcg_conv2d_fwd_add_mask if transposed else _lib.load().pcg_conv2d_dgrad_add_mask
-    with _Timed(g, "fwd" if transposed else "dgrad"):
-        check(fn(ctypes.byref(g), _p(dy), _p(w), _p(addend), _p(a_below), int(act), float(slope), _p(dx), _stream()), "pcg_conv2d_*_add_mask")
+    _conv2d(g, int(not transposed), in_=dy, w=w, out=dx, epi="add_mask", addend=addend, a_below=a_below, epi_act=int(act), epi_slope=float(slope))
     return dx
 
 
@@ -526,17 +533,10 @@ def conv2d_dgrad_add(g, dy, w, addend, out=None, bnsum=None, transposed=False):
             raise _lib.PcgError("conv2d_dgrad_add(bnsum=...): layer not eligible for the fused column sums")
         nparts = (lib.pcg_conv2d_fwd_bn_partial_rows if transposed else lib.pcg_conv2d_dgrad_bn_partial_rows)(ctypes.byref(g))
         partial = torch.empty(need // 4, dtype=torch.float32, device=dy.device)
-        fn = lib.pcg_conv2d_fwd_add_bnsum if transposed else lib.pcg_conv2d_dgrad_add_bnsum
-        with _Timed(g, "fwd" if transposed else "dgrad"):
-            check(fn(ctypes.byref(g), _p(dy), _p(w), _p(addend), _p(z_next), _p(mean), _p(invstd), float(scale),
-                     _p(dx), _p(partial), need, _stream()), "pcg_conv2d_*_add_bnsum")
+        _conv2d(g, int(not transposed), in_=dy, w=w, out=dx, epi="add_bnsum", addend=addend, z=z_next, mean=mean, invstd=invstd,
+                sum_scale=float(scale), partial=partial, partial_bytes=need)
         return dx, partial, nparts
-    if transposed:
-        with _Timed(g, "fwd"):
-            check(lib.pcg_conv2d_fwd_add(ctypes.byref(g), _p(dy), _p(w), _p(addend), _p(dx), None, 0, _stream()), "pcg_conv2d_fwd_add")
-        return dx
-    with _Timed(g, "dgrad"):
-        check(_lib.load().pcg_conv2d_dgrad_add(ctypes.byref(g), _p(dy), _p(w), _p(addend), _p(dx), None, 0, _stream()), "pcg_conv2d_dgrad_add")
+    _conv2d(g, int(not transposed), in_=dy, w=w, out=dx, epi="add", addend=addend)
     return dx
 
 
@@ -789,7 +789,7 @@ def group_dgrad_ok(g, groups):
 
 
 def conv_bn_train_g(g, a, w, bias, eps, momentum, running_mean, running_var, num_batches_tracked, groups):
-    """Conv2d forward over `groups` side-by-side batches + per-group training-mode BatchNorm statistics (pcg_conv2d_fwd_bn_g).
+    """Conv2d forward over `groups` side-by-side batches + per-group training-mode BatchNorm statistics (pcg_conv_args.groups).
     Returns (z, save_mean [groups, C], save_invstd [groups, C])."""
     _chk(a, "a"); _chk(w, "w")
     lib = _lib.load()
@@ -799,9 +799,8 @@ def conv_bn_train_g(g, a, w, bias, eps, momentum, running_mean, running_var, num
     mean = torch.empty((groups, C), dtype=torch.float32, device=a.device)
     invstd = torch.empty((groups, C), dtype=torch.float32, device=a.device)
     ws = workspace(need, a.device)
-    with _Timed(g, "fwd"):
-        check(lib.pcg_conv2d_fwd_bn_g(ctypes.byref(g), _p(a), _p(w), _p(bias), _p(z), eps, momentum, _p(mean), _p(invstd), _p(running_mean),
-                                      _p(running_var), _p(num_batches_tracked), int(groups), _p(ws), ws.numel(), _stream()), "pcg_conv2d_fwd_bn_g")
+    _conv2d(g, _lib.CONV_FWD, in_=a, w=w, bias=bias, out=z, stats=1, eps=eps, momentum=momentum, save_mean=mean, save_invstd=invstd,
+            running_mean=running_mean, running_var=running_var, num_batches_tracked=num_batches_tracked, groups=int(groups), **_ws_fields(ws))
     return z, mean, invstd
 
 
@@ -814,7 +813,7 @@ def bn_apply_act_g(x, C, mean, invstd, gamma, beta, act, slope, groups, out=None
 
 
 def conv_bwd_data_fused_g(g, d, w, below_act, below_slope, z_below, bn, groups):
-    """Grouped pcg_conv2d_dgrad_bnbwd: returns (dm, partial, nparts, nphases) for bn_bwd_partial_g."""
+    """The bnbwd grad-input on `groups` side-by-side batches: returns (dm, partial, nparts, nphases) for bn_bwd_partial_g."""
     lib = _lib.load()
     _chk(d, "d"); _chk(w, "w"); _chk(z_below, "z_below")
     out = torch.empty((g.B, g.IH, g.IW, g.Cin), dtype=torch.float32, device=d.device)
@@ -824,9 +823,8 @@ def conv_bwd_data_fused_g(g, d, w, below_act, below_slope, z_below, bn, groups):
     nparts = lib.pcg_conv2d_dgrad_bn_partial_rows(ctypes.byref(g))
     nphases = lib.pcg_conv2d_dgrad_bn_phases(ctypes.byref(g))
     partial = torch.empty(need // 4, dtype=torch.float32, device=d.device)
-    with _Timed(g, "dgrad"):
-        check(lib.pcg_conv2d_dgrad_bnbwd_g(ctypes.byref(g), _p(d), _p(w), _p(z_below), _p(mean), _p(invstd), _p(gamma), _p(beta), int(below_act),
-                                           float(below_slope), _p(out), _p(partial), need, int(groups), _stream()), "pcg_conv2d_dgrad_bnbwd_g")
+    _conv2d(g, _lib.CONV_DGRAD, in_=d, w=w, out=out, epi="bnbwd", z=z_below, mean=mean, invstd=invstd, gamma=gamma, beta=beta,
+            epi_act=int(below_act), epi_slope=float(below_slope), partial=partial, partial_bytes=need, groups=int(groups))
     return out, partial, nparts, nphases
 
 

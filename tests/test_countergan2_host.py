@@ -103,7 +103,7 @@ def test_new_symbols_structs_and_version():
     assert _lib.PROTOTYPES["pcg_prob_head_fwd"] == (ctypes.c_int, [ctypes.POINTER(_lib.ProbHeadFwdArgs), ctypes.c_void_p])
     assert _lib.PROTOTYPES["pcg_log_eps_loss_fwd_bwd"] == (ctypes.c_int, [ctypes.POINTER(_lib.LogEpsLossArgs), ctypes.c_void_p])
     assert _lib.PROTOTYPES["pcg_prob_head_workspace_bytes"] == (ctypes.c_size_t, [ctypes.c_int32, ctypes.c_int32])
-    assert lib.pcg_abi_version() == 6
+    assert lib.pcg_abi_version() == 7
     assert lib.pcg_prob_head_workspace_bytes(256, 4) == 16 + 4 * 256 * 4
     assert lib.pcg_prob_head_workspace_bytes(256, 1) == 16 + 4 * 256
     assert lib.pcg_prob_head_workspace_bytes(256, 0) == 16 + 4 * 256 and lib.pcg_prob_head_workspace_bytes(129, 0) == 16 + 4 * 129

@@ -135,7 +135,7 @@ def test_new_symbols_structs_and_version():
     for name in NEW_STRUCTS:
         assert name in _lib.STRUCTS and "} " + name + ";" in header, name
         assert lib.pcg_abi_struct_bytes(name.encode()) == ctypes.sizeof(_lib.STRUCTS[name]) > 0, name
-    assert lib.pcg_abi_version() == 6
+    assert lib.pcg_abi_version() == 7
     assert [ctypes.sizeof(_lib.STRUCTS[n]) for n in NEW_STRUCTS] == [5 * 8 + 6 * 4, 4 * 8 + 5 * 4 + 4, 4 * 8 + 2 * 4]
 
 

@@ -96,7 +96,7 @@ def test_new_symbols_structs_and_version():
     for name in NEW_STRUCTS:
         assert name in _lib.STRUCTS and "} " + name + ";" in header, name
         assert lib.pcg_abi_struct_bytes(name.encode()) == ctypes.sizeof(_lib.STRUCTS[name]) > 0, name
-    assert lib.pcg_abi_version() == 6
+    assert lib.pcg_abi_version() == 7
     assert lib.pcg_delta_gan_tail_workspace_bytes(128, 784) == 16 + 4 * 98
     assert lib.pcg_delta_gan_tail_workspace_bytes(0, 784) == 0
 

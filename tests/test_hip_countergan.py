@@ -423,7 +423,7 @@ def test_fused_bias_colsum_equals_separate_pass(pcg):
 
 def test_skip_add_bnsum_equals_separate_reduction(pcg):
     """countergan.FUSE_SKIP_BNSUM: bn2's backward column sums (sum 0.1*dh, sum 0.1*dh*xhat) come out of the previous block's
-    skip-add grad-input epilogue (pcg_conv2d_dgrad_add_bnsum) instead of a reduction pass over (dh, z2).  Same values summed in
+    skip-add grad-input epilogue (PCG_CONV_EPI_ADD_BNSUM) instead of a reduction pass over (dh, z2).  Same values summed in
     fp64 in another order: every gradient of the step agrees to fp32 rounding of the two means (1e-6 of the tensor's scale)."""
     K = pcg.countergan
     x, y, t, m = (a.to(DEV) for a in CR.synthetic_batch(16, seed=7))

@@ -42,7 +42,7 @@ def _nets(pcg, cfg, seed=1):
 
 @pytest.mark.parametrize("B,C,HW,groups", [(256, 128, 16, 2), (512, 256, 8, 2), (128, 64, 32, 2), (96, 128, 16, 3)])
 def test_grouped_conv_bn_matches_separate_passes(pcg, B, C, HW, groups):
-    """pcg_conv2d_fwd_bn_g + pcg_bn_apply_act_g against `groups` calls of pcg_conv2d_fwd_bn + pcg_bn_apply_act on the slices."""
+    """The grouped forward statistics (conv_bn_train_g) + pcg_bn_apply_act_g against `groups` calls of conv_bn_train + pcg_bn_apply_act on the slices."""
     ops = pcg.ops
     torch.manual_seed(0)
     Cin = C // 2

@@ -370,4 +370,4 @@ def test_launch_census(pcg, monkeypatch):
     gone = ("pcg_dropout_apply", "pcg_rand_bernoulli", "pcg_nhwc_to_nchw_flat", "pcg_act_fwd", "pcg_cross_entropy_fwd_bwd", "pcg_fill")
     assert not [w for s in per_step[1:] for w in s if w in gone]
     assert not [w for w in calls if w in gone and w != "pcg_fill"]          # (pcg_fill: the fresh Adam moments, in the first step)
-    assert per_step[0].count("pcg_conv2d_fwd_act") == 4 and per_step[2].count("pcg_conv2d_fwd_act") == 4      # conv1..3 and fc1 as a 1x1
+    assert per_step[0].count("pcg_conv2d fwd") == 4 and per_step[2].count("pcg_conv2d fwd") == 4      # conv1..3 and fc1 as a 1x1

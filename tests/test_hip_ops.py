@@ -391,8 +391,8 @@ def test_dgrad_gemm_col2im_path_equals_phase_kernel(pcg, B, Cin, Cout, H, W, k, 
     finally:
         ops.tune("dgrad_gemm", -1)
     got_phase = torch.empty_like(got_gemm)
-    _lib.check(lib.pcg_conv2d_dgrad_act(ctypes.byref(g), ops._p(dyd), ops._p(wd), ops._p(bd), O.ACT_RELU, 0.0, ops._p(got_phase), None, 0,
-                                        ops._stream()), "pcg_conv2d_dgrad_act")          # no workspace -> phase kernel
+    args = _lib.ConvArgs(op=_lib.CONV_DGRAD, in_=dyd.data_ptr(), w=wd.data_ptr(), bias=bd.data_ptr(), out=got_phase.data_ptr(), act=O.ACT_RELU)
+    _lib.check(lib.pcg_conv2d(ctypes.byref(g), ctypes.byref(args), ops._stream()), "pcg_conv2d dgrad")      # no workspace -> phase kernel
     ref = torch.nn.functional.conv_transpose2d(dy.permute(0, 3, 1, 2).double(), w.permute(0, 3, 1, 2).double(), b_in.double(), stride=s,
                                                padding=p, output_padding=(H + 2 * p - k) % s if H == W else 0)
     if ref.shape[2:] != (H, W):   # output_padding per axis
@@ -502,7 +502,7 @@ def test_input_transform_equals_bn_apply_then_conv(pcg, B, Cin, Cout, H, W, k, s
 @pytest.mark.parametrize("B,H,C", [(8, 64, 64), (3, 28, 64), (4, 28, 256)])
 @pytest.mark.parametrize("act,slope", [(O.ACT_RELU, 0.0), (O.ACT_LRELU, 0.2)])
 def test_input_transform_on_the_one_channel_transposed_layer(pcg, B, H, C, act, slope):
-    """pcg_conv2d_dgrad_xf / pcg_conv2d_wgrad_xf(xf_dy) on a Cin = 1, Cout = 64 k geometry (pcg_conv2d_xf_thin_ok: DCGAN's and WGAN-GP's
+    """The grad-input pcg_conv2d with xf / pcg_conv2d_wgrad_xf(xf_dy) on a Cin = 1, Cout = 64 k geometry (pcg_conv2d_xf_thin_ok: DCGAN's and WGAN-GP's
     last ConvTranspose2d) == the plain calls on bn_apply_act(z): bit for bit."""
     ops = pcg.ops
     g = ops.conv_geom(B, H, H, 1, C, 4, 4, 2, 1)

@@ -129,7 +129,7 @@ def test_argument_structs_have_the_librarys_sizes():
     lib = pcgan_amd.load()
     for name in ("pcg_patch_mask_bits_args", "pcg_mnist_cf_entry_args", "pcg_mnist_cf_tail_args", "pcg_mnist_cf_score_args"):
         assert lib.pcg_abi_struct_bytes(name.encode()) == ctypes.sizeof(_lib.STRUCTS[name]) > 0, name
-    assert lib.pcg_abi_version() == 6
+    assert lib.pcg_abi_version() == 7
     for name in ("pcg_patch_mask_bits", "pcg_mnist_cf_entry", "pcg_mnist_cf_tail", "pcg_mnist_cf_score"):
         assert name in _lib.PROTOTYPES and hasattr(lib, name)
 

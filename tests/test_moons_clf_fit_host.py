@@ -34,7 +34,7 @@ def test_new_symbols_declared_and_exported():
         assert hasattr(lib, name), f"{name} is not exported by the built library"
         assert name + "(" in header, f"{name} is not declared in include/pcgan_hip.h"
     assert "trainer.py:13-29" in header and "main.py:14-40" in header
-    assert _lib.load().pcg_abi_version() == 6, "the additions are additive"
+    assert _lib.load().pcg_abi_version() == 7, "the additions are additive"
 
 
 def _header_fields(header, name):

@@ -133,7 +133,7 @@ def test_header_declares_and_library_exports_the_sheet_entries():
         assert name in declared, f"{name} is not declared in pcgan_hip.h"
         assert hasattr(raw, name), f"{name} is not exported by libpcgan_hip.so"
         assert name in _lib.PROTOTYPES
-    assert lib.pcg_abi_version() == 6
+    assert lib.pcg_abi_version() == 7
     assert lib.pcg_abi_struct_bytes(b"pcg_image_sheet_args") == ctypes.sizeof(_lib.ImageSheetArgs) > 0
     assert lib.pcg_image_range_workspace_bytes() >= 16 + 8
     assert pcgan_amd.sheets is sheets and "sheets" in pcgan_amd.__all__
